@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- Mode-I TX frames/s of the MI355X-native DAB hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg3] [--frames B]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg3] [--frames B] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of B synthetic transmission
-frames (inputs resident in HBM before the timed region).  For N > 1 the driver
+frames (inputs resident in HBM before the timed region).  A plain run sets up,
+warms up, times the K steps and prints the line; --full adds everything else the
+bench measures (profiler counters, board power, the measured HBM peaks, the other
+workloads and modes, the host programs' rates, the CPU baseline).  For N > 1 the driver
 launches one rank per GPU through torch.distributed.run; frames are independent
 units, so every rank runs its own stream of batches (weak scaling, no data-path
 collective); the only collectives are the barrier around the timed region and
@@ -33,6 +36,8 @@ sys.path.insert(0, ROOT)
 PREWARM = 3            # untimed steps run before the W warm-up steps of the contract
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.29 TB/s measured copy)
 SMALL_BATCH_LANES = 3   # the library's default (dabgpu_set_lanes): batches in flight inside one context, B = 1 / 16 / 256
+DUMP_BYTES = 48 << 20   # --dump-outputs: whole frames of IQ up to this many bytes (a seeded sample of a larger batch)
+DUMP_SEED = 1234
 
 # ALGORITHMIC (compulsory) bytes per transmission frame, SURVEY 8(d) / BASELINE.md section 3
 ALGO_BYTES = {
@@ -226,6 +231,21 @@ def host_tools(device_index=0, budget_s=45.0):
     return out
 
 
+def dump_outputs(d, out):
+    """--dump-outputs DIR: the IQ the last timed step returned (out: frames x samples, complex64) as DIR/iq.npy, float32
+    frames x samples x (re, im).  A batch larger than DUMP_BYTES is sampled by whole frames, the same seeded choice in every
+    run; DIR/iq_frames.npy holds their indices in the batch."""
+    import numpy as np
+    import torch
+    frames = out.shape[0]
+    n = max(1, min(frames, DUMP_BYTES // (out[0].numel() * 8)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(frames, n, replace=False))
+    iq = torch.view_as_real(out.index_select(0, torch.from_numpy(idx).to(out.device))).cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "iq.npy"), np.ascontiguousarray(iq, dtype=np.float32))
+    np.save(os.path.join(d, "iq_frames.npy"), idx.astype(np.float64))
+
+
 def free_port():
     import socket
     sk = socket.socket()
@@ -319,14 +339,22 @@ def main():
                     help="transmission frames per step per GPU (32768 = 51.5 GB of IQ per step: sized for 288 GB of HBM)")
     ap.add_argument("--chunks", type=int, default=0, help="workgroups per frame (0 = auto)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--counters", choices=["live", "replay", "off"], default="live",
+    ap.add_argument("--counters", choices=["live", "replay", "off"], default=None,
                     help="profiler counters of the headline workload: collected by this run through rocprofv3 --pmc (N = 1; falls "
-                         "back to replay), replayed from profiles/traffic.json, or none")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads")
+                         "back to replay), replayed from profiles/traffic.json, or none (default: live with --full, else off)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: counters, board power, measured HBM peaks, the secondary "
+                         "workloads and modes, the host programs, the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the IQ of the last step to DIR/iq.npy (float32; a seeded sample of "
+                         "whole frames, at most 48 MB)")
     ap.add_argument("--gather", type=int, default=0, metavar="FRAMES",
                     help="after the timed region, gather FRAMES frames of IQ from every rank on rank 0 (the optional "
                          "final IQ gather over RCCL / xGMI) and report its time separately; 0 = off")
     args = ap.parse_args()
+    if args.counters is None:
+        args.counters = "live" if args.full else "off"
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
     env_world = os.environ.get("WORLD_SIZE")
@@ -362,9 +390,9 @@ def main():
     dev = torch.device("cuda", device_index)
 
     power_of = {}
-    probe0 = PowerProbe(device_index)      # (created before any load: its idle reading is the card's idle power)
+    probe0 = PowerProbe(device_index) if args.full else None  # (created before any load: its idle reading is the card's idle power)
 
-    def run_workload(workload, B, steps, warmup, fmt=None, option=None, power_seconds=0.0, lanes=0, repeats=1):
+    def run_workload(workload, B, steps, warmup, fmt=None, option=None, power_seconds=0.0, lanes=0, repeats=1, dump=None):
         """lanes > 0: the calls go to the context's OWN stream (dabgpu_chain_process_dev with stream NULL) and rotate over
         that many internal lanes -- batches in flight inside ONE context, include/dabgpu.h -- ordered against the timing
         stream by the two fences, so that the HIP events on it bracket all of them.  lanes = 0: every call on the timing
@@ -408,7 +436,7 @@ def main():
                 d_in = torch.zeros((B, 77 * 1536), dtype=torch.complex64, device=dev)
                 for f0 in range(0, B, 2048):          # (in slices: the torch temporaries are 5x the slice)
                     f1 = min(B, f0 + 2048)
-                    q = torch.randint(0, 4, (f1 - f0, 76 * 1536), device=dev)
+                    q = torch.randint(0, 4, (f1 - f0, 76 * 1536), device=dev, generator=gen)
                     ang = (q.float() * 2 + 1) * (np.pi / 4)
                     d_in[f0:f1, 1536:] = torch.polar(torch.ones_like(ang), ang)
                     del q, ang
@@ -455,6 +483,8 @@ def main():
                 runs.append((e0.elapsed_time(e1), w_))
             runs.sort()
             ev_ms, wall = runs[len(runs) // 2]
+            if dump:
+                dump_outputs(dump, d_out)
             if power_seconds > 0:
                 # OUTSIDE the timed region: about power_seconds of the same launches queued at once, the host samples the
                 # board's power and clock while the device works through them (verdict round 3: "the part is power-limited:
@@ -592,7 +622,8 @@ def main():
             print("bench.py: " + frames_note, file=sys.stderr)
     gather_info = {}
     wall, kern_ms = run_workload(args.workload, B, args.steps, args.warmup,
-                                 power_seconds=3.0 if (os.environ.get("WORLD_SIZE") is None and not args.no_extra) else 0.0)
+                                 power_seconds=3.0 if (os.environ.get("WORLD_SIZE") is None and args.full and not args.no_extra)
+                                 else 0.0, dump=args.dump_outputs if rank == 0 else None)
     value = grp.job_frames_per_second(B, args.steps, wall)
     algo = ALGO_BYTES[args.workload]
     achieved = algo * B / (kern_ms * 1e-3) / 1e9  # GB/s per GPU, per-launch HIP-event time
@@ -768,13 +799,13 @@ def main():
                      "simd_cycles_per_wave_iteration": measured_cycles,
                      "counters_source": replay},
     }
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         try:
             line["roofline"]["peak_measured_GBps"] = measured_peaks()
         except Exception as ex:
             line["roofline"]["peak_measured_GBps"] = {"error": str(ex)[:120]}
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_extra:
             extra = {}
             # the other BASELINE configs, and the headline workload one frame at a time (B = 1:

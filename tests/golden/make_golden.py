@@ -6,9 +6,11 @@ oracle/_ref/libdabref.so, which oracle/Makefile compiles from the reference's
 sources where they lie (never copied).  What is committed is data only:
 
   * the hot-path input bits per transmission mode (bits_mode<m>.bin), produced
-    by the pure-integer generator below (no libm, no RNG library), and
+    by the pure-integer generator below (no libm, no RNG library),
   * golden.json: SHA-256 of the byte image of each reference stage's output,
-    plus a few head samples as hex for human inspection.
+    plus a few head samples as hex for human inspection, and
+  * live_reference.json: the same digests for the inputs of the two tests
+    that run the reference's classes live where they are built.
 
 Integer stages (QpskSymbolMapper .. SignalMultiplexer) are fed from the bits.
 Float stages (GainControl, GuardIntervalInserter, FIRFilter, MemlessPoly) are
@@ -38,6 +40,35 @@ def sha(a):
 
 def head(a, n=4):
     return np.ascontiguousarray(a).view(np.uint32)[: 2 * n].tolist()
+
+
+def live_reference(fe_mod):
+    """The seeded inputs of the two tests that compare with the reference's classes live --
+    tests/test_oracle_golden.py::test_oracle_vs_live_reference_on_fresh_random_input and
+    tests/test_frontend.py::test_frontend_vs_live_reference_on_fresh_streams, the same recipes -- through those classes:
+    live_reference.json, what the two compare with where oracle/_ref is not built."""
+    from tests.golden.synth import synth_eti
+    mode = 4
+    m = O.mode_params(mode)
+    K, N = m["carriers"], m["spacing"]
+    bits = np.random.default_rng(2024).integers(0, 256, O.tf_input_bytes(mode), dtype=np.uint8)
+    q = O.ref_qpsk(bits, K)
+    fi = O.ref_freq_interleave(q, mode)
+    pr, _ = O.phase_reference(mode)
+    dm = O.ref_diff_mod(pr, fi, K)
+    t = O.ofdm_generate(O.signal_mux(np.zeros(K, np.complex64), dm), m["nb_symbols"] + 1, K, N)
+    stages = {"qpsk": sha(q), "freq_interleave": sha(fi), "diff_mod": sha(dm)}
+    for gm in (0, 1, 2):
+        stages["gain_control_%d" % gm] = sha(O.ref_gain_control(t, N, gm, 1.0, 1.0, 4.0))
+    ref = fe_mod.Frontend(fe_mod.bind(O.ref(), "ref_"), "ref_")
+    streams = {}
+    for seed, sub in ((91, ((0, 96, 0x21), (200, 48, 3))), (92, ((10, 18, 1), (60, 96, 0x24), (400, 60, 0x23)))):
+        streams[str(seed)] = sha(ref.eti_to_bits(synth_eti(36, subchannels=sub, seed=seed, first_fct=seed), 1))
+    live = {"_about": "SHA-256 of reference-class outputs on the seeded inputs of the live-reference tests; see "
+                      "make_golden.py", "oracle_mode4_seed2024": stages, "frontend_eti_to_bits": streams}
+    with open(os.path.join(HERE, "live_reference.json"), "w") as fo:
+        json.dump(live, fo, indent=1, sort_keys=True)
+    print("wrote", os.path.join(HERE, "live_reference.json"))
 
 
 def main():
@@ -124,6 +155,7 @@ def main():
     with open(os.path.join(HERE, "golden.json"), "w") as fo:
         json.dump(gold, fo, indent=1, sort_keys=True)
     print("wrote", os.path.join(HERE, "golden.json"))
+    live_reference(fe_mod)
 
 
 if __name__ == "__main__":

@@ -30,6 +30,33 @@ def test_bench_line_single_process():
     assert d["config"]["frames_per_step_per_gpu"] == 64
 
 
+def test_plain_bench_times_the_headline_only_and_dumps_what_its_last_step_computed(tmp_path):
+    """A plain run (no --full) prints the line without the secondary figures; --dump-outputs writes a seeded sample of whole
+    frames of the IQ its timed path returned -- the same in two runs, and the oracle's chain on the same input bits (drawn on
+    the device from a generator seeded with 42 on rank 0)."""
+    import numpy as np
+    import torch
+    import oracle as O
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / ("run%d" % k))
+        line = run_bench(["--steps", "3", "--dump-outputs", d], {})
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+        assert not {"other_workloads", "cpu_baseline"} & set(line) and "peak_measured_GBps" not in line["roofline"]
+        dumps.append((np.load(os.path.join(d, "iq.npy")), np.load(os.path.join(d, "iq_frames.npy"))))
+    (iq, idx), (iq2, idx2) = dumps
+    assert iq.dtype == np.float32 and iq.shape == (32, 196608, 2) and iq.nbytes + idx.nbytes <= 64 << 20
+    assert idx.dtype == np.float64 and len(set(idx.tolist())) == 32 and 0 <= idx.min() and idx.max() < 64
+    assert np.array_equal(idx, idx2) and np.array_equal(iq, iq2)
+    gen = torch.Generator(device="cuda:0")
+    gen.manual_seed(42)
+    bits = torch.randint(0, 256, (64, 28800), dtype=torch.uint8, device="cuda:0", generator=gen).cpu().numpy()
+    ref = O.Chain(mode=1, stages=3, gain_mode=2, normalise=1.0 / 50000.0).process(bits[idx.astype(np.int64)])
+    y = iq[..., 0] + 1j * iq[..., 1]
+    for f in range(len(idx)):
+        assert np.linalg.norm(y[f] - ref[f]) / np.linalg.norm(ref[f]) < 1e-6, f
+
+
 def test_bench_with_a_real_rccl_communicator_on_one_rank():
     """torch.distributed over RCCL initialised for WORLD_SIZE = 1: barrier, all_reduce(MAX) and the optional IQ
     gather run through the same code as on N ranks."""

@@ -203,6 +203,29 @@ def test_bench_one_rank_dry_run_needs_no_process_group():
     assert json.loads(r.stdout.strip())["n_gpus"] == 1
 
 
+def test_bench_dump_outputs_is_a_fixed_float32_sample_of_whole_frames(tmp_path):
+    """--dump-outputs DIR: whole frames of the last step's IQ as float32 (re, im), at most 64 MB in all, the same frames
+    in every run; a batch that fits is written whole."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    out = torch.randn(64, 196608, dtype=torch.complex64)
+    got = []
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), out)
+        got.append([np.load(str(tmp_path / str(k) / f)) for f in ("iq.npy", "iq_frames.npy")])
+    (iq, idx), (iq2, idx2) = got
+    assert iq.dtype == np.float32 and idx.dtype == np.float64 and iq.nbytes + idx.nbytes <= 64 << 20
+    assert iq.shape == (32, 196608, 2) and np.array_equal(np.unique(idx), idx) and 0 <= idx[0] and idx[-1] < 64
+    assert np.array_equal(iq[..., 0] + 1j * iq[..., 1], out.numpy()[idx.astype(np.int64)])
+    assert np.array_equal(iq, iq2) and np.array_equal(idx, idx2)
+    bench.dump_outputs(str(tmp_path / "small"), out[:3])
+    assert np.array_equal(np.load(str(tmp_path / "small" / "iq_frames.npy")), [0, 1, 2])
+
+
 def test_bench_under_torch_distributed_run_as_the_driver_launches_it():
     """The driver's N > 1 command: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port P bench.py --gpus N ... -- every process is one rank (no second launcher inside), rank 0 prints the one line."""

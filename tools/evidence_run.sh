@@ -14,8 +14,8 @@ bash tools/profile_variants.sh ${tag}v > $G/profile_variants_$tag.log 2>&1
 bash tools/prof_modes.sh 2>&1 | noids > $G/${tag}_modes_counters.txt
 cd $R
 t0=$SECONDS
-python bench.py > $G/${tag}_bench_line.json 2> $G/${tag}_bench_line.err
-echo "python bench.py (default flags): $((SECONDS - t0)) s wall" > $G/${tag}_bench_wall.txt
+python bench.py --full > $G/${tag}_bench_line.json 2> $G/${tag}_bench_line.err
+echo "python bench.py --full (default flags otherwise): $((SECONDS - t0)) s wall" > $G/${tag}_bench_wall.txt
 python tools/time_host_path.py 2>&1 | noids > $G/host_path.txt
 python tools/time_host_path.py s16 2>&1 | noids > $G/host_path_s16.txt
 python tools/time_small.py 2>&1 | noids > $G/time_small.txt
