@@ -1,5 +1,6 @@
-// api_chain.hip -- the chain dispatch: which kernels a stage mask runs for the context's settings (run_native: the frame kernel's
-// variant or the unfused sequence; run_chain: + TII, Resampler, MemlessPoly, FormatConverter), and the chain's entry points.
+// api_chain.hip -- the chain dispatch: which kernels a stage mask runs for the context's settings and which scratch they
+// take, decided once per call (plan_chain -> ChainPlan), what carries the plan out (run_native: the frame kernel's variant or
+// the unfused sequence; run_chain: + TII, Resampler, MemlessPoly, FormatConverter), and the chain's entry points.
 #include "dabgpu_ctx.h"
 
 using namespace dabgpu;
@@ -46,6 +47,12 @@ bool resampler_fast_ratio(const dabgpu_ctx *c)
     return c->rs_nout % c->rs_nin == 0 && (c->rs_nout / c->rs_nin == 2 || c->rs_nout / c->rs_nin == 4);
 }
 
+// the polynomial predistorter as an epilogue of the x2 / x4 resampler's store (LUT mode is a kernel of its own)
+bool poly_in_resampler(const dabgpu_ctx *c, unsigned mask)
+{
+    return (mask & DABGPU_STAGE_RESAMPLE) && (mask & DABGPU_STAGE_POLY) && !c->cur.poly_is_lut && resampler_fast_ratio(c);
+}
+
 // Ratios the kernels cover: L / M (reduced) with M a power of two up to the FFT size N of the transmission mode,
 // any L -- up- and down-sampling.  Then nin = 2 N is a power of two and the nout = (nin / M) L point transform
 // factors into L branches of nin / M points.  Every other ratio is one the reference itself cannot run on whole
@@ -66,13 +73,19 @@ const char *resampler_ratio_error(int N, size_t in_rate, size_t out_rate)
     return nullptr;
 }
 
-int check_resampler(dabgpu_ctx *c)
+const char *resampler_error(const dabgpu_ctx *c)
 {
     const char *e = resampler_ratio_error(c->g.N, c->cur.rs_in, c->cur.rs_out);
-    if (e) return fail(c, DABGPU_E_INVALID, e);
+    if (e) return e;
     if ((size_t)c->rs_nin != 2 * (size_t)c->g.N || (size_t)c->rs_nout != (size_t)c->rs_nin / c->rs_M * c->rs_L)
-        return fail(c, DABGPU_E_INVALID, "Resampler: inconsistent geometry");
-    return DABGPU_OK;
+        return "Resampler: inconsistent geometry";
+    return nullptr;
+}
+
+int check_resampler(dabgpu_ctx *c)
+{
+    const char *e = resampler_error(c);
+    return e ? fail(c, DABGPU_E_INVALID, e) : DABGPU_OK;
 }
 
 // stream of `total` samples at d_in -> resampled at d_out (stateful)
@@ -129,68 +142,212 @@ int run_poly(dabgpu_ctx *c, const float2 *d_in, size_t n, float2 *d_out, hipStre
     return DABGPU_OK;
 }
 
-size_t out_samples_per_frame(const dabgpu_ctx *c, unsigned mask, size_t L, size_t M)
-{
-    size_t n = (mask & DABGPU_STAGE_NOGUARD) ? (size_t)(c->g.nb_symbols + 1) * (size_t)c->g.N
-                                             : tf_samples(c->g);
-    if (mask & DABGPU_STAGE_RESAMPLE) n = n * L / M;
-    return n;
-}
-
 size_t bytes_per_sample(int fmt) { return fmt ? dabgpu_format_size(fmt) : sizeof(float2); }
 
-// The chain on device pointers.  from_bits: d_in is coded bits, else carriers.
-// The native-rate part of the chain (everything up to and including FIRFilter) for n_frames frames
-// into native_out (`native` samples per frame).
-// tii_seg / tii_done: the caller's cached TII segment; *tii_done says whether the frame kernel added it itself (else the caller
-// runs launch_tii_add on the result)
-// Tap count the frame kernel is given.  A filter of fewer than 45 taps runs as a 45-tap filter whose last taps are zero
-// (out[n] = sum_j taps[j] in[n + j]: zero taps add nothing; the device table is zero padded) -- the kernels with the compile-time
-// tap count, the equalised-boundary variant among them, then serve every filter up to the default length.
-int fused_ntaps(const dabgpu_ctx *c)
+// The one place a stage mask is normalised and a frame's output is sized: the Resampler at equal rates is not in the chain
+// (src/DabModulator.cpp:336-340), and behind it a frame has L / M (reduced) times its native-rate samples.
+unsigned normalised_mask(const Settings &st, unsigned mask)
 {
-    const size_t n = c->cur.taps.size();
-    return (n >= 1 && n < 45) ? 45 : (int)n;
+    return st.rs_in == st.rs_out ? mask & ~(unsigned)DABGPU_STAGE_RESAMPLE : mask;
 }
 
-// gain mode var by the reference's recurrence (dabgpu_set_gain_rounding): the chain call is split at GainControl
-bool gain_replay(const dabgpu_ctx *c, unsigned mask)
+size_t out_samples_per_frame(const Geometry &g, const Settings &st, unsigned mask)
 {
-    return c->cur.gain_reference_rounding && c->cur.gain_mode == DABGPU_GAIN_VAR && (mask & DABGPU_STAGE_GAIN);
+    size_t n = (mask & DABGPU_STAGE_NOGUARD) ? (size_t)(g.nb_symbols + 1) * (size_t)g.N : tf_samples(g);
+    if (!(normalised_mask(st, mask) & DABGPU_STAGE_RESAMPLE)) return n;
+    size_t a = st.rs_in, b = st.rs_out;
+    while (b) { size_t t = a % b; a = b; b = t; }
+    return n * (st.rs_out / a) / (st.rs_in / a);
 }
 
-int run_native(dabgpu_ctx *c, const void *d_in, bool from_bits, size_t n_frames, unsigned mask, bool windowed,
-               float2 *native_out, size_t native, float *gain1, hipStream_t s, bool keep_stats,
-               unsigned long long *s16_clipped, const float2 *tii_seg, bool *tii_done, int fused_fmt)
+// Which kernels a chain call runs and which per-lane scratch it reserves, decided ONCE: run_chain / run_native /
+// ensure_tii_segment do what the plan says, and the lane choice (api_lanes.hip) reads its scratch total.  Reads the applied
+// settings (c->cur) and the context facts the decision depends on (eq_ok, use_eq, chunks_cfg, call_lanes, handover_frames,
+// the resampler's geometry); calls nothing in HIP, reserves nothing, allocates nothing.  The tf_has_* predicates of
+// tf_launch.hip are the single source of "this variant exists in this build", and this function is their only caller
+// outside the launchers.
+// from_bits: the input is coded bits, else carriers.  keep_stats: the CFR statistics are the caller's to read (a chain call);
+// false for the chain's internal runs (the TII segment, the pieces of the hand-over).
+ChainPlan plan_chain(const dabgpu_ctx *c, bool from_bits, size_t n_frames, unsigned mask, bool apply_format, bool keep_stats)
 {
-    if (tii_done) *tii_done = false;
+    const Settings &st = c->cur;
+    const Geometry &g = c->g;
+    ChainPlan p;
+    p.from_bits = from_bits;
+    p.keep_stats = keep_stats;
+    p.n_frames = n_frames;
+    p.mask = mask = normalised_mask(st, mask);
+    const bool noguard = mask & DABGPU_STAGE_NOGUARD, fir = mask & DABGPU_STAGE_FIR, gain = mask & DABGPU_STAGE_GAIN,
+               resample = mask & DABGPU_STAGE_RESAMPLE, poly = mask & DABGPU_STAGE_POLY;
+    // FormatConverter as the last step of the chain (src/DabModulator.cpp:395-419): the stage-level entry points
+    // that borrow the chain (OfdmGenerator, the TII segment) stay complexf
+    p.fmt = apply_format ? st.out_format : 0;
+    p.per = out_samples_per_frame(g, st, mask);
+    p.native = noguard ? p.per : tf_samples(g);
+    p.out_bytes = n_frames * p.per * bytes_per_sample(p.fmt);
+    if (noguard && (fir || resample || poly)) p.error = "NOGUARD cannot be combined with FIR/RESAMPLE/POLY";
+    else if (fir && st.taps.empty()) p.error = "FIRFilter: no taps loaded";
+    else if (resample) p.error = resampler_error(c);
+    if (p.error || n_frames == 0) return p;
+
+    const int nsym = g.nb_symbols + 1, ntaps = (int)st.taps.size(), cp = g.sym_size - g.N;
+    const size_t nsymN = (size_t)nsym * (size_t)g.N;
+    const bool post = resample || poly;
+    const bool fast_ratio = resample && resampler_fast_ratio(c);
+    const bool fir_fits = ntaps - 1 <= cp && ntaps <= tf_max_fused_taps();
+    // one fused kernel, unless the guard interval is windowed or the filter does not fit it
+    // (then: IFFT[+CFR][+gain] -> guard kernel -> FIR kernel)
+    // (CFR has fused variants with the whole epilogue -- guard + FIR --, with none of it, and, from coded bits, with the
+    // guard interval alone)
+    const bool windowed = (st.overlap > 0 || (fir && !fir_fits) || (st.cfr_enable && !fir && !from_bits)) && !noguard;
+    if (windowed && st.overlap > (size_t)cp) {
+        p.error = "window overlap larger than the guard interval";
+        return p;
+    }
+    p.tii = from_bits && st.tii_enable;
+    // gain mode var by the reference's recurrence (dabgpu_set_gain_rounding): the chain call is split at GainControl
+    const bool replay = st.gain_reference_rounding && st.gain_mode == DABGPU_GAIN_VAR && gain;
+    // Tap count the frame kernel is given.  A filter of fewer than 45 taps runs as a 45-tap filter whose last taps are zero
+    // (out[n] = sum_j taps[j] in[n + j]: zero taps add nothing; the device table is zero padded) -- the kernels with the
+    // compile-time tap count, the equalised-boundary variant among them, then serve every filter up to the default length.
+    const int fused_ntaps = (ntaps >= 1 && ntaps < 45) ? 45 : ntaps;
+
+    // what the predicates look at
     TfArgs a{};
-    a.clipped = s16_clipped;
+    a.g = g;
+    a.t.eq_g = c->eq_ok ? (const float *)c->d_eqg.p : nullptr;
+    a.gain.mode = st.gain_mode;
+    a.ntaps = ntaps;
+    a.overlap = (int)st.overlap;
+    unsigned flags = (from_bits ? TF_FROM_BITS : 0) | (gain && !replay ? TF_GAIN : 0) | (st.cfr_enable ? TF_CFR : 0);
+    const unsigned ofmt = (from_bits && !post && !replay) ? tf_ofmt_flag(p.fmt) : 0;   // (the frame kernel is the chain's last)
+    p.chunks_per_frame = auto_chunks(c, n_frames);
+    bool lookahead = false;
+    p.form = ChainPlan::UNFUSED;
+    if (replay) {
+        // OfdmGenerator (+ CFR) alone, then the reference's recurrence on the unscaled symbols (src/GainControl.cpp:118-155),
+        // then guard interval / FIRFilter as kernels of their own, which scale the symbols as they read them
+        p.form = ChainPlan::GAIN_REPLAY;
+        p.scratch.d_gains = n_frames * (size_t)nsym * sizeof(float);
+    } else if (!windowed) {
+        p.form = ChainPlan::ONE_KERNEL;
+        flags |= (noguard ? 0 : TF_GUARD) | (fir ? TF_FIR : 0);
+        if (!st.cfr_enable) a.ntaps = fused_ntaps;      // (the CFR variants loop over the run-time tap count)
+        // cfg 3 chain: the filtered transform alone with equalised boundaries (dabgpu_set_fir_boundary_mode(ctx, 1): the
+        // packed dual transform)
+        if (c->use_eq && tf_has_eq(a, flags)) flags |= TF_EQ;
+        lookahead = fir;
+    } else if (tf_has_window(a, flags | TF_GUARD | (fir ? TF_FIR : 0))) {
+        // OFDM windowing on the coded-bits chain, with or without FIRFilter: the frame kernel windows the guard interval
+        // itself (and filters across the seams)
+        p.form = ChainPlan::ONE_KERNEL;
+        flags |= TF_GUARD | TF_WINDOW | (fir ? TF_FIR : 0);
+        if (c->use_eq && fir && !st.cfr_enable) {
+            // narrow overlaps on the cfg 3 chain: the equalised-boundary variant with the seam inside its boundary outputs
+            // (the filter run at the default length, as without windowing)
+            a.ntaps = fused_ntaps;
+            if (tf_has_eq(a, flags)) flags |= TF_EQ;
+            else a.ntaps = ntaps;
+        }
+        lookahead = true;
+    }
+    p.ntaps = a.ntaps;
+    p.syms_per_chunk = a.syms_per_chunk = run_symbols(nsym, p.chunks_per_frame, lookahead);
+    const bool one_kernel = p.form == ChainPlan::ONE_KERNEL;
+    // TII is added to the native-rate complexf stream afterwards unless the frame kernel adds it itself
+    p.tii_inside = p.tii && one_kernel && tf_has_tii(a, flags);
+    // An integer format leaves the LAST kernel of the chain directly where that kernel has a variant for it (every other
+    // combination converts afterwards, through d_fmt): the frame kernel -- asked of the kernels' own predicates, the ones
+    // their launchers test, so that the separate convert kernel is taken whenever a variant does not exist in this build.
+    // u8 / s8: its equalised-boundary and no-FIRFilter variants; s16: those, the pruned dual transform, CFR.  Of the forms
+    // with a windowed guard interval: the equalised-boundary one (every format, TII inside) and the chain without
+    // FIRFilter (s16, no TII).
+    if (ofmt && one_kernel && (!p.tii || p.tii_inside) && tf_has_fmt(a, flags | ofmt)) {
+        p.fuse_native = true;
+        flags |= ofmt;
+    }
+    p.tf_flags = flags;
+    // ... or the x2 / x4 resampler (s16; with the polynomial predistorter inside its store, or none)
+    p.fuse_poly = poly_in_resampler(c, mask);
+    if (p.fmt == DABGPU_FMT_S16 && from_bits && fast_ratio && (!poly || !st.poly_is_lut)) {
+        ResamplerArgs ra{};
+        ra.nin = c->rs_nin;
+        ra.nout = c->rs_nout;
+        p.fuse_post = resampler_has_s16(ra);
+    }
+
+    // ---- the per-lane scratch the call reserves
+    if (!one_kernel && !noguard) p.scratch.d_b = n_frames * nsymN * sizeof(float2);        // the symbols before the guard kernel
+    if (p.fmt && !p.fuse_native && !p.fuse_post) p.scratch.d_fmt = n_frames * p.per * sizeof(float2);
+    if (st.cfr_enable) {
+        // crest-factor reduction inside OfdmGenerator (f-3): statistics per frame
+        p.scratch.cfr_counts = n_frames * 2 * sizeof(unsigned);
+        p.scratch.cfr_mer = n_frames * 2 * sizeof(double);
+        p.scratch.cfr_papr = n_frames * (size_t)nsym * 4 * sizeof(double);
+        if (!keep_stats) p.scratch.cfr_tmp = p.scratch.cfr_counts + p.scratch.cfr_mer + p.scratch.cfr_papr + 16;
+    }
+    // The hand-over FIRFilter -> Resampler in cache-sized pieces (dabgpu_set_handover_frames): x2 / x4 with the predistorter
+    // inside the resampler's store or absent; CFR (per-frame statistics) and TII (per-frame gain, frame parity) keep the
+    // one-piece path.
+    const size_t piece = (size_t)c->handover_frames & ~(size_t)1;
+    if (fast_ratio && (p.fuse_poly || !poly) && !st.cfr_enable && !p.tii && piece >= 2 && n_frames > piece) {
+        p.piece = piece;
+        const size_t d_fmt = p.scratch.d_fmt;
+        // (what the native-rate part of one piece reserves, with a plan of its own; the two-piece ring)
+        p.scratch = plan_chain(c, from_bits, piece, mask & ~(unsigned)(DABGPU_STAGE_RESAMPLE | DABGPU_STAGE_POLY), false, false)
+                        .scratch;
+        p.scratch.d_a = 2 * piece * p.native * sizeof(float2);
+        p.scratch.d_fmt = d_fmt;
+    } else {
+        if (post) p.scratch.d_a = n_frames * p.native * sizeof(float2);     // the native-rate stream
+        if (resample && poly && !p.fuse_poly)                               // the resampled stream in front of the predistorter
+            p.scratch.d_b = std::max(p.scratch.d_b, n_frames * p.per * sizeof(float2));
+        if (p.tii) {
+            if (gain) p.scratch.d_gain1 = n_frames * sizeof(float);
+            // (the one-frame run from carriers that builds the cached TII segment, on this call's lane)
+            const ChainPlan::Scratch seg = plan_chain(c, false, 1, mask & (DABGPU_STAGE_FIR | DABGPU_STAGE_NOGUARD), false, false).scratch;
+            p.scratch.d_b = std::max(p.scratch.d_b, seg.d_b);
+            p.scratch.cfr_tmp = std::max(p.scratch.cfr_tmp, seg.cfr_tmp);
+        }
+    }
+    const ChainPlan::Scratch &sc = p.scratch;
+    p.scratch_bytes = sc.d_a + sc.d_b + sc.d_fmt + sc.d_gains + sc.d_gain1 + sc.cfr_tmp +
+                      (keep_stats ? sc.cfr_counts + sc.cfr_mer + sc.cfr_papr : 0);
+    return p;
+}
+
+// The native-rate part of the chain (everything up to and including FIRFilter) as the plan has it, into native_out
+// (p.native samples per frame).  TII: the frame kernel adds the cached segment where the plan says so (else run_chain does).
+int run_native(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, float2 *native_out, hipStream_t s)
+{
+    const int nsym = c->g.nb_symbols + 1;
+    const size_t n_frames = p.n_frames;
+    const bool noguard = p.mask & DABGPU_STAGE_NOGUARD;
+    float *gain1 = p.scratch.d_gain1 ? (float *)c->d_gain1.p : nullptr;
+    TfArgs a{};
+    a.clipped = p.fuse_native ? (unsigned long long *)c->d_clip.p : nullptr;   // (the frame kernel stores the integers itself)
 #ifdef DABGPU_PHASE_TIMING
     a.phase_cycles = (unsigned long long *)c->d_phase.p;
 #endif
     a.g = c->g;
     a.t = tables_of(c);
     a.gain = gain_of(c);
-    a.ntaps = (int)c->cur.taps.size();
+    a.ntaps = p.ntaps;
     a.n_frames = (int)n_frames;
-    a.bits = from_bits ? (const uint8_t *)d_in : nullptr;
-    a.carriers = from_bits ? nullptr : (const float2 *)d_in;
-    a.gain1 = from_bits ? gain1 : nullptr;
-    unsigned flags = from_bits ? TF_FROM_BITS : 0;
-    if (mask & DABGPU_STAGE_GAIN) flags |= TF_GAIN;
-    if (c->cur.cfr_enable) {
+    a.bits = p.from_bits ? (const uint8_t *)d_in : nullptr;
+    a.carriers = p.from_bits ? nullptr : (const float2 *)d_in;
+    a.gain1 = (p.from_bits && p.form != ChainPlan::GAIN_REPLAY) ? gain1 : nullptr;
+    a.overlap = (int)c->cur.overlap;
+    a.chunks_per_frame = p.chunks_per_frame;
+    a.syms_per_chunk = p.syms_per_chunk;
+    if (p.tf_flags & TF_CFR) {
         // crest-factor reduction inside OfdmGenerator (f-3): statistics per frame, zeroed per call
-        const size_t nsym = (size_t)c->g.nb_symbols + 1;
-        const size_t b0 = n_frames * 2 * sizeof(unsigned), b1 = n_frames * 2 * sizeof(double),
-                     b2 = n_frames * nsym * 4 * sizeof(double);
-        flags |= TF_CFR;
         a.cfr_clip = c->cur.cfr_clip;
         a.cfr_errclip = c->cur.cfr_errclip;
-        if (keep_stats) {
-            HIPCHK(c, c->d_cfr_counts.reserve(b0));
-            HIPCHK(c, c->d_cfr_mer.reserve(b1));
-            HIPCHK(c, c->d_cfr_papr.reserve(b2));
+        if (p.keep_stats) {
+            HIPCHK(c, c->d_cfr_counts.reserve(p.scratch.cfr_counts));
+            HIPCHK(c, c->d_cfr_mer.reserve(p.scratch.cfr_mer));
+            HIPCHK(c, c->d_cfr_papr.reserve(p.scratch.cfr_papr));
             a.cfr_counts = (unsigned *)c->d_cfr_counts.p;
             a.cfr_mer = (double *)c->d_cfr_mer.p;
             a.cfr_papr = (double *)c->d_cfr_papr.p;
@@ -198,121 +355,50 @@ int run_native(dabgpu_ctx *c, const void *d_in, bool from_bits, size_t n_frames,
             c->cfr_last_base = a.cfr_mer_base;
             c->cfr_last_frames = n_frames;
             c->cfr_last_stream = s;
-            c->cfr_mer_index = (int)((c->cfr_mer_index + n_frames) % nsym);
+            c->cfr_mer_index = (int)((c->cfr_mer_index + n_frames) % (size_t)nsym);
         } else {
-            HIPCHK(c, c->d_cfr_tmp.reserve(b0 + b1 + b2 + 16));
+            HIPCHK(c, c->d_cfr_tmp.reserve(p.scratch.cfr_tmp));
             a.cfr_mer = (double *)c->d_cfr_tmp.p;
             a.cfr_papr = a.cfr_mer + n_frames * 2;
-            a.cfr_counts = (unsigned *)(a.cfr_papr + n_frames * nsym * 4);
+            a.cfr_counts = (unsigned *)(a.cfr_papr + n_frames * (size_t)nsym * 4);
             a.cfr_mer_base = 0;
         }
-        HIPCHK(c, hipMemsetAsync(a.cfr_counts, 0, b0, s));
-        HIPCHK(c, hipMemsetAsync(a.cfr_mer, 0, b1, s));
-        HIPCHK(c, hipMemsetAsync(a.cfr_papr, 0, b2, s));
+        HIPCHK(c, hipMemsetAsync(a.cfr_counts, 0, p.scratch.cfr_counts, s));
+        HIPCHK(c, hipMemsetAsync(a.cfr_mer, 0, p.scratch.cfr_mer, s));
+        HIPCHK(c, hipMemsetAsync(a.cfr_papr, 0, p.scratch.cfr_papr, s));
     }
+    // the frame kernel writes the native-rate stream itself, or the symbols ((nb_symbols + 1) x N per frame) for the guard kernel
+    const bool one_kernel = p.form == ChainPlan::ONE_KERNEL;
+    float2 *x0 = native_out;
+    if (!one_kernel && !noguard) {
+        HIPCHK(c, c->d_b.reserve(p.scratch.d_b));
+        x0 = (float2 *)c->d_b.p;
+    }
+    a.out = x0;
+    a.out_stride = x0 == native_out ? p.native : (size_t)nsym * (size_t)c->g.N;
+    if (p.tii_inside) {
+        a.tii_seg = (const float2 *)c->d_tii_frame.p;
+        a.tii_insert0 = c->tii_insert ? 1 : 0;
+    }
+    HIPCHK(c, launch_tf(a, p.tf_flags, s));
+    if (one_kernel) return DABGPU_OK;
 
-    a.overlap = (int)c->cur.overlap;
-    const bool replay = gain_replay(c, mask);
-    if (replay) {
-        // OfdmGenerator (+ CFR) alone, then the reference's recurrence on the unscaled symbols (src/GainControl.cpp:118-155), then
-        // guard interval / FIRFilter as kernels of their own, which scale the symbols as they read them
-        flags &= ~(unsigned)TF_GAIN;
-        a.gain1 = nullptr;
-        const int nsym = c->g.nb_symbols + 1;
-        const size_t nsymN = (size_t)nsym * (size_t)c->g.N;
-        const bool noguard = mask & DABGPU_STAGE_NOGUARD;
-        float2 *x0 = native_out;
-        if (!noguard) {
-            HIPCHK(c, c->d_b.reserve(n_frames * nsymN * sizeof(float2)));
-            x0 = (float2 *)c->d_b.p;
-        }
-        a.chunks_per_frame = auto_chunks(c, n_frames);
-        a.syms_per_chunk = run_symbols(nsym, a.chunks_per_frame, false);
-        a.out = x0;
-        a.out_stride = noguard ? native : nsymN;
-        if (noguard && native != nsymN) return fail(c, DABGPU_E_DEVICE, "gain rounding: unexpected frame stride");
-        HIPCHK(c, launch_tf(a, flags, s));
-        HIPCHK(c, c->d_gains.reserve(n_frames * (size_t)nsym * sizeof(float)));
+    const float *gains = nullptr;
+    if (p.form == ChainPlan::GAIN_REPLAY) {
         // (the multipliers are applied by the guard kernel as it gathers the symbols; a chain that stops here scales in place)
-        const float *gains = (const float *)c->d_gains.p;
-        HIPCHK(c, launch_gain_replay(x0, n_frames, nsym, c->g.N, a.gain, (float *)c->d_gains.p, from_bits ? gain1 : nullptr,
+        HIPCHK(c, c->d_gains.reserve(p.scratch.d_gains));
+        gains = (const float *)c->d_gains.p;
+        HIPCHK(c, launch_gain_replay(x0, n_frames, nsym, c->g.N, a.gain, (float *)c->d_gains.p, p.from_bits ? gain1 : nullptr,
                                      noguard, s));
         if (noguard) return DABGPU_OK;
-        if (mask & DABGPU_STAGE_FIR)
-            HIPCHK(c, launch_guard_fir(x0, n_frames, c->g, (int)c->cur.overlap, (const float *)c->d_window.p,
-                                       c->cur.taps.data(), (int)c->cur.taps.size(), native_out, s, gains));
-        else if (c->cur.overlap > 0)
-            HIPCHK(c, launch_guard_window(x0, n_frames, c->g, (int)c->cur.overlap, (const float *)c->d_window.p, native_out, s,
-                                          gains));
-        else
-            HIPCHK(c, launch_guard_copy(x0, n_frames, c->g, native_out, s, gains));
-        return DABGPU_OK;
     }
-    if (!windowed) {
-        if (!(mask & DABGPU_STAGE_NOGUARD)) flags |= TF_GUARD;
-        if (mask & DABGPU_STAGE_FIR) flags |= TF_FIR;
-        if (s16_clipped) flags |= tf_ofmt_flag(fused_fmt);        // (the frame kernel stores the integers itself)
-        if (!(flags & TF_CFR)) a.ntaps = fused_ntaps(c);     // (the CFR variants loop over the run-time tap count)
-        // cfg 3 chain: the filtered transform alone with equalised boundaries (dabgpu_set_fir_boundary_mode(ctx, 1): the packed
-        // dual transform)
-        if (c->use_eq && tf_has_eq(a, flags)) flags |= TF_EQ;
-        a.chunks_per_frame = auto_chunks(c, n_frames);
-        a.syms_per_chunk = run_symbols(c->g.nb_symbols + 1, a.chunks_per_frame, flags & TF_FIR);
-        a.out = native_out;
-        a.out_stride = native;
-        if (tii_seg && tf_has_tii(a, flags)) {
-            a.tii_seg = tii_seg;
-            a.tii_insert0 = c->tii_insert ? 1 : 0;
-            if (tii_done) *tii_done = true;
-        }
-        HIPCHK(c, launch_tf(a, flags, s));
-    } else if (tf_has_window(a, flags | TF_GUARD | ((mask & DABGPU_STAGE_FIR) ? TF_FIR : 0))) {
-        // OFDM windowing on the coded-bits chain, with or without FIRFilter: the frame kernel windows the guard interval
-        // itself (and filters across the seams)
-        flags |= TF_GUARD | TF_WINDOW | ((mask & DABGPU_STAGE_FIR) ? TF_FIR : 0);
-        if (c->use_eq && (flags & TF_FIR) && !(flags & TF_CFR)) {
-            // narrow overlaps on the cfg 3 chain: the equalised-boundary variant with the seam inside its boundary outputs
-            // (the filter run at the default length, as without windowing)
-            TfArgs e = a;
-            e.ntaps = fused_ntaps(c);
-            if (tf_has_eq(e, flags)) {
-                a.ntaps = e.ntaps;
-                flags |= TF_EQ;
-                if (s16_clipped) flags |= tf_ofmt_flag(fused_fmt);    // (this form stores the integers itself)
-            }
-        }
-        // (the default chain -- no FIRFilter -- with a windowed guard interval: its s16 store; run_chain asked tf_has_fmt)
-        if (s16_clipped && !(flags & (TF_FIR | TF_CFR))) flags |= tf_ofmt_flag(fused_fmt);
-        a.chunks_per_frame = auto_chunks(c, n_frames);
-        a.syms_per_chunk = run_symbols(c->g.nb_symbols + 1, a.chunks_per_frame, true);
-        a.out = native_out;
-        a.out_stride = native;
-        if (tii_seg && tf_has_tii(a, flags)) {
-            a.tii_seg = tii_seg;
-            a.tii_insert0 = c->tii_insert ? 1 : 0;
-            if (tii_done) *tii_done = true;
-        }
-        HIPCHK(c, launch_tf(a, flags, s));
-    } else {
-        // OFDM windowing: IFFT(+gain) -> windowed guard -> FIR as separate kernels
-        const size_t nsymN = (size_t)(c->g.nb_symbols + 1) * (size_t)c->g.N;
-        HIPCHK(c, c->d_b.reserve(n_frames * nsymN * sizeof(float2)));
-        a.chunks_per_frame = auto_chunks(c, n_frames);
-        a.syms_per_chunk = run_symbols(c->g.nb_symbols + 1, a.chunks_per_frame, false);
-        a.out = (float2 *)c->d_b.p;
-        a.out_stride = nsymN;
-        HIPCHK(c, launch_tf(a, flags, s));
-        if (mask & DABGPU_STAGE_FIR)
-            HIPCHK(c, launch_guard_fir((const float2 *)c->d_b.p, n_frames, c->g, (int)c->cur.overlap,
-                                       (const float *)c->d_window.p, c->cur.taps.data(),
-                                       (int)c->cur.taps.size(), native_out, s));
-        else if (c->cur.overlap > 0)
-            HIPCHK(c, launch_guard_window((const float2 *)c->d_b.p, n_frames, c->g, (int)c->cur.overlap,
-                                          (const float *)c->d_window.p, native_out, s));
-        else
-            HIPCHK(c, launch_guard_copy((const float2 *)c->d_b.p, n_frames, c->g, native_out, s));
-    }
-
+    if (p.mask & DABGPU_STAGE_FIR)
+        HIPCHK(c, launch_guard_fir(x0, n_frames, c->g, (int)c->cur.overlap, (const float *)c->d_window.p, c->cur.taps.data(),
+                                   (int)c->cur.taps.size(), native_out, s, gains));
+    else if (c->cur.overlap > 0)
+        HIPCHK(c, launch_guard_window(x0, n_frames, c->g, (int)c->cur.overlap, (const float *)c->d_window.p, native_out, s, gains));
+    else
+        HIPCHK(c, launch_guard_copy(x0, n_frames, c->g, native_out, s, gains));
     return DABGPU_OK;
 }
 
@@ -345,10 +431,14 @@ int tii_carrier_set(int mode, int comb, int pattern, std::vector<uint8_t> &acp)
 
 // (Re)build the stream contribution of one TII null symbol at unit gain for this stage mask:
 // TII symbol -> IFFT -> guard interval (-> FIR) of a frame whose other symbols are blank.
-int ensure_tii_segment(dabgpu_ctx *c, unsigned mask, bool windowed, size_t native, hipStream_t s)
+int ensure_tii_segment(dabgpu_ctx *c, unsigned mask, hipStream_t s)
 {
     const unsigned key = mask & (DABGPU_STAGE_FIR | DABGPU_STAGE_NOGUARD);
     if (c->tii_seg_epoch != 0 && c->tii_seg_mask == key) return DABGPU_OK;
+    // the segment is built from CARRIERS, by a one-frame run with a plan of its own (CFR with the guard interval alone is
+    // fused from coded bits only: from carriers that combination takes the unfused IFFT + CFR -> guard kernels)
+    const ChainPlan seg = plan_chain(c, false, 1, key, false, false);
+    if (seg.error) return fail(c, DABGPU_E_INVALID, seg.error);
     const size_t K = (size_t)c->g.K, car_bytes = (size_t)(c->g.nb_symbols + 1) * K * sizeof(float2);
     std::vector<uint8_t> acp;
     if (tii_carrier_set(c->g.mode, c->cur.tii_comb, c->cur.tii_pattern, acp))
@@ -361,140 +451,78 @@ int ensure_tii_segment(dabgpu_ctx *c, unsigned mask, bool windowed, size_t nativ
     }
     HIPCHK(c, upload(c->d_acp, acp, s));
     HIPCHK(c, c->d_tii_car.reserve(car_bytes + K * sizeof(float2)));
-    HIPCHK(c, c->d_tii_frame.reserve(native * sizeof(float2)));
+    HIPCHK(c, c->d_tii_frame.reserve(seg.native * sizeof(float2)));
     HIPCHK(c, hipMemsetAsync(c->d_tii_car.p, 0, car_bytes, s));
     float2 *phase = (float2 *)((char *)c->d_tii_car.p + car_bytes);
     HIPCHK(c, launch_phase_reference((const uint8_t *)c->d_phq.p, c->g.K, phase, s));
     HIPCHK(c, launch_tii(phase, (const uint8_t *)c->d_acp.p, c->g.K, c->cur.tii_old_variant ? 1 : 0, 1,
                          (float2 *)c->d_tii_car.p, s));
-    // the segment is built from CARRIERS: CFR with the guard interval alone is fused from coded bits only (run_chain's
-    // `windowed` is false for it), so here that combination takes the unfused IFFT + CFR -> guard kernels
-    const bool seg_windowed = windowed || (c->cur.cfr_enable && !(key & (DABGPU_STAGE_FIR | DABGPU_STAGE_NOGUARD)));
-    int rc = run_native(c, c->d_tii_car.p, false, 1, key, seg_windowed, (float2 *)c->d_tii_frame.p, native, nullptr, s,
-                        false);
+    const int rc = run_native(c, seg, c->d_tii_car.p, (float2 *)c->d_tii_frame.p, s);
     if (rc) return rc;
     // the response of the null symbol: its own segment plus whatever a windowed guard interval spills
     // into the next one (zeros beyond; adding them is harmless)
     const size_t ext = (mask & DABGPU_STAGE_NOGUARD) ? (size_t)c->g.N
                                                      : (size_t)c->g.null_size + 2 * c->cur.overlap + 8;
-    c->tii_seg_len = (int)std::min(native, ext);
+    c->tii_seg_len = (int)std::min(seg.native, ext);
     HIPCHK(c, hipStreamSynchronize(s));   // (once per setting: the segment is read by whichever lane runs the next call)
     c->tii_seg_epoch = 1;
     c->tii_seg_mask = key;
     return DABGPU_OK;
 }
 
-int run_chain(dabgpu_ctx *c, const void *d_in, bool from_bits, size_t n_frames, unsigned mask,
-              void *d_out_v, size_t out_cap, size_t *out_bytes, hipStream_t s, bool apply_format, int lane)
+// The tail of the chain, cifRes -> cifPoly (src/DabModulator.cpp:403-419), on n samples at d_in into d_out (n_out samples):
+// the polynomial predistorter is an epilogue of the x2 / x4 resampler's store (fuse_poly; LUT mode is not), otherwise a kernel
+// of its own behind it, reading the resampled stream from d_b (d_b_bytes: what the caller's plan sized it to).
+int run_tail(dabgpu_ctx *c, unsigned mask, bool fuse_poly, const float2 *d_in, size_t n, float2 *d_out, size_t n_out,
+             size_t d_b_bytes, hipStream_t s, unsigned long long *s16_clipped)
 {
-    int rc = apply_settings(c);
-    if (rc) return rc;
+    int rc;
+    if (mask & DABGPU_STAGE_RESAMPLE) {
+        float2 *dst = d_out;
+        if ((mask & DABGPU_STAGE_POLY) && !fuse_poly) {
+            HIPCHK(c, c->d_b.reserve(d_b_bytes));
+            dst = (float2 *)c->d_b.p;
+        }
+        if ((rc = run_resampler(c, d_in, n, dst, s, fuse_poly, s16_clipped))) return rc;
+        if (dst == d_out) return DABGPU_OK;
+        d_in = dst;
+    }
+    return (mask & DABGPU_STAGE_POLY) ? run_poly(c, d_in, n_out, d_out, s) : DABGPU_OK;
+}
+
+// One chain call as planned: d_in (coded bits or carriers) -> d_out_v, on stream s with lane's scratch.
+int run_chain(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, void *d_out_v, size_t out_cap, size_t *out_bytes,
+              hipStream_t s, bool apply_format, int lane)
+{
+    int rc;
     LaneScope scratch(c, lane);
     if (c->cur.cfr_enable) c->cfr_last_lane = lane;   // (also the OfdmGenerator stage wrapper: ITS statistics are the most recent)
-    if ((mask & DABGPU_STAGE_NOGUARD) && (mask & (DABGPU_STAGE_FIR | DABGPU_STAGE_RESAMPLE | DABGPU_STAGE_POLY)))
-        return fail(c, DABGPU_E_INVALID, "NOGUARD cannot be combined with FIR/RESAMPLE/POLY");
-    if ((mask & DABGPU_STAGE_FIR) && c->cur.taps.empty())
-        return fail(c, DABGPU_E_INVALID, "FIRFilter: no taps loaded");
-    if ((mask & DABGPU_STAGE_RESAMPLE) && c->cur.rs_in == c->cur.rs_out) mask &= ~DABGPU_STAGE_RESAMPLE;
-    if (mask & DABGPU_STAGE_RESAMPLE)
-        if ((rc = check_resampler(c))) return rc;
-    // FormatConverter as the last step of the chain (src/DabModulator.cpp:395-419): the stage-level entry points
-    // that borrow the chain (OfdmGenerator, the TII segment) stay complexf
-    const int fmt = apply_format ? c->cur.out_format : 0;
-    const size_t per = out_samples_per_frame(c, mask, c->rs_L, c->rs_M);
-    const size_t need = n_frames * per * bytes_per_sample(fmt);
-    if (out_bytes) *out_bytes = need;
-    if (need > out_cap) return fail(c, DABGPU_E_CAPACITY, "output buffer too small");
+    if (p.error) return fail(c, DABGPU_E_INVALID, p.error);
+    if ((rc = check_out(c, p.out_bytes, out_cap, out_bytes))) return rc;
+    const size_t n_frames = p.n_frames, native = p.native, per = p.per;
     if (n_frames == 0) return DABGPU_OK;
 
-    const size_t native = (mask & DABGPU_STAGE_NOGUARD) ? per : tf_samples(c->g);
-    const bool post = mask & (DABGPU_STAGE_RESAMPLE | DABGPU_STAGE_POLY);
-    const bool fir_fits = (int)c->cur.taps.size() - 1 <= c->g.sym_size - c->g.N &&
-                          (int)c->cur.taps.size() <= tf_max_fused_taps();
-    // one fused kernel, unless the guard interval is windowed or the filter does not fit it
-    // (then: IFFT[+CFR][+gain] -> guard kernel -> FIR kernel)
-    // (CFR has fused variants with the whole epilogue -- guard + FIR --, with none of it, and, from coded bits, with the
-    // guard interval alone)
-    const bool windowed = (c->cur.overlap > 0 || ((mask & DABGPU_STAGE_FIR) && !fir_fits) ||
-                           (c->cur.cfr_enable && !(mask & DABGPU_STAGE_FIR) && !from_bits)) &&
-                          !(mask & DABGPU_STAGE_NOGUARD);
-    if (windowed && c->cur.overlap > 0) {
-        const size_t W = c->cur.overlap;
-        if (W > (size_t)(c->g.sym_size - c->g.N))
-            return fail(c, DABGPU_E_INVALID, "window overlap larger than the guard interval");
-    }
-    const bool tii = from_bits && c->cur.tii_enable;
-
-    // s16 leaves the LAST kernel of the chain directly where that kernel has a variant for it: the frame kernel
-    // (Mode I coded-bits chain with guard interval and the default-length filter) or the x2 / x4 resampler (with
-    // the polynomial predistorter inside, or none).  Every other combination, and u8 / s8, converts afterwards.
     unsigned long long *clip = nullptr;
-    bool fuse_native = false, fuse_post = false;
-    if (apply_format) c->clip_valid = fmt != 0;       // (a complexf call leaves no count behind: never the previous call's)
-    if (fmt) {
+    if (apply_format) c->clip_valid = p.fmt != 0;       // (a complexf call leaves no count behind: never the previous call's)
+    if (p.fmt) {
         HIPCHK(c, c->d_clip.reserve(16));
         HIPCHK(c, hipMemsetAsync(c->d_clip.p, 0, 16, s));
         clip = (unsigned long long *)c->d_clip.p;
         c->clip_stream = s;
         c->clip_lane = lane;
-        if (from_bits) {
-            // ask the kernels' own predicates (the ones their launchers test), so that the separate convert kernel is taken
-            // whenever a variant does not exist in this build
-            const bool poly_ok = !(mask & DABGPU_STAGE_POLY) || (!c->cur.poly_is_lut && (mask & DABGPU_STAGE_RESAMPLE));
-            TfArgs ta{};
-            ta.g = c->g;
-            ta.t = tables_of(c);
-            ta.gain = gain_of(c);
-            ta.ntaps = c->cur.cfr_enable ? (int)c->cur.taps.size() : fused_ntaps(c);
-            ta.chunks_per_frame = auto_chunks(c, n_frames);
-            ta.syms_per_chunk = run_symbols(c->g.nb_symbols + 1, ta.chunks_per_frame, mask & DABGPU_STAGE_FIR);
-            unsigned tflags = TF_FROM_BITS | ((mask & DABGPU_STAGE_GAIN) ? TF_GAIN : 0) |
-                              ((mask & DABGPU_STAGE_NOGUARD) ? 0 : TF_GUARD) | ((mask & DABGPU_STAGE_FIR) ? TF_FIR : 0) |
-                              (c->cur.cfr_enable ? TF_CFR : 0);
-            if (c->use_eq && tf_has_eq(ta, tflags)) tflags |= TF_EQ;
-            // (a windowed guard interval has variants without the integer store only, and TII is added to the native-rate
-            // complexf stream afterwards unless the frame kernel adds it itself: the frame kernel's own store is out then, the
-            // resampler's is not.  u8 / s8: the frame kernel's equalised-boundary and no-FIRFilter variants; s16: those, the
-            // pruned dual transform and the x2 / x4 resampler.)
-            fuse_native = !post && !windowed && (!tii || tf_has_tii(ta, tflags)) && tf_has_fmt(ta, tflags | tf_ofmt_flag(fmt));
-            if (!post && windowed && c->cur.overlap > 0 && !(tflags & TF_CFR)) {
-                // ... except where a windowed form has the store (the decisions run_native takes): narrow overlaps on the cfg 3
-                // chain (the equalised-boundary form, every format, TII inside), the chain without FIRFilter (s16, no TII)
-                const unsigned wflags = tflags | TF_WINDOW;
-                ta.overlap = (int)c->cur.overlap;
-                ta.ntaps = (int)c->cur.taps.size();
-                if (tf_has_window(ta, wflags)) {
-                    if (tflags & TF_FIR) {
-                        ta.ntaps = fused_ntaps(c);
-                        fuse_native = c->use_eq && tf_has_eq(ta, wflags) && tf_has_fmt(ta, wflags | TF_EQ | tf_ofmt_flag(fmt)) &&
-                                      (!tii || tf_has_tii(ta, wflags | TF_EQ));
-                    } else {
-                        fuse_native = !tii && tf_has_fmt(ta, wflags | tf_ofmt_flag(fmt));
-                    }
-                }
-            }
-            ResamplerArgs ra{};
-            ra.nin = c->rs_nin;
-            ra.nout = c->rs_nout;
-            fuse_post = fmt == DABGPU_FMT_S16 && (mask & DABGPU_STAGE_RESAMPLE) && resampler_fast_ratio(c) &&
-                        resampler_has_s16(ra) && poly_ok;
-        }
     }
-    if (gain_replay(c, mask)) fuse_native = false;     // (the frame kernel is not the chain's last kernel then)
+    // where the chain's last kernel writes: the caller's buffer, or d_fmt in front of the separate convert kernel
     float2 *d_out = (float2 *)d_out_v;
-    if (fmt && !fuse_native && !fuse_post) {
-        HIPCHK(c, c->d_fmt.reserve(n_frames * per * sizeof(float2)));
+    if (p.scratch.d_fmt) {
+        HIPCHK(c, c->d_fmt.reserve(p.scratch.d_fmt));
         d_out = (float2 *)c->d_fmt.p;
     }
+    const bool post = p.mask & (DABGPU_STAGE_RESAMPLE | DABGPU_STAGE_POLY);
+    if (post) HIPCHK(c, c->d_a.reserve(p.scratch.d_a));
 
-    // The hand-over FIRFilter -> Resampler in cache-sized pieces (dabgpu_set_handover_frames): x2 / x4 with the predistorter
-    // inside the resampler's store or absent; CFR (per-frame statistics) and TII (per-frame gain, frame parity) keep the
-    // one-piece path.
-    const bool fuse_poly = (mask & DABGPU_STAGE_POLY) && !c->cur.poly_is_lut && resampler_fast_ratio(c);
-    const size_t piece = (size_t)c->handover_frames & ~(size_t)1;
-    if ((mask & DABGPU_STAGE_RESAMPLE) && resampler_fast_ratio(c) && (fuse_poly || !(mask & DABGPU_STAGE_POLY)) &&
-        !c->cur.cfr_enable && !tii && piece >= 2 && n_frames > piece) {
-        HIPCHK(c, c->d_a.reserve(2 * piece * native * sizeof(float2)));
+    if (p.piece) {
+        // the hand-over in pieces: a two-piece ring in d_a, the producer (every piece with a plan of its own) on lane 1's stream
+        const size_t piece = p.piece;
         hipStream_t prod;
         if ((rc = lane_stream(c, 1, &prod))) return rc;
         if (!c->ho_start) {
@@ -507,82 +535,42 @@ int run_chain(dabgpu_ctx *c, const void *d_in, bool from_bits, size_t n_frames, 
         // the producer starts after whatever the caller queued on s (the input; the previous call's use of the ring)
         HIPCHK(c, hipEventRecord(c->ho_start, s));
         HIPCHK(c, hipStreamWaitEvent(prod, c->ho_start, 0));
-        const size_t in_per = from_bits ? tf_in_bytes(c->g) : (size_t)(c->g.nb_symbols + 1) * (size_t)c->g.K * sizeof(float2);
-        const size_t bps = bytes_per_sample((fuse_post && fmt) ? fmt : 0);
+        const size_t in_per = p.from_bits ? tf_in_bytes(c->g) : (size_t)(c->g.nb_symbols + 1) * (size_t)c->g.K * sizeof(float2);
+        const size_t bps = bytes_per_sample(p.fuse_post ? p.fmt : 0);
+        const unsigned native_mask = p.mask & ~(unsigned)(DABGPU_STAGE_RESAMPLE | DABGPU_STAGE_POLY);
+        ChainPlan pp = plan_chain(c, p.from_bits, piece, native_mask, false, false);
         size_t f0 = 0;
         for (int i = 0; f0 < n_frames; ++i, f0 += piece) {
             const size_t nf = std::min(piece, n_frames - f0);
+            if (nf != piece) pp = plan_chain(c, p.from_bits, nf, native_mask, false, false);   // (the batch's last, shorter piece)
             const int slot = i & 1;
             float2 *ring = (float2 *)c->d_a.p + (size_t)slot * piece * native;
             if (i >= 2) HIPCHK(c, hipStreamWaitEvent(prod, c->ho_cons[slot], 0));   // the consumer is done with piece i - 2
-            if ((rc = run_native(c, (const char *)d_in + f0 * in_per, from_bits, nf, mask, windowed, ring, native, nullptr,
-                                 prod)))
-                return rc;
+            if ((rc = run_native(c, pp, (const char *)d_in + f0 * in_per, ring, prod))) return rc;
             HIPCHK(c, hipEventRecord(c->ho_prod[slot], prod));
             HIPCHK(c, hipStreamWaitEvent(s, c->ho_prod[slot], 0));
-            if ((rc = run_resampler(c, ring, nf * native, (float2 *)((char *)d_out + f0 * per * bps), s, fuse_poly,
-                                    fuse_post ? clip : nullptr)))
+            if ((rc = run_resampler(c, ring, nf * native, (float2 *)((char *)d_out + f0 * per * bps), s, p.fuse_poly,
+                                    p.fuse_post ? clip : nullptr)))
                 return rc;
             HIPCHK(c, hipEventRecord(c->ho_cons[slot], s));
         }
-        if (from_bits && (n_frames & 1)) c->tii_insert = !c->tii_insert;   // (src/TII.cpp:241-242: toggles with TII off as well)
-        if (fmt && !fuse_native && !fuse_post)
-            HIPCHK(c, launch_format((const float *)d_out, 2 * n_frames * per, fmt, d_out_v, clip, s));
-        return DABGPU_OK;
-    }
-
-    // where the native-rate stream goes
-    float2 *native_out = d_out;
-    if (post) {
-        HIPCHK(c, c->d_a.reserve(n_frames * native * sizeof(float2)));
-        native_out = (float2 *)c->d_a.p;
-    }
-
-    float *gain1 = nullptr;
-    if (tii) {
-        if ((rc = ensure_tii_segment(c, mask, windowed, native, s))) return rc;
-        if (mask & DABGPU_STAGE_GAIN) {
-            HIPCHK(c, c->d_gain1.reserve(n_frames * sizeof(float)));
-            gain1 = (float *)c->d_gain1.p;
+    } else {
+        float2 *native_out = post ? (float2 *)c->d_a.p : d_out;       // where the native-rate stream goes
+        if (p.tii) {
+            if ((rc = ensure_tii_segment(c, p.mask, s))) return rc;
+            HIPCHK(c, c->d_gain1.reserve(p.scratch.d_gain1));
         }
-    }
-    bool tii_done = false;
-    if ((rc = run_native(c, d_in, from_bits, n_frames, mask, windowed, native_out, native, gain1, s, true,
-                         fuse_native ? clip : nullptr, tii ? (const float2 *)c->d_tii_frame.p : nullptr, &tii_done, fmt)))
-        return rc;
-    if (tii && !tii_done) {
-        if (fuse_native) return fail(c, DABGPU_E_DEVICE, "s16 stored by the frame kernel, TII still to be added");
-        HIPCHK(c, launch_tii_add(native_out, native, (const float2 *)c->d_tii_frame.p, c->tii_seg_len, gain1,
-                                 c->tii_insert ? 1 : 0, n_frames, s));
+        if ((rc = run_native(c, p, d_in, native_out, s))) return rc;
+        if (p.tii && !p.tii_inside)
+            HIPCHK(c, launch_tii_add(native_out, native, (const float2 *)c->d_tii_frame.p, c->tii_seg_len,
+                                     p.scratch.d_gain1 ? (const float *)c->d_gain1.p : nullptr, c->tii_insert ? 1 : 0, n_frames, s));
+        if (post && (rc = run_tail(c, p.mask, p.fuse_poly, native_out, n_frames * native, d_out, n_frames * per, p.scratch.d_b, s,
+                                   p.fuse_post ? clip : nullptr)))
+            return rc;
     }
     // the insert flag toggles once per frame of the stream whether or not TII is enabled (src/TII.cpp:241-242)
-    if (from_bits && (n_frames & 1)) c->tii_insert = !c->tii_insert;
-
-    if (post) {
-        const float2 *cur = native_out;
-        size_t n = n_frames * native;
-        bool poly_done = false;
-        if (mask & DABGPU_STAGE_RESAMPLE) {
-            // the polynomial predistorter is an epilogue of the resampler's store (LUT mode is not)
-            const bool fuse = (mask & DABGPU_STAGE_POLY) && !c->cur.poly_is_lut && resampler_fast_ratio(c);
-            float2 *dst = d_out;
-            if ((mask & DABGPU_STAGE_POLY) && !fuse) {
-                HIPCHK(c, c->d_b.reserve(n_frames * per * sizeof(float2)));
-                dst = (float2 *)c->d_b.p;
-            }
-            rc = run_resampler(c, cur, n, dst, s, fuse, fuse_post ? clip : nullptr);
-            if (rc) return rc;
-            cur = dst;
-            n = n_frames * per;
-            poly_done = fuse;
-        }
-        if ((mask & DABGPU_STAGE_POLY) && !poly_done) {
-            rc = run_poly(c, cur, n, d_out, s);
-            if (rc) return rc;
-        }
-    }
-    if (fmt && !fuse_native && !fuse_post)
-        HIPCHK(c, launch_format((const float *)d_out, 2 * n_frames * per, fmt, d_out_v, clip, s));
+    if (p.from_bits && (n_frames & 1)) c->tii_insert = !c->tii_insert;
+    if (p.scratch.d_fmt) HIPCHK(c, launch_format((const float *)d_out, 2 * n_frames * per, p.fmt, d_out_v, clip, s));
     return DABGPU_OK;
 }
 
@@ -594,19 +582,8 @@ extern "C" {
 size_t dabgpu_chain_out_bytes_per_frame(const dabgpu_ctx *c, unsigned mask)
 {
     if (!c) return 0;
-    size_t L = 1, M = 1;
-    {
-        std::lock_guard<std::mutex> lk(const_cast<dabgpu_ctx *>(c)->mu);
-        size_t a = c->set.rs_in, b = c->set.rs_out;
-        while (b) { size_t t = a % b; a = b; b = t; }
-        L = c->set.rs_out / a; M = c->set.rs_in / a;
-    }
-    int fmt;
-    {
-        std::lock_guard<std::mutex> lk(const_cast<dabgpu_ctx *>(c)->mu);
-        fmt = c->set.out_format;
-    }
-    return out_samples_per_frame(c, mask, L, M) * bytes_per_sample(fmt);
+    std::lock_guard<std::mutex> lk(const_cast<dabgpu_ctx *>(c)->mu);
+    return out_samples_per_frame(c->g, c->set, mask) * bytes_per_sample(c->set.out_format);
 }
 
 int dabgpu_chain_process_dev(dabgpu_ctx *c, const void *d_bits, size_t n_frames, unsigned mask,
@@ -634,7 +611,7 @@ int dabgpu_post_process_dev(dabgpu_ctx *c, const void *d_native, size_t n_sample
     if (!stream && (rc = own_stream_joins_lanes(c))) return rc;     // (d_native: a chain call's output on any lane)
     if (mask & ~(unsigned)(DABGPU_STAGE_RESAMPLE | DABGPU_STAGE_POLY))
         return fail(c, DABGPU_E_INVALID, "post-processing: DABGPU_STAGE_RESAMPLE and / or DABGPU_STAGE_POLY");
-    if ((mask & DABGPU_STAGE_RESAMPLE) && c->cur.rs_in == c->cur.rs_out) mask &= ~(unsigned)DABGPU_STAGE_RESAMPLE;
+    mask = normalised_mask(c->cur, mask);
     size_t n_out = n_samples;
     if (mask & DABGPU_STAGE_RESAMPLE) {
         if ((rc = check_resampler(c))) return rc;
@@ -644,23 +621,12 @@ int dabgpu_post_process_dev(dabgpu_ctx *c, const void *d_native, size_t n_sample
     if ((rc = check_out(c, n_out * sizeof(float2), out_cap, out_bytes))) return rc;
     if (n_samples == 0) return DABGPU_OK;
     TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    const float2 *cur = (const float2 *)d_native;
-    bool poly_done = !(mask & DABGPU_STAGE_POLY);
-    if (mask & DABGPU_STAGE_RESAMPLE) {
-        const bool fuse = (mask & DABGPU_STAGE_POLY) && !c->cur.poly_is_lut && resampler_fast_ratio(c);
-        float2 *dst = (float2 *)d_iq;
-        if (!poly_done && !fuse) {
-            HIPCHK(c, c->d_b.reserve(n_out * sizeof(float2)));
-            dst = (float2 *)c->d_b.p;
-        }
-        if ((rc = run_resampler(c, cur, n_samples, dst, s, fuse))) return rc;
-        cur = dst;
-        poly_done = poly_done || fuse;
-    }
-    if (!poly_done && (rc = run_poly(c, cur, n_out, (float2 *)d_iq, s))) return rc;
-    if (cur == (const float2 *)d_native && poly_done)     // (neither stage: the stream passes through)
+    if (!mask) {                                          // (neither stage: the stream passes through)
         HIPCHK(c, hipMemcpyAsync(d_iq, d_native, n_samples * sizeof(float2), hipMemcpyDeviceToDevice, s));
-    return DABGPU_OK;
+        return DABGPU_OK;
+    }
+    return run_tail(c, mask, poly_in_resampler(c, mask), (const float2 *)d_native, n_samples, (float2 *)d_iq, n_out,
+                    n_out * sizeof(float2), s, nullptr);
 }
 
 int dabgpu_chain_process(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, unsigned mask,
@@ -672,9 +638,8 @@ int dabgpu_chain_process(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, un
     c->clip_from_collect = false;
     int rc = apply_settings(c);
     if (rc) return rc;
-    unsigned m2 = mask;
-    if ((m2 & DABGPU_STAGE_RESAMPLE) && c->cur.rs_in == c->cur.rs_out) m2 &= ~DABGPU_STAGE_RESAMPLE;
-    const size_t need = n_frames * out_samples_per_frame(c, m2, c->rs_L, c->rs_M) * bytes_per_sample(c->cur.out_format);
+    const ChainPlan p = plan_chain(c, true, n_frames, mask);
+    const size_t need = p.out_bytes;
     if ((rc = check_out(c, need, out_cap, out_bytes))) return rc;
     HostIO io(c);
     if ((rc = io.in(c->d_in, bits, n_frames * tf_in_bytes(c->g)))) return rc;
@@ -683,7 +648,7 @@ int dabgpu_chain_process(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, un
     size_t ob = 0;
     {
         TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-        rc = run_chain(c, c->d_in.p, true, n_frames, mask, (float2 *)c->d_out.p, need, &ob, c->stream);
+        rc = run_chain(c, p, c->d_in.p, c->d_out.p, need, &ob, c->stream);
     }
     if (rc) return rc;
     return io.out(iq_out, c->d_out.p, need);

@@ -57,51 +57,45 @@ int drain_lanes(dabgpu_ctx *c)
     return DABGPU_OK;
 }
 
-// Which lane a call on the context's own stream goes to: the lanes in turn while a launch alone cannot fill the chip many
-// times over; lane 0 for everything that carries stream state (Resampler) and for large batches (nothing to gain, and
-// the scratch of some chains grows with the batch).
-int pick_lane(dabgpu_ctx *c, size_t n_frames, unsigned mask, bool *rotating)
+// Which lane a call on the context's own stream goes to, and the call's plan: the lanes in turn while a launch alone cannot
+// fill the chip many times over; lane 0 for everything that carries stream state (Resampler) and for large batches (nothing
+// to gain).  Every lane owns a set of per-call scratch buffers that grow to the largest call they have seen and are never
+// trimmed, so a call rotates only while what it reserves -- the plan's total, the very sizes run_chain reserves -- stays
+// within kLaneScratchBytes per lane: the small batches the lanes exist for.  (The settings are applied by now: the plan is
+// the one the call runs with.)
+int pick_lane(dabgpu_ctx *c, bool from_bits, size_t n_frames, unsigned mask, ChainPlan *p)
 {
-    *rotating = false;
-    bool resample;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        resample = (mask & DABGPU_STAGE_RESAMPLE) && c->set.rs_in != c->set.rs_out;
+    c->call_lanes = 1;
+    if (c->n_lanes > 1 && !(normalised_mask(c->cur, mask) & DABGPU_STAGE_RESAMPLE) &&
+        n_frames <= (size_t)dabgpu_ctx::kLaneMaxFrames) {
+        c->call_lanes = c->n_lanes;             // (planned as one of n_lanes launches in flight: auto_chunks)
+        *p = plan_chain(c, from_bits, n_frames, mask);
+        if (p->scratch_bytes <= (size_t)dabgpu_ctx::kLaneScratchBytes) return (int)(c->lane_seq++ % (unsigned long long)c->n_lanes);
+        c->call_lanes = 1;
     }
-    if (c->n_lanes <= 1 || resample || n_frames > (size_t)dabgpu_ctx::kLaneMaxFrames) return 0;
-    // Every lane owns a set of per-call scratch buffers that grow to the largest call they have seen and are never trimmed.
-    // The one-kernel chains need none; the others (a separate guard / FIRFilter / convert / predistorter kernel: up to two
-    // native-rate frames of 8 B per sample per frame) rotate only while that stays within kLaneScratchBytes per lane --
-    // the small batches the lanes exist for.
-    bool scratch;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        scratch = c->set.overlap > 0 || c->set.out_format != 0 || c->set.cfr_enable || c->set.tii_enable ||
-                  (c->set.gain_reference_rounding && c->set.gain_mode == DABGPU_GAIN_VAR && (mask & DABGPU_STAGE_GAIN)) ||
-                  (mask & DABGPU_STAGE_POLY) || (int)c->set.taps.size() > tf_max_fused_taps();
-    }
-    if (scratch && n_frames * 2 * tf_samples(c->g) * sizeof(float2) > (size_t)dabgpu_ctx::kLaneScratchBytes) return 0;
-    *rotating = true;
-    return (int)(c->lane_seq++ % (unsigned long long)c->n_lanes);
+    *p = plan_chain(c, from_bits, n_frames, mask);
+    return 0;
 }
 
 int chain_dev(dabgpu_ctx *c, const void *d_in, bool from_bits, size_t n_frames, unsigned mask, void *d_iq, size_t out_cap,
               size_t *out_bytes, void *stream)
 {
+    int rc = apply_settings(c);
+    if (rc) return rc;
     int lane = 0;
     hipStream_t s = (hipStream_t)stream;
-    c->call_lanes = 1;
+    ChainPlan p;
     if (!s) {
-        bool rotating = false;
-        lane = pick_lane(c, n_frames, mask, &rotating);
-        int rc = lane_stream(c, lane, &s);
-        if (rc) return rc;
+        lane = pick_lane(c, from_bits, n_frames, mask, &p);
+        if ((rc = lane_stream(c, lane, &s))) return rc;
         if ((rc = lane_joins_own_stream(c, lane))) return rc;
-        if (rotating) c->call_lanes = c->n_lanes;
+    } else {
+        c->call_lanes = 1;
+        p = plan_chain(c, from_bits, n_frames, mask);
     }
     c->clip_from_collect = false;
     TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    const int rc = run_chain(c, d_in, from_bits, n_frames, mask, (float2 *)d_iq, out_cap, out_bytes, s, true, lane);
+    rc = run_chain(c, p, d_in, d_iq, out_cap, out_bytes, s, true, lane);
     c->call_lanes = 1;
     return rc;
 }
@@ -188,14 +182,15 @@ int dabgpu_chain_submit(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, uns
         return fail(c, DABGPU_E_CAPACITY, "n_frames exceeds max_frames of the context");
     int rc = apply_settings(c);
     if (rc) return rc;
-    unsigned m2 = mask;
-    if ((m2 & DABGPU_STAGE_RESAMPLE) && c->cur.rs_in == c->cur.rs_out) m2 &= ~DABGPU_STAGE_RESAMPLE;
-    const size_t in_bytes = n_frames * tf_in_bytes(c->g);
-    const size_t need = n_frames * out_samples_per_frame(c, m2, c->rs_L, c->rs_M) * bytes_per_sample(c->cur.out_format);
     const int slot_index = (c->slot_head + c->slot_count) & 1;
     dabgpu_ctx::Slot &sl = c->slot[slot_index];
     // the two batches in flight run on two lanes where the chain carries no stream state: their kernels overlap
-    const int lane = (c->n_lanes > 1 && !(m2 & DABGPU_STAGE_RESAMPLE)) ? slot_index : 0;
+    const bool two_lanes = c->n_lanes > 1 && !(normalised_mask(c->cur, mask) & DABGPU_STAGE_RESAMPLE);
+    const int lane = two_lanes ? slot_index : 0;
+    c->call_lanes = two_lanes ? 2 : 1;                  // (the two batches in flight)
+    const ChainPlan p = plan_chain(c, true, n_frames, mask);
+    c->call_lanes = 1;
+    const size_t in_bytes = n_frames * tf_in_bytes(c->g), need = p.out_bytes;
     hipStream_t ls;
     if ((rc = lane_stream(c, lane, &ls))) return rc;
     if ((rc = lane_joins_own_stream(c, lane))) return rc;
@@ -234,8 +229,8 @@ int dabgpu_chain_submit(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, uns
     size_t ob = 0;
     {
         TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-        c->call_lanes = (c->n_lanes > 1 && !(m2 & DABGPU_STAGE_RESAMPLE)) ? 2 : 1;     // (the two batches in flight)
-        rc = run_chain(c, sl.d_in.p, true, n_frames, mask, (float2 *)sl.d_out.p, need, &ob, ls, true, lane);
+        c->call_lanes = two_lanes ? 2 : 1;              // (the TII segment's run, when this call builds it)
+        rc = run_chain(c, p, sl.d_in.p, sl.d_out.p, need, &ob, ls, true, lane);
         c->call_lanes = 1;
     }
     if (rc) return rc;

@@ -210,8 +210,9 @@ int dabgpu_ofdm_process(dabgpu_ctx *c, const void *in, size_t in_bytes, void *ou
     const size_t need = (size_t)(c->g.nb_symbols + 1) * (size_t)c->g.N * sizeof(float2);
     if ((rc = check_out(c, need, out_cap, out_bytes))) return rc;
     HIPCHK(c, c->d_b.reserve(need));
+    if ((rc = apply_settings(c))) return rc;
     size_t ob = 0;
-    rc = run_chain(c, c->d_c.p, false, 1, DABGPU_STAGE_NOGUARD, (float2 *)c->d_b.p, need, &ob, c->stream, false);
+    rc = run_chain(c, plan_chain(c, false, 1, DABGPU_STAGE_NOGUARD, false), c->d_c.p, c->d_b.p, need, &ob, c->stream, false);
     if (rc) return rc;
     return io.out(out, c->d_b.p, need);
 }

@@ -1,7 +1,9 @@
 // dabgpu_ctx.h -- the device context behind the C-ABI of include/dabgpu.h and the helpers its translation units share:
 //   api_context.hip   context, settings, device tables (apply_settings), setters, diagnostics
-//   api_chain.hip     the chain dispatch: which kernels a stage mask runs (run_native / run_chain), chain entry points
-//   api_lanes.hip     batches in flight inside one context: lanes, their ordering, submit / collect
+//   api_chain.hip     the chain dispatch: which kernels a stage mask runs and which scratch they take, decided once per call
+//                     (plan_chain -> ChainPlan) and carried out (run_native / run_chain), chain entry points
+//   api_lanes.hip     batches in flight inside one context: lanes (chosen from the plan's scratch total), their ordering,
+//                     submit / collect
 //   api_stages.hip    one host-buffer entry point per reference plugin, FormatConverter, CFR statistics
 #pragma once
 #include "dabgpu.h"
@@ -259,25 +261,44 @@ Tables tables_of(dabgpu_ctx *c);
 GainParams gain_of(const dabgpu_ctx *c);
 
 // ---- api_chain.hip
+// What one chain call runs and reserves: decided once, by plan_chain; run_chain / run_native do what it says.
+struct ChainPlan {
+    const char *error = nullptr;          // the request cannot run (DABGPU_E_INVALID, this text); only the sizes below are set then
+    bool from_bits = false, keep_stats = true;
+    size_t n_frames = 0;
+    unsigned mask = 0;                    // normalised: RESAMPLE dropped when the rates are equal
+    int fmt = 0;                          // the integer format of the call's output (0: complexf)
+    size_t per = 0, native = 0;           // samples per frame of the output / of the native-rate stream
+    size_t out_bytes = 0;
+    // the native-rate part: one frame kernel (TF_WINDOW in tf_flags: it windows the guard interval itself), or frame kernel
+    // -> guard / FIRFilter kernel, the latter with the reference's gain recurrence in between
+    enum Form { ONE_KERNEL, UNFUSED, GAIN_REPLAY } form = ONE_KERNEL;
+    unsigned tf_flags = 0;                // the frame kernel's final TF_* flags
+    int ntaps = 0, chunks_per_frame = 1, syms_per_chunk = 1;
+    bool tii = false, tii_inside = false; // the call adds the TII null symbol; the frame kernel does it itself
+    bool fuse_native = false, fuse_post = false;   // the integer format is stored by the frame kernel / by the resampler
+    bool fuse_poly = false;               // the predistorter rides in the resampler's store
+    size_t piece = 0;                     // the hand-over FIRFilter -> Resampler runs in pieces of this many frames (0: one piece)
+    // bytes of each per-lane scratch buffer the call reserves (the CFR statistics: the caller's set, or cfr_tmp for an
+    // internal run), and their sum
+    struct Scratch {
+        size_t d_a = 0, d_b = 0, d_fmt = 0, d_gains = 0, d_gain1 = 0, cfr_counts = 0, cfr_mer = 0, cfr_papr = 0, cfr_tmp = 0;
+    } scratch;
+    size_t scratch_bytes = 0;
+};
+ChainPlan plan_chain(const dabgpu_ctx *c, bool from_bits, size_t n_frames, unsigned mask, bool apply_format = true,
+                     bool keep_stats = true);
+unsigned normalised_mask(const Settings &st, unsigned mask);
 int auto_chunks(const dabgpu_ctx *c, size_t n_frames);
-int run_symbols(int nsym, int chunks, bool lookahead);
 bool is_pow2(size_t x);
-bool resampler_fast_ratio(const dabgpu_ctx *c);
 const char *resampler_ratio_error(int N, size_t in_rate, size_t out_rate);
 int check_resampler(dabgpu_ctx *c);
 int run_resampler(dabgpu_ctx *c, const float2 *d_in, size_t total, float2 *d_out, hipStream_t s, bool fuse_poly = false,
                   unsigned long long *s16_clipped = nullptr);
 int run_poly(dabgpu_ctx *c, const float2 *d_in, size_t n, float2 *d_out, hipStream_t s);
-size_t out_samples_per_frame(const dabgpu_ctx *c, unsigned mask, size_t L, size_t M);
-size_t bytes_per_sample(int fmt);
-int fused_ntaps(const dabgpu_ctx *c);
 int tii_carrier_set(int mode, int comb, int pattern, std::vector<uint8_t> &acp);
-int run_native(dabgpu_ctx *c, const void *d_in, bool from_bits, size_t n_frames, unsigned mask, bool windowed,
-               float2 *native_out, size_t native, float *gain1, hipStream_t s, bool keep_stats = true,
-               unsigned long long *s16_clipped = nullptr, const float2 *tii_seg = nullptr, bool *tii_done = nullptr,
-               int fused_fmt = DABGPU_FMT_S16);
-int run_chain(dabgpu_ctx *c, const void *d_in, bool from_bits, size_t n_frames, unsigned mask, void *d_out_v, size_t out_cap,
-              size_t *out_bytes, hipStream_t s, bool apply_format = true, int lane = 0);
+int run_chain(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, void *d_out_v, size_t out_cap, size_t *out_bytes,
+              hipStream_t s, bool apply_format = true, int lane = 0);
 
 // host-pointer stage wrapper: H2D, launch, D2H on the context stream
 struct HostIO {

@@ -765,3 +765,42 @@ def test_random_operation_sequences_on_three_lanes_equal_the_serial_context(pkg,
         assert bool((_u32(a) == _u32(b)).all()) if a.dtype == torch.complex64 else bool((a == b).all()), j
     # ... and the work was real: the outputs are not the zeros they were allocated as
     assert sum(int(bool(o.view(torch.uint8).any())) for o in results[3]) >= len(results[3]) - 1
+
+
+@pytest.mark.parametrize("case", ["gain_replay_s16_poly", "mode3_101_taps"])
+def test_calls_whose_scratch_exceeds_the_lane_bound_stay_on_lane_0(pkg, case):
+    """A call rotates over the lanes only while the per-lane scratch IT reserves stays within kLaneScratchBytes (256 MiB):
+    the bound is the call's own plan, not an estimate.  Sizes per frame, from the chain's plan (arithmetic, bytes):
+      gain_replay_s16_poly (Mode I; gain mode var by the reference's recurrence, s16, GAIN | FIR | POLY): the symbols in
+        front of the guard kernel 77 x 2048 x 8, the native-rate stream in front of the predistorter and the complexf stream in
+        front of FormatConverter 196608 x 8 each, 77 multipliers x 4 = 4 407 604: 282 MB at 64 frames (a two-buffer estimate says
+        201 MB), 71 MB at 16;
+      mode3_101_taps (Mode III, GAIN | FIR with a filter that fits the fused kernel's tap limit but not the cyclic prefix of
+        63 samples): the symbols in front of the guard / FIRFilter kernel 154 x 256 x 8 = 315 392: 323 MB at 1024 frames, 5 MB at 16.
+    Three calls on the context's own stream: the large ones leave no lane stream beyond the context's own behind, the
+    small ones (the control) create the other two.
+    (The third case the lane bound used to miss on paper, CFR from carriers without FIRFilter, has no separating batch size:
+    it reserves 1.26 MB per frame where the old estimate assumed 3.1 MB -- it rotated less than it may, never more.)"""
+    import torch
+    mode, big, stages = (1, 64, pkg.STAGE_GAIN | pkg.STAGE_FIR | pkg.STAGE_POLY) if case == "gain_replay_s16_poly" \
+        else (3, 1024, pkg.STAGE_GAIN | pkg.STAGE_FIR)
+    for B, lanes_created in ((big, 1), (16, 3)):
+        md = pkg.Modulator(mode=mode, max_frames=B)
+        try:
+            md.set_gain(pkg.GAIN_VAR, 1.0, 1.0, 4.0)
+            if case == "gain_replay_s16_poly":
+                md.set_gain_rounding(True)
+                md.set_poly(POLY_AM, POLY_PM)
+                md.set_output_format("s16")
+            else:
+                md.set_fir_taps(np.hanning(101).astype(np.float32) / 50)
+            md.set_lanes(3)
+            d_bits = torch.zeros((B, O.tf_input_bytes(mode)), dtype=torch.uint8, device="cuda")
+            d_out = torch.zeros((B, md.out_samples_per_frame(stages)), dtype=torch.int32 if mode == 1 else torch.complex64,
+                                device="cuda")
+            for _ in range(3):
+                md.chain_dev_queued(d_bits, B, stages, d_out)
+            md.synchronize()
+            assert md.lanes_info()[0] == lanes_created, (case, B, md.lanes_info())
+        finally:
+            md.close()
