@@ -111,7 +111,10 @@ DABGPU_API int dabgpu_set_fir_default_taps(dabgpu_ctx *ctx);
  * one-transform-per-symbol kernel of that chain.) */
 DABGPU_API int dabgpu_set_window_overlap(dabgpu_ctx *ctx, size_t overlap);
 /* Resampler(inputRate, outputRate, resolution = spacing), src/Resampler.cpp:51-112;
- * resets the stream state (prev-input halo and overlap tail).  Built: every ratio L / M (the
+ * resets the stream state at the next *_process call: the halo (the last two hops of native-rate
+ * input, which live in the context's device memory) to zeros and nothing else -- the TII frame
+ * parity is not the Resampler's.  The state is read, installed and computed from outside with
+ * dabgpu_get_stream_state / dabgpu_set_stream_state / dabgpu_chain_seed ("stream state" below).  Built: every ratio L / M (the
  * rates reduced by their gcd) with M a power of two up to the FFT size -- up- AND down-sampling
  * (1.024, 1.536, 2.4, 3.072, 4.096, 6.144, 8.192 ... Msps in Mode I; x2 and x4 have their own
  * faster kernel).  Any other ratio is refused HERE with DABGPU_E_INVALID (the reference's own
@@ -265,8 +268,11 @@ DABGPU_API size_t dabgpu_chain_out_bytes_per_frame(const dabgpu_ctx *ctx, unsign
 
 /* cifPart output (n_frames x tf_input_bytes) -> IQ.  Replaces the sub-graph
  * cifMap .. cifGuard/cifFilter/cifRes/cifPoly of src/DabModulator.cpp:385-419
- * with ONE plugin.  Frames are consecutive frames of one stream (the resampler
- * state carries from frame to frame and from call to call). */
+ * with ONE plugin.  Frames are consecutive frames of one stream: the stream state
+ * (the resampler's halo in the context's device memory, the TII frame parity in the
+ * context) carries from frame to frame and from call to call -- and, through
+ * dabgpu_get_stream_state / dabgpu_set_stream_state / dabgpu_chain_seed below, from
+ * context to context. */
 DABGPU_API int dabgpu_chain_process(dabgpu_ctx *ctx, const uint8_t *bits, size_t n_frames,
                                     unsigned stage_mask, void *iq_out, size_t out_cap,
                                     size_t *out_bytes);
@@ -283,9 +289,61 @@ DABGPU_API int dabgpu_symbols_process_dev(dabgpu_ctx *ctx, const void *d_carrier
 /* Resampler::process -> MemlessPoly::internal_process (cifRes -> cifPoly, src/DabModulator.cpp:403-406) on a native-rate
  * stream that is already in device memory: the tail of the chain by itself.  stage_mask = DABGPU_STAGE_RESAMPLE and / or
  * DABGPU_STAGE_POLY; n_samples complex samples in (a whole number of resampler hops), n_samples * L / M out.  Stateful like
- * the Resampler (the context's halo), asynchronous on `stream`. */
+ * the Resampler: it reads and advances the context's halo, the same one the chain calls and dabgpu_resampler_process use and
+ * dabgpu_get_stream_state returns; asynchronous on `stream`. */
 DABGPU_API int dabgpu_post_process_dev(dabgpu_ctx *ctx, const void *d_native, size_t n_samples, unsigned stage_mask,
                                        void *d_iq, size_t out_cap, size_t *out_bytes, void *stream);
+
+/* ---- stream state: one resampled stream checkpointed, moved, or split over contexts ---------------------------------- *
+ * A chain call with DABGPU_STAGE_RESAMPLE (at a ratio other than 1) reads and leaves two pieces of stream state:
+ *   - the Resampler's halo: the last rs_nin = 2 x FFT size native-rate INPUT samples, i.e. two hops (the overlap-add sits in
+ *     front of the forward transform; reference: the input window it keeps, src/Resampler.cpp:142-147, :188-191);
+ *   - the TII frame parity (TII::m_insert, src/TII.cpp:226-242), which every chain call from coded bits advances.
+ * The blob below is exactly that, in HOST memory, self-describing (all fields little endian, as the host has them):
+ *     offset  0  uint32  magic        DABGPU_STREAM_STATE_MAGIC ("DGSS")
+ *             4  uint32  version      DABGPU_STREAM_STATE_VERSION
+ *             8  uint32  mode         transmission mode 1..4
+ *            12  uint32  tii_insert   1: the next frame of the stream is one that carries TII
+ *            16  uint64  rs_in        the rates of dabgpu_set_resampler
+ *            24  uint64  rs_out
+ *            32  uint32  rs_nin       complex samples that follow: 2 x FFT size, or 0 at equal rates (no Resampler in the chain)
+ *            36  uint32  reserved     0
+ *            40  rs_nin x (float re, float im): what the next call reads as its halo, oldest sample first
+ * (Which of the library's two halo buffers is current never shows.  The symbol index of the CFR statistics' MER measurement,
+ * src/OfdmGenerator.cpp:198, is a statistic of the context, not stream state: it is not carried.)
+ * dabgpu_stream_state_bytes: the size of the blob for the settings as they stand.
+ * dabgpu_get_stream_state: waits for the context, as dabgpu_set_lanes does, then describes the stream after everything queued
+ *   on it so far (chain calls, dabgpu_resampler_process, dabgpu_post_process_dev on the context's own stream, the batches of
+ *   dabgpu_chain_submit); *bytes (may be NULL) receives the size; DABGPU_E_CAPACITY when cap is smaller.  A fresh context
+ *   gives a zero halo and tii_insert = 1; after dabgpu_set_resampler the halo is zero again and the parity is where it was.
+ * dabgpu_set_stream_state: waits, then installs the blob.  DABGPU_E_INVALID (with a message) for a NULL argument, a size that
+ *   is not the blob's, a wrong magic or version, and a blob taken in another mode, at another ratio or with another rs_nin.
+ *   A dabgpu_set_resampler after it resets the state as ever.
+ * dabgpu_chain_seed / _dev: leaves the context in the state it would have after frames 0 ... frame_index - 1 of a stream whose
+ *   frame frame_index - 1 has the coded bits `leadin_bits` (one frame, tf_input_bytes), under the settings in force: every
+ *   transmission frame is at least 96 hops long, so that state is a function of the settings, frame_index and that one frame.
+ *   frame_index == 0 is the start of a stream (zero halo, tii_insert = 1; leadin_bits may be NULL).  Otherwise the lead-in
+ *   frame runs through the part of stage_mask in front of the Resampler -- as complexf whatever the output format and gain
+ *   rounding, with the TII parity of frame frame_index - 1 --, its last rs_nin samples become the halo, and tii_insert =
+ *   (frame_index even).  No output; dabgpu_get_cfr_stats, dabgpu_get_num_clipped and dabgpu_debug_last_variant keep describing
+ *   the last real chain call.  Ordered like a chain call with DABGPU_STAGE_RESAMPLE: _dev is asynchronous on `stream` and uses
+ *   the context's scratch; stream == NULL and the host-pointer form go to lane 0, where the resampler chain calls that follow
+ *   go (the host-pointer form has staged the frame when it returns).  At equal rates the call is host-only: it sets the parity.
+ *   A seed that fails leaves halo and parity as they were when no kernel of it was queued; after a failure behind that point
+ *   (a HIP error) the parity is put back, the halo is undefined and the context is to be seeded or set again.
+ *   A context seeded this way produces frames frame_index ... bit for bit as the uninterrupted stream does
+ *   (tests/test_stream_state_gpu.py), which is what lets N contexts take the chunks of one stream in turn without waiting
+ *   for one another (odr-dabmod_amd/streams.py: PartitionedStream; dabmod_file --contexts). */
+#define DABGPU_STREAM_STATE_MAGIC 0x53534744u /* "DGSS" */
+#define DABGPU_STREAM_STATE_VERSION 1u
+#define DABGPU_STREAM_STATE_HEADER_BYTES 40
+DABGPU_API size_t dabgpu_stream_state_bytes(const dabgpu_ctx *ctx);
+DABGPU_API int dabgpu_get_stream_state(dabgpu_ctx *ctx, void *buf, size_t cap, size_t *bytes);
+DABGPU_API int dabgpu_set_stream_state(dabgpu_ctx *ctx, const void *buf, size_t bytes);
+DABGPU_API int dabgpu_chain_seed(dabgpu_ctx *ctx, const uint8_t *leadin_bits, unsigned stage_mask,
+                                 uint64_t frame_index);
+DABGPU_API int dabgpu_chain_seed_dev(dabgpu_ctx *ctx, const void *d_leadin_bits, unsigned stage_mask,
+                                     uint64_t frame_index, void *stream);
 
 /* ---- batches in flight inside one context --------------------------------- *
  * The reference overlaps its stages by handing frame i + 1 to a stage while frame i is still inside it
@@ -297,7 +355,7 @@ DABGPU_API int dabgpu_post_process_dev(dabgpu_ctx *ctx, const void *d_native, si
  *     order, for work queued on `stream` after dabgpu_stream_wait_for(ctx, stream);
  *   - inputs produced on a stream of the caller's are ordered in front with dabgpu_wait_for_stream(ctx, stream);
  *   - calls that carry stream state (DABGPU_STAGE_RESAMPLE at a ratio other than 1) and batches of more than 2048 frames
- *     stay on lane 0, in call order;
+ *     stay on lane 0, in call order (to overlap such calls, split the stream over contexts: "stream state" above);
  *   - a call with an explicit stream argument is what it always was: asynchronous on that stream, the context's scratch.
  *     Do not mix the two on one context without a dabgpu_synchronize in between.
  * dabgpu_set_lanes: 1 ... 4 (default 3: measured best at 1 ... 64 frames per call, tools/experiments/exp_r05.py lanes; 1 = every call on the one context stream, in order).  Waits for the context. */

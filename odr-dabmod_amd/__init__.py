@@ -36,6 +36,8 @@ EXPORTS = [
     "dabgpu_set_fir_boundary_mode", "dabgpu_debug_last_variant", "dabgpu_debug_trace",
     "dabgpu_set_lanes", "dabgpu_wait_for_stream", "dabgpu_stream_wait_for", "dabgpu_set_handover_frames",
     "dabgpu_post_process_dev", "dabgpu_debug_lanes", "dabgpu_set_gain_rounding",
+    "dabgpu_stream_state_bytes", "dabgpu_get_stream_state", "dabgpu_set_stream_state",
+    "dabgpu_chain_seed", "dabgpu_chain_seed_dev",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -152,6 +154,12 @@ def load_library():
     lib.dabgpu_stream_wait_for.argtypes = [vp, vp]
     lib.dabgpu_post_process_dev.argtypes = [vp, vp, sz, u, vp, sz, szp, vp]
     lib.dabgpu_fir_inverse_design.argtypes = [C.POINTER(C.c_float), sz, C.POINTER(C.c_float), C.POINTER(C.c_double)]
+    lib.dabgpu_stream_state_bytes.argtypes = [vp]
+    lib.dabgpu_stream_state_bytes.restype = sz
+    lib.dabgpu_get_stream_state.argtypes = [vp, vp, sz, szp]
+    lib.dabgpu_set_stream_state.argtypes = [vp, vp, sz]
+    lib.dabgpu_chain_seed.argtypes = [vp, vp, u, C.c_uint64]
+    lib.dabgpu_chain_seed_dev.argtypes = [vp, vp, u, C.c_uint64, vp]
     _lib = lib
     return lib
 
@@ -537,6 +545,51 @@ class Modulator:
         self._chk(self._lib.dabgpu_format_process_dev(self._h, d_in.data_ptr(), n, code, d_out.data_ptr(),
                                                       d_out.numel() * d_out.element_size(), C.byref(ob), None, None))
         return ob.value
+
+    # ---- stream state: the resampler's halo and the TII frame parity (include/dabgpu.h, "stream state") ----
+    def stream_state(self, capacity=None):
+        """The stream after everything queued on the context so far, as the self-describing blob of dabgpu_get_stream_state
+        (bytes).  Waits for the context.  `capacity`: the buffer to offer instead of dabgpu_stream_state_bytes()."""
+        cap = self._lib.dabgpu_stream_state_bytes(self._h) if capacity is None else int(capacity)
+        buf = C.create_string_buffer(max(cap, 1))
+        n = C.c_size_t()
+        self._chk(self._lib.dabgpu_get_stream_state(self._h, buf, cap, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def set_stream_state(self, blob):
+        """Install a blob of stream_state(), taken on a context with the same mode and resampling ratio.  Waits."""
+        blob = bytes(blob)
+        self._chk(self._lib.dabgpu_set_stream_state(self._h, blob, len(blob)))
+
+    def seed(self, bits, stages, frame_index):
+        """The state after frames 0 ... frame_index - 1 of a stream whose frame frame_index - 1 has the coded bits `bits`
+        (one frame, host array; None with frame_index 0, the start of a stream): dabgpu_chain_seed.  No output."""
+        p = None
+        if bits is not None:
+            bits = np.ascontiguousarray(bits, np.uint8).reshape(-1)
+            if bits.size != self.geometry["tf_input_bytes"]:
+                raise DabGpuError("seed: the lead-in is one frame of coded bits")
+            p = bits.ctypes.data
+        self._chk(self._lib.dabgpu_chain_seed(self._h, p, stages, int(frame_index)))
+
+    def seed_dev(self, d_bits, stages, frame_index, stream=None, queued=False):
+        """Same with the lead-in frame in device memory (a torch uint8 tensor, or None with frame_index 0), asynchronous on
+        the stream -- a HIP stream handle as for chain_dev, torch's current stream by default; queued=True: the context's own
+        stream (lane 0, behind and in front of the resampler chain calls queued there), without waiting for the device.  (The
+        first seed after a change of the TII, filter, window or CFR settings builds the cached TII segment, as the first
+        chain call would: that one waits for the context's lanes.)"""
+        import torch
+        if d_bits is not None and d_bits.numel() != self.geometry["tf_input_bytes"]:
+            raise DabGpuError("seed: the lead-in is one frame of coded bits")
+        if queued:
+            s = None
+        else:
+            where = d_bits if d_bits is not None else torch.empty(0, device=torch.device("cuda", self.device))
+            s = self._stream_handle(where, stream)
+        self._chk(self._lib.dabgpu_chain_seed_dev(self._h, d_bits.data_ptr() if d_bits is not None else None, stages,
+                                                  int(frame_index), s))
+        if not s and not queued:
+            self.synchronize()
 
     def post_process_dev(self, d_native, stages, d_out, stream=None):
         """cifRes -> cifPoly on a native-rate stream in device memory (stages: STAGE_RESAMPLE and / or STAGE_POLY)."""

@@ -470,6 +470,23 @@ int ensure_tii_segment(dabgpu_ctx *c, unsigned mask, hipStream_t s)
     return DABGPU_OK;
 }
 
+// The native-rate stream of a call with the TII null symbol in it (src/TII.cpp:226-242: every other frame, from
+// c->tii_insert on): run_native, with the cached segment built first and added afterwards where the frame kernel does not
+// add it itself.  What run_chain runs in front of the tail -- and what dabgpu_chain_seed runs on the lead-in frame.
+int run_native_tii(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, float2 *native_out, hipStream_t s)
+{
+    int rc;
+    if (p.tii) {
+        if ((rc = ensure_tii_segment(c, p.mask, s))) return rc;
+        HIPCHK(c, c->d_gain1.reserve(p.scratch.d_gain1));
+    }
+    if ((rc = run_native(c, p, d_in, native_out, s))) return rc;
+    if (p.tii && !p.tii_inside)
+        HIPCHK(c, launch_tii_add(native_out, p.native, (const float2 *)c->d_tii_frame.p, c->tii_seg_len,
+                                 p.scratch.d_gain1 ? (const float *)c->d_gain1.p : nullptr, c->tii_insert ? 1 : 0, p.n_frames, s));
+    return DABGPU_OK;
+}
+
 // The tail of the chain, cifRes -> cifPoly (src/DabModulator.cpp:403-419), on n samples at d_in into d_out (n_out samples):
 // the polynomial predistorter is an epilogue of the x2 / x4 resampler's store (fuse_poly; LUT mode is not), otherwise a kernel
 // of its own behind it, reading the resampled stream from d_b (d_b_bytes: what the caller's plan sized it to).
@@ -556,14 +573,7 @@ int run_chain(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, void *d_out_v
         }
     } else {
         float2 *native_out = post ? (float2 *)c->d_a.p : d_out;       // where the native-rate stream goes
-        if (p.tii) {
-            if ((rc = ensure_tii_segment(c, p.mask, s))) return rc;
-            HIPCHK(c, c->d_gain1.reserve(p.scratch.d_gain1));
-        }
-        if ((rc = run_native(c, p, d_in, native_out, s))) return rc;
-        if (p.tii && !p.tii_inside)
-            HIPCHK(c, launch_tii_add(native_out, native, (const float2 *)c->d_tii_frame.p, c->tii_seg_len,
-                                     p.scratch.d_gain1 ? (const float *)c->d_gain1.p : nullptr, c->tii_insert ? 1 : 0, n_frames, s));
+        if ((rc = run_native_tii(c, p, d_in, native_out, s))) return rc;
         if (post && (rc = run_tail(c, p.mask, p.fuse_poly, native_out, n_frames * native, d_out, n_frames * per, p.scratch.d_b, s,
                                    p.fuse_post ? clip : nullptr)))
             return rc;

@@ -501,7 +501,7 @@ void dabgpu_destroy(dabgpu_ctx *c)
         if (l.stream) (void)hipStreamSynchronize(l.stream);
     for (DevBuf *b : {&c->d_twiddle, &c->d_src, &c->d_dst, &c->d_phq, &c->d_mag, &c->d_taps, &c->d_firh, &c->d_eqg,
                       &c->d_window, &c->d_coef, &c->d_rs_window, &c->d_rs_tw_in, &c->d_rs_tw_out,
-                      &c->d_rs_halo, &c->d_rs_tw_s, &c->d_rs_tw_l, &c->d_a, &c->d_b, &c->d_c, &c->d_in, &c->d_out, &c->d_count, &c->d_fmt, &c->d_clip, &c->d_phase,
+                      &c->d_rs_halo, &c->d_rs_tw_s, &c->d_rs_tw_l, &c->d_a, &c->d_b, &c->d_c, &c->d_in, &c->d_out, &c->d_count, &c->d_fmt, &c->d_clip, &c->d_phase, &c->d_seed,
                       &c->d_acp, &c->d_tii_car, &c->d_tii_frame, &c->d_gain1, &c->d_gains, &c->d_cic,
                       &c->d_cfr_counts, &c->d_cfr_mer, &c->d_cfr_papr, &c->d_cfr_tmp})
         b->release();
@@ -515,6 +515,10 @@ void dabgpu_destroy(dabgpu_ctx *c)
     }
     for (void *h : c->h_out)
         if (h) (void)hipHostFree(h);
+    for (void *h : c->h_seed)
+        if (h) (void)hipHostFree(h);
+    for (hipEvent_t e : c->seed_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto &l : c->lane) {
         if (l.stream) { (void)hipStreamSynchronize(l.stream); (void)hipStreamDestroy(l.stream); }
         if (l.ev) (void)hipEventDestroy(l.ev);

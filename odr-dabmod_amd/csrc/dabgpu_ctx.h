@@ -5,6 +5,7 @@
 //   api_lanes.hip     batches in flight inside one context: lanes (chosen from the plan's scratch total), their ordering,
 //                     submit / collect
 //   api_stages.hip    one host-buffer entry point per reference plugin, FormatConverter, CFR statistics
+//   api_state.hip     the stream state (resampler halo, TII frame parity): read, installed, computed from a lead-in frame
 #pragma once
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
@@ -120,6 +121,12 @@ struct dabgpu_ctx {
     float rs_factor = 1.f;
     // scratch
     dabgpu_api::DevBuf d_a, d_b, d_c, d_in, d_out, d_count, d_fmt, d_clip;
+    // dabgpu_chain_seed: the lead-in frame's coded bits, through two pinned staging frames in turn (the host never waits
+    // for the seed before the last one)
+    dabgpu_api::DevBuf d_seed;
+    void *h_seed[2] = {nullptr, nullptr};
+    hipEvent_t seed_ev[2] = {nullptr, nullptr};
+    unsigned long long seed_seq = 0;
     dabgpu_api::DevBuf d_phase;                        // tool builds only (-DDABGPU_PHASE_TIMING): the frame kernel's per-phase cycle counters
     hipStream_t clip_stream = nullptr;     // stream of the most recent chain call that converted its output
     // TII (f-4): carrier set, the one-frame carrier image and its native-rate response, gain of symbol 1
@@ -297,6 +304,7 @@ int run_resampler(dabgpu_ctx *c, const float2 *d_in, size_t total, float2 *d_out
                   unsigned long long *s16_clipped = nullptr);
 int run_poly(dabgpu_ctx *c, const float2 *d_in, size_t n, float2 *d_out, hipStream_t s);
 int tii_carrier_set(int mode, int comb, int pattern, std::vector<uint8_t> &acp);
+int run_native_tii(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, float2 *native_out, hipStream_t s);
 int run_chain(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, void *d_out_v, size_t out_cap, size_t *out_bytes,
               hipStream_t s, bool apply_format = true, int lane = 0);
 

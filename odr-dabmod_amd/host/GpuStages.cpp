@@ -960,6 +960,26 @@ void DabGpuChain::submit(const void *bits, size_t n_frames)
     m_ctx.check(dabgpu_chain_submit(m_ctx.get(), static_cast<const uint8_t *>(bits), n_frames, stage_mask()));
 }
 
+void DabGpuChain::seed(const void *leadin_bits, uint64_t frame_index)
+{
+    before_frames();            // (the lead-in frame runs under the settings the frames behind it run under)
+    m_ctx.check(dabgpu_chain_seed(m_ctx.get(), static_cast<const uint8_t *>(leadin_bits), stage_mask(), frame_index));
+}
+
+std::vector<uint8_t> DabGpuChain::get_stream_state()
+{
+    std::vector<uint8_t> blob(dabgpu_stream_state_bytes(m_ctx.get()));
+    size_t n = 0;
+    m_ctx.check(dabgpu_get_stream_state(m_ctx.get(), blob.data(), blob.size(), &n));
+    blob.resize(n);
+    return blob;
+}
+
+void DabGpuChain::set_stream_state(const std::vector<uint8_t> &blob)
+{
+    m_ctx.check(dabgpu_set_stream_state(m_ctx.get(), blob.data(), blob.size()));
+}
+
 size_t DabGpuChain::collect(const void **iq)
 {
     size_t n = 0;

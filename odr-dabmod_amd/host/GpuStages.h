@@ -443,6 +443,14 @@ public:
     // Same stream state (resampler halo, TII parity) and the same samples as process() frame by frame.
     void submit(const void *bits, size_t n_frames);
     size_t collect(const void **iq);
+    // One stream over several chains, or a stream moved from one chain to another (include/dabgpu.h, "stream state"):
+    // seed() puts the chain where it would be after frames 0 ... frame_index - 1 of a stream whose frame
+    // frame_index - 1 has the coded bits leadin_bits (one frame; nullptr with frame_index 0, the start of a stream) --
+    // the Resampler's input window (src/Resampler.cpp:142-147,188-191) and the TII frame parity (src/TII.cpp:226-242)
+    // follow from that one frame.  get_stream_state() / set_stream_state() carry the same state as a blob.
+    void seed(const void *leadin_bits, uint64_t frame_index);
+    std::vector<uint8_t> get_stream_state();
+    void set_stream_state(const std::vector<uint8_t> &blob);
     size_t input_bytes_per_frame() const { return m_in_bytes; }
     size_t output_bytes_per_frame() const;
     int process(Buffer *const dataIn, Buffer *dataOut) override;

@@ -21,6 +21,10 @@
 //                        of the equivalent reference graph (GainControl, FIRFilter, MemlessPoly: src/ModPlugin.cpp:90-115)
 //   --reference-gain     gain mode var: the reference's running fp32 recurrence (src/GainControl.cpp:251-340) instead of the
 //                        exact variance (DabGpuChain::Settings::referenceGainRounding)
+//   --contexts N         with --batch B > 1: the batches of the stream go to N chains (1 ... 4, default 1) on the same device in
+//                        turn, batch j to chain j mod N, which is first seeded from the last frame of batch j - 1
+//                        (DabGpuChain::seed): the same bytes as one chain, the chains' kernels side by side
+//                        (N > 1 needs the streaming path: not with --bits-only or --separate-converter)
 #include "Frontend.h"
 #include "GpuStages.h"
 
@@ -41,7 +45,10 @@ namespace {
                          "       [--ofdmwindowing W] [--tii comb,pattern] [--cfr clip,errorclip] [--loop N] [--bits-only]\n"
                          "       [--batch N]   N transmission frames per GPU call, two calls in flight (default 1: frame by frame)\n"
                          "       [--reference-latency]   drop the frames the reference's pipelined stages never emit\n"
-                         "       [--reference-gain]      gain mode var by the reference's running recurrence (bit-equal scalars, slower)\n");
+                         "       [--reference-gain]      gain mode var by the reference's running recurrence (bit-equal scalars, slower)\n"
+                         "       [--contexts N]   with --batch B > 1: split the stream's batches over N = 1 ... 4 chains on the device\n"
+                         "                        (batch j to chain j mod N, seeded from the frame before it; the same bytes as N = 1;\n"
+                         "                        N > 1 not with --bits-only or --separate-converter)\n");
     std::exit(2);
 }
 }  // namespace
@@ -58,6 +65,7 @@ int main(int argc, char **argv)
     bool bits_only = false;
     size_t batch = 1;
     bool reference_latency = false;
+    long contexts = 1;
     try {
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
@@ -92,8 +100,16 @@ int main(int argc, char **argv)
             else if (a == "--batch") batch = std::max<size_t>(1, std::stoul(val()));
             else if (a == "--reference-latency") reference_latency = true;
             else if (a == "--reference-gain") gs.referenceGainRounding = true;
+            else if (a == "--contexts") {
+                const std::string v = val();
+                size_t used = 0;
+                contexts = std::stol(v, &used);
+                if (used != v.size()) usage();
+            }
             else usage();
         }
+        // (several chains take whole batches of the streaming path in turn: nothing to split frame by frame)
+        if (contexts < 1 || contexts > 4 || (contexts > 1 && (batch <= 1 || separate_converter || bits_only))) usage();
 
         InputFileReader reader;
         if (reader.Open(in_path, false) != 0) {
@@ -108,7 +124,11 @@ int main(int argc, char **argv)
         }
 
         std::unique_ptr<EtiFrontend> frontend;
-        std::unique_ptr<DabGpuChain> chain;
+        std::unique_ptr<DabGpuChain> chain;               // the one chain; with --contexts N: chain 0
+        std::vector<std::unique_ptr<DabGpuChain>> more;   // --contexts N: chains 1 ... N - 1
+        auto chain_of = [&](size_t j) -> DabGpuChain * { return j % contexts ? more[j % contexts - 1].get() : chain.get(); };
+        size_t n_batches = 0, n_collected = 0, n_submitted = 0;     // batches queued / written, frames queued
+        std::vector<uint8_t> leadin;              // --contexts N: the last frame of the batch queued last
         std::unique_ptr<FormatConverter> converter;
         Buffer bits, iq, converted;
         uint8_t frame[6144];
@@ -117,13 +137,26 @@ int main(int argc, char **argv)
         std::deque<std::vector<uint8_t>> held;    // --batch with --reference-latency: the frames "inside the pipeline"
         size_t n_out = 0;                         // transmission frames written
         int in_flight = 0;
+        // the oldest batch in flight, in stream order: batch j lives on chain j mod N
         auto drain_one = [&]() {
+            DabGpuChain *ch = chain_of(n_collected++);
             const void *p = nullptr;
-            const size_t n = chain->collect(&p);
-            n_out += n / chain->output_bytes_per_frame();
-            if (format != "complexf") clipped += chain->get_num_clipped_samples();
+            const size_t n = ch->collect(&p);
+            n_out += n / ch->output_bytes_per_frame();
+            if (format != "complexf") clipped += ch->get_num_clipped_samples();
             out.write(static_cast<const char *>(p), static_cast<std::streamsize>(n));
             --in_flight;
+        };
+        // two batches in flight per chain; the owning chain starts from the state behind the frame before its batch
+        auto submit_batch = [&](size_t frames) {
+            if (in_flight == 2 * contexts) drain_one();
+            DabGpuChain *ch = chain_of(n_batches++);
+            if (contexts > 1) ch->seed(n_submitted ? leadin.data() : nullptr, n_submitted);
+            ch->submit(pending.data(), frames);
+            if (contexts > 1) leadin.assign(pending.begin() + (frames - 1) * ch->input_bytes_per_frame(),
+                                            pending.begin() + frames * ch->input_bytes_per_frame());
+            n_submitted += frames;
+            ++in_flight;
         };
         for (int l = 0; l < loops; ++l) {
             if (l && reader.Open(in_path, false) != 0) return 1;
@@ -150,6 +183,7 @@ int main(int argc, char **argv)
                         gs.outputFormat = format;
                         gs.maxBatchFrames = batch;
                         chain.reset(new DabGpuChain(gs));
+                        for (long k = 1; k < contexts; ++k) more.emplace_back(new DabGpuChain(gs));
                         pending.reserve(batch * bits.getLength());
                     }
                     const uint8_t *b = static_cast<const uint8_t *>(bits.getData());
@@ -162,9 +196,7 @@ int main(int argc, char **argv)
                     } else
                     pending.insert(pending.end(), b, b + bits.getLength());
                     if (pending.size() == batch * chain->input_bytes_per_frame()) {
-                        if (in_flight == 2) { drain_one(); }
-                        chain->submit(pending.data(), batch);
-                        ++in_flight;
+                        submit_batch(batch);
                         pending.clear();
                     }
                     continue;
@@ -197,11 +229,7 @@ int main(int argc, char **argv)
         if (chain && batch > 1 && !separate_converter) {
             // the tail: a last, shorter batch, then whatever is still in flight, in order
             const size_t rest = pending.size() / chain->input_bytes_per_frame();
-            if (rest) {
-                if (in_flight == 2) drain_one();
-                chain->submit(pending.data(), rest);
-                ++in_flight;
-            }
+            if (rest) submit_batch(rest);
             while (in_flight) drain_one();
         }
         if (bits_only) n_out = n_tf;

@@ -1,11 +1,80 @@
 """Multi-GPU harness: one process per GPU, each modulating its own independent
 stream of transmission frames (frames are independent units, so the
-path shards with NO data-path collective).  torch.distributed (backend "nccl" =
+path shards with NO data-path collective) -- or, with partition_chunks / my_chunks /
+PartitionedStream, its share of ONE stream, whose state in front of a chunk follows
+from the one frame before it.  torch.distributed (backend "nccl" =
 RCCL on ROCm, "gloo" in CPU tests) is used only to bracket the timed region and
 to combine the ranks' clocks."""
 import os
 import sys
 import time
+
+import numpy as np
+
+
+def partition_chunks(n_frames, chunk, parts):
+    """ONE stream of n_frames transmission frames cut into chunks of `chunk` frames (the last may be short), chunk j going
+    to part j mod parts: per part the list of (start, stop) it modulates, in stream order.  The owner of a chunk needs no
+    other part's result: its stream state in front of frame `start` follows from frame start - 1 alone (the lead-in frame
+    of Modulator.seed; none for start == 0)."""
+    n_frames, chunk, parts = int(n_frames), int(chunk), int(parts)
+    if n_frames < 0 or chunk < 1 or parts < 1:
+        raise ValueError("partition_chunks: n_frames >= 0, chunk >= 1, parts >= 1")
+    out = [[] for _ in range(parts)]
+    for j, start in enumerate(range(0, n_frames, chunk)):
+        out[j % parts].append((start, min(start + chunk, n_frames)))
+    return out
+
+
+class PartitionedStream:
+    """One stream split over several contexts (on one GPU or on several): chunk j of the stream goes to context j mod N,
+    which first computes its own starting state from the chunk's lead-in frame (Modulator.seed_dev) and so waits for no
+    other context.  All contexts must have been given the same settings by the caller.  Every context runs on one lane (a
+    chain call with the Resampler uses lane 0 only, and so does the seed in front of it); contexts in one process share the
+    runtime's hardware queues, whose number is the process's to choose."""
+
+    def __init__(self, modulators):
+        self.mods = list(modulators)
+        if not self.mods:
+            raise ValueError("PartitionedStream: at least one context")
+        for md in self.mods:
+            md.set_lanes(1)
+
+    def modulate(self, bits, stages, chunk, out=None):
+        """bits: n_frames x tf_input_bytes coded bits of consecutive frames, frame 0 the start of the stream -- a numpy
+        array, or a torch uint8 tensor on the GPU (then `out`, if given, is the device tensor to fill, and the result is
+        one).  Queues every seed and every chunk before it waits for anything; returns the frames in stream order, the
+        bytes one context gives for the whole stream."""
+        import torch
+        md0 = self.mods[0]
+        per = md0.geometry["tf_input_bytes"]
+        host = not isinstance(bits, torch.Tensor)
+        dev = torch.device("cuda", md0.device)
+        d_bits = (torch.from_numpy(np.ascontiguousarray(bits, np.uint8).reshape(-1, per)).to(dev) if host
+                  else bits.reshape(-1, per))
+        n = d_bits.shape[0]
+        dt = np.dtype(getattr(md0, "_out_dtype", np.complex64))
+        per_out = md0.out_bytes_per_frame(stages) // dt.itemsize
+        tdt = {"complex64": torch.complex64, "int16": torch.int16, "uint8": torch.uint8, "int8": torch.int8}[dt.name]
+        d_out = out if (out is not None and not host) else torch.empty((n, per_out), dtype=tdt, device=dev)
+        if d_out.numel() != n * per_out or d_out.dtype != tdt or not d_out.is_contiguous():
+            raise ValueError("PartitionedStream: output tensor does not match (%s, %d elements, contiguous)" % (tdt, n * per_out))
+        d_out = d_out.reshape(n, per_out)
+        torch.cuda.current_stream(dev).synchronize()          # (the input is in place before any context reads it)
+        chunks = sorted((c, i) for i, part in enumerate(partition_chunks(n, chunk, len(self.mods))) for c in part)
+        for (start, stop), i in chunks:
+            md = self.mods[i]
+            md.seed_dev(d_bits[start - 1] if start else None, stages, start, queued=True)
+            md.chain_dev_queued(d_bits[start:stop], stop - start, stages, d_out[start:stop])
+        for md in self.mods:
+            md.synchronize()
+        if not host:
+            return d_out
+        res = d_out.cpu().numpy()
+        if out is not None:
+            np.copyto(out.reshape(res.shape), res)
+            return out.reshape(res.shape)
+        return res
 
 
 class StreamGroup:
@@ -69,6 +138,11 @@ class StreamGroup:
         t = self._torch.tensor([int(value)], dtype=self._torch.int64, device=dev)
         self._dist.all_reduce(t, op=self._dist.ReduceOp.MIN)
         return int(t.item())
+
+    def my_chunks(self, n_frames, chunk):
+        """This rank's chunks of ONE stream split over the ranks (partition_chunks over rank and world size): each rank
+        seeds its context from frame start - 1 and modulates [start, stop) without hearing from the others."""
+        return partition_chunks(n_frames, chunk, self.world)[self.rank]
 
     def stream_seed(self, base=42):
         """Every rank modulates a different stream (different synthetic input)."""
