@@ -402,6 +402,73 @@ DABGPU_API int dabgpu_debug_last_variant(dabgpu_ctx *ctx, char *buf, size_t cap)
  * mutex). */
 DABGPU_API int dabgpu_debug_trace(dabgpu_ctx *ctx, int enable);
 
+/* ---- the front-end on the device: ETI(NI) frames -> coded bits -> IQ ------------------------------------------------- *
+ * The sub-graph in front of the chain (the CPU classes of odr-dabmod_amd/host/Frontend.h) as two kernels:
+ * energy dispersal, the K = 7 mother code and puncturing per (ETI frame, FIC or sub-channel); then the 16-frame time
+ * interleaver, CIF assembly over the padding sequence and the BlockPartitioner layout per output word.  Pure integer work:
+ * the same bytes as the CPU front-end (tests/test_gpu_frontend_gpu.py).
+ *
+ * dabgpu_frontend_describe: host only, no context, no device.  Reads FC and the STC words of one raw 6144-byte ETI(NI) frame
+ *   and fills the layout below.  DABGPU_E_INVALID, with the message of the CPU class that throws (dabgpu_last_error(NULL),
+ *   per thread), for: FICF = 0 (EtiReader::loadEtiData); a protection profile without rules or without a size
+ *   (SubchannelSource); a punctured size that is neither 8 x CU nor 8 x CU - 1 (PuncturingEncoder::process); a sub-channel
+ *   that ends behind CU 864 (FrameMultiplexer::process); payload that overruns the 6144 bytes (EtiReader).
+ * Stream state: the time interleaver reads the last fifteen punctured frames of the stream; they live in the context's device
+ *   memory, zero after configure / reset, like the Resampler's halo.  The stream-state blob does NOT carry them (a seed
+ *   would need fifteen lead-in ETI frames, not one transmission frame): dabgpu_chain_seed / _dev after a
+ *   dabgpu_frontend_configure is refused.
+ * All calls below take whole transmission frames (n_eti a multiple of 4 / 1 / 1 / 2 in modes I ... IV; at most max_frames
+ *   transmission frames per call), and the frame phase FP of a call's first frame must be a multiple of that count.  Finding
+ *   the start of the stream -- the first frame with FP = 0, src/DabMod.cpp:684-693 -- stays with the caller.  The host-pointer
+ *   entries compare byte 5 (FICF, NST), the MID bits and the STC words of every frame with the configured layout: a
+ *   difference is DABGPU_E_INVALID ("FrameMultiplexer detected ...", as the reference throws on a multiplex reconfiguration),
+ *   nothing is queued and the history stays as it was, as after every call that fails before its first launch.  They carry
+ *   stream state, so they stay on lane 0 in call order, like resampler chains. */
+#define DABGPU_FE_MAX_SUBCH 127 /* NST is a 7-bit field */
+#define DABGPU_FE_MAX_RULES 4
+typedef struct {
+    uint32_t groups;  /* 4-byte groups of mother-code output the rule covers (PuncturingRule::length() / 4) */
+    uint32_t pattern; /* 32-bit puncturing vector, MSB first */
+} dabgpu_fe_rule;
+typedef struct {
+    uint32_t sad, stl, tpl; /* start address in capacity units, length in 64-bit words, protection (6 bits) */
+    uint32_t framesize;     /* 8 x STL: bytes of payload per ETI frame */
+    uint32_t cu;            /* capacity units of 64 bits in the CIF */
+    uint32_t padding_byte;  /* 1: the punctured size is 8 x CU - 1 (EN 300 401 table 31), one zero byte follows */
+    uint32_t offset;        /* of the payload inside the 6144-byte frame */
+    uint32_t n_rules;
+    dabgpu_fe_rule rule[DABGPU_FE_MAX_RULES];
+} dabgpu_fe_subch;
+typedef struct {
+    uint32_t mode;       /* 1..4, from MID (0 reads as Mode IV) */
+    uint32_t fic_bytes;  /* 96, or 128 in Mode III */
+    uint32_t fic_offset; /* 12 + 4 x NST */
+    uint32_t fic_n_rules;
+    dabgpu_fe_rule fic_rule[DABGPU_FE_MAX_RULES];
+    uint32_t tail_bytes, tail_pattern; /* the tail rule of every unit: 3 bytes, 0xcccccc */
+    uint32_t nst;
+    dabgpu_fe_subch sub[DABGPU_FE_MAX_SUBCH]; /* in STC order */
+} dabgpu_fe_layout;
+DABGPU_API int dabgpu_frontend_describe(const uint8_t frame[6144], dabgpu_fe_layout *out);
+/* describes `frame6144`, checks its mode against the context's, uploads the tables, zeroes the history; waits for the context */
+DABGPU_API int dabgpu_frontend_configure(dabgpu_ctx *ctx, const uint8_t *frame6144);
+/* zero history, layout kept; waits for the context */
+DABGPU_API int dabgpu_frontend_reset(dabgpu_ctx *ctx);
+/* n_eti raw ETI(NI) frames (n_eti x 6144 bytes) -> the chain's input, n_eti / (4|1|1|2) x tf_input_bytes: the sub-graph
+ * cifFicPrbs ... cifPart of src/DabModulator.cpp:281-385 (PrbsGenerator, ConvEncoder, PuncturingEncoder, TimeInterleaver,
+ * FrameMultiplexer, BlockPartitioner) */
+DABGPU_API int dabgpu_frontend_process(dabgpu_ctx *ctx, const uint8_t *eti, size_t n_eti, void *bits, size_t out_cap,
+                                       size_t *out_bytes);
+/* same, device-resident and asynchronous on `stream`.  This entry CANNOT look at the frames: layout, FICF and FP are the
+ * caller's to check (a frame of another layout gives bytes of no meaning, within the buffers). */
+DABGPU_API int dabgpu_frontend_process_dev(dabgpu_ctx *ctx, const void *d_eti, size_t n_eti, void *d_bits, size_t out_cap,
+                                           size_t *out_bytes, void *stream);
+/* ETI in, IQ out: dabgpu_frontend_process and dabgpu_chain_process in one call; the coded bits never leave the device */
+DABGPU_API int dabgpu_chain_process_eti(dabgpu_ctx *ctx, const uint8_t *eti, size_t n_eti, unsigned stage_mask, void *iq_out,
+                                        size_t out_cap, size_t *out_bytes);
+/* the streaming shape: dabgpu_chain_submit from ETI frames (lane 0, in call order); dabgpu_chain_collect as it is */
+DABGPU_API int dabgpu_chain_submit_eti(dabgpu_ctx *ctx, const uint8_t *eti, size_t n_eti, unsigned stage_mask);
+
 /* wait for everything queued on the context's own stream(s): every lane */
 DABGPU_API int dabgpu_synchronize(dabgpu_ctx *ctx);
 

@@ -38,6 +38,8 @@ EXPORTS = [
     "dabgpu_post_process_dev", "dabgpu_debug_lanes", "dabgpu_set_gain_rounding",
     "dabgpu_stream_state_bytes", "dabgpu_get_stream_state", "dabgpu_set_stream_state",
     "dabgpu_chain_seed", "dabgpu_chain_seed_dev",
+    "dabgpu_frontend_describe", "dabgpu_frontend_configure", "dabgpu_frontend_reset", "dabgpu_frontend_process",
+    "dabgpu_frontend_process_dev", "dabgpu_chain_process_eti", "dabgpu_chain_submit_eti",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -85,6 +87,25 @@ class _Geometry(C.Structure):
                 ("spacing", C.c_int), ("null_size", C.c_int), ("sym_size", C.c_int),
                 ("tf_input_bytes", C.c_size_t), ("tf_samples", C.c_size_t)]
 
+
+class _FeRule(C.Structure):
+    _fields_ = [("groups", C.c_uint32), ("pattern", C.c_uint32)]
+
+
+class _FeSubch(C.Structure):
+    _fields_ = [("sad", C.c_uint32), ("stl", C.c_uint32), ("tpl", C.c_uint32), ("framesize", C.c_uint32),
+                ("cu", C.c_uint32), ("padding_byte", C.c_uint32), ("offset", C.c_uint32), ("n_rules", C.c_uint32),
+                ("rule", _FeRule * 4)]
+
+
+class _FeLayout(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("fic_bytes", C.c_uint32), ("fic_offset", C.c_uint32), ("fic_n_rules", C.c_uint32),
+                ("fic_rule", _FeRule * 4), ("tail_bytes", C.c_uint32), ("tail_pattern", C.c_uint32), ("nst", C.c_uint32),
+                ("sub", _FeSubch * 127)]
+
+
+ETI_FRAME_BYTES = 6144
+CIFS_PER_FRAME = {1: 4, 2: 1, 3: 1, 4: 2}      # ETI frames per transmission frame
 
 _lib = None
 
@@ -160,6 +181,13 @@ def load_library():
     lib.dabgpu_set_stream_state.argtypes = [vp, vp, sz]
     lib.dabgpu_chain_seed.argtypes = [vp, vp, u, C.c_uint64]
     lib.dabgpu_chain_seed_dev.argtypes = [vp, vp, u, C.c_uint64, vp]
+    lib.dabgpu_frontend_describe.argtypes = [vp, C.POINTER(_FeLayout)]
+    lib.dabgpu_frontend_configure.argtypes = [vp, vp]
+    lib.dabgpu_frontend_reset.argtypes = [vp]
+    lib.dabgpu_frontend_process.argtypes = [vp, vp, sz, vp, sz, szp]
+    lib.dabgpu_frontend_process_dev.argtypes = [vp, vp, sz, vp, sz, szp, vp]
+    lib.dabgpu_chain_process_eti.argtypes = [vp, vp, sz, u, vp, sz, szp]
+    lib.dabgpu_chain_submit_eti.argtypes = [vp, vp, sz, u]
     _lib = lib
     return lib
 
@@ -440,6 +468,90 @@ class Modulator:
         self._chk(self._lib.dabgpu_chain_process(self._h, bits.ctypes.data, n, stages,
                                                  out.ctypes.data, out.nbytes, C.byref(ob)))
         return out.reshape(n, per_out)
+
+    # ---- the front-end on the device: ETI(NI) frames -> coded bits -> IQ (include/dabgpu.h) ----
+    @staticmethod
+    def _eti(eti):
+        eti = np.ascontiguousarray(eti, np.uint8).reshape(-1)
+        if eti.size % ETI_FRAME_BYTES:
+            raise DabGpuError("frontend: ETI frames are 6144 bytes")
+        return eti, eti.size // ETI_FRAME_BYTES
+
+    @staticmethod
+    def frontend_describe(frame):
+        """The layout of one raw ETI(NI) frame (host only: needs the library, no device): a dictionary of mode, fic_bytes,
+        fic_offset, fic_rules [(groups, pattern)], tail (bytes, pattern), nst and, per sub-channel in STC order, sad, stl,
+        tpl, framesize, cu, padding_byte, offset, rules.  Raises DabGpuError with the message of the CPU class that refuses
+        the frame."""
+        lib = load_library()
+        frame = np.ascontiguousarray(frame, np.uint8).reshape(-1)
+        if frame.size != ETI_FRAME_BYTES:
+            raise DabGpuError("frontend: ETI frames are 6144 bytes")
+        lay = _FeLayout()
+        if lib.dabgpu_frontend_describe(frame.ctypes.data, C.byref(lay)) != 0:
+            raise DabGpuError(lib.dabgpu_last_error(None).decode())
+        rules = lambda r, n: [(int(r[i].groups), int(r[i].pattern)) for i in range(n)]  # noqa: E731
+        subs = []
+        for i in range(lay.nst):
+            s = lay.sub[i]
+            d = {k: int(getattr(s, k)) for k in ("sad", "stl", "tpl", "framesize", "cu", "padding_byte", "offset")}
+            d["rules"] = rules(s.rule, s.n_rules)
+            subs.append(d)
+        return {"mode": int(lay.mode), "fic_bytes": int(lay.fic_bytes), "fic_offset": int(lay.fic_offset),
+                "fic_rules": rules(lay.fic_rule, lay.fic_n_rules), "tail": (int(lay.tail_bytes), int(lay.tail_pattern)),
+                "nst": int(lay.nst), "subchannels": subs}
+
+    def frontend_configure(self, frame):
+        """Layout from one ETI frame (the stream's first, FP = 0: finding it is the caller's), zero history.  Waits."""
+        frame = np.ascontiguousarray(frame, np.uint8).reshape(-1)
+        if frame.size != ETI_FRAME_BYTES:
+            raise DabGpuError("frontend: ETI frames are 6144 bytes")
+        self._chk(self._lib.dabgpu_frontend_configure(self._h, frame.ctypes.data))
+
+    def frontend_reset(self):
+        """Zero history (the start of a stream), layout kept.  Waits."""
+        self._chk(self._lib.dabgpu_frontend_reset(self._h))
+
+    def eti_to_bits(self, eti):
+        """Host path: whole transmission frames of ETI (n x 6144 uint8) -> (n_tf x tf_input_bytes) coded bits."""
+        eti, n = self._eti(eti)
+        per = self.geometry["tf_input_bytes"]
+        out = np.empty(max(n // CIFS_PER_FRAME[self.geometry["mode"]], 1) * per, np.uint8)
+        ob = C.c_size_t()
+        self._chk(self._lib.dabgpu_frontend_process(self._h, eti.ctypes.data, n, out.ctypes.data, out.nbytes, C.byref(ob)))
+        return out[:ob.value].reshape(-1, per)
+
+    def eti_to_bits_dev(self, d_eti, n_eti, d_bits, stream=None):
+        """Device path on torch uint8 tensors, asynchronous on the stream (as chain_dev).  The frames are not looked at."""
+        s = self._stream_handle(d_eti, stream)
+        ob = C.c_size_t()
+        self._chk(self._lib.dabgpu_frontend_process_dev(self._h, d_eti.data_ptr(), n_eti, d_bits.data_ptr(),
+                                                        d_bits.numel() * d_bits.element_size(), C.byref(ob), s))
+        if not s:
+            self.synchronize()
+        return ob.value
+
+    def chain_eti(self, eti, stages, out=None):
+        """Host path, ETI in, IQ out (chain() with the front-end in front; the coded bits stay on the device)."""
+        eti, n = self._eti(eti)
+        cifs = CIFS_PER_FRAME[self.geometry["mode"]]
+        n_tf = n // cifs
+        dt = np.dtype(getattr(self, "_out_dtype", np.complex64))
+        per_out = self.out_bytes_per_frame(stages) // dt.itemsize
+        if out is None:
+            out = np.empty(n_tf * per_out, dt)
+        if not isinstance(out, np.ndarray) or out.dtype != dt or out.size != n_tf * per_out or not out.flags.c_contiguous:
+            raise DabGpuError("chain: output buffer does not match (dtype %s, %d elements, C-contiguous)" % (dt, n_tf * per_out))
+        flat = out.reshape(-1)
+        ob = C.c_size_t()
+        self._chk(self._lib.dabgpu_chain_process_eti(self._h, eti.ctypes.data, n, stages, flat.ctypes.data, flat.nbytes,
+                                                     C.byref(ob)))
+        return flat.reshape(n_tf, per_out)
+
+    def submit_eti(self, eti, stages):
+        """Asynchronous host path from ETI frames (at most two batches in flight; collect() as for submit())."""
+        eti, n = self._eti(eti)
+        self._chk(self._lib.dabgpu_chain_submit_eti(self._h, eti.ctypes.data, n, stages))
 
     def submit(self, bits, stages):
         """Asynchronous host path: queue a batch (at most two in flight)."""

@@ -172,11 +172,16 @@ int dabgpu_stream_wait_for(dabgpu_ctx *c, void *stream)
     return DABGPU_OK;
 }
 
+}  // extern "C"
+
 // ---- asynchronous host path ------------------------------------------------------
 
-int dabgpu_chain_submit(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, unsigned mask)
+namespace dabgpu_api {
+// dabgpu_chain_submit (src = coded bits) and dabgpu_chain_submit_eti (src = n_frames x cifs-per-frame ETI frames, checked by
+// the caller: the front-end runs in front of the chain on the batch's stream, and the batch stays on lane 0 -- it carries
+// the time interleaver's state)
+int chain_submit(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, unsigned mask, bool eti)
 {
-    CTXCHK(c);
     if (c->slot_count == 2) return fail(c, DABGPU_E_CAPACITY, "two batches are already in flight: collect one first");
     if (n_frames > (size_t)c->max_frames)
         return fail(c, DABGPU_E_CAPACITY, "n_frames exceeds max_frames of the context");
@@ -185,12 +190,14 @@ int dabgpu_chain_submit(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, uns
     const int slot_index = (c->slot_head + c->slot_count) & 1;
     dabgpu_ctx::Slot &sl = c->slot[slot_index];
     // the two batches in flight run on two lanes where the chain carries no stream state: their kernels overlap
-    const bool two_lanes = c->n_lanes > 1 && !(normalised_mask(c->cur, mask) & DABGPU_STAGE_RESAMPLE);
+    const bool two_lanes = !eti && c->n_lanes > 1 && !(normalised_mask(c->cur, mask) & DABGPU_STAGE_RESAMPLE);
     const int lane = two_lanes ? slot_index : 0;
     c->call_lanes = two_lanes ? 2 : 1;                  // (the two batches in flight)
     const ChainPlan p = plan_chain(c, true, n_frames, mask);
     c->call_lanes = 1;
-    const size_t in_bytes = n_frames * tf_in_bytes(c->g), need = p.out_bytes;
+    if (eti && p.error) return fail(c, DABGPU_E_INVALID, p.error);     // (before the front-end advances its history)
+    const size_t bits_bytes = n_frames * tf_in_bytes(c->g), need = p.out_bytes;
+    const size_t in_bytes = eti ? n_frames * (size_t)c->fe_cifs * 6144 : bits_bytes;
     hipStream_t ls;
     if ((rc = lane_stream(c, lane, &ls))) return rc;
     if ((rc = lane_joins_own_stream(c, lane))) return rc;
@@ -222,10 +229,12 @@ int dabgpu_chain_submit(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, uns
         HIPCHK(c, hipHostMalloc(&c->h_out[ho], std::max<size_t>(need, 16), hipHostMallocDefault));
         c->h_out_cap[ho] = need;
     }
-    HIPCHK(c, sl.d_in.reserve(std::max<size_t>(in_bytes, 16)));
+    HIPCHK(c, sl.d_in.reserve(std::max<size_t>(bits_bytes, 16)));
+    if (eti) HIPCHK(c, sl.d_eti.reserve(std::max<size_t>(in_bytes, 16)));
     HIPCHK(c, sl.d_out.reserve(std::max<size_t>(need, 16)));
-    std::memcpy(sl.h_in, bits, in_bytes);                       // 28.8 kB per frame
-    if (in_bytes) HIPCHK(c, hipMemcpyAsync(sl.d_in.p, sl.h_in, in_bytes, hipMemcpyHostToDevice, ls));
+    std::memcpy(sl.h_in, bits, in_bytes);                       // 28.8 kB per frame (24.6 kB as ETI)
+    if (in_bytes) HIPCHK(c, hipMemcpyAsync(eti ? sl.d_eti.p : sl.d_in.p, sl.h_in, in_bytes, hipMemcpyHostToDevice, ls));
+    if (eti && (rc = run_frontend(c, sl.d_eti.p, n_frames * (size_t)c->fe_cifs, sl.d_in.p, ls))) return rc;
     size_t ob = 0;
     {
         TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
@@ -253,6 +262,14 @@ int dabgpu_chain_submit(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, uns
     ++c->slot_count;
     ++c->submit_seq;
     return DABGPU_OK;
+}
+}  // namespace dabgpu_api
+
+extern "C" {
+int dabgpu_chain_submit(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, unsigned mask)
+{
+    CTXCHK(c);
+    return chain_submit(c, bits, n_frames, mask, false);
 }
 
 int dabgpu_chain_collect(dabgpu_ctx *c, const void **iq, size_t *out_bytes)

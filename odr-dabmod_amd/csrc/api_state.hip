@@ -88,6 +88,10 @@ int seed_dev(dabgpu_ctx *c, const void *d_bits, unsigned mask, uint64_t frame_in
     c->tii_insert = (frame_index & 1) == 0;            // TII on frames 0, 2, 4 ... of the stream (src/TII.cpp:226-242)
     return DABGPU_OK;
 }
+// The time interleaver's history (api_frontend.hip) is stream state the blob does not carry and one transmission frame
+// cannot reproduce (it spans fifteen ETI frames): a context with a configured front-end is not seeded.
+const char *const kSeedWithFrontend =
+    "chain seed: the context carries front-end state (dabgpu_frontend_configure) that a seed from one transmission frame cannot reproduce";
 }  // namespace
 
 extern "C" {
@@ -147,6 +151,7 @@ int dabgpu_set_stream_state(dabgpu_ctx *c, const void *buf, size_t bytes)
 int dabgpu_chain_seed_dev(dabgpu_ctx *c, const void *d_leadin_bits, unsigned mask, uint64_t frame_index, void *stream)
 {
     CTXCHK(c);
+    if (c->fe_configured) return fail(c, DABGPU_E_INVALID, kSeedWithFrontend);
     const int rc = apply_settings(c);
     if (rc) return rc;
     // (stream == NULL: lane 0, where the resampler chain calls that follow go -- api_lanes.hip, pick_lane)
@@ -156,6 +161,7 @@ int dabgpu_chain_seed_dev(dabgpu_ctx *c, const void *d_leadin_bits, unsigned mas
 int dabgpu_chain_seed(dabgpu_ctx *c, const uint8_t *leadin_bits, unsigned mask, uint64_t frame_index)
 {
     CTXCHK(c);
+    if (c->fe_configured) return fail(c, DABGPU_E_INVALID, kSeedWithFrontend);
     int rc = apply_settings(c);
     if (rc) return rc;
     const void *d_bits = nullptr;

@@ -6,6 +6,7 @@
 //                     submit / collect
 //   api_stages.hip    one host-buffer entry point per reference plugin, FormatConverter, CFR statistics
 //   api_state.hip     the stream state (resampler halo, TII frame parity): read, installed, computed from a lead-in frame
+//   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ
 #pragma once
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
@@ -127,6 +128,14 @@ struct dabgpu_ctx {
     void *h_seed[2] = {nullptr, nullptr};
     hipEvent_t seed_ev[2] = {nullptr, nullptr};
     unsigned long long seed_seq = 0;
+    // The front-end on the device (api_frontend.hip, frontend.hip).  d_fe_hist is the stream state: [15 + n_eti][6912] punctured,
+    // not yet time-interleaved CIF rows, rows 0 ... 14 = the last fifteen frames of the stream (zero after configure / reset).
+    bool fe_configured = false;
+    dabgpu_fe_layout fe_layout{};
+    int fe_units = 0;                     // FIC + sub-channels: workgroups per ETI frame of the encode kernel
+    int fe_cifs = 1, fe_fic_out = 288;    // ETI frames per transmission frame; punctured FIC bytes per ETI frame
+    std::vector<uint8_t> fe_header;       // bytes 5 ... 8 + 4 NST of the frame the layout was read from (byte 6: MID bits only)
+    dabgpu_api::DevBuf d_fe_prbs, d_fe_units, d_fe_owner, d_fe_hist, d_fe_tmp, d_fe_fic, d_fe_eti;
     dabgpu_api::DevBuf d_phase;                        // tool builds only (-DDABGPU_PHASE_TIMING): the frame kernel's per-phase cycle counters
     hipStream_t clip_stream = nullptr;     // stream of the most recent chain call that converted its output
     // TII (f-4): carrier set, the one-frame carrier image and its native-rate response, gain of symbol 1
@@ -191,6 +200,7 @@ struct dabgpu_ctx {
         int h_out_index = 0;                           // which of the three pinned output buffers this batch lands in
         unsigned long long *h_clip = nullptr;          // pinned: this batch's clipped-component count (output formats)
         dabgpu_api::DevBuf d_in, d_out;
+        dabgpu_api::DevBuf d_eti;                      // dabgpu_chain_submit_eti: the batch's ETI frames (d_in then holds the coded bits)
         hipEvent_t computed = nullptr, copied = nullptr;
         hipStream_t stream = nullptr;                  // the lane this batch's kernels were queued on
         bool busy = false;
@@ -247,6 +257,17 @@ struct LaneScope {
     }
 };
 
+
+// ---- api_frontend.hip
+// the host-pointer checks of an ETI batch against the configured layout (nothing queued, nothing changed when it fails)
+int frontend_check_host(dabgpu_ctx *c, const uint8_t *eti, size_t n_eti);
+// shape checks every entry shares (configured, whole transmission frames, max_frames); *n_tf: transmission frames
+int frontend_check_shape(dabgpu_ctx *c, size_t n_eti, size_t *n_tf);
+// the two launches and the history's move to the front, on `s`; d_bits receives n_eti / cifs-per-frame x tf_input_bytes
+int run_frontend(dabgpu_ctx *c, const void *d_eti, size_t n_eti, void *d_bits, hipStream_t s);
+
+// ---- api_lanes.hip (the streaming host path; eti: `src` holds ETI frames, n_frames still counts transmission frames)
+int chain_submit(dabgpu_ctx *c, const uint8_t *src, size_t n_frames, unsigned mask, bool eti);
 
 // ---- api_context.hip
 extern const float kDefaultTaps[45];

@@ -150,6 +150,32 @@ hipError_t launch_format(const float *in, size_t nfloats, int fmt, void *out, un
 hipError_t launch_lut(const float2 *in, size_t nsamples, float scale, const float *lut,
                       float2 *out, hipStream_t s);
 
+// The front-end (frontend.hip).  One FeUnit per FIC / sub-channel: where its payload lies in the ETI frame, where its punctured
+// bytes go, and the flattened puncturing segments -- segment r covers the 4-byte groups g0[r] ... g0[r + 1] - 1 of the mother
+// code's output with pattern pat[r], its first kept bit at bit base[r] of the unit's output; entry nseg is the 24-bit tail.
+constexpr int kFeCifBytes = 864 * 8;      // one CIF; also the length of the dispersal table
+constexpr int kFeHistory = 15;            // frames the time interleaver looks back
+struct FeUnit {
+    uint32_t in_off, in_bytes;            // payload inside the 6144-byte frame
+    uint32_t out_bytes;                   // punctured and padded: the FIC's 288 / 384, or 8 x CU
+    uint32_t dst_off;                     // byte offset inside the CIF row (8 x SAD); 0 for the FIC
+    int32_t owner;                        // sub-channel index in STC order; -1: the FIC
+    uint32_t nseg;
+    uint32_t g0[6], base[6], pat[6];      // (4 rules + the tail + the end)
+};
+struct FeArgs {
+    const uint8_t *eti;                   // n_eti x 6144
+    const uint8_t *prbs;                  // kFeCifBytes: the x^9 + x^5 + 1 sequence
+    const FeUnit *units;
+    const int16_t *owner;                 // 864: which sub-channel a capacity unit belongs to (the last in STC order), -1 padding
+    uint8_t *hist;                        // (kFeHistory + n_eti) x kFeCifBytes
+    uint8_t *fic;                         // n_eti x fic_out
+    uint8_t *out;                         // n_tf x cifs x (fic_out + kFeCifBytes)
+    int n_eti, n_units, cifs, fic_out;
+};
+hipError_t launch_fe_encode(const FeArgs &a, hipStream_t s);
+hipError_t launch_fe_assemble(const FeArgs &a, hipStream_t s);
+
 // Resampler (reference src/Resampler.cpp:131-195), power-of-two FFT sizes.
 struct ResamplerArgs {
     int nin, nout;          // FFT sizes (e.g. 4096 -> 16384)

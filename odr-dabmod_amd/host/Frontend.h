@@ -2,9 +2,14 @@
 // ETI(NI) frame -> FIC / sub-channel sources -> energy dispersal -> convolutional code ->
 // puncturing -> time interleaving -> CIF assembly -> BlockPartitioner.
 //
-// Serial, bit-level, ~60 kB per transmission frame: it stays on the CPU (there is nothing for a
-// GPU to win), written from scratch with the reference's class names and constructor signatures
-// (file:line at each class) so that src/DabModulator.cpp:131-139,281-385 wires it unchanged.
+// Bit-level integer work, ~60 kB per transmission frame, written from scratch with the reference's
+// class names and constructor signatures (file:line at each class) so that
+// src/DabModulator.cpp:131-139,281-385 wires it unchanged.  One core runs it at 31 k transmission
+// frames/s -- two orders of magnitude below the chain it feeds --, so the same sub-graph also exists
+// as two device kernels behind the C-ABI (dabgpu_frontend_* / dabgpu_chain_process_eti in
+// include/dabgpu.h, csrc/frontend.hip; DabGpuChain::submit_eti, dabmod_file --gpu-frontend), whose
+// bytes are checked against THESE classes (tests/test_gpu_frontend_gpu.py).  This is the default
+// and the reference for that path; protection_tables.inc is shared with it.
 // Pure integer work: bit-exact against the reference's classes (tests/test_frontend.py and the
 // goldens it reads).  Not restated: timestamp decoding (MNSC/TIST -> metadata), EDI
 // input, FIC decoding for the remote control -- metadata and I/O, SURVEY 2 rows 19-20.

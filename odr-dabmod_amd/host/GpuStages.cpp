@@ -960,6 +960,19 @@ void DabGpuChain::submit(const void *bits, size_t n_frames)
     m_ctx.check(dabgpu_chain_submit(m_ctx.get(), static_cast<const uint8_t *>(bits), n_frames, stage_mask()));
 }
 
+void DabGpuChain::configure_frontend(const void *frame6144)
+{
+    m_ctx.check(dabgpu_frontend_configure(m_ctx.get(), static_cast<const uint8_t *>(frame6144)));
+}
+
+void DabGpuChain::submit_eti(const void *eti_frames, size_t n_eti)
+{
+    if (m_drops)
+        throw std::runtime_error("DabGpuChain::submit_eti: Settings::emulatePipelineDrops applies to process() only");
+    before_frames();
+    m_ctx.check(dabgpu_chain_submit_eti(m_ctx.get(), static_cast<const uint8_t *>(eti_frames), n_eti, stage_mask()));
+}
+
 void DabGpuChain::seed(const void *leadin_bits, uint64_t frame_index)
 {
     before_frames();            // (the lead-in frame runs under the settings the frames behind it run under)

@@ -443,6 +443,14 @@ public:
     // Same stream state (resampler halo, TII parity) and the same samples as process() frame by frame.
     void submit(const void *bits, size_t n_frames);
     size_t collect(const void **iq);
+    // The front-end on the device (include/dabgpu.h, "the front-end on the device"): configure_frontend() reads the
+    // multiplex layout from one raw 6144-byte ETI(NI) frame -- the stream's first, the one with FP = 0, which the caller
+    // finds (src/DabMod.cpp:684-693) -- and starts a stream (zero time-interleaver history); submit_eti() is submit() from
+    // n_eti raw ETI frames, whole transmission frames (4 / 1 / 1 / 2 per frame in modes I ... IV), in place of the
+    // sub-graph cifFicPrbs ... cifPart (src/DabModulator.cpp:281-385) and the chain behind it.  A frame of another layout
+    // throws ("FrameMultiplexer detected ...") and leaves the stream where it was.  Not together with seed().
+    void configure_frontend(const void *frame6144);
+    void submit_eti(const void *eti_frames, size_t n_eti);
     // One stream over several chains, or a stream moved from one chain to another (include/dabgpu.h, "stream state"):
     // seed() puts the chain where it would be after frames 0 ... frame_index - 1 of a stream whose frame
     // frame_index - 1 has the coded bits leadin_bits (one frame; nullptr with frame_index 0, the start of a stream) --

@@ -5,6 +5,8 @@
 //   InputFileReader -> EtiFrontend (CPU: ETI -> coded bits)        odr-dabmod_amd/host/Frontend.h
 //                   -> DabGpuChain (MI355X: coded bits -> IQ)       odr-dabmod_amd/host/GpuStages.h
 //                   -> [FormatConverter] -> file
+// or, with --gpu-frontend, the front-end on the device as well (DabGpuChain::submit_eti):
+//   InputFileReader -> DabGpuChain (MI355X: ETI frames -> coded bits -> IQ) -> file
 //
 // usage: dabmod_file <in.eti> <out> [options]
 //   --mode N             transmission mode 1..4 (default: from the ETI header, 0 -> 4)
@@ -25,6 +27,13 @@
 //                        turn, batch j to chain j mod N, which is first seeded from the last frame of batch j - 1
 //                        (DabGpuChain::seed): the same bytes as one chain, the chains' kernels side by side
 //                        (N > 1 needs the streaming path: not with --bits-only or --separate-converter)
+//   --gpu-frontend       ETI frames go to the device as they are (DabGpuChain::configure_frontend / submit_eti): the program
+//                        skips frames until FP = 0, reads the multiplex layout from that frame and hands whole batches of ETI
+//                        frames over (--batch transmission frames each, default 1).  The same file as without the option.
+//                        The library wants the frame phase of every call's first frame aligned to the transmission frame:
+//                        on a stream whose FP jumps (the CPU front-end never looks at FP after the start) the program
+//                        stops with that message.  Not with --contexts above 1 (the time interleaver's history is not part of the stream state a
+//                        chain is seeded with), --bits-only or --separate-converter.
 #include "Frontend.h"
 #include "GpuStages.h"
 
@@ -48,7 +57,9 @@ namespace {
                          "       [--reference-gain]      gain mode var by the reference's running recurrence (bit-equal scalars, slower)\n"
                          "       [--contexts N]   with --batch B > 1: split the stream's batches over N = 1 ... 4 chains on the device\n"
                          "                        (batch j to chain j mod N, seeded from the frame before it; the same bytes as N = 1;\n"
-                         "                        N > 1 not with --bits-only or --separate-converter)\n");
+                         "                        N > 1 not with --bits-only or --separate-converter)\n"
+                         "       [--gpu-frontend]   ETI -> coded bits on the device as well (not with --contexts above 1, --bits-only,\n"
+                         "                        --separate-converter)\n");
     std::exit(2);
 }
 }  // namespace
@@ -66,6 +77,7 @@ int main(int argc, char **argv)
     size_t batch = 1;
     bool reference_latency = false;
     long contexts = 1;
+    bool gpu_frontend = false;
     try {
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
@@ -100,6 +112,7 @@ int main(int argc, char **argv)
             else if (a == "--batch") batch = std::max<size_t>(1, std::stoul(val()));
             else if (a == "--reference-latency") reference_latency = true;
             else if (a == "--reference-gain") gs.referenceGainRounding = true;
+            else if (a == "--gpu-frontend") gpu_frontend = true;
             else if (a == "--contexts") {
                 const std::string v = val();
                 size_t used = 0;
@@ -110,6 +123,15 @@ int main(int argc, char **argv)
         }
         // (several chains take whole batches of the streaming path in turn: nothing to split frame by frame)
         if (contexts < 1 || contexts > 4 || (contexts > 1 && (batch <= 1 || separate_converter || bits_only))) usage();
+
+        if (gpu_frontend && (contexts > 1 || bits_only || separate_converter)) {
+            std::fprintf(stderr, "dabmod_file: --gpu-frontend does not go with %s\n",
+                         contexts > 1 ? "--contexts above 1: the front-end's state (the time interleaver's history) is not part of "
+                                        "the stream state a chain is seeded with"
+                         : bits_only  ? "--bits-only: the coded bits stay on the device"
+                                      : "--separate-converter: the streaming path converts inside the chain");
+            return 2;
+        }
 
         InputFileReader reader;
         if (reader.Open(in_path, false) != 0) {
@@ -158,11 +180,48 @@ int main(int argc, char **argv)
             n_submitted += frames;
             ++in_flight;
         };
+        // --gpu-frontend: the ETI frames of the batch being filled, and with --reference-latency the frames held back
+        std::vector<uint8_t> pending_eti;
+        std::deque<std::vector<uint8_t>> held_eti;
+        size_t cifs = 1, n_gated = 0;             // ETI frames per transmission frame; frames since the one with FP = 0
+        auto submit_eti_batch = [&](size_t frames) {
+            if (in_flight == 2) drain_one();
+            ++n_batches;
+            chain->submit_eti(pending_eti.data(), frames * cifs);
+            pending_eti.erase(pending_eti.begin(), pending_eti.begin() + frames * cifs * 6144);
+            n_submitted += frames;
+            ++in_flight;
+        };
         for (int l = 0; l < loops; ++l) {
             if (l && reader.Open(in_path, false) != 0) return 1;
             int got;
             while ((got = reader.GetNextFrame(frame)) == 6144) {
                 ++n_eti;
+                if (gpu_frontend) {
+                    if (!chain) {
+                        if ((frame[6] >> 5) != 0) continue;          // align the frame groups (src/DabMod.cpp:684-693)
+                        if (gs.dabMode == 0) {
+                            const unsigned mid = (frame[6] >> 3) & 3;
+                            gs.dabMode = mid ? mid : 4;
+                        }
+                        cifs = gs.dabMode == 1 ? 4 : gs.dabMode == 4 ? 2 : 1;
+                        gs.outputFormat = format;
+                        gs.maxBatchFrames = batch;
+                        chain.reset(new DabGpuChain(gs));
+                        chain->configure_frontend(frame);
+                    }
+                    if (++n_gated % cifs == 0) ++n_tf;
+                    if (reference_latency) {
+                        // transmission frame i is modulated when frame i + k is complete; the last k never are
+                        held_eti.emplace_back(frame, frame + 6144);
+                        if (held_eti.size() <= gs.referencePipelineDepth() * cifs) continue;
+                        pending_eti.insert(pending_eti.end(), held_eti.front().begin(), held_eti.front().end());
+                        held_eti.pop_front();
+                    } else
+                        pending_eti.insert(pending_eti.end(), frame, frame + 6144);
+                    if (pending_eti.size() == batch * cifs * 6144) submit_eti_batch(batch);
+                    continue;
+                }
                 if (!frontend) {
                     if (gs.dabMode == 0) {
                         // MID of the first frame; 0 means mode IV (EN 300 799 5.3.2)
@@ -226,7 +285,12 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
-        if (chain && batch > 1 && !separate_converter) {
+        if (chain && gpu_frontend) {
+            // the tail: the whole transmission frames left over, then whatever is still in flight, in order
+            const size_t rest = pending_eti.size() / (cifs * 6144);
+            if (rest) submit_eti_batch(rest);
+            while (in_flight) drain_one();
+        } else if (chain && batch > 1 && !separate_converter) {
             // the tail: a last, shorter batch, then whatever is still in flight, in order
             const size_t rest = pending.size() / chain->input_bytes_per_frame();
             if (rest) submit_batch(rest);
