@@ -416,7 +416,7 @@ DABGPU_API int dabgpu_debug_trace(dabgpu_ctx *ctx, int enable);
  * Stream state: the time interleaver reads the last fifteen punctured frames of the stream; they live in the context's device
  *   memory, zero after configure / reset, like the Resampler's halo.  The stream-state blob does NOT carry them (a seed
  *   would need fifteen lead-in ETI frames, not one transmission frame): dabgpu_chain_seed / _dev after a
- *   dabgpu_frontend_configure is refused.
+ *   dabgpu_frontend_configure is refused.  They have a blob and seeds of their own: "front-end stream state" below.
  * All calls below take whole transmission frames (n_eti a multiple of 4 / 1 / 1 / 2 in modes I ... IV; at most max_frames
  *   transmission frames per call), and the frame phase FP of a call's first frame must be a multiple of that count.  Finding
  *   the start of the stream -- the first frame with FP = 0, src/DabMod.cpp:684-693 -- stays with the caller.  The host-pointer
@@ -468,6 +468,70 @@ DABGPU_API int dabgpu_chain_process_eti(dabgpu_ctx *ctx, const uint8_t *eti, siz
                                         size_t out_cap, size_t *out_bytes);
 /* the streaming shape: dabgpu_chain_submit from ETI frames (lane 0, in call order); dabgpu_chain_collect as it is */
 DABGPU_API int dabgpu_chain_submit_eti(dabgpu_ctx *ctx, const uint8_t *eti, size_t n_eti, unsigned stage_mask);
+
+/* ---- front-end stream state: an ETI-fed stream checkpointed, handed over, or split over contexts ------------------------ *
+ * A context with a configured front-end carries three pieces of stream state: the Resampler's halo and the TII frame parity
+ * ("stream state" above, unchanged: same blob, same version, same size with or without a front-end) and the time
+ * interleaver's history, the last DABGPU_FE_HISTORY_FRAMES punctured ETI frames.  A WHOLE ETI-fed stream is moved with BOTH
+ * blobs: dabgpu_get_stream_state + dabgpu_frontend_get_state on the one side, dabgpu_frontend_configure (from a frame of the
+ * stream), dabgpu_set_stream_state + dabgpu_frontend_set_state on the other.
+ * The front-end blob, in HOST memory, self-describing, of one size for every layout (all fields little endian):
+ *     offset  0  uint32  magic      DABGPU_FE_STATE_MAGIC ("DGFS")
+ *             4  uint32  version    DABGPU_FE_STATE_VERSION
+ *             8  uint32  mode       transmission mode 1..4
+ *            12  uint32  fc         byte 5 of the ETI frame (FICF, NST) | the MID bits of byte 6 (mask 0x18) << 8
+ *            16  uint32  rows       DABGPU_FE_HISTORY_FRAMES
+ *            20  uint32  row_bytes  6912 (one CIF)
+ *            24  uint32  nst        sub-channels
+ *            28  uint32  reserved   0
+ *            32  127 x 4 bytes      the STC words of the layout as the ETI frame has them, nst of them, zeros behind
+ *           540  rows x row_bytes   the history, oldest frame first: row r is the punctured CIF (before time interleaving) of
+ *                                   ETI frame e - 15 + r, zero where that lies before the start of the stream and on every
+ *                                   capacity unit no sub-channel owns
+ *   (mode, fc, nst and the STC words are the layout identity the host-pointer entries compare every frame with.)  Blobs taken
+ *   at the same position of the same stream are equal byte for byte, however the context got there: through calls of any
+ *   size, an installed blob or a seed.
+ * dabgpu_frontend_state_bytes: the size of the blob (DABGPU_FE_STATE_HEADER_BYTES + 15 x 6912).
+ * dabgpu_frontend_get_state: waits for the context, as dabgpu_get_stream_state does, then describes the history after
+ *   everything queued so far; *bytes (may be NULL) receives the size; DABGPU_E_CAPACITY when cap is smaller, DABGPU_E_INVALID
+ *   when the front-end is not configured.
+ * dabgpu_frontend_set_state: waits, then installs the history.  DABGPU_E_INVALID (with a message), the history untouched, when
+ *   the front-end is not configured, for a blob from another mode or another multiplex layout, and for a malformed one (size,
+ *   magic, version).
+ * The seeds compute the state from the ETI frames in front of a position of the stream.  e = the index in the stream of the
+ *   first ETI frame the context is to process next (0 = the start of the stream), a multiple of cifs = 4 / 1 / 1 / 2 in modes
+ *   I ... IV; the lead-in is the n_leadin frames e - n_leadin ... e - 1, in stream order.
+ * dabgpu_frontend_seed / _dev: the history in front of frame e.  n_leadin = min(e, 15), anything else is DABGPU_E_INVALID;
+ *   rows from before the start of the stream are zero; e == 0 is dabgpu_frontend_reset under another name.  Cost: one memset
+ *   and one launch of the encode kernel over the sub-channels of the lead-in frames -- no FIC, no assembly, no output.
+ * dabgpu_chain_seed_eti / _dev: the front-end seed and dabgpu_chain_seed together, for a chain fed from ETI frames.
+ *   n_leadin = min(e, 15 + cifs).  The first n_leadin - cifs frames give the history in front of transmission frame
+ *   e / cifs - 1; the last cifs frames ARE that transmission frame: they go through the front-end into scratch, and their
+ *   coded bits seed the chain as dabgpu_chain_seed does with frame_index = e / cifs (halo, TII parity).  Afterwards the history
+ *   is the one in front of frame e.  No output; dabgpu_get_cfr_stats, dabgpu_get_num_clipped and dabgpu_debug_last_variant
+ *   keep describing the last real chain call.  (dabgpu_chain_seed / _dev keep refusing a context with a front-end.)
+ * The host-pointer forms compare every lead-in frame with the configured layout, as the other host-pointer entries do, and
+ *   want the frame phase of the LAST lead-in frame at cifs - 1 modulo cifs (the lead-in ends where a transmission frame ends;
+ *   its first frame need not start one); they return when the frames have been read.  The _dev forms cannot look at the
+ *   frames; they are asynchronous on `stream` -- NULL: lane 0, the context's own stream -- in order with the calls that
+ *   follow there.  Every refusal (not configured, e, n_leadin, a frame of another layout, a ratio the Resampler does not run)
+ *   comes before anything is queued: history, halo and parity stay as they were.
+ * A context seeded this way produces frames e ... byte for byte as the uninterrupted stream does
+ *   (tests/test_frontend_state_gpu.py; odr-dabmod_amd/streams.py: PartitionedStream.modulate_eti). */
+#define DABGPU_FE_HISTORY_FRAMES 15
+#define DABGPU_FE_STATE_MAGIC 0x53464744u /* "DGFS" */
+#define DABGPU_FE_STATE_VERSION 1u
+#define DABGPU_FE_STATE_HEADER_BYTES 540
+DABGPU_API size_t dabgpu_frontend_state_bytes(const dabgpu_ctx *ctx);
+DABGPU_API int dabgpu_frontend_get_state(dabgpu_ctx *ctx, void *buf, size_t cap, size_t *bytes);
+DABGPU_API int dabgpu_frontend_set_state(dabgpu_ctx *ctx, const void *buf, size_t bytes);
+DABGPU_API int dabgpu_frontend_seed(dabgpu_ctx *ctx, const uint8_t *eti_leadin, size_t n_leadin, uint64_t e);
+DABGPU_API int dabgpu_frontend_seed_dev(dabgpu_ctx *ctx, const void *d_eti_leadin, size_t n_leadin, uint64_t e,
+                                        void *stream);
+DABGPU_API int dabgpu_chain_seed_eti(dabgpu_ctx *ctx, const uint8_t *eti_leadin, size_t n_leadin, unsigned stage_mask,
+                                     uint64_t e);
+DABGPU_API int dabgpu_chain_seed_eti_dev(dabgpu_ctx *ctx, const void *d_eti_leadin, size_t n_leadin,
+                                         unsigned stage_mask, uint64_t e, void *stream);
 
 /* wait for everything queued on the context's own stream(s): every lane */
 DABGPU_API int dabgpu_synchronize(dabgpu_ctx *ctx);

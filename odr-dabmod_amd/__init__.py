@@ -40,6 +40,8 @@ EXPORTS = [
     "dabgpu_chain_seed", "dabgpu_chain_seed_dev",
     "dabgpu_frontend_describe", "dabgpu_frontend_configure", "dabgpu_frontend_reset", "dabgpu_frontend_process",
     "dabgpu_frontend_process_dev", "dabgpu_chain_process_eti", "dabgpu_chain_submit_eti",
+    "dabgpu_frontend_state_bytes", "dabgpu_frontend_get_state", "dabgpu_frontend_set_state",
+    "dabgpu_frontend_seed", "dabgpu_frontend_seed_dev", "dabgpu_chain_seed_eti", "dabgpu_chain_seed_eti_dev",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -106,6 +108,7 @@ class _FeLayout(C.Structure):
 
 ETI_FRAME_BYTES = 6144
 CIFS_PER_FRAME = {1: 4, 2: 1, 3: 1, 4: 2}      # ETI frames per transmission frame
+FE_HISTORY_FRAMES = 15                         # ETI frames the time interleaver looks back (DABGPU_FE_HISTORY_FRAMES)
 
 _lib = None
 
@@ -188,6 +191,14 @@ def load_library():
     lib.dabgpu_frontend_process_dev.argtypes = [vp, vp, sz, vp, sz, szp, vp]
     lib.dabgpu_chain_process_eti.argtypes = [vp, vp, sz, u, vp, sz, szp]
     lib.dabgpu_chain_submit_eti.argtypes = [vp, vp, sz, u]
+    lib.dabgpu_frontend_state_bytes.argtypes = [vp]
+    lib.dabgpu_frontend_state_bytes.restype = sz
+    lib.dabgpu_frontend_get_state.argtypes = [vp, vp, sz, szp]
+    lib.dabgpu_frontend_set_state.argtypes = [vp, vp, sz]
+    lib.dabgpu_frontend_seed.argtypes = [vp, vp, sz, C.c_uint64]
+    lib.dabgpu_frontend_seed_dev.argtypes = [vp, vp, sz, C.c_uint64, vp]
+    lib.dabgpu_chain_seed_eti.argtypes = [vp, vp, sz, u, C.c_uint64]
+    lib.dabgpu_chain_seed_eti_dev.argtypes = [vp, vp, sz, u, C.c_uint64, vp]
     _lib = lib
     return lib
 
@@ -553,6 +564,50 @@ class Modulator:
         eti, n = self._eti(eti)
         self._chk(self._lib.dabgpu_chain_submit_eti(self._h, eti.ctypes.data, n, stages))
 
+    # ---- front-end stream state: the time interleaver's history (include/dabgpu.h, "front-end stream state") ----
+    def frontend_state(self):
+        """The time interleaver's history after everything queued on the context so far, as the self-describing blob of
+        dabgpu_frontend_get_state (bytes).  Waits for the context.  A whole ETI-fed stream is this blob AND stream_state()."""
+        cap = self._lib.dabgpu_frontend_state_bytes(self._h)
+        buf = C.create_string_buffer(cap)
+        n = C.c_size_t()
+        self._chk(self._lib.dabgpu_frontend_get_state(self._h, buf, cap, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def set_frontend_state(self, blob):
+        """Install a blob of frontend_state(), taken on a context of the same mode and multiplex layout.  Waits."""
+        blob = bytes(blob)
+        self._chk(self._lib.dabgpu_frontend_set_state(self._h, blob, len(blob)))
+
+    def frontend_seed(self, eti, e):
+        """The history in front of ETI frame `e` of a stream from the min(e, 15) frames before it (host array, in stream
+        order; None or empty with e = 0, the start of a stream): dabgpu_frontend_seed.  No output."""
+        eti, n = self._eti(eti if eti is not None else np.empty(0, np.uint8))
+        self._chk(self._lib.dabgpu_frontend_seed(self._h, eti.ctypes.data if n else None, n, int(e)))
+
+    def seed_eti(self, eti, stages, e):
+        """Front-end AND chain in the state in front of ETI frame `e` (a multiple of the frames per transmission frame), from
+        the min(e, 15 + that count) frames before it (streams.eti_leadin): dabgpu_chain_seed_eti.  No output."""
+        eti, n = self._eti(eti if eti is not None else np.empty(0, np.uint8))
+        self._chk(self._lib.dabgpu_chain_seed_eti(self._h, eti.ctypes.data if n else None, n, stages, int(e)))
+
+    def seed_eti_dev(self, d_eti, n_leadin, stages, e, stream=None, queued=False):
+        """Same with the lead-in frames in device memory (a torch uint8 tensor, or None with e = 0), asynchronous on the
+        stream -- a HIP stream handle as for chain_dev, torch's current stream by default; queued=True: the context's own
+        stream, in order with the queued calls that follow, without waiting for the device.  The frames are not looked at."""
+        import torch
+        if d_eti is not None and d_eti.numel() != n_leadin * ETI_FRAME_BYTES:
+            raise DabGpuError("seed: the lead-in is n_leadin ETI frames of 6144 bytes")
+        if queued:
+            s = None
+        else:
+            where = d_eti if d_eti is not None else torch.empty(0, device=torch.device("cuda", self.device))
+            s = self._stream_handle(where, stream)
+        self._chk(self._lib.dabgpu_chain_seed_eti_dev(self._h, d_eti.data_ptr() if d_eti is not None and n_leadin else None,
+                                                      n_leadin, stages, int(e), s))
+        if not s and not queued:
+            self.synchronize()
+
     def submit(self, bits, stages):
         """Asynchronous host path: queue a batch (at most two in flight)."""
         bits = np.ascontiguousarray(bits, np.uint8).reshape(-1)
@@ -640,6 +695,15 @@ class Modulator:
         self._chk(fn(self._h, d_in.data_ptr(), n_frames, stages, d_out.data_ptr(),
                      d_out.numel() * d_out.element_size(), C.byref(ob), None))
         return ob.value
+
+    def chain_eti_dev_queued(self, d_eti, n_eti, stages, d_bits, d_out):
+        """ETI frames in device memory -> IQ on the context's OWN stream, returning at once: the front-end into d_bits
+        (n_eti / frames-per-transmission-frame x tf_input_bytes, the caller's scratch), the chain from there; ordered like
+        chain_dev_queued, behind a seed_eti_dev(..., queued=True) before it.  The frames are not looked at."""
+        ob = C.c_size_t()
+        self._chk(self._lib.dabgpu_frontend_process_dev(self._h, d_eti.data_ptr(), n_eti, d_bits.data_ptr(),
+                                                        d_bits.numel() * d_bits.element_size(), C.byref(ob), None))
+        return self.chain_dev_queued(d_bits, n_eti // CIFS_PER_FRAME[self.geometry["mode"]], stages, d_out)
 
     def post_process_dev_queued(self, d_native, stages, d_out):
         """dabgpu_post_process_dev on the context's OWN stream (stream argument NULL), returning at once: ordered behind every

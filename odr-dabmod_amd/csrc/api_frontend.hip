@@ -1,6 +1,7 @@
 // api_frontend.hip -- the front-end on the device (include/dabgpu.h, "the front-end on the device"): the layout of an ETI(NI)
 // frame (host only), configure / reset, ETI -> coded bits, ETI -> IQ.  The kernels are in frontend.hip; the stream state (the
-// time interleaver's fifteen frames of history) lives in dabgpu_ctx::d_fe_hist.
+// time interleaver's fifteen frames of history) lives in dabgpu_ctx::d_fe_hist: read into a host blob, installed from one,
+// or computed from the ETI frames in front of a position of the stream (dabgpu_frontend_seed).
 #include "dabgpu_ctx.h"
 
 using namespace dabgpu;
@@ -157,11 +158,40 @@ FeUnit make_unit(const dabgpu_fe_rule *rule, uint32_t n_rules, uint32_t in_off, 
     return u;
 }
 
-// the start of a stream: rows 0 ... 14 of the history are zero (TimeInterleaver's ring at construction)
-hipError_t zero_history(dabgpu_ctx *c)
+// the start of a stream: rows 0 ... 14 of the history are zero (TimeInterleaver's ring at construction).  configure zeroes
+// the rows behind them too (`rows` in all): a call writes only the capacity units a sub-channel owns, so every other byte
+// of every row is zero from then on, whichever way the rows were filled -- what makes two front-end state blobs taken at
+// the same position of a stream equal byte for byte.
+hipError_t zero_history(dabgpu_ctx *c, size_t rows = kFeHistory)
 {
-    const hipError_t e = hipMemsetAsync(c->d_fe_hist.p, 0, (size_t)kFeHistory * kFeCifBytes, c->stream);
+    const hipError_t e = hipMemsetAsync(c->d_fe_hist.p, 0, rows * kFeCifBytes, c->stream);
     return e != hipSuccess ? e : hipStreamSynchronize(c->stream);
+}
+
+const char *const kNotConfigured = "frontend: not configured (dabgpu_frontend_configure comes first)";
+
+// the front-end state blob's header (include/dabgpu.h documents the layout); the fifteen history rows follow, oldest first
+struct FeStateHeader {
+    uint32_t magic, version, mode, fc, rows, row_bytes, nst, reserved;
+    uint8_t stc[4 * DABGPU_FE_MAX_SUBCH];
+};
+static_assert(sizeof(FeStateHeader) == DABGPU_FE_STATE_HEADER_BYTES && kFeHistory == DABGPU_FE_HISTORY_FRAMES,
+              "the layout include/dabgpu.h documents");
+constexpr size_t kFeStateBytes = sizeof(FeStateHeader) + (size_t)kFeHistory * kFeCifBytes;
+
+// what frontend_check_host compares, as the blob carries it: FICF / NST, the MID bits, the NST STC words
+FeStateHeader state_header(const dabgpu_ctx *c)
+{
+    FeStateHeader h{};
+    h.magic = DABGPU_FE_STATE_MAGIC;
+    h.version = DABGPU_FE_STATE_VERSION;
+    h.mode = (uint32_t)(c->g.mode ? c->g.mode : 4);
+    h.fc = (uint32_t)c->fe_header[0] | (uint32_t)c->fe_header[1] << 8;
+    h.rows = kFeHistory;
+    h.row_bytes = kFeCifBytes;
+    h.nst = c->fe_layout.nst;
+    std::memcpy(h.stc, c->fe_header.data() + 3, 4 * (size_t)h.nst);
+    return h;
 }
 
 }  // namespace
@@ -170,7 +200,7 @@ namespace dabgpu_api {
 
 int frontend_check_shape(dabgpu_ctx *c, size_t n_eti, size_t *n_tf)
 {
-    if (!c->fe_configured) return fail(c, DABGPU_E_INVALID, "frontend: not configured (dabgpu_frontend_configure comes first)");
+    if (!c->fe_configured) return fail(c, DABGPU_E_INVALID, kNotConfigured);
     if (n_eti % (size_t)c->fe_cifs)
         return fail(c, DABGPU_E_INVALID, "frontend: ETI frames come as whole transmission frames (a multiple of " +
                                              std::to_string(c->fe_cifs) + " in this mode)");
@@ -185,6 +215,11 @@ int frontend_check_host(dabgpu_ctx *c, const uint8_t *eti, size_t n_eti)
     if (n_eti && (eti[6] >> 5) % (unsigned)c->fe_cifs)
         return fail(c, DABGPU_E_INVALID, "frontend: the frame phase of a call's first frame must be a multiple of " +
                                              std::to_string(c->fe_cifs) + " (FP = " + std::to_string(eti[6] >> 5) + ")");
+    return frontend_check_layout(c, eti, n_eti);
+}
+
+int frontend_check_layout(dabgpu_ctx *c, const uint8_t *eti, size_t n_eti)
+{
     const std::vector<uint8_t> &h = c->fe_header;
     const size_t nst = c->fe_layout.nst;
     for (size_t k = 0; k < n_eti; ++k) {
@@ -212,6 +247,7 @@ int run_frontend(dabgpu_ctx *c, const void *d_eti, size_t n_eti, void *d_bits, h
     a.fic = (uint8_t *)c->d_fe_fic.p;
     a.out = (uint8_t *)d_bits;
     a.n_eti = (int)n_eti; a.n_units = c->fe_units; a.cifs = c->fe_cifs; a.fic_out = c->fe_fic_out;
+    a.unit0 = 0; a.row0 = kFeHistory;
     HIPCHK(c, launch_fe_encode(a, s));
     HIPCHK(c, launch_fe_assemble(a, s));
     // the last fifteen rows of the call move to the front, in stream order (through a second buffer where they overlap)
@@ -223,6 +259,52 @@ int run_frontend(dabgpu_ctx *c, const void *d_eti, size_t n_eti, void *d_bits, h
         HIPCHK(c, hipMemcpyAsync(c->d_fe_tmp.p, last, hist, hipMemcpyDeviceToDevice, s));
         HIPCHK(c, hipMemcpyAsync(a.hist, c->d_fe_tmp.p, hist, hipMemcpyDeviceToDevice, s));
     }
+    return DABGPU_OK;
+}
+
+int frontend_seed_check(dabgpu_ctx *c, size_t n_leadin, uint64_t e, size_t reach)
+{
+    if (!c->fe_configured) return fail(c, DABGPU_E_INVALID, kNotConfigured);
+    if (e % (uint64_t)c->fe_cifs)
+        return fail(c, DABGPU_E_INVALID, "frontend seed: a stream is taken up at a whole transmission frame (e a multiple of " +
+                                             std::to_string(c->fe_cifs) + " in this mode)");
+    const size_t want = (size_t)std::min<uint64_t>(e, reach);
+    if (n_leadin != want)
+        return fail(c, DABGPU_E_INVALID, "frontend seed: the lead-in in front of ETI frame " + std::to_string(e) + " is " +
+                                             std::to_string(want) + " frames (given: " + std::to_string(n_leadin) + ")");
+    return DABGPU_OK;
+}
+
+int frontend_check_leadin_host(dabgpu_ctx *c, const uint8_t *eti, size_t n_leadin)
+{
+    if (!n_leadin) return DABGPU_OK;
+    if (!eti) return fail(c, DABGPU_E_INVALID, "null argument");
+    const int rc = frontend_check_layout(c, eti, n_leadin);
+    if (rc) return rc;
+    const unsigned fp = eti[(n_leadin - 1) * 6144 + 6] >> 5, cifs = (unsigned)c->fe_cifs;
+    if (fp % cifs != cifs - 1)
+        return fail(c, DABGPU_E_INVALID, "frontend seed: the last lead-in frame closes a transmission frame (FP = " +
+                                             std::to_string(fp) + ", not " + std::to_string(cifs - 1) + " modulo " +
+                                             std::to_string(cifs) + ")");
+    return DABGPU_OK;
+}
+
+int frontend_seed_rows(dabgpu_ctx *c, const void *d_eti, size_t m, hipStream_t s)
+{
+    if (m > (size_t)kFeHistory) return fail(c, DABGPU_E_INVALID, "frontend seed: more lead-in frames than the history holds");
+    // rows that lie before the start of the stream are zero, as after configure; the others keep the bytes no sub-channel
+    // owns, which are zero since configure and which no launch writes
+    if (m < (size_t)kFeHistory) HIPCHK(c, hipMemsetAsync(c->d_fe_hist.p, 0, ((size_t)kFeHistory - m) * kFeCifBytes, s));
+    if (!m) return DABGPU_OK;
+    FeArgs a{};
+    a.eti = (const uint8_t *)d_eti;
+    a.prbs = (const uint8_t *)c->d_fe_prbs.p;
+    a.units = (const FeUnit *)c->d_fe_units.p;
+    a.owner = (const int16_t *)c->d_fe_owner.p;
+    a.hist = (uint8_t *)c->d_fe_hist.p;
+    a.n_eti = (int)m; a.n_units = c->fe_units; a.cifs = c->fe_cifs; a.fic_out = c->fe_fic_out;
+    a.unit0 = 1; a.row0 = kFeHistory - (int)m;
+    HIPCHK(c, launch_fe_encode(a, s));
     return DABGPU_OK;
 }
 
@@ -287,7 +369,7 @@ int dabgpu_frontend_configure(dabgpu_ctx *c, const uint8_t *frame)
     const size_t rows = (size_t)kFeHistory + (size_t)c->max_frames * cifs;
     HIPCHK(c, c->d_fe_hist.reserve(rows * kFeCifBytes));
     HIPCHK(c, c->d_fe_tmp.reserve((size_t)kFeHistory * kFeCifBytes));
-    HIPCHK(c, zero_history(c));
+    HIPCHK(c, zero_history(c, rows));
     c->fe_layout = L;
     c->fe_units = (int)units.size();
     c->fe_cifs = cifs;
@@ -301,10 +383,73 @@ int dabgpu_frontend_configure(dabgpu_ctx *c, const uint8_t *frame)
 int dabgpu_frontend_reset(dabgpu_ctx *c)
 {
     CTXCHK(c);
-    if (!c->fe_configured) return fail(c, DABGPU_E_INVALID, "frontend: not configured (dabgpu_frontend_configure comes first)");
+    if (!c->fe_configured) return fail(c, DABGPU_E_INVALID, kNotConfigured);
     int rc = dabgpu_synchronize(c);
     if (rc) return rc;
     HIPCHK(c, zero_history(c));
+    return DABGPU_OK;
+}
+
+size_t dabgpu_frontend_state_bytes(const dabgpu_ctx *c) { return c ? kFeStateBytes : 0; }
+
+int dabgpu_frontend_get_state(dabgpu_ctx *c, void *buf, size_t cap, size_t *bytes)
+{
+    CTXCHK(c);
+    if (!buf) return fail(c, DABGPU_E_INVALID, "null argument");
+    if (!c->fe_configured) return fail(c, DABGPU_E_INVALID, kNotConfigured);
+    const int rc = dabgpu_synchronize(c);
+    if (rc) return rc;
+    if (bytes) *bytes = kFeStateBytes;
+    if (kFeStateBytes > cap) return fail(c, DABGPU_E_CAPACITY, "frontend state: buffer too small");
+    const FeStateHeader h = state_header(c);
+    std::memcpy(buf, &h, sizeof h);
+    HIPCHK(c, hipMemcpy((char *)buf + sizeof h, c->d_fe_hist.p, (size_t)kFeHistory * kFeCifBytes, hipMemcpyDeviceToHost));
+    return DABGPU_OK;
+}
+
+int dabgpu_frontend_set_state(dabgpu_ctx *c, const void *buf, size_t bytes)
+{
+    CTXCHK(c);
+    if (!buf) return fail(c, DABGPU_E_INVALID, "null argument");
+    if (!c->fe_configured) return fail(c, DABGPU_E_INVALID, kNotConfigured);
+    const int rc = dabgpu_synchronize(c);
+    if (rc) return rc;
+    FeStateHeader h;
+    if (bytes < sizeof h) return fail(c, DABGPU_E_INVALID, "frontend state: shorter than its header");
+    std::memcpy(&h, buf, sizeof h);
+    if (h.magic != DABGPU_FE_STATE_MAGIC) return fail(c, DABGPU_E_INVALID, "frontend state: not a front-end state (magic)");
+    if (h.version != DABGPU_FE_STATE_VERSION) return fail(c, DABGPU_E_INVALID, "frontend state: unknown version");
+    if (bytes != kFeStateBytes || h.rows != (uint32_t)kFeHistory || h.row_bytes != (uint32_t)kFeCifBytes || h.reserved)
+        return fail(c, DABGPU_E_INVALID, "frontend state: size does not match its header");
+    const FeStateHeader mine = state_header(c);
+    if (h.mode != mine.mode) return fail(c, DABGPU_E_INVALID, "frontend state: taken in another transmission mode");
+    if (h.fc != mine.fc || h.nst != mine.nst || std::memcmp(h.stc, mine.stc, sizeof h.stc) != 0)
+        return fail(c, DABGPU_E_INVALID, "frontend state: taken on another multiplex layout");
+    HIPCHK(c, hipMemcpy(c->d_fe_hist.p, (const char *)buf + sizeof h, (size_t)kFeHistory * kFeCifBytes, hipMemcpyHostToDevice));
+    return DABGPU_OK;
+}
+
+int dabgpu_frontend_seed_dev(dabgpu_ctx *c, const void *d_eti_leadin, size_t n_leadin, uint64_t e, void *stream)
+{
+    CTXCHK(c);
+    int rc = frontend_seed_check(c, n_leadin, e, kFeHistory);
+    if (rc) return rc;
+    if (n_leadin && !d_eti_leadin) return fail(c, DABGPU_E_INVALID, "null argument");
+    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;
+    return frontend_seed_rows(c, d_eti_leadin, n_leadin, stream ? (hipStream_t)stream : c->stream);
+}
+
+int dabgpu_frontend_seed(dabgpu_ctx *c, const uint8_t *eti_leadin, size_t n_leadin, uint64_t e)
+{
+    CTXCHK(c);
+    int rc = frontend_seed_check(c, n_leadin, e, kFeHistory);
+    if (rc) return rc;
+    if ((rc = frontend_check_leadin_host(c, eti_leadin, n_leadin))) return rc;
+    if ((rc = own_stream_joins_lanes(c))) return rc;
+    HostIO io(c);
+    if ((rc = io.in(c->d_fe_eti, eti_leadin, n_leadin * 6144))) return rc;
+    if ((rc = frontend_seed_rows(c, c->d_fe_eti.p, n_leadin, c->stream))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));               // (the caller's frames have been read)
     return DABGPU_OK;
 }
 

@@ -2,7 +2,8 @@
 // native-rate input samples, src/Resampler.cpp:142-147,188-191 -- and the TII frame parity (TII::m_insert,
 // src/TII.cpp:226-242).  Read into a host blob, installed from one, or computed from the coded bits of ONE lead-in frame
 // (every transmission frame is at least 96 hops long: the state behind frame k - 1 depends on the settings, on k and on that
-// frame alone), so that one stream can be checkpointed, moved, or split over several contexts.
+// frame alone), so that one stream can be checkpointed, moved, or split over several contexts.  With the front-end on the
+// device the lead-in is ETI frames, and the seed sets the time interleaver's history as well (dabgpu_chain_seed_eti).
 #include "dabgpu_ctx.h"
 
 using namespace dabgpu;
@@ -44,31 +45,44 @@ int settle(dabgpu_ctx *c)
     return DABGPU_OK;
 }
 
-// dabgpu_chain_seed / _dev: d_bits is the lead-in frame in device memory (not read when the call is host-only)
-int seed_dev(dabgpu_ctx *c, const void *d_bits, unsigned mask, uint64_t frame_index, hipStream_t s)
+// What a seed refuses and what it runs, decided before anything is queued (dabgpu_chain_seed / _dev, dabgpu_chain_seed_eti /
+// _dev): have_bits = the caller has a lead-in frame of coded bits for it
+struct SeedPlan {
+    bool resample = false;
+    ChainPlan p;                          // the lead-in frame's run in front of the Resampler (resample && frame_index only)
+};
+int plan_seed(dabgpu_ctx *c, unsigned mask, uint64_t frame_index, bool have_bits, SeedPlan *sp)
 {
     mask = normalised_mask(c->cur, mask);
-    const bool resample = mask & DABGPU_STAGE_RESAMPLE;
-    if (resample) {
+    sp->resample = mask & DABGPU_STAGE_RESAMPLE;
+    if (sp->resample) {
         const int rc = check_resampler(c);
         if (rc) return rc;
     }
+    if (frame_index == 0 || !sp->resample) return DABGPU_OK;
+    if (!have_bits) return fail(c, DABGPU_E_INVALID, "chain seed: no lead-in frame");
+    // Frame frame_index - 1 through everything in front of the Resampler, as complexf whatever the output format, with
+    // the TII parity it has in the stream; on the context's own scratch (lane 0), its CFR statistics in the scratch set
+    // of the chain's internal runs, its launches outside the trace: the most recent chain call stays the one that
+    // dabgpu_get_cfr_stats / dabgpu_get_num_clipped / dabgpu_debug_last_variant describe.
+    c->call_lanes = 1;
+    sp->p = plan_chain(c, true, 1, mask & ~(unsigned)(DABGPU_STAGE_RESAMPLE | DABGPU_STAGE_POLY), false, false);
+    if (sp->p.error) return fail(c, DABGPU_E_INVALID, sp->p.error);
+    if (sp->p.native < (size_t)c->rs_nin) return fail(c, DABGPU_E_INVALID, "chain seed: frame shorter than the halo");
+    return DABGPU_OK;
+}
+
+// d_bits is the lead-in frame in device memory (not read when the call is host-only)
+int run_seed(dabgpu_ctx *c, const SeedPlan &sp, const void *d_bits, uint64_t frame_index, hipStream_t s)
+{
     if (frame_index == 0) {
         // stream start: what dabgpu_set_resampler leaves
-        if (resample) HIPCHK(c, hipMemsetAsync(current_halo(c), 0, (size_t)c->rs_nin * sizeof(float2), s));
+        if (sp.resample) HIPCHK(c, hipMemsetAsync(current_halo(c), 0, (size_t)c->rs_nin * sizeof(float2), s));
         c->tii_insert = true;
         return DABGPU_OK;
     }
-    if (resample) {
-        if (!d_bits) return fail(c, DABGPU_E_INVALID, "chain seed: no lead-in frame");
-        // Frame frame_index - 1 through everything in front of the Resampler, as complexf whatever the output format, with
-        // the TII parity it has in the stream; on the context's own scratch (lane 0), its CFR statistics in the scratch set
-        // of the chain's internal runs, its launches outside the trace: the most recent chain call stays the one that
-        // dabgpu_get_cfr_stats / dabgpu_get_num_clipped / dabgpu_debug_last_variant describe.
-        c->call_lanes = 1;
-        const ChainPlan p = plan_chain(c, true, 1, mask & ~(unsigned)(DABGPU_STAGE_RESAMPLE | DABGPU_STAGE_POLY), false, false);
-        if (p.error) return fail(c, DABGPU_E_INVALID, p.error);
-        if (p.native < (size_t)c->rs_nin) return fail(c, DABGPU_E_INVALID, "chain seed: frame shorter than the halo");
+    if (sp.resample) {
+        const ChainPlan &p = sp.p;
         HIPCHK(c, c->d_a.reserve(p.native * sizeof(float2)));
         // (a seed that fails from here on puts the parity back: never one that belongs to neither stream)
         const bool insert_before = c->tii_insert;
@@ -87,6 +101,30 @@ int seed_dev(dabgpu_ctx *c, const void *d_bits, unsigned mask, uint64_t frame_in
     }
     c->tii_insert = (frame_index & 1) == 0;            // TII on frames 0, 2, 4 ... of the stream (src/TII.cpp:226-242)
     return DABGPU_OK;
+}
+
+int seed_dev(dabgpu_ctx *c, const void *d_bits, unsigned mask, uint64_t frame_index, hipStream_t s)
+{
+    SeedPlan sp;
+    const int rc = plan_seed(c, mask, frame_index, d_bits != nullptr, &sp);
+    return rc ? rc : run_seed(c, sp, d_bits, frame_index, s);
+}
+
+// dabgpu_chain_seed_eti / _dev behind their checks: d_eti holds the n_leadin = min(e, 15 + cifs) ETI frames in front of
+// frame e.  All but the last cifs of them give the history in front of transmission frame e / cifs - 1; that frame then
+// goes through the ordinary front-end -- which leaves the history in front of frame e -- into scratch, and its coded bits
+// seed the chain.  In stream order on s: memset, seed encode, the front-end's encode / assemble / shift, the chain's seed.
+int seed_eti_dev(dabgpu_ctx *c, const void *d_eti, size_t n_leadin, unsigned mask, uint64_t e, hipStream_t s)
+{
+    const size_t cifs = (size_t)c->fe_cifs;
+    SeedPlan sp;
+    int rc = plan_seed(c, mask, e / cifs, true, &sp);
+    if (rc) return rc;
+    if (n_leadin) HIPCHK(c, c->d_fe_seed.reserve(tf_in_bytes(c->g)));
+    const size_t m = n_leadin ? n_leadin - cifs : 0;
+    if ((rc = frontend_seed_rows(c, d_eti, m, s))) return rc;
+    if (n_leadin && (rc = run_frontend(c, (const uint8_t *)d_eti + m * 6144, cifs, c->d_fe_seed.p, s))) return rc;
+    return run_seed(c, sp, c->d_fe_seed.p, e / cifs, s);
 }
 // The time interleaver's history (api_frontend.hip) is stream state the blob does not carry and one transmission frame
 // cannot reproduce (it spans fifteen ETI frames): a context with a configured front-end is not seeded.
@@ -184,6 +222,32 @@ int dabgpu_chain_seed(dabgpu_ctx *c, const uint8_t *leadin_bits, unsigned mask, 
         d_bits = d;
     }
     return seed_dev(c, d_bits, mask, frame_index, c->stream);
+}
+
+int dabgpu_chain_seed_eti_dev(dabgpu_ctx *c, const void *d_eti_leadin, size_t n_leadin, unsigned mask, uint64_t e, void *stream)
+{
+    CTXCHK(c);
+    int rc = frontend_seed_check(c, n_leadin, e, (size_t)kFeHistory + (size_t)(c->fe_configured ? c->fe_cifs : 0));
+    if (rc) return rc;
+    if (n_leadin && !d_eti_leadin) return fail(c, DABGPU_E_INVALID, "null argument");
+    if ((rc = apply_settings(c))) return rc;
+    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;
+    return seed_eti_dev(c, d_eti_leadin, n_leadin, mask, e, stream ? (hipStream_t)stream : c->stream);
+}
+
+int dabgpu_chain_seed_eti(dabgpu_ctx *c, const uint8_t *eti_leadin, size_t n_leadin, unsigned mask, uint64_t e)
+{
+    CTXCHK(c);
+    int rc = frontend_seed_check(c, n_leadin, e, (size_t)kFeHistory + (size_t)(c->fe_configured ? c->fe_cifs : 0));
+    if (rc) return rc;
+    if ((rc = frontend_check_leadin_host(c, eti_leadin, n_leadin))) return rc;
+    if ((rc = apply_settings(c))) return rc;
+    if ((rc = own_stream_joins_lanes(c))) return rc;
+    HostIO io(c);
+    if ((rc = io.in(c->d_fe_eti, eti_leadin, n_leadin * 6144))) return rc;
+    if ((rc = seed_eti_dev(c, c->d_fe_eti.p, n_leadin, mask, e, c->stream))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));               // (the caller's frames have been read)
+    return DABGPU_OK;
 }
 
 }  // extern "C"

@@ -6,7 +6,9 @@
 //                     submit / collect
 //   api_stages.hip    one host-buffer entry point per reference plugin, FormatConverter, CFR statistics
 //   api_state.hip     the stream state (resampler halo, TII frame parity): read, installed, computed from a lead-in frame
-//   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ
+//                     of coded bits or, with the front-end's, from the ETI frames in front of a chunk
+//   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
+//                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
 #pragma once
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
@@ -136,6 +138,7 @@ struct dabgpu_ctx {
     int fe_cifs = 1, fe_fic_out = 288;    // ETI frames per transmission frame; punctured FIC bytes per ETI frame
     std::vector<uint8_t> fe_header;       // bytes 5 ... 8 + 4 NST of the frame the layout was read from (byte 6: MID bits only)
     dabgpu_api::DevBuf d_fe_prbs, d_fe_units, d_fe_owner, d_fe_hist, d_fe_tmp, d_fe_fic, d_fe_eti;
+    dabgpu_api::DevBuf d_fe_seed;          // dabgpu_chain_seed_eti: the coded bits of the lead-in transmission frame
     dabgpu_api::DevBuf d_phase;                        // tool builds only (-DDABGPU_PHASE_TIMING): the frame kernel's per-phase cycle counters
     hipStream_t clip_stream = nullptr;     // stream of the most recent chain call that converted its output
     // TII (f-4): carrier set, the one-frame carrier image and its native-rate response, gain of symbol 1
@@ -265,6 +268,15 @@ int frontend_check_host(dabgpu_ctx *c, const uint8_t *eti, size_t n_eti);
 int frontend_check_shape(dabgpu_ctx *c, size_t n_eti, size_t *n_tf);
 // the two launches and the history's move to the front, on `s`; d_bits receives n_eti / cifs-per-frame x tf_input_bytes
 int run_frontend(dabgpu_ctx *c, const void *d_eti, size_t n_eti, void *d_bits, hipStream_t s);
+// the layout half of frontend_check_host: FICF / NST, the MID bits and the STC words of every frame
+int frontend_check_layout(dabgpu_ctx *c, const uint8_t *eti, size_t n_eti);
+// The seeds (dabgpu_frontend_seed, dabgpu_chain_seed_eti).  _check: configured, e on a transmission frame, n_leadin =
+// min(e, reach); _check_leadin_host: the layout of the lead-in frames and the frame phase of the last one; _rows: the
+// history in front of a frame from the m <= 15 ETI frames before it (device memory), on `s` -- a memset of the rows that
+// lie before the start of the stream and the encode launch's seed form, nothing else
+int frontend_seed_check(dabgpu_ctx *c, size_t n_leadin, uint64_t e, size_t reach);
+int frontend_check_leadin_host(dabgpu_ctx *c, const uint8_t *eti, size_t n_leadin);
+int frontend_seed_rows(dabgpu_ctx *c, const void *d_eti, size_t m, hipStream_t s);
 
 // ---- api_lanes.hip (the streaming host path; eti: `src` holds ETI frames, n_frames still counts transmission frames)
 int chain_submit(dabgpu_ctx *c, const uint8_t *src, size_t n_frames, unsigned mask, bool eti);

@@ -172,6 +172,10 @@ struct FeArgs {
     uint8_t *fic;                         // n_eti x fic_out
     uint8_t *out;                         // n_tf x cifs x (fic_out + kFeCifBytes)
     int n_eti, n_units, cifs, fic_out;
+    // the encode launch: the first unit it runs and the history row frame 0 goes to.  0 and kFeHistory in a call that
+    // produces output (FIC and sub-channels, rows 15 ...); 1 and r0 <= kFeHistory - n_eti for a seed: the sub-channel units
+    // alone, straight into rows r0 ... r0 + n_eti - 1 of the history
+    int unit0, row0;
 };
 hipError_t launch_fe_encode(const FeArgs &a, hipStream_t s);
 hipError_t launch_fe_assemble(const FeArgs &a, hipStream_t s);

@@ -3,6 +3,9 @@
 //   fe_encode_kernel    one workgroup per (ETI frame, unit); a unit is the FIC or one sub-channel.  Energy dispersal
 //                       (PrbsGenerator, src/PrbsGenerator.cpp:112-123), the K = 7 mother code (ConvEncoder,
 //                       src/ConvEncoder.cpp:95-139) and puncturing (PuncturingEncoder, src/PuncturingEncoder.cpp:152-196).
+//                       The seed form of the launch (FeArgs::unit0 = 1, FeArgs::row0 below kFeHistory) runs the sub-channel
+//                       units alone and leaves them in history rows row0 ...: the state in front of a frame, from the frames
+//                       before it, with no FIC, no assembly and no shift behind it.
 //   fe_assemble_kernel  one lane per output dword: the 16-frame time interleaver (src/TimeInterleaver.cpp:66-93), the CIF over
 //                       its padding (FrameMultiplexer, src/FrameMultiplexer.cpp:58-92) and the BlockPartitioner layout
 //                       (src/BlockPartitioner.cpp:111-117).
@@ -48,8 +51,9 @@ __global__ __launch_bounds__(kFeThreads) void fe_encode_kernel(FeArgs a)
     // the dispersed payload as bytes; the unit's output as a bit stream in words whose MSB is the first bit
     __shared__ uint8_t s_in[6144];
     __shared__ uint32_t s_out[kFeRowWords + 1];
-    const int f = blockIdx.x / a.n_units;
-    const FeUnit &u = a.units[blockIdx.x % a.n_units];
+    // (unit0 = 1: the FIC, unit 0, is left out -- the seed form)
+    const int per_frame = a.n_units - a.unit0, f = blockIdx.x / per_frame;
+    const FeUnit &u = a.units[a.unit0 + blockIdx.x % per_frame];
     const uint32_t in_bytes = u.in_bytes, out_words = u.out_bytes / 4;
     const uint8_t *src = a.eti + (size_t)f * 6144 + u.in_off;
     for (uint32_t i = threadIdx.x; i < in_bytes; i += kFeThreads) s_in[i] = src[i] ^ a.prbs[i];
@@ -76,9 +80,10 @@ __global__ __launch_bounds__(kFeThreads) void fe_encode_kernel(FeArgs a)
         uint32_t *dst = (uint32_t *)(a.fic + (size_t)f * a.fic_out);
         for (uint32_t d = threadIdx.x; d < out_words; d += kFeThreads) dst[d] = __builtin_bswap32(s_out[d]);
     } else {
-        // row 15 + f of the history, at the sub-channel's place in the CIF; a capacity unit that a later sub-channel of the
-        // STC list covers as well is that one's (the reference's memcpy order: the last one wins)
-        uint32_t *dst = (uint32_t *)(a.hist + (size_t)(kFeHistory + f) * kFeCifBytes + u.dst_off);
+        // row row0 + f of the history (15 + f in a call that produces output), at the sub-channel's place in the CIF; a
+        // capacity unit that a later sub-channel of the STC list covers as well is that one's (the reference's memcpy order:
+        // the last one wins)
+        uint32_t *dst = (uint32_t *)(a.hist + (size_t)(a.row0 + f) * kFeCifBytes + u.dst_off);
         const int16_t *own = a.owner + (u.dst_off >> 3);
         for (uint32_t d = threadIdx.x; d < out_words; d += kFeThreads)
             if (own[d >> 1] == u.owner) dst[d] = __builtin_bswap32(s_out[d]);
@@ -124,8 +129,11 @@ __global__ __launch_bounds__(kFeThreads) void fe_assemble_kernel(FeArgs a, size_
 
 hipError_t launch_fe_encode(const FeArgs &a, hipStream_t s)
 {
-    if (a.n_eti <= 0 || a.n_units <= 0) return hipSuccess;
-    DABGPU_LAUNCH(fe_encode_kernel, dim3((unsigned)a.n_eti * (unsigned)a.n_units), dim3(kFeThreads), 0, s, a);
+    // (the rows a launch may write: the history and the call's own in the ordinary form, the history alone in the seed form)
+    if (a.unit0 < 0 || a.unit0 > 1 || a.row0 < 0 || (a.unit0 ? a.row0 + a.n_eti > kFeHistory : a.row0 != kFeHistory))
+        return hipErrorInvalidValue;
+    if (a.n_eti <= 0 || a.n_units - a.unit0 <= 0) return hipSuccess;
+    DABGPU_LAUNCH(fe_encode_kernel, dim3((unsigned)a.n_eti * (unsigned)(a.n_units - a.unit0)), dim3(kFeThreads), 0, s, a);
     return hipGetLastError();
 }
 

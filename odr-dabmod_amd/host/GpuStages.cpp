@@ -993,6 +993,26 @@ void DabGpuChain::set_stream_state(const std::vector<uint8_t> &blob)
     m_ctx.check(dabgpu_set_stream_state(m_ctx.get(), blob.data(), blob.size()));
 }
 
+std::vector<uint8_t> DabGpuChain::frontend_state()
+{
+    std::vector<uint8_t> blob(dabgpu_frontend_state_bytes(m_ctx.get()));
+    size_t n = 0;
+    m_ctx.check(dabgpu_frontend_get_state(m_ctx.get(), blob.data(), blob.size(), &n));
+    blob.resize(n);
+    return blob;
+}
+
+void DabGpuChain::set_frontend_state(const std::vector<uint8_t> &blob)
+{
+    m_ctx.check(dabgpu_frontend_set_state(m_ctx.get(), blob.data(), blob.size()));
+}
+
+void DabGpuChain::seed_eti(const void *frames, size_t n_leadin, uint64_t e)
+{
+    before_frames();            // (the lead-in transmission frame runs under the settings the frames behind it run under)
+    m_ctx.check(dabgpu_chain_seed_eti(m_ctx.get(), static_cast<const uint8_t *>(frames), n_leadin, stage_mask(), e));
+}
+
 size_t DabGpuChain::collect(const void **iq)
 {
     size_t n = 0;

@@ -448,7 +448,7 @@ public:
     // finds (src/DabMod.cpp:684-693) -- and starts a stream (zero time-interleaver history); submit_eti() is submit() from
     // n_eti raw ETI frames, whole transmission frames (4 / 1 / 1 / 2 per frame in modes I ... IV), in place of the
     // sub-graph cifFicPrbs ... cifPart (src/DabModulator.cpp:281-385) and the chain behind it.  A frame of another layout
-    // throws ("FrameMultiplexer detected ...") and leaves the stream where it was.  Not together with seed().
+    // throws ("FrameMultiplexer detected ...") and leaves the stream where it was.  Not together with seed(): seed_eti() below.
     void configure_frontend(const void *frame6144);
     void submit_eti(const void *eti_frames, size_t n_eti);
     // One stream over several chains, or a stream moved from one chain to another (include/dabgpu.h, "stream state"):
@@ -459,6 +459,13 @@ public:
     void seed(const void *leadin_bits, uint64_t frame_index);
     std::vector<uint8_t> get_stream_state();
     void set_stream_state(const std::vector<uint8_t> &blob);
+    // The same for a chain fed from ETI frames (include/dabgpu.h, "front-end stream state"): the time interleaver's last
+    // fifteen punctured frames are a blob of their own -- a whole ETI-fed stream is moved with get_stream_state() AND
+    // frontend_state() --, and seed_eti() puts front-end and chain where they are in front of ETI frame e (a multiple of
+    // the 4 / 1 / 1 / 2 frames per transmission frame) from the n_leadin = min(e, 15 + that count) frames before it.
+    std::vector<uint8_t> frontend_state();
+    void set_frontend_state(const std::vector<uint8_t> &blob);
+    void seed_eti(const void *frames, size_t n_leadin, uint64_t e);
     size_t input_bytes_per_frame() const { return m_in_bytes; }
     size_t output_bytes_per_frame() const;
     int process(Buffer *const dataIn, Buffer *dataOut) override;

@@ -34,6 +34,14 @@
 //                        on a stream whose FP jumps (the CPU front-end never looks at FP after the start) the program
 //                        stops with that message.  Not with --contexts above 1 (the time interleaver's history is not part of the stream state a
 //                        chain is seeded with), --bits-only or --separate-converter.
+//   --state-out FILE     with --gpu-frontend: after the last frame, write where the stream stands -- the number of ETI frames
+//                        modulated since FP = 0 and both stream-state blobs (DabGpuChain::get_stream_state /
+//                        frontend_state) -- so that another run continues it
+//   --state-in FILE      with --gpu-frontend: continue the stream a --state-out run left.  The input is the ETI frames that
+//                        follow: no skipping to FP = 0, the first frame must open a transmission frame (FP a multiple of
+//                        4 / 1 / 1 / 2 in modes I ... IV); the layout is read from it and both blobs are installed.  The
+//                        two runs' output files, one behind the other, are the file one run over the whole input writes.
+//                        (Both need --gpu-frontend: the CPU front-end's time interleaver is host state the file does not carry.)
 #include "Frontend.h"
 #include "GpuStages.h"
 
@@ -43,6 +51,7 @@
 #include <deque>
 #include <fstream>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -59,8 +68,51 @@ namespace {
                          "                        (batch j to chain j mod N, seeded from the frame before it; the same bytes as N = 1;\n"
                          "                        N > 1 not with --bits-only or --separate-converter)\n"
                          "       [--gpu-frontend]   ETI -> coded bits on the device as well (not with --contexts above 1, --bits-only,\n"
-                         "                        --separate-converter)\n");
+                         "                        --separate-converter)\n"
+                         "       [--state-out FILE] [--state-in FILE]   with --gpu-frontend: leave / take up the stream's state\n");
     std::exit(2);
+}
+
+// --state-out / --state-in: "DABMODST", uint64 version 1, uint64 ETI frames modulated since FP = 0, then the front-end blob
+// and the chain's stream-state blob, each behind its uint64 length (the blobs describe themselves: include/dabgpu.h)
+struct StreamStateFile {
+    uint64_t n_eti;
+    std::vector<uint8_t> frontend, chain;
+};
+const char kStateMagic[8] = {'D', 'A', 'B', 'M', 'O', 'D', 'S', 'T'};
+
+void write_state(const std::string &path, const StreamStateFile &st)
+{
+    std::ofstream f(path, std::ios::binary);
+    const uint64_t head[2] = {1, st.n_eti};
+    f.write(kStateMagic, sizeof kStateMagic);
+    f.write(reinterpret_cast<const char *>(head), sizeof head);
+    for (const std::vector<uint8_t> *b : {&st.frontend, &st.chain}) {
+        const uint64_t n = b->size();
+        f.write(reinterpret_cast<const char *>(&n), sizeof n);
+        f.write(reinterpret_cast<const char *>(b->data()), static_cast<std::streamsize>(n));
+    }
+    if (!f.flush()) throw std::runtime_error("cannot write " + path);
+}
+
+StreamStateFile read_state(const std::string &path)
+{
+    std::ifstream f(path, std::ios::binary);
+    char magic[8];
+    uint64_t head[2];
+    StreamStateFile st{};
+    if (!f.read(magic, sizeof magic) || std::memcmp(magic, kStateMagic, sizeof magic) != 0 ||
+        !f.read(reinterpret_cast<char *>(head), sizeof head) || head[0] != 1)
+        throw std::runtime_error(path + " is not a stream state written by --state-out");
+    st.n_eti = head[1];
+    for (std::vector<uint8_t> *b : {&st.frontend, &st.chain}) {
+        uint64_t n = 0;
+        if (!f.read(reinterpret_cast<char *>(&n), sizeof n) || n > (1u << 24)) throw std::runtime_error(path + " is cut short");
+        b->resize(n);
+        if (n && !f.read(reinterpret_cast<char *>(b->data()), static_cast<std::streamsize>(n)))
+            throw std::runtime_error(path + " is cut short");
+    }
+    return st;
 }
 }  // namespace
 
@@ -78,6 +130,7 @@ int main(int argc, char **argv)
     bool reference_latency = false;
     long contexts = 1;
     bool gpu_frontend = false;
+    std::string state_in, state_out;
     try {
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
@@ -113,6 +166,8 @@ int main(int argc, char **argv)
             else if (a == "--reference-latency") reference_latency = true;
             else if (a == "--reference-gain") gs.referenceGainRounding = true;
             else if (a == "--gpu-frontend") gpu_frontend = true;
+            else if (a == "--state-in") state_in = val();
+            else if (a == "--state-out") state_out = val();
             else if (a == "--contexts") {
                 const std::string v = val();
                 size_t used = 0;
@@ -130,6 +185,13 @@ int main(int argc, char **argv)
                                         "the stream state a chain is seeded with"
                          : bits_only  ? "--bits-only: the coded bits stay on the device"
                                       : "--separate-converter: the streaming path converts inside the chain");
+            return 2;
+        }
+
+        if (!gpu_frontend && !(state_in.empty() && state_out.empty())) {
+            std::fprintf(stderr, "dabmod_file: %s does not go with the CPU front-end (it needs --gpu-frontend): the CPU front-end's "
+                                 "time interleaver is host state the file does not carry\n",
+                         state_in.empty() ? "--state-out" : "--state-in");
             return 2;
         }
 
@@ -184,6 +246,7 @@ int main(int argc, char **argv)
         std::vector<uint8_t> pending_eti;
         std::deque<std::vector<uint8_t>> held_eti;
         size_t cifs = 1, n_gated = 0;             // ETI frames per transmission frame; frames since the one with FP = 0
+        uint64_t n_before = 0;                    // --state-in: ETI frames the runs before this one modulated
         auto submit_eti_batch = [&](size_t frames) {
             if (in_flight == 2) drain_one();
             ++n_batches;
@@ -199,16 +262,28 @@ int main(int argc, char **argv)
                 ++n_eti;
                 if (gpu_frontend) {
                     if (!chain) {
-                        if ((frame[6] >> 5) != 0) continue;          // align the frame groups (src/DabMod.cpp:684-693)
+                        // align the frame groups (src/DabMod.cpp:684-693); a continued stream is aligned where it was left
+                        if (state_in.empty() && (frame[6] >> 5) != 0) continue;
                         if (gs.dabMode == 0) {
                             const unsigned mid = (frame[6] >> 3) & 3;
                             gs.dabMode = mid ? mid : 4;
                         }
                         cifs = gs.dabMode == 1 ? 4 : gs.dabMode == 4 ? 2 : 1;
+                        if (!state_in.empty() && (frame[6] >> 5) % cifs) {
+                            std::fprintf(stderr, "dabmod_file: --state-in: the first frame must open a transmission frame (FP = %u, "
+                                                 "not a multiple of %zu)\n", unsigned(frame[6] >> 5), cifs);
+                            return 1;
+                        }
                         gs.outputFormat = format;
                         gs.maxBatchFrames = batch;
                         chain.reset(new DabGpuChain(gs));
                         chain->configure_frontend(frame);
+                        if (!state_in.empty()) {
+                            const StreamStateFile st = read_state(state_in);
+                            chain->set_frontend_state(st.frontend);
+                            chain->set_stream_state(st.chain);
+                            n_before = st.n_eti;
+                        }
                     }
                     if (++n_gated % cifs == 0) ++n_tf;
                     if (reference_latency) {
@@ -290,11 +365,17 @@ int main(int argc, char **argv)
             const size_t rest = pending_eti.size() / (cifs * 6144);
             if (rest) submit_eti_batch(rest);
             while (in_flight) drain_one();
+            if (!state_out.empty())
+                write_state(state_out, {n_before + n_submitted * cifs, chain->frontend_state(), chain->get_stream_state()});
         } else if (chain && batch > 1 && !separate_converter) {
             // the tail: a last, shorter batch, then whatever is still in flight, in order
             const size_t rest = pending.size() / chain->input_bytes_per_frame();
             if (rest) submit_batch(rest);
             while (in_flight) drain_one();
+        }
+        if (gpu_frontend && !chain && !state_out.empty()) {
+            std::fprintf(stderr, "dabmod_file: --state-out: no frame was modulated, there is no state to write\n");
+            return 1;
         }
         if (bits_only) n_out = n_tf;
         std::fprintf(stderr, "dabmod_file: %zu ETI frames -> %zu transmission frames in, %zu out (mode %u)", n_eti, n_tf, n_out, gs.dabMode);

@@ -2,7 +2,8 @@
 stream of transmission frames (frames are independent units, so the
 path shards with NO data-path collective) -- or, with partition_chunks / my_chunks /
 PartitionedStream, its share of ONE stream, whose state in front of a chunk follows
-from the one frame before it.  torch.distributed (backend "nccl" =
+from the one frame before it (from the ETI frames eti_leadin names, where the front-end
+runs on the device too).  torch.distributed (backend "nccl" =
 RCCL on ROCm, "gloo" in CPU tests) is used only to bracket the timed region and
 to combine the ranks' clocks."""
 import os
@@ -24,6 +25,17 @@ def partition_chunks(n_frames, chunk, parts):
     for j, start in enumerate(range(0, n_frames, chunk)):
         out[j % parts].append((start, min(start + chunk, n_frames)))
     return out
+
+
+def eti_leadin(e, cifs, with_chain=True):
+    """The ETI frames a context reads to take a stream up at ETI frame `e` (a multiple of cifs, the frames per
+    transmission frame): (start, stop) with stop = e.  The time interleaver looks fifteen frames back (Modulator.frontend_seed);
+    with the chain behind it the transmission frame in front of e is needed whole, and the fifteen frames in front of THAT
+    one (Modulator.seed_eti).  Shorter where the stream starts."""
+    e, cifs = int(e), int(cifs)
+    if e < 0 or cifs < 1 or e % cifs:
+        raise ValueError("eti_leadin: e >= 0, a multiple of cifs >= 1")
+    return max(0, e - (15 + (cifs if with_chain else 0))), e
 
 
 class PartitionedStream:
@@ -66,6 +78,52 @@ class PartitionedStream:
             md = self.mods[i]
             md.seed_dev(d_bits[start - 1] if start else None, stages, start, queued=True)
             md.chain_dev_queued(d_bits[start:stop], stop - start, stages, d_out[start:stop])
+        for md in self.mods:
+            md.synchronize()
+        if not host:
+            return d_out
+        res = d_out.cpu().numpy()
+        if out is not None:
+            np.copyto(out.reshape(res.shape), res)
+            return out.reshape(res.shape)
+        return res
+
+
+    def modulate_eti(self, eti, stages, chunk, out=None):
+        """modulate() from raw ETI frames: eti is n x 6144 bytes of consecutive frames, frame 0 the start of the stream (FP =
+        0), whole transmission frames -- a numpy array or a torch uint8 tensor on the GPU; `chunk` counts transmission
+        frames.  Every context has been configured from eti[0] by the caller (Modulator.frontend_configure).  Chunk j goes
+        to context j mod N, which first seeds front-end and chain from the frames in front of the chunk (eti_leadin,
+        Modulator.seed_eti_dev) and then runs the chunk from the device's copy of the frames; the coded bits never leave
+        the device.  Returns the bytes one context's chain_eti gives for the whole stream."""
+        import torch
+        md0 = self.mods[0]
+        cifs = {1: 4, 2: 1, 3: 1, 4: 2}[md0.geometry["mode"]]
+        per = md0.geometry["tf_input_bytes"]
+        host = not isinstance(eti, torch.Tensor)
+        dev = torch.device("cuda", md0.device)
+        d_eti = (torch.from_numpy(np.ascontiguousarray(eti, np.uint8).reshape(-1, 6144)).to(dev) if host
+                 else eti.reshape(-1, 6144))
+        if d_eti.shape[0] % cifs:
+            raise ValueError("PartitionedStream: ETI frames come as whole transmission frames (a multiple of %d)" % cifs)
+        n = d_eti.shape[0] // cifs
+        dt = np.dtype(getattr(md0, "_out_dtype", np.complex64))
+        per_out = md0.out_bytes_per_frame(stages) // dt.itemsize
+        tdt = {"complex64": torch.complex64, "int16": torch.int16, "uint8": torch.uint8, "int8": torch.int8}[dt.name]
+        d_out = out if (out is not None and not host) else torch.empty((n, per_out), dtype=tdt, device=dev)
+        if d_out.numel() != n * per_out or d_out.dtype != tdt or not d_out.is_contiguous():
+            raise ValueError("PartitionedStream: output tensor does not match (%s, %d elements, contiguous)" % (tdt, n * per_out))
+        d_out = d_out.reshape(n, per_out)
+        # the coded bits of a chunk: scratch per context (a context's calls run in order)
+        d_bits = [torch.empty((min(int(chunk), max(n, 1)), per), dtype=torch.uint8, device=dev) for _ in self.mods]
+        torch.cuda.current_stream(dev).synchronize()          # (the input is in place before any context reads it)
+        chunks = sorted((c, i) for i, part in enumerate(partition_chunks(n, chunk, len(self.mods))) for c in part)
+        for (start, stop), i in chunks:
+            md = self.mods[i]
+            a, e = eti_leadin(start * cifs, cifs)
+            md.seed_eti_dev(d_eti[a:e] if e > a else None, e - a, stages, e, queued=True)
+            md.chain_eti_dev_queued(d_eti[e:stop * cifs], (stop - start) * cifs, stages, d_bits[i][:stop - start],
+                                    d_out[start:stop])
         for md in self.mods:
             md.synchronize()
         if not host:
