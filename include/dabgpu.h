@@ -201,11 +201,34 @@ DABGPU_API int dabgpu_tii_process(dabgpu_ctx *ctx, const void *in, size_t in_byt
 
 /* CicEqualizer(nbCarriers, spacing, R)::process, src/CicEqualizer.cpp:29-91: every
  * symbol of `carriers` samples times the per-carrier compensation gain of an R-fold, 4-stage CIC
- * interpolator.  Stage drop-in only: the fused chain does not apply it (the reference wires it in only
- * when an FPGA clockRate is configured, src/DabModulator.cpp:154-176). */
+ * interpolator.  The stage drop-in; in the fused chain it is a setting, dabgpu_set_cic_equalizer below (the reference wires it in
+ * only when an FPGA clockRate is configured, src/DabModulator.cpp:154-176). */
 DABGPU_API int dabgpu_cic_equalizer_process(dabgpu_ctx *ctx, size_t spacing, int R, const void *in,
                                             size_t in_bytes, void *out, size_t out_cap,
                                             size_t *out_bytes);
+/* CicEqualizer inside the fused chain: the reference's decision to wire it in (src/DabModulator.cpp:155-176: a configured
+ * dac_clk_rate gives cic_ratio = clockRate / outputRate / 4 and the constructor arguments (carriers, spacing * outputRate /
+ * 2048000, cic_ratio)) stays with the caller; this is its result.  enable = 0 (the default): no equaliser, spacing and R are
+ * ignored.  enable with spacing == 0 or R <= 0 is DABGPU_E_INVALID with the stage entry's message.  While it is on, every chain
+ * call (dabgpu_chain_process / _process_dev / _submit / _process_eti / _submit_eti, the seeds) runs carriers first: ONE kernel
+ * forms the equalised carriers of the call's frames from the coded bits -- cifMap ... cifSig with the TII symbol in place of
+ * the null symbol on the frames that carry it, times the per-carrier factor as CicEqualizer::process does
+ * (src/CicEqualizer.cpp:66-91) -- and the from-carriers chain (what dabgpu_symbols_process_dev runs) does the rest, with every
+ * gain mode, filter, window, CFR, resampler, predistorter and output format; dabgpu_symbols_process_dev equalises the carriers
+ * it is handed (the reference's cifCicEq sits behind cifSig, :399).  The stage entry above keeps a table of its own.  The
+ * table is a setting like the taps: it takes effect at the next *_process call, after the context has drained. */
+DABGPU_API int dabgpu_set_cic_equalizer(dabgpu_ctx *ctx, int enable, size_t spacing, int R);
+/* Coded bits -> the SignalMultiplexer output, (nb_symbols + 1) x carriers cf32 per frame in the order
+ * dabgpu_symbols_process_dev takes: the sub-graph cifMap -> cifFreq -> cifDiff(+cifRef) -> cifSig(+NullSymbol / TII)
+ * [-> cifCicEq] of src/DabModulator.cpp:385-399 in one kernel, bit for bit the reference's classes
+ * (QpskSymbolMapper::process, src/QpskSymbolMapper.cpp:39-213 ... CicEqualizer::process, src/CicEqualizer.cpp:66-91).  With
+ * the context's TII and CIC settings; consecutive frames of the stream: advances the TII frame parity like a chain call.
+ * in_bytes: a whole number of frames of tf_input_bytes, anything else is DABGPU_E_INVALID. */
+DABGPU_API int dabgpu_carriers_process(dabgpu_ctx *ctx, const uint8_t *bits, size_t in_bytes, void *out, size_t out_cap,
+                                       size_t *out_bytes);
+/* same (src/DabModulator.cpp:385-399), device-resident and asynchronous on `stream` (NULL: the context's own stream, behind every lane) */
+DABGPU_API int dabgpu_carriers_process_dev(dabgpu_ctx *ctx, const void *d_bits, size_t n_frames, void *d_carriers,
+                                           size_t out_cap, size_t *out_bytes, void *stream);
 
 /* FormatConverter::process, float input path, src/FormatConverter.cpp:111-178:
  * cf32 -> interleaved s16 / u8 / s8 with the reference's range test, truncation toward zero and

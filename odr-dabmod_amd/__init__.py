@@ -42,6 +42,7 @@ EXPORTS = [
     "dabgpu_frontend_process_dev", "dabgpu_chain_process_eti", "dabgpu_chain_submit_eti",
     "dabgpu_frontend_state_bytes", "dabgpu_frontend_get_state", "dabgpu_frontend_set_state",
     "dabgpu_frontend_seed", "dabgpu_frontend_seed_dev", "dabgpu_chain_seed_eti", "dabgpu_chain_seed_eti_dev",
+    "dabgpu_set_cic_equalizer", "dabgpu_carriers_process", "dabgpu_carriers_process_dev",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -163,6 +164,9 @@ def load_library():
     lib.dabgpu_set_cfr.argtypes = [vp, C.c_int, C.c_float, C.c_float]
     lib.dabgpu_get_cfr_stats.argtypes = [vp, sz, C.POINTER(_CfrStats)]
     lib.dabgpu_cic_equalizer_process.argtypes = [vp, sz, C.c_int, vp, sz, vp, sz, szp]
+    lib.dabgpu_set_cic_equalizer.argtypes = [vp, C.c_int, sz, C.c_int]
+    lib.dabgpu_carriers_process.argtypes = [vp, vp, sz, vp, sz, szp]
+    lib.dabgpu_carriers_process_dev.argtypes = [vp, vp, sz, vp, sz, szp, vp]
     lib.dabgpu_set_tii.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.dabgpu_tii_process.argtypes = [vp, vp, sz, vp, sz, szp]
     lib.dabgpu_format_size.argtypes = [C.c_int]
@@ -379,6 +383,34 @@ class Modulator:
         self._chk(self._lib.dabgpu_cic_equalizer_process(self._h, spacing, R, x.ctypes.data, x.nbytes,
                                                          out.ctypes.data, out.nbytes, C.byref(n)))
         return out
+
+    def set_cic_equalizer(self, enable, spacing=0, R=0):
+        """CicEqualizer(carriers, spacing, R) between cifSig and cifOfdm of every chain call (src/DabModulator.cpp:155-176,
+        :399): the chain then forms the equalised carriers first (one kernel) and runs from carriers.  Off by default."""
+        self._chk(self._lib.dabgpu_set_cic_equalizer(self._h, int(bool(enable)), int(spacing), int(R)))
+
+    def carriers(self, bits):
+        """Host path: coded bits (n_frames x tf_input_bytes uint8) -> the SignalMultiplexer output, complex64
+        (n_frames x (nb_symbols + 1) * carriers), with the TII and CIC settings applied; advances the TII frame parity."""
+        bits = np.ascontiguousarray(bits, np.uint8).reshape(-1)
+        g = self.geometry
+        per_out = (g["nb_symbols"] + 1) * g["carriers"]
+        n = bits.size // g["tf_input_bytes"]
+        out = np.empty(max(n, 1) * per_out, np.complex64)
+        ob = C.c_size_t()
+        self._chk(self._lib.dabgpu_carriers_process(self._h, bits.ctypes.data, bits.size, out.ctypes.data, out.nbytes,
+                                                    C.byref(ob)))
+        return out[:ob.value // 8].reshape(n, per_out)
+
+    def carriers_dev(self, d_bits, n_frames, d_out, stream=None):
+        """Device path on torch tensors (coded bits -> carriers), asynchronous on the stream as chain_dev."""
+        s = self._stream_handle(d_bits, stream)
+        ob = C.c_size_t()
+        self._chk(self._lib.dabgpu_carriers_process_dev(self._h, d_bits.data_ptr(), n_frames, d_out.data_ptr(),
+                                                        d_out.numel() * d_out.element_size(), C.byref(ob), s))
+        if not s:
+            self.synchronize()
+        return ob.value
 
     def set_tii(self, enable, comb=0, pattern=0, old_variant=False):
         self._chk(self._lib.dabgpu_set_tii(self._h, int(enable), comb, pattern, int(old_variant)))

@@ -168,10 +168,22 @@ size_t out_samples_per_frame(const Geometry &g, const Settings &st, unsigned mas
 // outside the launchers.
 // from_bits: the input is coded bits, else carriers.  keep_stats: the CFR statistics are the caller's to read (a chain call);
 // false for the chain's internal runs (the TII segment, the pieces of the hand-over).
-ChainPlan plan_chain(const dabgpu_ctx *c, bool from_bits, size_t n_frames, unsigned mask, bool apply_format, bool keep_stats)
+// cic: carriers first -- the front kernel (coded bits -> equalised carriers, or cic_kernel on the caller's carriers) into
+// d_car, then exactly the plan this function gives for the same mask from carriers.
+ChainPlan plan_chain(const dabgpu_ctx *c, bool from_bits, size_t n_frames, unsigned mask, bool apply_format, bool keep_stats,
+                     bool cic)
 {
     const Settings &st = c->cur;
     const Geometry &g = c->g;
+    if (cic) {
+        ChainPlan p = plan_chain(c, /*from_bits=*/false, n_frames, mask, apply_format, keep_stats, false);
+        p.front = from_bits ? ChainPlan::FRONT_BITS : ChainPlan::FRONT_CIC;
+        if (!p.error && n_frames) {
+            p.scratch.d_car = n_frames * (size_t)(g.nb_symbols + 1) * (size_t)g.K * sizeof(float2);
+            p.scratch_bytes += p.scratch.d_car;
+        }
+        return p;
+    }
     ChainPlan p;
     p.from_bits = from_bits;
     p.keep_stats = keep_stats;
@@ -487,6 +499,62 @@ int run_native_tii(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, float2 *
     return DABGPU_OK;
 }
 
+// The TII carrier set the carriers kernel reads, for the settings in force.  One buffer for all lanes: kernels in flight on
+// another lane read the old set -- they finish before it is rewritten (as ensure_tii_segment does with its tables).
+int ensure_carrier_acp(dabgpu_ctx *c, hipStream_t s)
+{
+    if (c->car_acp_comb == c->cur.tii_comb && c->car_acp_pattern == c->cur.tii_pattern) return DABGPU_OK;
+    std::vector<uint8_t> acp;
+    if (tii_carrier_set(c->g.mode, c->cur.tii_comb, c->cur.tii_pattern, acp))
+        return fail(c, DABGPU_E_INVALID, "TII::enable_carrier invalid k!");
+    const int rc = drain_lanes(c);
+    if (rc) return rc;
+    c->car_acp_comb = c->car_acp_pattern = -1;
+    HIPCHK(c, upload(c->d_car_acp, acp, s));              // (waits for s: the set is complete before any lane reads it)
+    c->car_acp_comb = c->cur.tii_comb;
+    c->car_acp_pattern = c->cur.tii_pattern;
+    return DABGPU_OK;
+}
+
+// coded bits -> carriers (carriers_from_bits_kernel) for n_frames frames of the stream, from the TII parity as it stands
+int run_carriers(dabgpu_ctx *c, const void *d_bits, size_t n_frames, float2 *d_car, bool cic, hipStream_t s)
+{
+    CarrierArgs a{};
+    a.g = c->g;
+    a.t = tables_of(c);
+    a.bits = (const uint8_t *)d_bits;
+    a.out = d_car;
+    a.n_frames = (int)n_frames;
+    a.cic = cic ? (const float *)c->d_cic_chain.p : nullptr;
+    if (c->cur.tii_enable && (c->g.mode == 1 || c->g.mode == 2)) {
+        const int rc = ensure_carrier_acp(c, s);
+        if (rc) return rc;
+        a.acp = (const uint8_t *)c->d_car_acp.p;
+        a.tii_old_variant = c->cur.tii_old_variant ? 1 : 0;
+        a.tii_insert0 = c->tii_insert ? 1 : 0;
+    }
+    HIPCHK(c, launch_carriers_from_bits(a, s));
+    return DABGPU_OK;
+}
+
+// The front kernel of a carriers-first plan: *d_in (coded bits, or the caller's carriers) -> d_car, which *d_in then names.
+// CicEqualizer sits behind cifSig (src/DabModulator.cpp:399), so carriers handed in are equalised as they are.
+int run_front(dabgpu_ctx *c, const ChainPlan &p, const void **d_in, hipStream_t s)
+{
+    if (p.front == ChainPlan::FRONT_NONE) return DABGPU_OK;
+    HIPCHK(c, c->d_car.reserve(p.scratch.d_car));
+    float2 *car = (float2 *)c->d_car.p;
+    if (p.front == ChainPlan::FRONT_BITS) {
+        const int rc = run_carriers(c, *d_in, p.n_frames, car, true, s);
+        if (rc) return rc;
+    } else {
+        HIPCHK(c, launch_cic((const float2 *)*d_in, p.n_frames * (size_t)(c->g.nb_symbols + 1) * (size_t)c->g.K, c->g.K,
+                             (const float *)c->d_cic_chain.p, car, s));
+    }
+    *d_in = car;
+    return DABGPU_OK;
+}
+
 // The tail of the chain, cifRes -> cifPoly (src/DabModulator.cpp:403-419), on n samples at d_in into d_out (n_out samples):
 // the polynomial predistorter is an epilogue of the x2 / x4 resampler's store (fuse_poly; LUT mode is not), otherwise a kernel
 // of its own behind it, reading the resampled stream from d_b (d_b_bytes: what the caller's plan sized it to).
@@ -536,6 +604,8 @@ int run_chain(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, void *d_out_v
     }
     const bool post = p.mask & (DABGPU_STAGE_RESAMPLE | DABGPU_STAGE_POLY);
     if (post) HIPCHK(c, c->d_a.reserve(p.scratch.d_a));
+    // carriers first (the CIC equaliser): from here on d_in names the equalised carriers and p the from-carriers chain
+    if ((rc = run_front(c, p, &d_in, s))) return rc;
 
     if (p.piece) {
         // the hand-over in pieces: a two-piece ring in d_a, the producer (every piece with a plan of its own) on lane 1's stream
@@ -579,7 +649,7 @@ int run_chain(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, void *d_out_v
             return rc;
     }
     // the insert flag toggles once per frame of the stream whether or not TII is enabled (src/TII.cpp:241-242)
-    if (p.from_bits && (n_frames & 1)) c->tii_insert = !c->tii_insert;
+    if ((p.from_bits || p.front == ChainPlan::FRONT_BITS) && (n_frames & 1)) c->tii_insert = !c->tii_insert;
     if (p.scratch.d_fmt) HIPCHK(c, launch_format((const float *)d_out, 2 * n_frames * per, p.fmt, d_out_v, clip, s));
     return DABGPU_OK;
 }
@@ -608,6 +678,45 @@ int dabgpu_symbols_process_dev(dabgpu_ctx *c, const void *d_car, size_t n_frames
 {
     CTXCHK(c);
     return chain_dev(c, d_car, false, n_frames, mask, d_iq, out_cap, out_bytes, stream);
+}
+
+// coded bits -> carriers: cifMap ... cifSig [-> cifCicEq] by itself (src/DabModulator.cpp:385-399)
+int dabgpu_carriers_process_dev(dabgpu_ctx *c, const void *d_bits, size_t n_frames, void *d_carriers, size_t out_cap,
+                                size_t *out_bytes, void *stream)
+{
+    CTXCHK(c);
+    int rc = apply_settings(c);
+    if (rc) return rc;
+    const size_t need = n_frames * (size_t)(c->g.nb_symbols + 1) * (size_t)c->g.K * sizeof(float2);
+    if ((rc = check_out(c, need, out_cap, out_bytes))) return rc;
+    if (n_frames == 0) return DABGPU_OK;
+    if (!d_bits || !d_carriers) return fail(c, DABGPU_E_INVALID, "null argument");
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;
+    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
+    if ((rc = run_carriers(c, d_bits, n_frames, (float2 *)d_carriers, chain_cic(c), s))) return rc;
+    if (n_frames & 1) c->tii_insert = !c->tii_insert;          // like a chain call (src/TII.cpp:241-242)
+    return DABGPU_OK;
+}
+
+int dabgpu_carriers_process(dabgpu_ctx *c, const uint8_t *bits, size_t in_bytes, void *out, size_t out_cap, size_t *out_bytes)
+{
+    CTXCHK(c);
+    const size_t per = tf_in_bytes(c->g);
+    if (!bits || in_bytes == 0 || in_bytes % per)
+        return fail(c, DABGPU_E_INVALID, "carriers: input size not valid (whole transmission frames of coded bits)");
+    const size_t n_frames = in_bytes / per;
+    if (n_frames > (size_t)c->max_frames) return fail(c, DABGPU_E_CAPACITY, "n_frames exceeds max_frames of the context");
+    const size_t need = n_frames * (size_t)(c->g.nb_symbols + 1) * (size_t)c->g.K * sizeof(float2);
+    int rc = check_out(c, need, out_cap, out_bytes);
+    if (rc) return rc;
+    if ((rc = dabgpu_synchronize(c))) return rc;               // (d_in / d_out are the synchronous host path's)
+    HostIO io(c);
+    if ((rc = io.in(c->d_in, bits, in_bytes))) return rc;
+    HIPCHK(c, c->d_out.reserve(need));
+    size_t ob = 0;
+    if ((rc = dabgpu_carriers_process_dev(c, c->d_in.p, n_frames, c->d_out.p, need, &ob, c->stream))) return rc;
+    return io.out(out, c->d_out.p, need);
 }
 
 // cifRes -> cifPoly on a native-rate stream that is already in device memory: the tail of the chain by itself
@@ -648,7 +757,7 @@ int dabgpu_chain_process(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, un
     c->clip_from_collect = false;
     int rc = apply_settings(c);
     if (rc) return rc;
-    const ChainPlan p = plan_chain(c, true, n_frames, mask);
+    const ChainPlan p = plan_chain(c, true, n_frames, mask, true, true, chain_cic(c));
     const size_t need = p.out_bytes;
     if ((rc = check_out(c, need, out_cap, out_bytes))) return rc;
     HostIO io(c);

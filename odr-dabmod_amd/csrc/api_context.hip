@@ -25,6 +25,7 @@ const float kDefaultTaps[45] = {
     -0.00183473504148f, -0.00254214904271f, 0.00419321097434f, -0.00355578539893f,
     0.00184351124335f, -0.000187368263141f, -0.000840645749122f, 0.00120703084394f,
     -0.00110450468492f};
+const char *const kCicBadParameters = "CicEqualizer: spacing and R must be positive";
 }  // namespace dabgpu_api
 namespace {
 
@@ -287,8 +288,10 @@ int apply_settings_groups(dabgpu_ctx *c)
     const bool window_changed = c->cur.overlap && (first || prev.window_key() != c->cur.window_key());
     const bool coef_changed = first || !prev.coef_equal(c->cur);
     const bool rs_changed = first || prev.resampler_key() != c->cur.resampler_key() || c->cur.resampler_reset;
+    // (off: the table is not read, and the next time the equaliser is turned on the keys differ again)
+    const bool cic_changed = c->cur.cic_on() && (first || prev.cic_key() != c->cur.cic_key());
     if (prev.tii_segment_key() != c->cur.tii_segment_key()) c->tii_seg_epoch = 0;   // the cached segment went through the old filter / CFR / window
-    if (!(taps_changed || window_changed || coef_changed || rs_changed)) return DABGPU_OK;
+    if (!(taps_changed || window_changed || coef_changed || rs_changed || cic_changed)) return DABGPU_OK;
     if (!first) HIPCHK(c, hipDeviceSynchronize());
     hipStream_t s = c->stream;
     if (taps_changed) {
@@ -333,6 +336,7 @@ int apply_settings_groups(dabgpu_ctx *c)
         std::copy(c->cur.lut, c->cur.lut + 32, coef.begin() + 16);
         HIPCHK(c, upload(c->d_coef, coef, s));
     }
+    if (cic_changed) HIPCHK(c, upload(c->d_cic_chain, cic_filter((size_t)c->g.K, c->cur.cic_spacing, c->cur.cic_R), s));
     c->tables_valid = true;
 
     // resampler geometry, src/Resampler.cpp:65-112
@@ -399,6 +403,27 @@ int apply_settings(dabgpu_ctx *c)
         c->rs_nin = c->rs_nout = 0;           // (the resampler's tables and halo are rebuilt as well)
     }
     return rc;
+}
+
+// CicEqualizer's constructor, src/CicEqualizer.cpp:38-55, in float with the libm float functions: the per-carrier compensation
+// gain of an R-fold, 4-stage CIC interpolator.  One function for the stage entry and the chain's setting.
+std::vector<float> cic_filter(size_t K, size_t spacing, int R)
+{
+    std::vector<float> filter(K);
+    const int M = 1, N = 4;
+    const float pi = 4.0f * atanf(1.0f);
+    for (size_t i = 0; i < K; ++i) {
+        const int k = i < (K + 1) / 2 ? (int)i + (int)((K & 1) ^ 1) : (int)i - (int)K;
+        const float angle = pi * k / spacing;
+        if (k == 0) {
+            filter[i] = 1.0f;
+        } else {
+            float f = sinf(angle / R) / sinf(angle * M);
+            f = fabsf(f) * R * M;
+            filter[i] = powf(f, N);
+        }
+    }
+    return filter;
 }
 
 Tables tables_of(dabgpu_ctx *c)
@@ -501,7 +526,7 @@ void dabgpu_destroy(dabgpu_ctx *c)
         if (l.stream) (void)hipStreamSynchronize(l.stream);
     for (DevBuf *b : {&c->d_twiddle, &c->d_src, &c->d_dst, &c->d_phq, &c->d_mag, &c->d_taps, &c->d_firh, &c->d_eqg,
                       &c->d_window, &c->d_coef, &c->d_rs_window, &c->d_rs_tw_in, &c->d_rs_tw_out,
-                      &c->d_rs_halo, &c->d_rs_tw_s, &c->d_rs_tw_l, &c->d_a, &c->d_b, &c->d_c, &c->d_in, &c->d_out, &c->d_count, &c->d_fmt, &c->d_clip, &c->d_phase, &c->d_seed,
+                      &c->d_rs_halo, &c->d_rs_tw_s, &c->d_rs_tw_l, &c->d_a, &c->d_b, &c->d_c, &c->d_car, &c->d_cic_chain, &c->d_car_acp, &c->d_in, &c->d_out, &c->d_count, &c->d_fmt, &c->d_clip, &c->d_phase, &c->d_seed,
                       &c->d_acp, &c->d_tii_car, &c->d_tii_frame, &c->d_gain1, &c->d_gains, &c->d_cic,
                       &c->d_cfr_counts, &c->d_cfr_mer, &c->d_cfr_papr, &c->d_cfr_tmp,
                       &c->d_fe_prbs, &c->d_fe_units, &c->d_fe_owner, &c->d_fe_hist, &c->d_fe_tmp, &c->d_fe_fic, &c->d_fe_eti,
@@ -525,7 +550,7 @@ void dabgpu_destroy(dabgpu_ctx *c)
     for (auto &l : c->lane) {
         if (l.stream) { (void)hipStreamSynchronize(l.stream); (void)hipStreamDestroy(l.stream); }
         if (l.ev) (void)hipEventDestroy(l.ev);
-        for (DevBuf *b : {&l.d_a, &l.d_b, &l.d_fmt, &l.d_clip, &l.d_gain1, &l.d_gains, &l.d_cfr_counts, &l.d_cfr_mer, &l.d_cfr_papr, &l.d_cfr_tmp})
+        for (DevBuf *b : {&l.d_a, &l.d_b, &l.d_fmt, &l.d_clip, &l.d_gain1, &l.d_gains, &l.d_cfr_counts, &l.d_cfr_mer, &l.d_cfr_papr, &l.d_cfr_tmp, &l.d_car})
             b->release();
     }
     for (hipEvent_t e : {c->ho_prod[0], c->ho_prod[1], c->ho_cons[0], c->ho_cons[1], c->ho_start, c->ho_join, c->own_ev})
@@ -628,6 +653,20 @@ int dabgpu_set_tii(dabgpu_ctx *c, int enable, int comb, int pattern, int old_var
     c->set.tii_comb = comb;
     c->set.tii_pattern = pattern;
     c->set.tii_old_variant = old_variant != 0;
+    ++c->set.epoch;
+    return DABGPU_OK;
+}
+
+int dabgpu_set_cic_equalizer(dabgpu_ctx *c, int enable, size_t spacing, int R)
+{
+    if (!c) return DABGPU_E_INVALID;
+    if (enable && (!spacing || R <= 0)) return fail(c, DABGPU_E_INVALID, kCicBadParameters);
+    std::lock_guard<std::mutex> lk(c->mu);
+    const size_t sp = enable ? spacing : 0;
+    const int r = enable ? R : 0;
+    if (c->set.cic_spacing == sp && c->set.cic_R == r) return DABGPU_OK;
+    c->set.cic_spacing = sp;
+    c->set.cic_R = r;
     ++c->set.epoch;
     return DABGPU_OK;
 }

@@ -496,7 +496,7 @@ int dabgpu_chain_process_eti(dabgpu_ctx *c, const uint8_t *eti, size_t n_eti, un
     if ((rc = frontend_check_host(c, eti, n_eti))) return rc;
     c->clip_from_collect = false;
     if ((rc = apply_settings(c))) return rc;
-    const ChainPlan p = plan_chain(c, true, n_tf, mask);
+    const ChainPlan p = plan_chain(c, true, n_tf, mask, true, true, chain_cic(c));
     if (p.error) return fail(c, DABGPU_E_INVALID, p.error);          // (before the front-end advances its history)
     const size_t need = p.out_bytes;
     if ((rc = check_out(c, need, out_cap, out_bytes))) return rc;

@@ -69,11 +69,11 @@ int pick_lane(dabgpu_ctx *c, bool from_bits, size_t n_frames, unsigned mask, Cha
     if (c->n_lanes > 1 && !(normalised_mask(c->cur, mask) & DABGPU_STAGE_RESAMPLE) &&
         n_frames <= (size_t)dabgpu_ctx::kLaneMaxFrames) {
         c->call_lanes = c->n_lanes;             // (planned as one of n_lanes launches in flight: auto_chunks)
-        *p = plan_chain(c, from_bits, n_frames, mask);
+        *p = plan_chain(c, from_bits, n_frames, mask, true, true, chain_cic(c));
         if (p->scratch_bytes <= (size_t)dabgpu_ctx::kLaneScratchBytes) return (int)(c->lane_seq++ % (unsigned long long)c->n_lanes);
         c->call_lanes = 1;
     }
-    *p = plan_chain(c, from_bits, n_frames, mask);
+    *p = plan_chain(c, from_bits, n_frames, mask, true, true, chain_cic(c));
     return 0;
 }
 
@@ -91,7 +91,7 @@ int chain_dev(dabgpu_ctx *c, const void *d_in, bool from_bits, size_t n_frames, 
         if ((rc = lane_joins_own_stream(c, lane))) return rc;
     } else {
         c->call_lanes = 1;
-        p = plan_chain(c, from_bits, n_frames, mask);
+        p = plan_chain(c, from_bits, n_frames, mask, true, true, chain_cic(c));
     }
     c->clip_from_collect = false;
     TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
@@ -193,7 +193,7 @@ int chain_submit(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, unsigned m
     const bool two_lanes = !eti && c->n_lanes > 1 && !(normalised_mask(c->cur, mask) & DABGPU_STAGE_RESAMPLE);
     const int lane = two_lanes ? slot_index : 0;
     c->call_lanes = two_lanes ? 2 : 1;                  // (the two batches in flight)
-    const ChainPlan p = plan_chain(c, true, n_frames, mask);
+    const ChainPlan p = plan_chain(c, true, n_frames, mask, true, true, chain_cic(c));
     c->call_lanes = 1;
     if (eti && p.error) return fail(c, DABGPU_E_INVALID, p.error);     // (before the front-end advances its history)
     const size_t bits_bytes = n_frames * tf_in_bytes(c->g), need = p.out_bytes;

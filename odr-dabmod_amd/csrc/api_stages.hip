@@ -125,26 +125,12 @@ int dabgpu_cic_equalizer_process(dabgpu_ctx *c, size_t spacing, int R, const voi
     CTXCHK(c);
     const size_t K = (size_t)c->g.K;
     if (in_bytes % (K * sizeof(float2))) return fail(c, DABGPU_E_INVALID, "CicEqualizer::process input size not valid!");
-    if (!spacing || R <= 0) return fail(c, DABGPU_E_INVALID, "CicEqualizer: spacing and R must be positive");
+    if (!spacing || R <= 0) return fail(c, DABGPU_E_INVALID, kCicBadParameters);
     int rc = check_out(c, in_bytes, out_cap, out_bytes);
     if (rc) return rc;
     if (c->cic_spacing != spacing || c->cic_R != R) {
-        // the reference's constructor, src/CicEqualizer.cpp:38-55, in float with the libm float functions
-        std::vector<float> filter(K);
-        const int M = 1, N = 4;
-        const float pi = 4.0f * atanf(1.0f);
-        for (size_t i = 0; i < K; ++i) {
-            const int k = i < (K + 1) / 2 ? (int)i + (int)((K & 1) ^ 1) : (int)i - (int)K;
-            const float angle = pi * k / spacing;
-            if (k == 0) {
-                filter[i] = 1.0f;
-            } else {
-                float f = sinf(angle / R) / sinf(angle * M);
-                f = fabsf(f) * R * M;
-                filter[i] = powf(f, N);
-            }
-        }
-        HIPCHK(c, upload(c->d_cic, filter, c->stream));
+        // (this entry's own table, d_cic: the chain's, a setting, lives in d_cic_chain)
+        HIPCHK(c, upload(c->d_cic, cic_filter(K, spacing, R), c->stream));
         c->cic_spacing = spacing;
         c->cic_R = R;
     }

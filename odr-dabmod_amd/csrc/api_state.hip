@@ -66,7 +66,7 @@ int plan_seed(dabgpu_ctx *c, unsigned mask, uint64_t frame_index, bool have_bits
     // of the chain's internal runs, its launches outside the trace: the most recent chain call stays the one that
     // dabgpu_get_cfr_stats / dabgpu_get_num_clipped / dabgpu_debug_last_variant describe.
     c->call_lanes = 1;
-    sp->p = plan_chain(c, true, 1, mask & ~(unsigned)(DABGPU_STAGE_RESAMPLE | DABGPU_STAGE_POLY), false, false);
+    sp->p = plan_chain(c, true, 1, mask & ~(unsigned)(DABGPU_STAGE_RESAMPLE | DABGPU_STAGE_POLY), false, false, chain_cic(c));
     if (sp->p.error) return fail(c, DABGPU_E_INVALID, sp->p.error);
     if (sp->p.native < (size_t)c->rs_nin) return fail(c, DABGPU_E_INVALID, "chain seed: frame shorter than the halo");
     return DABGPU_OK;
@@ -87,7 +87,10 @@ int run_seed(dabgpu_ctx *c, const SeedPlan &sp, const void *d_bits, uint64_t fra
         // (a seed that fails from here on puts the parity back: never one that belongs to neither stream)
         const bool insert_before = c->tii_insert;
         c->tii_insert = ((frame_index - 1) & 1) == 0;
-        int rc = run_native_tii(c, p, d_bits, (float2 *)c->d_a.p, s);
+        // (CIC equaliser on: the carriers kernel first, with the parity just set -- TII is in the carriers)
+        const void *d_in = d_bits;
+        int rc = run_front(c, p, &d_in, s);
+        if (!rc) rc = run_native_tii(c, p, d_in, (float2 *)c->d_a.p, s);
         // the halo = the last two hops of the input so far (src/Resampler.cpp:188-191)
         if (!rc) {
             const hipError_t e = hipMemcpyAsync(current_halo(c), (const float2 *)c->d_a.p + (p.native - (size_t)c->rs_nin),

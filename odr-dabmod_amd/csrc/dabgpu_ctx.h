@@ -62,6 +62,8 @@ struct Settings {
     int out_format = 0;                    // 0 = complexf, else DABGPU_FMT_*: FormatConverter as the chain's last step
     bool tii_enable = false, tii_old_variant = false;   // src/TII.h:42-69 (tii_config_t)
     int tii_comb = 0, tii_pattern = 0;
+    size_t cic_spacing = 0;                // dabgpu_set_cic_equalizer: CicEqualizer(carriers, spacing, R) between cifSig and
+    int cic_R = 0;                         // cifOfdm of every chain call (src/DabModulator.cpp:155-176,399); 0 / 0 = off
     unsigned long long epoch = 1;  // bumped by every setter
     bool resampler_reset = true;
 
@@ -77,6 +79,9 @@ struct Settings {
         return poly_is_lut == o.poly_is_lut && lut_scale == o.lut_scale && !std::memcmp(am, o.am, sizeof am) &&
                !std::memcmp(pm, o.pm, sizeof pm) && !std::memcmp(lut, o.lut, sizeof lut);
     }
+    //   the chain's table of CicEqualizer factors
+    auto cic_key() const { return std::tie(cic_spacing, cic_R); }
+    bool cic_on() const { return cic_spacing != 0 && cic_R > 0; }
     //   the resampler's window, twiddles and geometry
     auto resampler_key() const { return std::tie(rs_in, rs_out); }
     //   the cached unit-gain TII segment (TII symbol -> IFFT -> [CFR] -> guard [window] -> [FIR]); gain scales it at use
@@ -124,6 +129,7 @@ struct dabgpu_ctx {
     float rs_factor = 1.f;
     // scratch
     dabgpu_api::DevBuf d_a, d_b, d_c, d_in, d_out, d_count, d_fmt, d_clip;
+    dabgpu_api::DevBuf d_car;             // CIC equaliser on: the carriers between the front kernel and the from-carriers chain
     // dabgpu_chain_seed: the lead-in frame's coded bits, through two pinned staging frames in turn (the host never waits
     // for the seed before the last one)
     dabgpu_api::DevBuf d_seed;
@@ -144,8 +150,12 @@ struct dabgpu_ctx {
     // TII (f-4): carrier set, the one-frame carrier image and its native-rate response, gain of symbol 1
     dabgpu_api::DevBuf d_acp, d_tii_car, d_tii_frame, d_gain1, d_cic;
     dabgpu_api::DevBuf d_gains;           // gain rounding REFERENCE: the multipliers of a call's symbols
-    size_t cic_spacing = 0;               // what d_cic was built for (CicEqualizer, a12)
+    size_t cic_spacing = 0;               // what d_cic was built for (CicEqualizer, a12: the STAGE entry's table)
     int cic_R = 0;
+    // the chain's own CicEqualizer table (a setting: uploaded by apply_settings for cur.cic_key(), never touched by the stage
+    // entry) and the TII carrier set the carriers kernel reads (rewritten after the lanes have drained: ensure_carrier_acp)
+    dabgpu_api::DevBuf d_cic_chain, d_car_acp;
+    int car_acp_comb = -1, car_acp_pattern = -1;
     // CFR statistics (f-3) of the most recent chain / OfdmGenerator call, and a scratch set for internal runs
     dabgpu_api::DevBuf d_cfr_counts, d_cfr_mer, d_cfr_papr, d_cfr_tmp;
     int cfr_mer_index = 0;                // myMERCalcIndex (src/OfdmGenerator.h:109): advances once per frame
@@ -167,7 +177,7 @@ struct dabgpu_ctx {
     struct Lane {
         hipStream_t stream = nullptr;
         hipEvent_t ev = nullptr;
-        dabgpu_api::DevBuf d_a, d_b, d_fmt, d_clip, d_gain1, d_gains, d_cfr_counts, d_cfr_mer, d_cfr_papr, d_cfr_tmp;
+        dabgpu_api::DevBuf d_a, d_b, d_fmt, d_clip, d_gain1, d_gains, d_cfr_counts, d_cfr_mer, d_cfr_papr, d_cfr_tmp, d_car;
     };
     enum { kMaxLanes = 4, kLaneMaxFrames = 2048, kLaneScratchBytes = 256 << 20 };
     Lane lane[kMaxLanes];                 // (entry 0: only `ev` is used)
@@ -256,7 +266,7 @@ struct LaneScope {
         dabgpu_ctx::Lane &l = c->lane[i];
         std::swap(c->d_a, l.d_a); std::swap(c->d_b, l.d_b); std::swap(c->d_fmt, l.d_fmt); std::swap(c->d_clip, l.d_clip);
         std::swap(c->d_gain1, l.d_gain1); std::swap(c->d_gains, l.d_gains); std::swap(c->d_cfr_counts, l.d_cfr_counts); std::swap(c->d_cfr_mer, l.d_cfr_mer);
-        std::swap(c->d_cfr_papr, l.d_cfr_papr); std::swap(c->d_cfr_tmp, l.d_cfr_tmp);
+        std::swap(c->d_cfr_papr, l.d_cfr_papr); std::swap(c->d_cfr_tmp, l.d_cfr_tmp); std::swap(c->d_car, l.d_car);
     }
 };
 
@@ -283,6 +293,7 @@ int chain_submit(dabgpu_ctx *c, const uint8_t *src, size_t n_frames, unsigned ma
 
 // ---- api_context.hip
 extern const float kDefaultTaps[45];
+extern const char *const kCicBadParameters;          // the refusal of the stage entry and of the setter
 bool mode_geometry(int mode, Geometry *g);
 size_t tf_in_bytes(const Geometry &g);
 size_t tf_samples(const Geometry &g);
@@ -313,6 +324,11 @@ struct ChainPlan {
     // the native-rate part: one frame kernel (TF_WINDOW in tf_flags: it windows the guard interval itself), or frame kernel
     // -> guard / FIRFilter kernel, the latter with the reference's gain recurrence in between
     enum Form { ONE_KERNEL, UNFUSED, GAIN_REPLAY } form = ONE_KERNEL;
+    // Carriers first (the CIC equaliser is on): a kernel in front leaves the equalised carriers in d_car and everything above
+    // describes the from-carriers chain that runs on them (from_bits = false, no TII of its own: it is in the carriers).
+    // FRONT_BITS: the call's input is coded bits (carriers_from_bits_kernel, which also advances the TII parity);
+    // FRONT_CIC: it is the caller's carriers (cic_kernel).
+    enum Front { FRONT_NONE, FRONT_BITS, FRONT_CIC } front = FRONT_NONE;
     unsigned tf_flags = 0;                // the frame kernel's final TF_* flags
     int ntaps = 0, chunks_per_frame = 1, syms_per_chunk = 1;
     bool tii = false, tii_inside = false; // the call adds the TII null symbol; the frame kernel does it itself
@@ -323,11 +339,19 @@ struct ChainPlan {
     // internal run), and their sum
     struct Scratch {
         size_t d_a = 0, d_b = 0, d_fmt = 0, d_gains = 0, d_gain1 = 0, cfr_counts = 0, cfr_mer = 0, cfr_papr = 0, cfr_tmp = 0;
+        size_t d_car = 0;
     } scratch;
     size_t scratch_bytes = 0;
 };
+// (cic: the call is a chain entry point's and the context's CIC equaliser applies -- chain_cic(c); the stage entries and the
+// chain's internal runs that borrow the dispatch never equalise)
 ChainPlan plan_chain(const dabgpu_ctx *c, bool from_bits, size_t n_frames, unsigned mask, bool apply_format = true,
-                     bool keep_stats = true);
+                     bool keep_stats = true, bool cic = false);
+inline bool chain_cic(const dabgpu_ctx *c) { return c->cur.cic_on(); }
+// the front kernel of a carriers-first plan, or dabgpu_carriers_process: coded bits -> carriers with the context's TII and CIC
+// settings (cic: apply the equaliser), from the TII parity as it stands; does NOT advance the parity
+int run_carriers(dabgpu_ctx *c, const void *d_bits, size_t n_frames, float2 *d_car, bool cic, hipStream_t s);
+std::vector<float> cic_filter(size_t K, size_t spacing, int R);
 unsigned normalised_mask(const Settings &st, unsigned mask);
 int auto_chunks(const dabgpu_ctx *c, size_t n_frames);
 bool is_pow2(size_t x);
@@ -338,6 +362,7 @@ int run_resampler(dabgpu_ctx *c, const float2 *d_in, size_t total, float2 *d_out
 int run_poly(dabgpu_ctx *c, const float2 *d_in, size_t n, float2 *d_out, hipStream_t s);
 int tii_carrier_set(int mode, int comb, int pattern, std::vector<uint8_t> &acp);
 int run_native_tii(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, float2 *native_out, hipStream_t s);
+int run_front(dabgpu_ctx *c, const ChainPlan &p, const void **d_in, hipStream_t s);
 int run_chain(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, void *d_out_v, size_t out_cap, size_t *out_bytes,
               hipStream_t s, bool apply_format = true, int lane = 0);
 

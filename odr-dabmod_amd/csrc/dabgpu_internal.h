@@ -139,6 +139,19 @@ hipError_t launch_poly(const float2 *in, size_t nsamples, const float *am, const
                        float2 *out, hipStream_t s);
 // a12 CicEqualizer: out[i] = in[i] * filter[i % K]
 hipError_t launch_cic(const float2 *in, size_t nsamples, int K, const float *filter, float2 *out, hipStream_t s);
+// carriers.hip: coded bits -> the SignalMultiplexer output ([frame][nb_symbols + 1][K] cf32), with TII and CicEqualizer applied
+struct CarrierArgs {
+    Geometry g;
+    Tables t;                 // src_carrier, phase_q, mag
+    const uint8_t *bits;      // n_frames x (nb_symbols - 1) * K / 4 bytes, dword aligned
+    float2 *out;
+    int n_frames;
+    const float *cic;         // K per-carrier factors, or nullptr: no CicEqualizer
+    const uint8_t *acp;       // K: the TII carrier set A_{c,p} (tii_carrier_set), or nullptr: the null symbol is blank
+    int tii_old_variant;
+    int tii_insert0;          // frame 0 of this launch carries TII (then every other one)
+};
+hipError_t launch_carriers_from_bits(const CarrierArgs &a, hipStream_t s);
 // f-4 TII: the sparse symbol (stand-alone stage), and its addition to a stream whose null symbol is blank
 hipError_t launch_tii(const float2 *in, const uint8_t *acp, int K, int old_variant, int insert, float2 *out,
                       hipStream_t s);

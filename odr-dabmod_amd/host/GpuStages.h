@@ -414,6 +414,11 @@ public:
         // instead of the exact variance -- the reference's scalars bit for bit on the same symbols, at about 30 % of
         // the chain's rate (dabgpu_set_gain_rounding).  Off by default.
         bool referenceGainRounding = false;
+        // CicEqualizer(carriers, cicSpacing, cicRatio) between cifSig and cifOfdm (src/DabModulator.cpp:155-176, :399: wired in
+        // when a dac_clk_rate is configured; cicRatio = clockRate / outputRate / 4, cicSpacing = spacing x outputRate /
+        // 2048000).  0 / 0 = off, the default.  Fixed at construction, as in the reference (dabgpu_set_cic_equalizer).
+        size_t cicSpacing = 0;
+        int cicRatio = 0;
         unsigned referencePipelineDepth() const
         {
             return (enableGain ? 1u : 0u) + (filterTapsFilename.empty() ? 0u : 1u) + (polyCoefFilename.empty() ? 0u : 1u);

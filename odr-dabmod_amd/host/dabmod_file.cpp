@@ -17,6 +17,8 @@
 //   --poly <coeffile>    MemlessPoly coefficient file
 //   --ofdmwindowing W    raised-cosine overlap in samples
 //   --tii comb,pattern   --cfr clip,errorclip
+//   --cic SPACING,R      CicEqualizer(carriers, SPACING, R) between the signal multiplexer and OfdmGenerator, what the reference
+//                        wires in for a configured dac_clk_rate (src/DabModulator.cpp:155-176): the chain runs carriers first
 //   --loop N             read the file N times
 //   --bits-only          stop after the front-end: write the hot path's input blocks (no GPU needed)
 //   --reference-latency  emit exactly the frames the reference emits: one transmission frame fewer per pipelined stage
@@ -60,7 +62,7 @@ namespace {
 {
     std::fprintf(stderr, "usage: dabmod_file <in.eti> <out> [--mode N] [--format complexf|s16|u8|s8] [--gainmode var|fix|max]\n"
                          "       [--digital G] [--normalise X] [--var V] [--fir none|default|file] [--rate R] [--poly file]\n"
-                         "       [--ofdmwindowing W] [--tii comb,pattern] [--cfr clip,errorclip] [--loop N] [--bits-only]\n"
+                         "       [--ofdmwindowing W] [--tii comb,pattern] [--cfr clip,errorclip] [--cic spacing,R] [--loop N] [--bits-only]\n"
                          "       [--batch N]   N transmission frames per GPU call, two calls in flight (default 1: frame by frame)\n"
                          "       [--reference-latency]   drop the frames the reference's pipelined stages never emit\n"
                          "       [--reference-gain]      gain mode var by the reference's running recurrence (bit-equal scalars, slower)\n"
@@ -159,6 +161,11 @@ int main(int argc, char **argv)
             else if (a == "--cfr") {
                 if (std::sscanf(val().c_str(), "%f,%f", &gs.cfrClip, &gs.cfrErrorClip) != 2) usage();
                 gs.enableCfr = true;
+            }
+            else if (a == "--cic") {
+                unsigned long spacing = 0;
+                if (std::sscanf(val().c_str(), "%lu,%d", &spacing, &gs.cicRatio) != 2 || !spacing || gs.cicRatio <= 0) usage();
+                gs.cicSpacing = spacing;
             }
             else if (a == "--loop") loops = std::atoi(val().c_str());
             else if (a == "--bits-only") bits_only = true;

@@ -764,6 +764,43 @@ int run_chainrc(int argc, char **argv)
     return 0;
 }
 
+// DabGpuChain::Settings::cicSpacing / cicRatio reach the context (dabgpu_set_cic_equalizer): the chain's frames with them are
+// the caller's to compare with the library's own (tests/test_cic_host.py); half a parameter pair is refused at construction
+int run_cic(int argc, char **argv)
+{
+    if (argc < 7) {
+        std::fprintf(stderr, "usage: host_selftest cic <bits file> <nframes> <spacing> <R> <out.iq>\n");
+        return 2;
+    }
+    const std::vector<uint8_t> bits = read_all(argv[2]);
+    const size_t nframes = std::strtoul(argv[3], nullptr, 10);
+    DabGpuChain::Settings s;
+    s.dabMode = 1;
+    s.normalise = 1.0f / 50000.0f;
+    s.filterTapsFilename = "default";
+    s.cicSpacing = std::strtoul(argv[4], nullptr, 10);
+    s.cicRatio = std::atoi(argv[5]);
+    bool threw = false;
+    try {
+        DabGpuChain::Settings bad = s;
+        bad.cicRatio = 0;
+        DabGpuChain refused(bad);
+    } catch (const std::runtime_error &e) {
+        threw = std::string(e.what()).find("CicEqualizer") != std::string::npos;
+    }
+    CHECK(threw);
+    auto chain = std::make_shared<DabGpuChain>(s);
+    auto source = std::make_shared<NumberedSource>(bits, chain->input_bytes_per_frame());
+    auto sink = std::make_shared<ReportingSink>(argv[6]);
+    Flowgraph fg;
+    fg.connect(source, chain);
+    fg.connect(chain, sink);
+    for (size_t i = 0; i < nframes; ++i) fg.run();
+    CHECK(static_cast<size_t>(sink->frames) == nframes);
+    std::printf("cic: %d frames written\n", sink->frames);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -774,6 +811,7 @@ int main(int argc, char **argv)
         if (argc >= 2 && std::string(argv[1]) == "cfg4") return run_cfg4(argc, argv);
         if (argc >= 2 && std::string(argv[1]) == "memlesspoly") return run_memlesspoly(argc, argv);
         if (argc >= 2 && std::string(argv[1]) == "chainrc") return run_chainrc(argc, argv);
+        if (argc >= 2 && std::string(argv[1]) == "cic") return run_cic(argc, argv);
         std::fprintf(stderr, "usage: host_selftest cpu | gpu ...\n");
         return 2;
     } catch (const std::exception &e) {

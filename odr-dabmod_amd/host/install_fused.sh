@@ -8,7 +8,8 @@
 #
 #   DabModulator.cpp  the block that creates the stage objects (from "const bool fixedPoint = ..." to the line before
 #                     "m_output = make_shared<OutputMemory>(dataOut);") becomes the construction of the chain -- the
-#                     RC-mutable values stay in mod_settings_t, by pointer, as the reference's stages take them by reference
+#                     RC-mutable values stay in mod_settings_t, by pointer, as the reference's stages take them by reference;
+#                     a configured dac_clk_rate becomes the chain's CIC equaliser by the rule of the block it replaces
 #                     -- and the enrolment of its remote-controllables; the wiring from "connect(cifPart, cifMap)" to the
 #                     end of the plugin loop becomes two connects; "num_clipped_samples" reads the chain.
 #   DabModulator.h    one member more: std::shared_ptr<DabGpuChain> m_gpuChain.
@@ -48,9 +49,17 @@ function construct() {
     print "        if (m_settings.fftEngine != FFTEngine::FFTW)"
     print "            throw std::runtime_error(\"OfdmGenerator: the fixed-point engine (fft_engine=kiss) is not offloaded to the GPU; \""
     print "                                     \"set fft_engine=fftw\");"
-    print "        if (m_settings.clockRate)"
-    print "            throw std::runtime_error(\"DabGpuChain: the CIC equaliser is not part of the fused chain (use the per-stage drop-ins)\");"
     print "        DabGpuChain::Settings gs;"
+    print "        if (m_settings.clockRate) {"
+    print "            // the CIC equaliser inside the chain (DabGpuChain::Settings::cicSpacing / cicRatio): the decision this block replaces"
+    print "            // (the interpolation the FPGA still does behind its fixed x4 stage; a 400 MHz clock -- USRP2 -- equalises odd ratios only)"
+    print "            const unsigned ratio = m_settings.clockRate / m_settings.outputRate / 4;"
+    print "            const bool usrp2 = m_settings.clockRate == 400000000;"
+    print "            if (!usrp2 || ratio % 2 == 1) {"
+    print "                gs.cicRatio = static_cast<int>(ratio);"
+    print "                gs.cicSpacing = static_cast<size_t>((float)m_spacing * (float)m_settings.outputRate / 2048000.0f);"
+    print "            }"
+    print "        }"
     print "        gs.dabMode = mode;"
     print "        gs.gainMode = m_settings.gainMode;"
     print "        gs.digitalGain = m_settings.digitalgain;"
