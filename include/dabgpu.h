@@ -556,6 +556,51 @@ DABGPU_API int dabgpu_chain_seed_eti(dabgpu_ctx *ctx, const uint8_t *eti_leadin,
 DABGPU_API int dabgpu_chain_seed_eti_dev(dabgpu_ctx *ctx, const void *d_eti_leadin, size_t n_leadin,
                                          unsigned stage_mask, uint64_t e, void *stream);
 
+/* ---- the receiver: native-rate IQ -> coded bits, per-frame MER and bit errors --------------------------------------------- *
+ * The modulator's output decoded back on the device: per OFDM symbol the forward transform over the window that ends `early`
+ * samples before the end of the symbol, differential demodulation against the symbol before, hard QPSK decisions, the
+ * frequency interleaver undone -- ETSI EN 300 401 14.5 - 14.7 backwards.  The reference has no receiver; these entries replace
+ * nothing of its flowgraph.  No synchronisation and no channel estimate: the input is whole transmission frames as a chain
+ * call without the Resampler writes them (tf_samples each), complexf (format 0) or DABGPU_FMT_S16; u8 / s8 are not taken.
+ * `early` (0 ... sym_size - spacing, the data symbols' cyclic prefix; anything else is DABGPU_E_INVALID) moves the window away
+ * from what FIRFilter's look-ahead and the guard window's overlap leave at the end of a symbol: ntaps - 1 for a filtered
+ * chain, plus the overlap for a windowed one.  Any window inside the cyclic extension only rotates all symbols alike.
+ * Output: n_frames x tf_input_bytes, the layout dabgpu_chain_process takes.  Per frame, over all data symbols and carriers,
+ * with d = z_s conj(z_{s-1}) per carrier and c = ((1 - 2 I) + j (1 - 2 Q)) / sqrt(2) its decided point:
+ *   sum_signal      sum |d|^2
+ *   sum_quadrature  sum Im(d conj(c))^2 -- the part of d at right angles to its decision; independent of the per-symbol gain,
+ *                   of |H[k]|^2 and of `early`.  MER in dB = 10 log10(sum_signal / sum_quadrature), formed by the caller
+ *   bit_errors      bits that differ from the reference bits, n_bits the number compared (0 without reference bits)
+ *   min_margin      min of min(|Re d|, |Im d|) / |d|: how close the worst decision came (at most sqrt(1/2))
+ * The sums are float64 sums of fp32 terms, added in no fixed order: they repeat to about 1e-7, not bit for bit.
+ * dabgpu_demod_dev: device pointers (four-byte aligned), asynchronous on `stream` (NULL: the context's own stream, behind every
+ *   lane); d_bits_out and d_ref_bits may be NULL.  dabgpu_demod: the host-pointer form.  dabgpu_get_demod_stats: frame `frame`
+ *   of the most recent of these calls or monitored chain call, after waiting for it, as dabgpu_get_cfr_stats does. */
+typedef struct dabgpu_demod_stats {
+    double sum_signal, sum_quadrature;
+    uint64_t bit_errors, n_bits;
+    double min_margin;
+} dabgpu_demod_stats;
+DABGPU_API int dabgpu_demod_dev(dabgpu_ctx *ctx, const void *d_iq, int format, size_t n_frames, int early,
+                                void *d_bits_out, const void *d_ref_bits, void *stream);
+DABGPU_API int dabgpu_demod(dabgpu_ctx *ctx, const void *iq, int format, size_t n_frames, int early, uint8_t *bits_out,
+                            const uint8_t *ref_bits);
+DABGPU_API int dabgpu_get_demod_stats(dabgpu_ctx *ctx, size_t frame, dabgpu_demod_stats *out);
+/* host only, no context, no device: the range test of `early` for a transmission mode (1..4; 0 = IV), with the message the
+ * entries above give (dabgpu_last_error(NULL), per thread) */
+DABGPU_API int dabgpu_demod_check_early(int mode, int early);
+/* The monitor: off by default, and while it is off nothing changes.  While it is on, every dabgpu_chain_process /
+ * _process_dev / _process_eti call runs the receiver behind its last kernel, on the same stream, on the call's own output
+ * against the call's own coded bits (the ETI form: the front-end's), without a bit output; dabgpu_get_demod_stats then
+ * describes the most recent such call.  early < 0: (ntaps - 1 if FIRFilter is in the call's mask) + the window overlap.
+ * The IQ is what the call writes with the monitor off.  Monitored calls stay on lane 0, like resampler chains.  Refused with
+ * DABGPU_E_INVALID before anything is queued: a mask with the Resampler (at a ratio other than 1) or without the guard
+ * interval, u8 / s8 output, dabgpu_chain_submit* -- and an `early` beyond the cyclic prefix.  Takes effect at the next call. */
+DABGPU_API int dabgpu_set_monitor(dabgpu_ctx *ctx, int enable, int early);
+/* Diagnostic: data symbols per workgroup of the receiver's kernel (a workgroup transforms one symbol more than it decides);
+ * 0 (the default) = chosen from the batch size.  Same bits for every value; exists so that a test can walk the run geometry. */
+DABGPU_API int dabgpu_debug_demod_run_symbols(dabgpu_ctx *ctx, int symbols);
+
 /* wait for everything queued on the context's own stream(s): every lane */
 DABGPU_API int dabgpu_synchronize(dabgpu_ctx *ctx);
 

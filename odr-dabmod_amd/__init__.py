@@ -43,6 +43,8 @@ EXPORTS = [
     "dabgpu_frontend_state_bytes", "dabgpu_frontend_get_state", "dabgpu_frontend_set_state",
     "dabgpu_frontend_seed", "dabgpu_frontend_seed_dev", "dabgpu_chain_seed_eti", "dabgpu_chain_seed_eti_dev",
     "dabgpu_set_cic_equalizer", "dabgpu_carriers_process", "dabgpu_carriers_process_dev",
+    "dabgpu_demod", "dabgpu_demod_dev", "dabgpu_get_demod_stats", "dabgpu_demod_check_early", "dabgpu_set_monitor",
+    "dabgpu_debug_demod_run_symbols",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -83,6 +85,11 @@ class _CfrStats(C.Structure):
     _fields_ = [("num_clip", C.c_uint64), ("num_error_clip", C.c_uint64), ("num_samples", C.c_uint64),
                 ("mer_symbol", C.c_int), ("mer_sum_iq", C.c_double), ("mer_sum_delta", C.c_double),
                 ("nb_symbols", C.c_int), ("papr_before", C.c_double * 2 * 154), ("papr_after", C.c_double * 2 * 154)]
+
+
+class _DemodStats(C.Structure):
+    _fields_ = [("sum_signal", C.c_double), ("sum_quadrature", C.c_double), ("bit_errors", C.c_uint64),
+                ("n_bits", C.c_uint64), ("min_margin", C.c_double)]
 
 
 class _Geometry(C.Structure):
@@ -203,8 +210,22 @@ def load_library():
     lib.dabgpu_frontend_seed_dev.argtypes = [vp, vp, sz, C.c_uint64, vp]
     lib.dabgpu_chain_seed_eti.argtypes = [vp, vp, sz, u, C.c_uint64]
     lib.dabgpu_chain_seed_eti_dev.argtypes = [vp, vp, sz, u, C.c_uint64, vp]
+    lib.dabgpu_demod.argtypes = [vp, vp, C.c_int, sz, C.c_int, vp, vp]
+    lib.dabgpu_demod_dev.argtypes = [vp, vp, C.c_int, sz, C.c_int, vp, vp, vp]
+    lib.dabgpu_get_demod_stats.argtypes = [vp, sz, C.POINTER(_DemodStats)]
+    lib.dabgpu_demod_check_early.argtypes = [C.c_int, C.c_int]
+    lib.dabgpu_set_monitor.argtypes = [vp, C.c_int, C.c_int]
+    lib.dabgpu_debug_demod_run_symbols.argtypes = [vp, C.c_int]
     _lib = lib
     return lib
+
+
+def demod_check_early(mode, early):
+    """Host only (needs the library, no device): raises DabGpuError when `early` lies outside the cyclic prefix of the mode's
+    data symbols, with the message demod() / set_monitor() give."""
+    lib = load_library()
+    if lib.dabgpu_demod_check_early(int(mode), int(early)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
 
 
 def fir_inverse_design(taps):
@@ -689,6 +710,75 @@ class Modulator:
         if not s:
             self.synchronize()
         return ob.value
+
+    # ---- the receiver: native-rate IQ -> coded bits, per-frame MER and bit errors (include/dabgpu.h, "the receiver") ----
+    @staticmethod
+    def _iq_format(dtype):
+        if dtype == np.complex64:
+            return 0
+        if dtype == np.int16:
+            return FORMATS["s16"][0]
+        raise DabGpuError("demod: input is complex64 or int16 (interleaved re, im)")
+
+    def demod(self, iq, early=0, ref_bits=None, want_bits=True):
+        """Host path: whole transmission frames of native-rate IQ (complex64, or int16 interleaved re, im) -> the coded bits
+        (n_frames x tf_input_bytes uint8; None with want_bits=False).  ref_bits: bits to count the errors against.  The
+        per-frame figures are monitor_stats(frame)."""
+        iq = np.ascontiguousarray(iq)
+        fmt = self._iq_format(iq.dtype)
+        per = self.geometry["tf_samples"] * (2 if fmt else 1)
+        if iq.size == 0 or iq.size % per:
+            raise DabGpuError("demod: input size not valid (whole transmission frames at the native rate)")
+        n = iq.size // per
+        nb = self.geometry["tf_input_bytes"]
+        out = np.empty((n, nb), np.uint8) if want_bits else None
+        ref = None
+        if ref_bits is not None:
+            ref = np.ascontiguousarray(ref_bits, np.uint8).reshape(-1)
+            if ref.size != n * nb:
+                raise DabGpuError("demod: reference bits do not match the frames")
+        self._chk(self._lib.dabgpu_demod(self._h, iq.ctypes.data, fmt, n, int(early),
+                                         out.ctypes.data if want_bits else None, ref.ctypes.data if ref is not None else None))
+        return out
+
+    def demod_dev(self, d_iq, n_frames, early=0, d_bits_out=None, d_ref_bits=None, stream=None):
+        """Device path on torch tensors (complex64, or int16 pairs), asynchronous on the stream as chain_dev; d_bits_out
+        (uint8, n_frames x tf_input_bytes) and d_ref_bits may be None."""
+        import torch
+        fmt = 0 if d_iq.dtype == torch.complex64 else (FORMATS["s16"][0] if d_iq.dtype == torch.int16 else -1)
+        if fmt < 0:
+            raise DabGpuError("demod: input is complex64 or int16 (interleaved re, im)")
+        if d_iq.numel() != n_frames * self.geometry["tf_samples"] * (2 if fmt else 1):
+            raise DabGpuError("demod: input size not valid (whole transmission frames at the native rate)")
+        for tns in (d_bits_out, d_ref_bits):
+            if tns is not None and tns.numel() * tns.element_size() != n_frames * self.geometry["tf_input_bytes"]:
+                raise DabGpuError("demod: bit buffers are n_frames x tf_input_bytes")
+        s = self._stream_handle(d_iq, stream)
+        self._chk(self._lib.dabgpu_demod_dev(self._h, d_iq.data_ptr(), fmt, n_frames, int(early),
+                                             d_bits_out.data_ptr() if d_bits_out is not None else None,
+                                             d_ref_bits.data_ptr() if d_ref_bits is not None else None, s))
+        if not s:
+            self.synchronize()
+
+    def set_monitor(self, enable, early=-1):
+        """Demodulate every native-rate chain call's output against its own coded bits (off by default); early < 0: from
+        the call's filter and window.  The figures: monitor_stats(frame)."""
+        self._chk(self._lib.dabgpu_set_monitor(self._h, int(bool(enable)), int(early)))
+
+    def monitor_stats(self, frame=0):
+        """Frame `frame` of the most recent demod() / demod_dev() or monitored chain call (waits for it): sum_signal,
+        sum_quadrature, bit_errors, n_bits, min_margin, and mer_db = 10 log10(sum_signal / sum_quadrature)."""
+        st = _DemodStats()
+        self._chk(self._lib.dabgpu_get_demod_stats(self._h, frame, C.byref(st)))
+        d = {k: getattr(st, k) for k, _ in _DemodStats._fields_}
+        d["bit_errors"], d["n_bits"] = int(d["bit_errors"]), int(d["n_bits"])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            d["mer_db"] = float(10.0 * np.log10(np.float64(st.sum_signal) / np.float64(st.sum_quadrature)))
+        return d
+
+    def set_demod_run_symbols(self, symbols=0):
+        """Diagnostic: data symbols per workgroup of the receiver's kernel (0: chosen from the batch size)."""
+        self._chk(self._lib.dabgpu_debug_demod_run_symbols(self._h, int(symbols)))
 
     def synchronize(self):
         """Wait for everything the context has queued, on every lane."""

@@ -759,6 +759,8 @@ int dabgpu_chain_process(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, un
     if (rc) return rc;
     const ChainPlan p = plan_chain(c, true, n_frames, mask, true, true, chain_cic(c));
     const size_t need = p.out_bytes;
+    if (!p.error)
+        if (const char *why = monitor_refusal(c, p)) return fail(c, DABGPU_E_INVALID, why);
     if ((rc = check_out(c, need, out_cap, out_bytes))) return rc;
     HostIO io(c);
     if ((rc = io.in(c->d_in, bits, n_frames * tf_in_bytes(c->g)))) return rc;
@@ -768,6 +770,7 @@ int dabgpu_chain_process(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, un
     {
         TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
         rc = run_chain(c, p, c->d_in.p, c->d_out.p, need, &ob, c->stream);
+        if (!rc) rc = run_monitor(c, p, c->d_in.p, c->d_out.p, c->stream);
     }
     if (rc) return rc;
     return io.out(iq_out, c->d_out.p, need);

@@ -1,0 +1,163 @@
+// api_demod.hip -- the receiver of demod.hip behind the C-ABI: native-rate IQ -> coded bits and per-frame quality figures, as
+// entries of their own (dabgpu_demod / _dev) and as the monitor that rides on a chain call (dabgpu_set_monitor).  The reference
+// has no receiver: nothing here replaces a plugin of its flowgraph, which is why no entry is named *_process.
+#include "dabgpu_ctx.h"
+
+using namespace dabgpu;
+using namespace dabgpu_api;
+
+namespace dabgpu_api {
+const char *const kMonitorNoSubmit =
+    "monitor: dabgpu_chain_submit* is not monitored (statistics per streaming slot are not kept); turn the monitor off";
+
+namespace {
+const char *const kEarlyRange = "demod: early must lie inside the cyclic prefix (0 ... sym_size - spacing)";
+
+// zero records, one launch; on `s`.  d_iq: n_frames x tf_samples samples of `format` (0 = cf32, DABGPU_FMT_S16).
+int queue_demod(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *d_bits_out, const void *d_ref,
+                hipStream_t s)
+{
+    HIPCHK(c, c->d_demod_stats.reserve(std::max<size_t>(n_frames, 1) * sizeof(DemodFrameStats)));
+    HIPCHK(c, hipMemsetAsync(c->d_demod_stats.p, 0, n_frames * sizeof(DemodFrameStats), s));
+    DemodArgs a{};
+    a.g = c->g;
+    a.t = tables_of(c);
+    a.iq = d_iq;
+    a.fmt = format;
+    a.frame_stride = tf_samples(c->g);
+    a.n_frames = (int)n_frames;
+    demod_runs(c->g, n_frames, c->demod_run_symbols, &a.runs_per_frame, &a.syms_per_run);
+    a.early = early;
+    a.bits_out = (uint8_t *)d_bits_out;
+    a.ref_bits = (const uint8_t *)d_ref;
+    a.stats = (DemodFrameStats *)c->d_demod_stats.p;
+    HIPCHK(c, launch_demod(a, s));
+    c->demod_frames = n_frames;
+    c->demod_has_ref = d_ref != nullptr;
+    c->demod_stream = s;
+    return DABGPU_OK;
+}
+
+int check_demod(dabgpu_ctx *c, const void *iq, int format, size_t n_frames, int early, const void *bits_out, const void *ref)
+{
+    if (format != 0 && format != DABGPU_FMT_S16)
+        return fail(c, DABGPU_E_INVALID, "demod: input format is complexf (0) or DABGPU_FMT_S16");
+    if (early < 0 || early > c->g.sym_size - c->g.N) return fail(c, DABGPU_E_INVALID, kEarlyRange);
+    if (n_frames > (size_t)c->max_frames) return fail(c, DABGPU_E_CAPACITY, "n_frames exceeds max_frames of the context");
+    if (n_frames && !iq) return fail(c, DABGPU_E_INVALID, "null argument");
+    if (((uintptr_t)iq | (uintptr_t)bits_out | (uintptr_t)ref) & 3u)
+        return fail(c, DABGPU_E_INVALID, "demod: buffers must be aligned to four bytes");
+    return DABGPU_OK;
+}
+}  // namespace
+
+const char *monitor_refusal(const dabgpu_ctx *c, const ChainPlan &p)
+{
+    if (!c->cur.monitor || (!p.from_bits && p.front != ChainPlan::FRONT_BITS)) return nullptr;
+    if (p.mask & DABGPU_STAGE_RESAMPLE)
+        return "monitor: a chain with the Resampler is not monitored (the receiver takes the native rate); turn the monitor off";
+    if (p.mask & DABGPU_STAGE_NOGUARD)
+        return "monitor: a chain without the guard interval is not monitored; turn the monitor off";
+    if (p.fmt != 0 && p.fmt != DABGPU_FMT_S16)
+        return "monitor: u8 / s8 output is not monitored (the receiver takes complexf or s16); turn the monitor off";
+    int early = c->cur.monitor_early;
+    if (early < 0)
+        early = ((p.mask & DABGPU_STAGE_FIR) ? (int)c->cur.taps.size() - 1 : 0) + (int)c->cur.overlap;
+    if (early > c->g.sym_size - c->g.N) return kEarlyRange;
+    return nullptr;
+}
+
+int run_monitor(dabgpu_ctx *c, const ChainPlan &p, const void *d_bits, const void *d_iq, hipStream_t s)
+{
+    if (!c->cur.monitor || p.n_frames == 0) return DABGPU_OK;
+    int early = c->cur.monitor_early;
+    if (early < 0)
+        early = ((p.mask & DABGPU_STAGE_FIR) ? (int)c->cur.taps.size() - 1 : 0) + (int)c->cur.overlap;
+    return queue_demod(c, d_iq, p.fmt, p.n_frames, early, nullptr, d_bits, s);
+}
+}  // namespace dabgpu_api
+
+extern "C" {
+int dabgpu_demod_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *d_bits_out,
+                     const void *d_ref_bits, void *stream)
+{
+    CTXCHK(c);
+    int rc = apply_settings(c);
+    if (rc) return rc;
+    if ((rc = check_demod(c, d_iq, format, n_frames, early, d_bits_out, d_ref_bits))) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;       // (d_iq: a chain call's output on any lane)
+    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
+    return queue_demod(c, d_iq, format, n_frames, early, d_bits_out, d_ref_bits, s);
+}
+
+int dabgpu_demod(dabgpu_ctx *c, const void *iq, int format, size_t n_frames, int early, uint8_t *bits_out,
+                 const uint8_t *ref_bits)
+{
+    CTXCHK(c);
+    int rc = check_demod(c, iq, format, n_frames, early, nullptr, nullptr);
+    if (rc) return rc;
+    if ((rc = dabgpu_synchronize(c))) return rc;                      // (d_out is the synchronous host path's)
+    const size_t iq_bytes = n_frames * tf_samples(c->g) * (format ? 4 : sizeof(float2));
+    const size_t bit_bytes = n_frames * tf_in_bytes(c->g);
+    HostIO io(c);
+    if ((rc = io.in(c->d_out, iq, iq_bytes))) return rc;
+    if (ref_bits && (rc = io.in(c->d_demod_ref, ref_bits, bit_bytes))) return rc;
+    if (bits_out) HIPCHK(c, c->d_demod_bits.reserve(std::max<size_t>(bit_bytes, 16)));
+    if ((rc = dabgpu_demod_dev(c, c->d_out.p, format, n_frames, early, bits_out ? c->d_demod_bits.p : nullptr,
+                               ref_bits ? c->d_demod_ref.p : nullptr, c->stream)))
+        return rc;
+    return io.out(bits_out, c->d_demod_bits.p, bits_out ? bit_bytes : 0);
+}
+
+int dabgpu_get_demod_stats(dabgpu_ctx *c, size_t frame, dabgpu_demod_stats *out)
+{
+    CTXCHK(c);
+    if (!out) return fail(c, DABGPU_E_INVALID, "null argument");
+    if (frame >= c->demod_frames)
+        return fail(c, DABGPU_E_INVALID, "no demodulator statistics for this frame (no call yet, or frame index out of range)");
+    HIPCHK(c, hipStreamSynchronize(c->demod_stream ? c->demod_stream : c->stream));
+    DemodFrameStats st;
+    HIPCHK(c, hipMemcpy(&st, (const DemodFrameStats *)c->d_demod_stats.p + frame, sizeof st, hipMemcpyDeviceToHost));
+    std::memset(out, 0, sizeof *out);
+    out->sum_signal = st.sum_signal;
+    out->sum_quadrature = st.sum_quadrature;
+    out->bit_errors = st.bit_errors;
+    out->n_bits = c->demod_has_ref ? 8 * (uint64_t)tf_in_bytes(c->g) : 0;
+    const unsigned mbits = ~st.min_margin_inv;
+    float m;
+    std::memcpy(&m, &mbits, sizeof m);
+    out->min_margin = st.min_margin_inv ? (double)m : 0.0;
+    return DABGPU_OK;
+}
+
+int dabgpu_demod_check_early(int mode, int early)
+{
+    Geometry g;
+    if (!mode_geometry(mode, &g)) return fail(nullptr, DABGPU_E_INVALID, "demod: transmission mode not valid");
+    if (early < 0 || early > g.sym_size - g.N) return fail(nullptr, DABGPU_E_INVALID, kEarlyRange);
+    return DABGPU_OK;
+}
+
+int dabgpu_set_monitor(dabgpu_ctx *c, int enable, int early)
+{
+    if (!c) return DABGPU_E_INVALID;
+    if (enable && early > c->g.sym_size - c->g.N) return fail(c, DABGPU_E_INVALID, kEarlyRange);
+    std::lock_guard<std::mutex> lk(c->mu);
+    const int e = early < 0 ? -1 : early;
+    if (c->set.monitor == (enable != 0) && c->set.monitor_early == e) return DABGPU_OK;
+    c->set.monitor = enable != 0;
+    c->set.monitor_early = e;
+    ++c->set.epoch;
+    return DABGPU_OK;
+}
+
+int dabgpu_debug_demod_run_symbols(dabgpu_ctx *c, int symbols)
+{
+    if (!c) return DABGPU_E_INVALID;
+    if (symbols < 0) return fail(c, DABGPU_E_INVALID, "demod: symbols per run: a positive number, or 0 = by the batch size");
+    c->demod_run_symbols = symbols;
+    return DABGPU_OK;
+}
+
+}  // extern "C"

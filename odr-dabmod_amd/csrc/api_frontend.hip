@@ -498,6 +498,7 @@ int dabgpu_chain_process_eti(dabgpu_ctx *c, const uint8_t *eti, size_t n_eti, un
     if ((rc = apply_settings(c))) return rc;
     const ChainPlan p = plan_chain(c, true, n_tf, mask, true, true, chain_cic(c));
     if (p.error) return fail(c, DABGPU_E_INVALID, p.error);          // (before the front-end advances its history)
+    if (const char *why = monitor_refusal(c, p)) return fail(c, DABGPU_E_INVALID, why);
     const size_t need = p.out_bytes;
     if ((rc = check_out(c, need, out_cap, out_bytes))) return rc;
     HIPCHK(c, c->d_in.reserve(std::max<size_t>(n_tf * tf_in_bytes(c->g), 16)));
@@ -509,6 +510,7 @@ int dabgpu_chain_process_eti(dabgpu_ctx *c, const uint8_t *eti, size_t n_eti, un
     {
         TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
         rc = run_chain(c, p, c->d_in.p, c->d_out.p, need, &ob, c->stream);
+        if (!rc) rc = run_monitor(c, p, c->d_in.p, c->d_out.p, c->stream);
     }
     if (rc) return rc;
     return io.out(iq_out, c->d_out.p, need);

@@ -7,6 +7,8 @@
 //   api_stages.hip    one host-buffer entry point per reference plugin, FormatConverter, CFR statistics
 //   api_state.hip     the stream state (resampler halo, TII frame parity): read, installed, computed from a lead-in frame
 //                     of coded bits or, with the front-end's, from the ETI frames in front of a chunk
+//   api_demod.hip     the receiver (demod.hip): IQ -> coded bits and per-frame quality figures, stand-alone and as the monitor
+//                     that rides on a chain call
 //   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
 //                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
 #pragma once
@@ -64,6 +66,8 @@ struct Settings {
     int tii_comb = 0, tii_pattern = 0;
     size_t cic_spacing = 0;                // dabgpu_set_cic_equalizer: CicEqualizer(carriers, spacing, R) between cifSig and
     int cic_R = 0;                         // cifOfdm of every chain call (src/DabModulator.cpp:155-176,399); 0 / 0 = off
+    bool monitor = false;                  // dabgpu_set_monitor: every native-rate chain call is demodulated against its own bits
+    int monitor_early = -1;                //   the FFT window's lead in samples; < 0: from the call's filter and window
     unsigned long long epoch = 1;  // bumped by every setter
     bool resampler_reset = true;
 
@@ -162,6 +166,13 @@ struct dabgpu_ctx {
     int cfr_last_base = 0;
     size_t cfr_last_frames = 0;
     hipStream_t cfr_last_stream = nullptr;
+    // The receiver (api_demod.hip): the records of the most recent dabgpu_demod* call or monitored chain call, the stream
+    // they are complete on, and the staging of the host-pointer entry.  Monitored calls stay on lane 0: one set.
+    dabgpu_api::DevBuf d_demod_stats, d_demod_bits, d_demod_ref;
+    size_t demod_frames = 0;
+    bool demod_has_ref = false;
+    hipStream_t demod_stream = nullptr;
+    int demod_run_symbols = 0;            // dabgpu_debug_demod_run_symbols: symbols per workgroup, 0 = by the batch size
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII
     bool tables_valid = false;            // apply_settings has uploaded every table group once
     unsigned long long tii_seg_epoch = 0; // 1 while the cached segment matches the settings (apply_settings zeroes it), and its stage mask
@@ -365,6 +376,14 @@ int run_native_tii(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, float2 *
 int run_front(dabgpu_ctx *c, const ChainPlan &p, const void **d_in, hipStream_t s);
 int run_chain(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, void *d_out_v, size_t out_cap, size_t *out_bytes,
               hipStream_t s, bool apply_format = true, int lane = 0);
+
+// ---- api_demod.hip
+// The monitor (dabgpu_set_monitor) on a chain call from coded bits.  monitor_refusal: the message when the monitor is on and
+// the planned call cannot be demodulated (nullptr: off, or fine) -- asked before anything is queued.  run_monitor: behind
+// run_chain on the same stream, the call's output against the call's own bits; nothing when the monitor is off.
+const char *monitor_refusal(const dabgpu_ctx *c, const ChainPlan &p);
+extern const char *const kMonitorNoSubmit;
+int run_monitor(dabgpu_ctx *c, const ChainPlan &p, const void *d_bits, const void *d_iq, hipStream_t s);
 
 // host-pointer stage wrapper: H2D, launch, D2H on the context stream
 struct HostIO {

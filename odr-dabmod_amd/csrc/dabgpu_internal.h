@@ -152,6 +152,28 @@ struct CarrierArgs {
     int tii_insert0;          // frame 0 of this launch carries TII (then every other one)
 };
 hipError_t launch_carriers_from_bits(const CarrierArgs &a, hipStream_t s);
+// demod.hip: native-rate IQ of whole transmission frames -> coded bits and per-frame quality figures (dabgpu_demod*, the monitor)
+struct DemodFrameStats {                  // zeroed before the launch; every run of the frame adds its share
+    double sum_signal, sum_quadrature;
+    unsigned long long bit_errors;
+    unsigned min_margin_inv;              // ~(bit pattern of the smallest margin so far); 0: no decision yet
+    unsigned reserved;
+};
+struct DemodArgs {
+    Geometry g;
+    Tables t;                 // twiddle, src_carrier
+    const void *iq;           // n_frames x frame_stride samples: cf32 (fmt 0) or s16 pairs (fmt 1 = DABGPU_FMT_S16)
+    int fmt;
+    size_t frame_stride;      // samples per frame
+    int n_frames;
+    int runs_per_frame, syms_per_run;   // (demod_runs)
+    int early;                // the FFT window ends this many samples before the end of the symbol; 0 ... sym_size - N
+    uint8_t *bits_out;        // nullptr, or n_frames x (nb_symbols - 1) * K / 4 bytes, dword aligned
+    const uint8_t *ref_bits;  // nullptr, or the same shape: differing bits are counted
+    DemodFrameStats *stats;   // n_frames records
+};
+void demod_runs(const Geometry &g, size_t n_frames, int forced, int *runs_per_frame, int *syms_per_run);
+hipError_t launch_demod(const DemodArgs &a, hipStream_t s);
 // f-4 TII: the sparse symbol (stand-alone stage), and its addition to a stream whose null symbol is blank
 hipError_t launch_tii(const float2 *in, const uint8_t *acp, int K, int old_variant, int insert, float2 *out,
                       hipStream_t s);

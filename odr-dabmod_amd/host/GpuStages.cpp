@@ -917,6 +917,48 @@ DabGpuChain::DabGpuChain(const Settings &s, const LiveSettings &live)
         m_ctx.check(dabgpu_set_resampler(dev, 2048000, s.outputRate));
     }
     if (!coefFile.empty()) m_rc_poly.reset(new PolyParameters(dev, coefFile));   // (in the mask while its settings are valid)
+    if (s.monitor) {
+        m_ctx.check(dabgpu_set_monitor(dev, 1, s.monitorEarly));
+        m_monitor = true;
+    }
+}
+
+DabGpuChain::MonitorTotals DabGpuChain::read_monitor(size_t n_frames)
+{
+    MonitorTotals t;
+    for (size_t f = 0; f < n_frames; ++f) {
+        dabgpu_demod_stats st;
+        m_ctx.check(dabgpu_get_demod_stats(m_ctx.get(), f, &st));
+        const double mer = 10.0 * std::log10(st.sum_signal / st.sum_quadrature);
+        t.worst_mer_db = t.frames ? std::min(t.worst_mer_db, mer) : mer;
+        t.sum_mer_db += mer;
+        t.bit_errors += st.bit_errors;
+        t.n_bits += st.n_bits;
+        ++t.frames;
+    }
+    return t;
+}
+
+// submit() / submit_eti() of a monitored chain: the synchronous entry, which the library monitors, into a buffer of the chain's
+void DabGpuChain::run_monitored(const void *src, size_t n, bool eti)
+{
+    if (m_mon_queue.size() == 2) throw std::runtime_error("two batches are already in flight: collect one first");
+    const unsigned mask = stage_mask();
+    dabgpu_geometry g;
+    m_ctx.check(dabgpu_get_geometry(m_ctx.get(), &g));
+    const size_t cifs = g.mode == 1 ? 4 : g.mode == 4 ? 2 : 1;
+    const size_t n_frames = eti ? n / cifs : n;
+    MonitoredBatch b;
+    b.iq.resize(std::max<size_t>(n_frames * dabgpu_chain_out_bytes_per_frame(m_ctx.get(), mask), 1));
+    size_t got = 0;
+    if (eti)
+        m_ctx.check(dabgpu_chain_process_eti(m_ctx.get(), static_cast<const uint8_t *>(src), n, mask, b.iq.data(), b.iq.size(), &got));
+    else
+        m_ctx.check(dabgpu_chain_process(m_ctx.get(), static_cast<const uint8_t *>(src), n, mask, b.iq.data(), b.iq.size(), &got));
+    b.iq.resize(got);
+    b.totals = read_monitor(n_frames);
+    if (m_own.outputFormat != "complexf") m_ctx.check(dabgpu_get_num_clipped(m_ctx.get(), &b.clipped));
+    m_mon_queue.push_back(std::move(b));
 }
 
 std::vector<RemoteControllable *> DabGpuChain::remote_controllables() const
@@ -958,6 +1000,7 @@ void DabGpuChain::submit(const void *bits, size_t n_frames)
     if (m_drops)
         throw std::runtime_error("DabGpuChain::submit: Settings::emulatePipelineDrops applies to process() only");
     before_frames();
+    if (m_monitor) return run_monitored(bits, n_frames, false);
     m_ctx.check(dabgpu_chain_submit(m_ctx.get(), static_cast<const uint8_t *>(bits), n_frames, stage_mask()));
 }
 
@@ -971,6 +1014,7 @@ void DabGpuChain::submit_eti(const void *eti_frames, size_t n_eti)
     if (m_drops)
         throw std::runtime_error("DabGpuChain::submit_eti: Settings::emulatePipelineDrops applies to process() only");
     before_frames();
+    if (m_monitor) return run_monitored(eti_frames, n_eti, true);
     m_ctx.check(dabgpu_chain_submit_eti(m_ctx.get(), static_cast<const uint8_t *>(eti_frames), n_eti, stage_mask()));
 }
 
@@ -1016,6 +1060,16 @@ void DabGpuChain::seed_eti(const void *frames, size_t n_leadin, uint64_t e)
 
 size_t DabGpuChain::collect(const void **iq)
 {
+    if (m_monitor) {
+        if (m_mon_queue.empty()) throw std::runtime_error("no batch in flight");
+        MonitoredBatch &keep = m_mon_out[m_mon_seq++ & 1];
+        keep = std::move(m_mon_queue.front());
+        m_mon_queue.pop_front();
+        m_mon_last = keep.totals;
+        m_mon_collected = true;
+        *iq = keep.iq.data();
+        return keep.iq.size();
+    }
     size_t n = 0;
     m_ctx.check(dabgpu_chain_collect(m_ctx.get(), iq, &n));
     return n;
@@ -1028,6 +1082,7 @@ size_t DabGpuChain::output_bytes_per_frame() const
 
 size_t DabGpuChain::get_num_clipped_samples() const
 {
+    if (m_monitor && m_mon_collected) return m_mon_out[(m_mon_seq - 1) & 1].clipped;
     size_t n = 0;
     m_ctx.check(dabgpu_get_num_clipped(m_ctx.get(), &n));
     return n;
@@ -1071,5 +1126,9 @@ int DabGpuChain::process(Buffer *const dataIn, Buffer *dataOut)
                                      dataOut->getData(), dataOut->getLength(), &n));
     dataOut->setLength(n);
     after_frames();
+    if (m_monitor) {
+        m_mon_last = read_monitor(1);
+        m_mon_collected = false;
+    }
     return static_cast<int>(n);
 }

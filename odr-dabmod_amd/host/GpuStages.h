@@ -419,6 +419,14 @@ public:
         // 2048000).  0 / 0 = off, the default.  Fixed at construction, as in the reference (dabgpu_set_cic_equalizer).
         size_t cicSpacing = 0;
         int cicRatio = 0;
+        // The receiver behind every call (dabgpu_set_monitor; include/dabgpu.h, "the receiver"): the call's own output is
+        // demodulated on the device against the call's own coded bits; monitor_totals() then describes the frames of the
+        // last process() / collect().  Native-rate complexf or s16 output only (the constructor of a chain with a Resampler
+        // or u8 / s8 output throws at the first frame, with the library's message).  The library does not monitor its streaming
+        // entries, so submit() / submit_eti() of a monitored chain run their batch at once and collect() hands it out: the
+        // same bytes, without the overlap of copy and kernels.  Off by default, and nothing changes while it is off.
+        bool monitor = false;
+        int monitorEarly = -1;            // the FFT window's lead in samples; < 0: from the filter and the window
         unsigned referencePipelineDepth() const
         {
             return (enableGain ? 1u : 0u) + (filterTapsFilename.empty() ? 0u : 1u) + (polyCoefFilename.empty() ? 0u : 1u);
@@ -437,8 +445,16 @@ public:
         bool *enableCfr = nullptr;
         float *cfrClip = nullptr, *cfrErrorClip = nullptr;
     };
+    // what the monitor counted on the frames of one call; MER in dB per frame, 10 log10(sum_signal / sum_quadrature)
+    struct MonitorTotals {
+        size_t frames = 0;
+        uint64_t bit_errors = 0, n_bits = 0;
+        double worst_mer_db = 0.0, sum_mer_db = 0.0;     // (mean = sum_mer_db / frames)
+    };
     explicit DabGpuChain(const Settings &s);
     DabGpuChain(const Settings &s, const LiveSettings &live);
+    // Settings::monitor: the frames of the most recent process() or collect(); all zero before the first, or with the monitor off
+    const MonitorTotals &monitor_totals() const { return m_mon_last; }
     ~DabGpuChain() override;
     // the RemoteControllables to enrol (rcs.enrol(p), lib/RemoteControl.h:141); owned by the chain
     std::vector<RemoteControllable *> remote_controllables() const;
@@ -483,6 +499,19 @@ private:
     unsigned stage_mask();                // the live mask: predistortion leaves it while its settings are invalid
     void before_frames();                 // live parameters -> context
     void after_frames();                  // CFR statistics
+    MonitorTotals read_monitor(size_t n_frames);      // the figures of the call that just ran
+    struct MonitoredBatch {               // Settings::monitor: a batch submit() ran at once, until collect() hands it out
+        std::vector<uint8_t> iq;
+        MonitorTotals totals;
+        size_t clipped = 0;
+    };
+    void run_monitored(const void *src, size_t n, bool eti);
+    std::deque<MonitoredBatch> m_mon_queue;
+    MonitoredBatch m_mon_out[2];          // the two batches handed out last (collect()'s pointer stays valid as documented)
+    unsigned m_mon_seq = 0;
+    MonitorTotals m_mon_last;
+    bool m_monitor = false;
+    bool m_mon_collected = false;         // get_num_clipped_samples() answers for the batch collect() returned last
     dabgpu_host::Context m_ctx;
     Settings m_own;                       // the values no LiveSettings pointer claims
     unsigned m_mask = 0;

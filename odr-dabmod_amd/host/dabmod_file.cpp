@@ -36,6 +36,10 @@
 //                        on a stream whose FP jumps (the CPU front-end never looks at FP after the start) the program
 //                        stops with that message.  Not with --contexts above 1 (the time interleaver's history is not part of the stream state a
 //                        chain is seeded with), --bits-only or --separate-converter.
+//   --monitor            the receiver behind every GPU call (DabGpuChain::Settings::monitor): every frame written is decoded on the
+//                        device against the coded bits it was made from.  After the run: frames, bit errors, worst and mean MER
+//                        on stderr; exit status 2 when a bit error was counted.  The output file is the one without the option.
+//                        Native-rate complexf / s16 output; with --batch the batches run one at a time.
 //   --state-out FILE     with --gpu-frontend: after the last frame, write where the stream stands -- the number of ETI frames
 //                        modulated since FP = 0 and both stream-state blobs (DabGpuChain::get_stream_state /
 //                        frontend_state) -- so that another run continues it
@@ -71,6 +75,7 @@ namespace {
                          "                        N > 1 not with --bits-only or --separate-converter)\n"
                          "       [--gpu-frontend]   ETI -> coded bits on the device as well (not with --contexts above 1, --bits-only,\n"
                          "                        --separate-converter)\n"
+                         "       [--monitor]   decode every frame written on the device; totals on stderr, exit 2 on a bit error\n"
                          "       [--state-out FILE] [--state-in FILE]   with --gpu-frontend: leave / take up the stream's state\n");
     std::exit(2);
 }
@@ -173,6 +178,7 @@ int main(int argc, char **argv)
             else if (a == "--reference-latency") reference_latency = true;
             else if (a == "--reference-gain") gs.referenceGainRounding = true;
             else if (a == "--gpu-frontend") gpu_frontend = true;
+            else if (a == "--monitor") gs.monitor = true;
             else if (a == "--state-in") state_in = val();
             else if (a == "--state-out") state_out = val();
             else if (a == "--contexts") {
@@ -192,6 +198,12 @@ int main(int argc, char **argv)
                                         "the stream state a chain is seeded with"
                          : bits_only  ? "--bits-only: the coded bits stay on the device"
                                       : "--separate-converter: the streaming path converts inside the chain");
+            return 2;
+        }
+
+        if (gs.monitor && (bits_only || separate_converter)) {
+            std::fprintf(stderr, "dabmod_file: --monitor does not go with %s\n",
+                         bits_only ? "--bits-only: nothing is modulated" : "--separate-converter: the chain's own output is what is decoded");
             return 2;
         }
 
@@ -228,11 +240,23 @@ int main(int argc, char **argv)
         std::deque<std::vector<uint8_t>> held;    // --batch with --reference-latency: the frames "inside the pipeline"
         size_t n_out = 0;                         // transmission frames written
         int in_flight = 0;
+        DabGpuChain::MonitorTotals mon;           // --monitor: summed over the calls (and the contexts)
+        auto add_monitor = [&](const DabGpuChain *ch) {
+            if (!gs.monitor) return;
+            const DabGpuChain::MonitorTotals &t = ch->monitor_totals();
+            if (!t.frames) return;
+            mon.worst_mer_db = mon.frames ? std::min(mon.worst_mer_db, t.worst_mer_db) : t.worst_mer_db;
+            mon.frames += t.frames;
+            mon.bit_errors += t.bit_errors;
+            mon.n_bits += t.n_bits;
+            mon.sum_mer_db += t.sum_mer_db;
+        };
         // the oldest batch in flight, in stream order: batch j lives on chain j mod N
         auto drain_one = [&]() {
             DabGpuChain *ch = chain_of(n_collected++);
             const void *p = nullptr;
             const size_t n = ch->collect(&p);
+            add_monitor(ch);
             n_out += n / ch->output_bytes_per_frame();
             if (format != "complexf") clipped += ch->get_num_clipped_samples();
             out.write(static_cast<const char *>(p), static_cast<std::streamsize>(n));
@@ -351,6 +375,7 @@ int main(int argc, char **argv)
                     if (separate_converter && format != "complexf") converter.reset(new FormatConverter(false, format));
                 }
                 if (chain->process(&bits, &iq) == 0) continue;       // (a frame inside the emulated pipeline: nothing yet)
+                add_monitor(chain.get());
                 ++n_out;
                 const Buffer *o = &iq;
                 if (converter) {
@@ -389,6 +414,12 @@ int main(int argc, char **argv)
         if (format != "complexf") std::fprintf(stderr, ", %zu clipped components", clipped);
         std::fprintf(stderr, "\n");
         std::printf("%zu %zu %zu\n", n_eti, n_tf, n_out);
+        if (gs.monitor) {
+            std::fprintf(stderr, "dabmod_file: monitor: %zu frames decoded, %llu bit errors in %llu bits, MER worst %.2f dB, mean %.2f dB\n",
+                         mon.frames, static_cast<unsigned long long>(mon.bit_errors), static_cast<unsigned long long>(mon.n_bits),
+                         mon.worst_mer_db, mon.frames ? mon.sum_mer_db / static_cast<double>(mon.frames) : 0.0);
+            if (mon.bit_errors) return 2;
+        }
         return 0;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "dabmod_file: %s\n", e.what());
