@@ -601,6 +601,74 @@ DABGPU_API int dabgpu_set_monitor(dabgpu_ctx *ctx, int enable, int early);
  * 0 (the default) = chosen from the batch size.  Same bits for every value; exists so that a test can walk the run geometry. */
 DABGPU_API int dabgpu_debug_demod_run_symbols(dabgpu_ctx *ctx, int symbols);
 
+/* ---- the spectrum monitor: Welch power spectrum of any sample buffer, mask check ----------------------------------------- *
+ * The other half of what a transmitter operator watches: the out-of-band shoulders FIRFilter exists for, which CFR, the
+ * predistorter, the guard window and the integer formats all trade against MER.  The reference has no such stage; these
+ * entries replace nothing of its flowgraph.  The estimate is an averaged periodogram: segments of 2048 samples (in every
+ * transmission mode) at a hop of 1024, segment i = samples 1024 i ... 1024 i + 2047 for i = 0 ... floor((n_samples - 2048) /
+ * 1024); fewer than 2048 samples give no segment, the tail that fills no segment is not used, segments never span two calls.
+ * Each segment is multiplied by a window table (fp32), transformed on the device (fp32) and |X_w[k]|^2 is added in float64.
+ * It needs no symbol timing, no native rate and no particular format: `format` is 0 (complexf), DABGPU_FMT_S16 (int16 pairs,
+ * value as it is), DABGPU_FMT_U8 (byte - 128: what FormatConverter adds, undone) or DABGPU_FMT_S8 (value as it is).  The
+ * null symbol and whatever else lies in the buffer are part of the estimate.  There are no floating-point atomics: the sums
+ * are a function of input, window and run geometry alone, and repeat bit for bit.
+ * dabgpu_spectrum_window: host only, no context.  window 0 rectangular, 1 Hann 0.5 - 0.5 cos(2 pi k / N), 2 four-term
+ *   Blackman-Harris (0.35875, 0.48829, 0.14128, 0.01168); periodic form, evaluated in float64 and rounded to fp32 -- the very
+ *   table the kernel multiplies by.  DABGPU_E_INVALID for another window or a null pointer (dabgpu_last_error(NULL)).
+ * dabgpu_spectrum_dev: device pointer aligned to the sample size (8 / 4 / 2 / 2 bytes), asynchronous on `stream` (NULL: the
+ *   context's own stream, behind every lane).  accumulate 0: the sums start over with this call; otherwise it adds to them,
+ *   and must use the window they were formed with.  n_samples < 2048 is accepted and adds nothing.  Calls on different streams
+ *   share one accumulator and one scratch: the caller orders them.  dabgpu_spectrum: the host-pointer form.
+ * dabgpu_get_spectrum: waits for the most recent spectrum work, then raw[k] = sum over segments of |X_w[k]|^2, bins in FFT
+ *   order (k = 0 is DC, k >= 1024 the negative frequencies), and info (either may be NULL).  A power density estimate is
+ *   raw / (segments * sum_w2).  rate_hz: 2 048 000 L / M of the context's resampler for monitored chain calls (2 048 000
+ *   without the Resampler in the mask), 0 for the stand-alone entries, which do not know the rate.
+ * dabgpu_reset_spectrum: sums and segment count to zero.
+ * Refused with DABGPU_E_INVALID and a message before anything is queued: unknown format or window, a pointer not aligned to
+ * the sample size, a null pointer with samples, accumulating with another window than the sums hold. */
+typedef struct dabgpu_spectrum_info {
+    uint64_t segments;
+    int nfft, window;
+    double sum_w2;      /* sum of w^2 over the fp32 table, in float64 */
+    double rate_hz;
+} dabgpu_spectrum_info;
+DABGPU_API int dabgpu_spectrum_window(int window, float *out2048);
+DABGPU_API int dabgpu_spectrum_dev(dabgpu_ctx *ctx, const void *d_iq, int format, size_t n_samples, int window,
+                                   int accumulate, void *stream);
+DABGPU_API int dabgpu_spectrum(dabgpu_ctx *ctx, const void *iq, int format, size_t n_samples, int window, int accumulate);
+DABGPU_API int dabgpu_get_spectrum(dabgpu_ctx *ctx, double *raw2048, dabgpu_spectrum_info *info);
+DABGPU_API int dabgpu_reset_spectrum(dabgpu_ctx *ctx);
+/* dabgpu_set_spectrum_monitor -- the spectrum monitor: off by default, and while it is off launches, bytes and trace are what they were.  While it is on,
+ * every dabgpu_chain_process / _process_dev / _process_eti call queues the two kernels behind its last kernel (behind the
+ * receiver's when dabgpu_set_monitor is on too), on the same stream, over whatever samples the call wrote, in the call's
+ * output format -- chains with the Resampler, MemlessPoly, u8 / s8 output and without the guard interval included -- and the
+ * sums accumulate from call to call until dabgpu_reset_spectrum (or until the window or the output rate changes, which starts
+ * them over; a stand-alone dabgpu_spectrum / _dev call in between takes the sums for itself, so the next monitored call starts
+ * them over as well).  The IQ is what the call writes with the monitor off.  Monitored calls stay on lane 0: two reduce kernels must
+ * not race on the sums.  dabgpu_chain_submit* is refused before anything is queued.  Takes effect at the next call. */
+DABGPU_API int dabgpu_set_spectrum_monitor(dabgpu_ctx *ctx, int enable, int window);
+/* dabgpu_debug_spectrum_run_segments -- diagnostic: segments per workgroup of spectrum_kernel; 0 (the default) = chosen from the input size (about 1024 workgroups,
+ * four segments or more each).  At most 65536 workgroups whatever is asked.  The sums agree to float64 reordering for every
+ * value; exists so that a test can walk the run geometry. */
+DABGPU_API int dabgpu_debug_spectrum_run_segments(dabgpu_ctx *ctx, int segments);
+/* dabgpu_spectrum_check_mask -- host only, no context, no device: a spectrum against a mask.  Bin k of nfft lies at f_k = (k < nfft/2 ? k : k - nfft) rate_hz
+ * / nfft.  ref = mean of raw over the bins with 0 < |f_k| <= 768 kHz (the occupied band in all four modes); level_k =
+ * 10 log10(raw[k] / ref).  The mask is n_points (offs_hz, limit_db) pairs with offs_hz strictly increasing: the limit at |f_k| is
+ * piecewise linear in dB between the points, the last value holds beyond the last offset, bins below the first offset are not
+ * checked.  Out: ref, worst_margin_db = min over the checked bins of limit - level and the frequency it lies at, the number of
+ * bins with level > limit, and oob_max_db = max level over |f_k| >= oob_from_hz with its frequency (callers default to 970 kHz,
+ * which is only a default; -infinity when no bin lies there).  With n_points = 0 only ref and oob_max_db are formed (worst_margin_db 0, n_checked 0).  Refused
+ * (DABGPU_E_INVALID, dabgpu_last_error(NULL)): null raw / out, nfft < 2, a rate_hz with no bin in the band, offsets not strictly
+ * increasing, a ref that is zero or not finite. */
+typedef struct dabgpu_mask_result {
+    double ref;
+    double worst_margin_db, worst_freq_hz;
+    int n_violations, n_checked;
+    double oob_max_db, oob_freq_hz;
+} dabgpu_mask_result;
+DABGPU_API int dabgpu_spectrum_check_mask(const double *raw, int nfft, double rate_hz, const double *offs_hz,
+                                          const double *limit_db, int n_points, double oob_from_hz, dabgpu_mask_result *out);
+
 /* wait for everything queued on the context's own stream(s): every lane */
 DABGPU_API int dabgpu_synchronize(dabgpu_ctx *ctx);
 

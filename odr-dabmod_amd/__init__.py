@@ -45,6 +45,8 @@ EXPORTS = [
     "dabgpu_set_cic_equalizer", "dabgpu_carriers_process", "dabgpu_carriers_process_dev",
     "dabgpu_demod", "dabgpu_demod_dev", "dabgpu_get_demod_stats", "dabgpu_demod_check_early", "dabgpu_set_monitor",
     "dabgpu_debug_demod_run_symbols",
+    "dabgpu_spectrum_window", "dabgpu_spectrum", "dabgpu_spectrum_dev", "dabgpu_get_spectrum", "dabgpu_reset_spectrum",
+    "dabgpu_set_spectrum_monitor", "dabgpu_debug_spectrum_run_segments", "dabgpu_spectrum_check_mask",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -90,6 +92,21 @@ class _CfrStats(C.Structure):
 class _DemodStats(C.Structure):
     _fields_ = [("sum_signal", C.c_double), ("sum_quadrature", C.c_double), ("bit_errors", C.c_uint64),
                 ("n_bits", C.c_uint64), ("min_margin", C.c_double)]
+
+
+class _SpectrumInfo(C.Structure):
+    _fields_ = [("segments", C.c_uint64), ("nfft", C.c_int), ("window", C.c_int), ("sum_w2", C.c_double),
+                ("rate_hz", C.c_double)]
+
+
+class _MaskResult(C.Structure):
+    _fields_ = [("ref", C.c_double), ("worst_margin_db", C.c_double), ("worst_freq_hz", C.c_double),
+                ("n_violations", C.c_int), ("n_checked", C.c_int), ("oob_max_db", C.c_double), ("oob_freq_hz", C.c_double)]
+
+
+SPECTRUM_NFFT = 2048
+WINDOWS = {"rect": 0, "hann": 1, "blackman-harris": 2}
+OOB_FROM_HZ = 970e3                                # where callers start to look for the out-of-band maximum by default
 
 
 class _Geometry(C.Structure):
@@ -216,6 +233,15 @@ def load_library():
     lib.dabgpu_demod_check_early.argtypes = [C.c_int, C.c_int]
     lib.dabgpu_set_monitor.argtypes = [vp, C.c_int, C.c_int]
     lib.dabgpu_debug_demod_run_symbols.argtypes = [vp, C.c_int]
+    dp = C.POINTER(C.c_double)
+    lib.dabgpu_spectrum_window.argtypes = [C.c_int, C.POINTER(C.c_float)]
+    lib.dabgpu_spectrum.argtypes = [vp, vp, C.c_int, sz, C.c_int, C.c_int]
+    lib.dabgpu_spectrum_dev.argtypes = [vp, vp, C.c_int, sz, C.c_int, C.c_int, vp]
+    lib.dabgpu_get_spectrum.argtypes = [vp, dp, C.POINTER(_SpectrumInfo)]
+    lib.dabgpu_reset_spectrum.argtypes = [vp]
+    lib.dabgpu_set_spectrum_monitor.argtypes = [vp, C.c_int, C.c_int]
+    lib.dabgpu_debug_spectrum_run_segments.argtypes = [vp, C.c_int]
+    lib.dabgpu_spectrum_check_mask.argtypes = [dp, C.c_int, C.c_double, dp, dp, C.c_int, C.c_double, C.POINTER(_MaskResult)]
     _lib = lib
     return lib
 
@@ -226,6 +252,37 @@ def demod_check_early(mode, early):
     lib = load_library()
     if lib.dabgpu_demod_check_early(int(mode), int(early)) != 0:
         raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def spectrum_window(window):
+    """Host only (needs the library, no device): the 2048-entry fp32 window table the spectrum kernel multiplies by --
+    0 rectangular, 1 Hann, 2 four-term Blackman-Harris, periodic form."""
+    lib = load_library()
+    out = np.empty(SPECTRUM_NFFT, np.float32)
+    if lib.dabgpu_spectrum_window(int(window), out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return out
+
+
+def spectrum_freqs(rate_hz, nfft=SPECTRUM_NFFT):
+    """The frequency of every bin in FFT order: f_k = (k < nfft/2 ? k : k - nfft) rate_hz / nfft."""
+    k = np.arange(nfft)
+    return np.where(k < nfft // 2, k, k - nfft) * (float(rate_hz) / nfft)
+
+
+def check_mask(raw, rate_hz, mask=(), oob_from_hz=OOB_FROM_HZ):
+    """Host only: dabgpu_spectrum_check_mask on raw sums in FFT order.  mask: (offset_hz, limit_db) pairs, offsets strictly
+    increasing (empty: only ref and the out-of-band maximum are formed).  Returns a dict of the result's fields."""
+    lib = load_library()
+    raw = np.ascontiguousarray(raw, np.float64).reshape(-1)
+    pts = np.ascontiguousarray(mask, np.float64).reshape(-1, 2)
+    offs, lim = np.ascontiguousarray(pts[:, 0]), np.ascontiguousarray(pts[:, 1])
+    dp = C.POINTER(C.c_double)
+    res = _MaskResult()
+    if lib.dabgpu_spectrum_check_mask(raw.ctypes.data_as(dp), raw.size, float(rate_hz), offs.ctypes.data_as(dp),
+                                      lim.ctypes.data_as(dp), offs.size, float(oob_from_hz), C.byref(res)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return {k: getattr(res, k) for k, _ in _MaskResult._fields_}
 
 
 def fir_inverse_design(taps):
@@ -779,6 +836,67 @@ class Modulator:
     def set_demod_run_symbols(self, symbols=0):
         """Diagnostic: data symbols per workgroup of the receiver's kernel (0: chosen from the batch size)."""
         self._chk(self._lib.dabgpu_debug_demod_run_symbols(self._h, int(symbols)))
+
+    # ---- the spectrum monitor: Welch power spectrum of any sample buffer (include/dabgpu.h, "the spectrum monitor") ----
+    def spectrum(self, iq, window=2, accumulate=False):
+        """Host path: consecutive samples as numpy complex64, or int16 / uint8 / int8 interleaved (re, im), into the Welch
+        sums (2048-point segments at a hop of 1024).  The result: spectrum_stats()."""
+        iq = np.ascontiguousarray(iq).reshape(-1)
+        fmt = {np.dtype(np.complex64): 0, np.dtype(np.int16): 1, np.dtype(np.uint8): 2, np.dtype(np.int8): 3}.get(iq.dtype)
+        if fmt is None:
+            raise DabGpuError("spectrum: input is complex64, or int16 / uint8 / int8 (interleaved re, im)")
+        if fmt and iq.size % 2:
+            raise DabGpuError("spectrum: integer input is (re, im) pairs")
+        n = iq.size if fmt == 0 else iq.size // 2
+        self._chk(self._lib.dabgpu_spectrum(self._h, iq.ctypes.data if n else None, fmt, n, int(window),
+                                            int(bool(accumulate))))
+
+    def spectrum_dev(self, d_iq, window=2, accumulate=False, stream=None, n_samples=None):
+        """Device path on a torch tensor (complex64, or int16 / uint8 / int8 pairs), asynchronous on the stream as
+        chain_dev; n_samples: the first so many samples of the tensor (default: all of it)."""
+        import torch
+        fmt = {torch.complex64: 0, torch.int16: 1, torch.uint8: 2, torch.int8: 3}.get(d_iq.dtype)
+        if fmt is None:
+            raise DabGpuError("spectrum: input is complex64, or int16 / uint8 / int8 (interleaved re, im)")
+        if not d_iq.is_contiguous():
+            raise DabGpuError("spectrum: the tensor must be contiguous (consecutive samples in memory)")
+        if fmt and d_iq.numel() % 2:
+            raise DabGpuError("spectrum: integer input is (re, im) pairs")
+        have = d_iq.numel() if fmt == 0 else d_iq.numel() // 2
+        n = have if n_samples is None else int(n_samples)
+        if n > have:
+            raise DabGpuError("spectrum: n_samples exceeds the tensor")
+        s = self._stream_handle(d_iq, stream)
+        self._chk(self._lib.dabgpu_spectrum_dev(self._h, d_iq.data_ptr() if n else None, fmt, n, int(window),
+                                                int(bool(accumulate)), s))
+        if not s:
+            self.synchronize()
+
+    def set_spectrum_monitor(self, enable, window=2):
+        """Every chain call's output, whatever its rate and format, goes into the Welch sums (off by default); they
+        accumulate until reset_spectrum().  The figures: spectrum_stats()."""
+        self._chk(self._lib.dabgpu_set_spectrum_monitor(self._h, int(bool(enable)), int(window)))
+
+    def reset_spectrum(self):
+        self._chk(self._lib.dabgpu_reset_spectrum(self._h))
+
+    def spectrum_stats(self, rate_hz=None):
+        """Waits for the most recent spectrum work: raw (sum over segments of |X_w[k]|^2, FFT order, float64), segments,
+        nfft, window, sum_w2, rate_hz (the library's for monitored chain calls, else the argument, else 0),
+        psd = raw / (segments sum_w2), and freqs (Hz per bin in FFT order) when the rate is known."""
+        raw = np.empty(SPECTRUM_NFFT, np.float64)
+        info = _SpectrumInfo()
+        self._chk(self._lib.dabgpu_get_spectrum(self._h, raw.ctypes.data_as(C.POINTER(C.c_double)), C.byref(info)))
+        d = {"raw": raw, "segments": int(info.segments), "nfft": int(info.nfft), "window": int(info.window),
+             "sum_w2": float(info.sum_w2), "rate_hz": float(rate_hz) if rate_hz else float(info.rate_hz)}
+        with np.errstate(divide="ignore", invalid="ignore"):
+            d["psd"] = raw / (d["segments"] * d["sum_w2"]) if d["segments"] and d["sum_w2"] else np.zeros_like(raw)
+        d["freqs"] = spectrum_freqs(d["rate_hz"]) if d["rate_hz"] else None
+        return d
+
+    def set_spectrum_run_segments(self, segments=0):
+        """Diagnostic: segments per workgroup of the spectrum kernel (0: chosen from the input size)."""
+        self._chk(self._lib.dabgpu_debug_spectrum_run_segments(self._h, int(segments)))
 
     def synchronize(self):
         """Wait for everything the context has queued, on every lane."""

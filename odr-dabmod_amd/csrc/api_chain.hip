@@ -771,6 +771,7 @@ int dabgpu_chain_process(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, un
         TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
         rc = run_chain(c, p, c->d_in.p, c->d_out.p, need, &ob, c->stream);
         if (!rc) rc = run_monitor(c, p, c->d_in.p, c->d_out.p, c->stream);
+        if (!rc) rc = run_spectrum_monitor(c, p, c->d_out.p, c->stream);
     }
     if (rc) return rc;
     return io.out(iq_out, c->d_out.p, need);

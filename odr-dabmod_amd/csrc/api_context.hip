@@ -530,7 +530,8 @@ void dabgpu_destroy(dabgpu_ctx *c)
                       &c->d_acp, &c->d_tii_car, &c->d_tii_frame, &c->d_gain1, &c->d_gains, &c->d_cic,
                       &c->d_cfr_counts, &c->d_cfr_mer, &c->d_cfr_papr, &c->d_cfr_tmp,
                       &c->d_fe_prbs, &c->d_fe_units, &c->d_fe_owner, &c->d_fe_hist, &c->d_fe_tmp, &c->d_fe_fic, &c->d_fe_eti,
-                      &c->d_fe_seed, &c->d_demod_stats, &c->d_demod_bits, &c->d_demod_ref})
+                      &c->d_fe_seed, &c->d_demod_stats, &c->d_demod_bits, &c->d_demod_ref,
+                      &c->d_spec_tw, &c->d_spec_win, &c->d_spec_rows, &c->d_spec_acc, &c->d_spec_in})
         b->release();
     for (auto &sl : c->slot) {
         sl.d_eti.release();

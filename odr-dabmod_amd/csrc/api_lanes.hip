@@ -66,7 +66,7 @@ int drain_lanes(dabgpu_ctx *c)
 int pick_lane(dabgpu_ctx *c, bool from_bits, size_t n_frames, unsigned mask, ChainPlan *p)
 {
     c->call_lanes = 1;
-    if (c->n_lanes > 1 && !c->cur.monitor && !(normalised_mask(c->cur, mask) & DABGPU_STAGE_RESAMPLE) &&
+    if (c->n_lanes > 1 && !c->cur.monitor && !c->cur.spectrum && !(normalised_mask(c->cur, mask) & DABGPU_STAGE_RESAMPLE) &&
         n_frames <= (size_t)dabgpu_ctx::kLaneMaxFrames) {
         c->call_lanes = c->n_lanes;             // (planned as one of n_lanes launches in flight: auto_chunks)
         *p = plan_chain(c, from_bits, n_frames, mask, true, true, chain_cic(c));
@@ -101,6 +101,7 @@ int chain_dev(dabgpu_ctx *c, const void *d_in, bool from_bits, size_t n_frames, 
     rc = run_chain(c, p, d_in, d_iq, out_cap, out_bytes, s, true, lane);
     c->call_lanes = 1;
     if (!rc && monitored) rc = run_monitor(c, p, d_in, d_iq, s);
+    if (!rc && from_bits) rc = run_spectrum_monitor(c, p, d_iq, s);
     return rc;
 }
 
@@ -192,6 +193,7 @@ int chain_submit(dabgpu_ctx *c, const uint8_t *bits, size_t n_frames, unsigned m
     int rc = apply_settings(c);
     if (rc) return rc;
     if (c->cur.monitor) return fail(c, DABGPU_E_INVALID, kMonitorNoSubmit);
+    if (c->cur.spectrum) return fail(c, DABGPU_E_INVALID, kSpectrumNoSubmit);
     const int slot_index = (c->slot_head + c->slot_count) & 1;
     dabgpu_ctx::Slot &sl = c->slot[slot_index];
     // the two batches in flight run on two lanes where the chain carries no stream state: their kernels overlap

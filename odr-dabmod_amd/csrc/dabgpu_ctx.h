@@ -9,6 +9,8 @@
 //                     of coded bits or, with the front-end's, from the ETI frames in front of a chunk
 //   api_demod.hip     the receiver (demod.hip): IQ -> coded bits and per-frame quality figures, stand-alone and as the monitor
 //                     that rides on a chain call
+//   api_spectrum.hip  the spectrum monitor (spectrum.hip): Welch power spectrum of any sample buffer, stand-alone and behind a
+//                     chain call; the window tables and the mask check (host only)
 //   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
 //                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
 #pragma once
@@ -68,6 +70,8 @@ struct Settings {
     int cic_R = 0;                         // cifOfdm of every chain call (src/DabModulator.cpp:155-176,399); 0 / 0 = off
     bool monitor = false;                  // dabgpu_set_monitor: every native-rate chain call is demodulated against its own bits
     int monitor_early = -1;                //   the FFT window's lead in samples; < 0: from the call's filter and window
+    bool spectrum = false;                 // dabgpu_set_spectrum_monitor: every chain call's output goes into the Welch sums
+    int spectrum_window = 2;               //   the window table (dabgpu_spectrum_window)
     unsigned long long epoch = 1;  // bumped by every setter
     bool resampler_reset = true;
 
@@ -173,6 +177,15 @@ struct dabgpu_ctx {
     bool demod_has_ref = false;
     hipStream_t demod_stream = nullptr;
     int demod_run_symbols = 0;            // dabgpu_debug_demod_run_symbols: symbols per workgroup, 0 = by the batch size
+    // The spectrum monitor (api_spectrum.hip): the 2048-entry twiddle table (the context's own in Mode I), the three window
+    // tables, the rows of one launch, the sums (2048 float64 and the segment count) and the host-pointer entry's staging.
+    // One accumulator: monitored calls stay on lane 0.  spec_window: the window the sums were formed with, -1 = none yet.
+    dabgpu_api::DevBuf d_spec_tw, d_spec_win, d_spec_rows, d_spec_acc, d_spec_in;
+    bool spec_ready = false;
+    int spec_window = -1;
+    double spec_rate_hz = 0.0;
+    hipStream_t spec_stream = nullptr;
+    int spec_run_segments = 0;            // dabgpu_debug_spectrum_run_segments: segments per workgroup, 0 = by the input size
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII
     bool tables_valid = false;            // apply_settings has uploaded every table group once
     unsigned long long tii_seg_epoch = 0; // 1 while the cached segment matches the settings (apply_settings zeroes it), and its stage mask
@@ -384,6 +397,12 @@ int run_chain(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, void *d_out_v
 const char *monitor_refusal(const dabgpu_ctx *c, const ChainPlan &p);
 extern const char *const kMonitorNoSubmit;
 int run_monitor(dabgpu_ctx *c, const ChainPlan &p, const void *d_bits, const void *d_iq, hipStream_t s);
+
+// ---- api_spectrum.hip
+// The spectrum monitor (dabgpu_set_spectrum_monitor) on a chain call from coded bits: behind run_chain (and run_monitor) on
+// the same stream, over the samples the call wrote; nothing when it is off.
+extern const char *const kSpectrumNoSubmit;
+int run_spectrum_monitor(dabgpu_ctx *c, const ChainPlan &p, const void *d_iq, hipStream_t s);
 
 // host-pointer stage wrapper: H2D, launch, D2H on the context stream
 struct HostIO {

@@ -174,6 +174,22 @@ struct DemodArgs {
 };
 void demod_runs(const Geometry &g, size_t n_frames, int forced, int *runs_per_frame, int *syms_per_run);
 hipError_t launch_demod(const DemodArgs &a, hipStream_t s);
+// spectrum.hip: Welch periodogram of one sample buffer (dabgpu_spectrum*, the spectrum monitor): segments of SPECTRUM_NFFT
+// samples at a hop of half that, in every transmission mode
+enum { SPECTRUM_NFFT = 2048, kSpectrumMaxRuns = 1 << 16 };
+struct SpectrumArgs {
+    const void *iq;           // the samples: cf32 (fmt 0), s16 pairs (1), u8 pairs, value byte - 128 (2), s8 pairs (3)
+    int fmt;
+    long long n_segments;     // floor((n_samples - 2048) / 1024) + 1, or 0
+    int n_runs, segs_per_run; // (spectrum_runs)
+    const float2 *twiddle;    // exp(+2 pi i m / 2048), 2048 entries
+    const float *window;      // 2048 fp32 factors
+    double *rows;             // scratch, n_runs x 2048: a workgroup's partial sums, bins in FFT order
+    double *acc;              // 2048 sums, then the segment count as one unsigned long long
+    int accumulate;           // the reduce kernel adds to acc (else stores)
+};
+void spectrum_runs(long long n_segments, int forced, int *n_runs, int *segs_per_run);
+hipError_t launch_spectrum(const SpectrumArgs &a, hipStream_t s);
 // f-4 TII: the sparse symbol (stand-alone stage), and its addition to a stream whose null symbol is blank
 hipError_t launch_tii(const float2 *in, const uint8_t *acp, int K, int old_variant, int insert, float2 *out,
                       hipStream_t s);

@@ -921,6 +921,23 @@ DabGpuChain::DabGpuChain(const Settings &s, const LiveSettings &live)
         m_ctx.check(dabgpu_set_monitor(dev, 1, s.monitorEarly));
         m_monitor = true;
     }
+    if (s.spectrum) {
+        m_ctx.check(dabgpu_set_spectrum_monitor(dev, 1, s.spectrumWindow));
+        m_spectrum = true;
+    }
+}
+
+DabGpuChain::SpectrumTotals DabGpuChain::spectrum_totals()
+{
+    SpectrumTotals t;
+    t.raw.assign(2048, 0.0);
+    dabgpu_spectrum_info info;
+    m_ctx.check(dabgpu_get_spectrum(m_ctx.get(), t.raw.data(), &info));
+    t.segments = info.segments;
+    t.rate_hz = info.rate_hz;
+    t.sum_w2 = info.sum_w2;
+    t.window = info.window;
+    return t;
 }
 
 DabGpuChain::MonitorTotals DabGpuChain::read_monitor(size_t n_frames)
@@ -956,7 +973,7 @@ void DabGpuChain::run_monitored(const void *src, size_t n, bool eti)
     else
         m_ctx.check(dabgpu_chain_process(m_ctx.get(), static_cast<const uint8_t *>(src), n, mask, b.iq.data(), b.iq.size(), &got));
     b.iq.resize(got);
-    b.totals = read_monitor(n_frames);
+    if (m_monitor) b.totals = read_monitor(n_frames);
     if (m_own.outputFormat != "complexf") m_ctx.check(dabgpu_get_num_clipped(m_ctx.get(), &b.clipped));
     m_mon_queue.push_back(std::move(b));
 }
@@ -1000,7 +1017,7 @@ void DabGpuChain::submit(const void *bits, size_t n_frames)
     if (m_drops)
         throw std::runtime_error("DabGpuChain::submit: Settings::emulatePipelineDrops applies to process() only");
     before_frames();
-    if (m_monitor) return run_monitored(bits, n_frames, false);
+    if (m_monitor || m_spectrum) return run_monitored(bits, n_frames, false);
     m_ctx.check(dabgpu_chain_submit(m_ctx.get(), static_cast<const uint8_t *>(bits), n_frames, stage_mask()));
 }
 
@@ -1014,7 +1031,7 @@ void DabGpuChain::submit_eti(const void *eti_frames, size_t n_eti)
     if (m_drops)
         throw std::runtime_error("DabGpuChain::submit_eti: Settings::emulatePipelineDrops applies to process() only");
     before_frames();
-    if (m_monitor) return run_monitored(eti_frames, n_eti, true);
+    if (m_monitor || m_spectrum) return run_monitored(eti_frames, n_eti, true);
     m_ctx.check(dabgpu_chain_submit_eti(m_ctx.get(), static_cast<const uint8_t *>(eti_frames), n_eti, stage_mask()));
 }
 
@@ -1060,7 +1077,7 @@ void DabGpuChain::seed_eti(const void *frames, size_t n_leadin, uint64_t e)
 
 size_t DabGpuChain::collect(const void **iq)
 {
-    if (m_monitor) {
+    if (m_monitor || m_spectrum) {
         if (m_mon_queue.empty()) throw std::runtime_error("no batch in flight");
         MonitoredBatch &keep = m_mon_out[m_mon_seq++ & 1];
         keep = std::move(m_mon_queue.front());
@@ -1082,7 +1099,7 @@ size_t DabGpuChain::output_bytes_per_frame() const
 
 size_t DabGpuChain::get_num_clipped_samples() const
 {
-    if (m_monitor && m_mon_collected) return m_mon_out[(m_mon_seq - 1) & 1].clipped;
+    if ((m_monitor || m_spectrum) && m_mon_collected) return m_mon_out[(m_mon_seq - 1) & 1].clipped;
     size_t n = 0;
     m_ctx.check(dabgpu_get_num_clipped(m_ctx.get(), &n));
     return n;
@@ -1126,9 +1143,7 @@ int DabGpuChain::process(Buffer *const dataIn, Buffer *dataOut)
                                      dataOut->getData(), dataOut->getLength(), &n));
     dataOut->setLength(n);
     after_frames();
-    if (m_monitor) {
-        m_mon_last = read_monitor(1);
-        m_mon_collected = false;
-    }
+    if (m_monitor) m_mon_last = read_monitor(1);
+    if (m_monitor || m_spectrum) m_mon_collected = false;
     return static_cast<int>(n);
 }

@@ -427,6 +427,12 @@ public:
         // same bytes, without the overlap of copy and kernels.  Off by default, and nothing changes while it is off.
         bool monitor = false;
         int monitorEarly = -1;            // the FFT window's lead in samples; < 0: from the filter and the window
+        // The spectrum monitor behind every call (dabgpu_set_spectrum_monitor; include/dabgpu.h, "the spectrum monitor"): the
+        // samples every call writes -- any rate, any output format -- go into one Welch power spectrum that accumulates over
+        // the chain's life; spectrum_totals() reads it.  submit() / submit_eti() batches run at once through the synchronous
+        // entry, as with `monitor`.  Off by default, and nothing changes while it is off.
+        bool spectrum = false;
+        int spectrumWindow = 2;           // 0 rectangular, 1 Hann, 2 Blackman-Harris (dabgpu_spectrum_window)
         unsigned referencePipelineDepth() const
         {
             return (enableGain ? 1u : 0u) + (filterTapsFilename.empty() ? 0u : 1u) + (polyCoefFilename.empty() ? 0u : 1u);
@@ -451,10 +457,20 @@ public:
         uint64_t bit_errors = 0, n_bits = 0;
         double worst_mer_db = 0.0, sum_mer_db = 0.0;     // (mean = sum_mer_db / frames)
     };
+    // the spectrum monitor's sums so far: raw[k] = sum over segments of |X_w[k]|^2 in FFT order (2048 bins), the segments
+    // behind them, the sample rate of the chain's output and the window's sum of squares (psd = raw / (segments * sum_w2))
+    struct SpectrumTotals {
+        std::vector<double> raw;
+        uint64_t segments = 0;
+        double rate_hz = 0.0, sum_w2 = 0.0;
+        int window = -1;
+    };
     explicit DabGpuChain(const Settings &s);
     DabGpuChain(const Settings &s, const LiveSettings &live);
     // Settings::monitor: the frames of the most recent process() or collect(); all zero before the first, or with the monitor off
     const MonitorTotals &monitor_totals() const { return m_mon_last; }
+    // Settings::spectrum: waits for the chain's work; all zero before the first frame, or with the spectrum monitor off
+    SpectrumTotals spectrum_totals();
     ~DabGpuChain() override;
     // the RemoteControllables to enrol (rcs.enrol(p), lib/RemoteControl.h:141); owned by the chain
     std::vector<RemoteControllable *> remote_controllables() const;
@@ -511,6 +527,7 @@ private:
     unsigned m_mon_seq = 0;
     MonitorTotals m_mon_last;
     bool m_monitor = false;
+    bool m_spectrum = false;              // Settings::spectrum: batches run at once too, the totals stay the receiver's
     bool m_mon_collected = false;         // get_num_clipped_samples() answers for the batch collect() returned last
     dabgpu_host::Context m_ctx;
     Settings m_own;                       // the values no LiveSettings pointer claims

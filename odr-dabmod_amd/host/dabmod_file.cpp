@@ -40,6 +40,15 @@
 //                        device against the coded bits it was made from.  After the run: frames, bit errors, worst and mean MER
 //                        on stderr; exit status 2 when a bit error was counted.  The output file is the one without the option.
 //                        Native-rate complexf / s16 output; with --batch the batches run one at a time.
+//   --spectrum FILE      the spectrum monitor behind every GPU call (DabGpuChain::Settings::spectrum): a Welch power spectrum of
+//                        everything written -- any rate, any format -- 2048 bins, Blackman-Harris window.  After the run FILE
+//                        holds one "offset_hz level_db" line per bin in ascending frequency, level relative to the mean over
+//                        the occupied band (+-768 kHz); stderr gets the segments and the out-of-band maximum (from --oob-from
+//                        HZ, default 970000) with its frequency.  The output file is the one without the option.  With
+//                        --contexts N the contexts' sums are added.  Not with --bits-only or --separate-converter.
+//   --mask MASKFILE      with --spectrum: "offset_hz limit_db" per line (# starts a comment), offsets increasing; the limit is
+//                        piecewise linear in dB between the points (dabgpu_spectrum_check_mask).  stderr gets the worst margin
+//                        and where it lies; exit status 3 when a bin lies above the mask (2 stays the monitor's).
 //   --state-out FILE     with --gpu-frontend: after the last frame, write where the stream stands -- the number of ETI frames
 //                        modulated since FP = 0 and both stream-state blobs (DabGpuChain::get_stream_state /
 //                        frontend_state) -- so that another run continues it
@@ -50,6 +59,7 @@
 //                        (Both need --gpu-frontend: the CPU front-end's time interleaver is host state the file does not carry.)
 #include "Frontend.h"
 #include "GpuStages.h"
+#include "dabgpu.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -76,6 +86,8 @@ namespace {
                          "       [--gpu-frontend]   ETI -> coded bits on the device as well (not with --contexts above 1, --bits-only,\n"
                          "                        --separate-converter)\n"
                          "       [--monitor]   decode every frame written on the device; totals on stderr, exit 2 on a bit error\n"
+                         "       [--spectrum FILE [--mask MASKFILE] [--oob-from HZ]]   power spectrum of everything written, per bin into FILE;\n"
+                         "                        exit 3 when it lies above the mask (lines of: offset_hz limit_db)\n"
                          "       [--state-out FILE] [--state-in FILE]   with --gpu-frontend: leave / take up the stream's state\n");
     std::exit(2);
 }
@@ -138,6 +150,8 @@ int main(int argc, char **argv)
     long contexts = 1;
     bool gpu_frontend = false;
     std::string state_in, state_out;
+    std::string spectrum_path, mask_path;
+    double oob_from = 970000.0;
     try {
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
@@ -179,6 +193,9 @@ int main(int argc, char **argv)
             else if (a == "--reference-gain") gs.referenceGainRounding = true;
             else if (a == "--gpu-frontend") gpu_frontend = true;
             else if (a == "--monitor") gs.monitor = true;
+            else if (a == "--spectrum") { spectrum_path = val(); gs.spectrum = true; }
+            else if (a == "--mask") mask_path = val();
+            else if (a == "--oob-from") oob_from = std::stod(val());
             else if (a == "--state-in") state_in = val();
             else if (a == "--state-out") state_out = val();
             else if (a == "--contexts") {
@@ -205,6 +222,40 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "dabmod_file: --monitor does not go with %s\n",
                          bits_only ? "--bits-only: nothing is modulated" : "--separate-converter: the chain's own output is what is decoded");
             return 2;
+        }
+
+        if (gs.spectrum && (bits_only || separate_converter)) {
+            std::fprintf(stderr, "dabmod_file: --spectrum does not go with %s\n",
+                         bits_only ? "--bits-only: nothing is modulated" : "--separate-converter: the chain's own output is what is measured");
+            return 2;
+        }
+        if (!mask_path.empty() && !gs.spectrum) {
+            std::fprintf(stderr, "dabmod_file: --mask needs --spectrum\n");
+            return 2;
+        }
+        std::vector<double> mask_offs, mask_limit;
+        if (!mask_path.empty()) {
+            std::ifstream mf(mask_path);
+            if (!mf) {
+                std::fprintf(stderr, "dabmod_file: cannot read %s\n", mask_path.c_str());
+                return 1;
+            }
+            std::string line;
+            while (std::getline(mf, line)) {
+                line = line.substr(0, line.find('#'));
+                double o, l;
+                char rest;
+                const int n = std::sscanf(line.c_str(), " %lf %lf %c", &o, &l, &rest);
+                if (n == 2) { mask_offs.push_back(o); mask_limit.push_back(l); }
+                else if (n != EOF && n != 0) {
+                    std::fprintf(stderr, "dabmod_file: %s: a line is \"offset_hz limit_db\"\n", mask_path.c_str());
+                    return 1;
+                }
+            }
+            if (mask_offs.empty()) {
+                std::fprintf(stderr, "dabmod_file: %s holds no mask point\n", mask_path.c_str());
+                return 1;
+            }
         }
 
         if (!gpu_frontend && !(state_in.empty() && state_out.empty())) {
@@ -418,8 +469,53 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "dabmod_file: monitor: %zu frames decoded, %llu bit errors in %llu bits, MER worst %.2f dB, mean %.2f dB\n",
                          mon.frames, static_cast<unsigned long long>(mon.bit_errors), static_cast<unsigned long long>(mon.n_bits),
                          mon.worst_mer_db, mon.frames ? mon.sum_mer_db / static_cast<double>(mon.frames) : 0.0);
-            if (mon.bit_errors) return 2;
         }
+        int mask_violations = 0;
+        if (gs.spectrum) {
+            // the contexts' sums added: one spectrum of the whole file
+            std::vector<double> raw(2048, 0.0);
+            uint64_t segments = 0;
+            double rate = 0.0;
+            auto add = [&](DabGpuChain *ch) {
+                const DabGpuChain::SpectrumTotals t = ch->spectrum_totals();
+                if (!t.segments) return;
+                for (size_t k = 0; k < raw.size(); ++k) raw[k] += t.raw[k];
+                segments += t.segments;
+                rate = t.rate_hz;
+            };
+            if (chain) add(chain.get());
+            for (auto &m : more) add(m.get());
+            if (!segments) {
+                std::fprintf(stderr, "dabmod_file: --spectrum: nothing was modulated, there is no spectrum to write\n");
+                return 1;
+            }
+            dabgpu_mask_result res;
+            if (dabgpu_spectrum_check_mask(raw.data(), 2048, rate, mask_offs.data(), mask_limit.data(), static_cast<int>(mask_offs.size()),
+                                           oob_from, &res) != 0)
+                throw std::runtime_error(std::string("--spectrum: ") + dabgpu_last_error(nullptr));
+            std::FILE *sf = std::fopen(spectrum_path.c_str(), "w");
+            if (!sf) {
+                std::fprintf(stderr, "dabmod_file: cannot write %s\n", spectrum_path.c_str());
+                return 1;
+            }
+            for (int i = 0; i < 2048; ++i) {
+                const int k = (i + 1024) & 2047;                       // ascending frequency: bins 1024 ... 2047, then 0 ... 1023
+                std::fprintf(sf, "%.3f %.6f\n", static_cast<double>(k < 1024 ? k : k - 2048) * rate / 2048.0, 10.0 * std::log10(raw[k] / res.ref));
+            }
+            if (std::fclose(sf) != 0) {
+                std::fprintf(stderr, "dabmod_file: cannot write %s\n", spectrum_path.c_str());
+                return 1;
+            }
+            std::fprintf(stderr, "dabmod_file: spectrum: %llu segments at %.0f Hz, out-of-band maximum %.2f dB at %.0f Hz (from %.0f Hz)\n",
+                         static_cast<unsigned long long>(segments), rate, res.oob_max_db, res.oob_freq_hz, oob_from);
+            if (!mask_offs.empty()) {
+                std::fprintf(stderr, "dabmod_file: mask: worst margin %.2f dB at %.0f Hz, %d of %d bins above the mask\n",
+                             res.worst_margin_db, res.worst_freq_hz, res.n_violations, res.n_checked);
+                mask_violations = res.n_violations;
+            }
+        }
+        if (gs.monitor && mon.bit_errors) return 2;
+        if (mask_violations) return 3;
         return 0;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "dabmod_file: %s\n", e.what());
