@@ -669,6 +669,116 @@ typedef struct dabgpu_mask_result {
 DABGPU_API int dabgpu_spectrum_check_mask(const double *raw, int nfft, double rate_hz, const double *offs_hz,
                                           const double *limit_db, int n_points, double oob_from_hz, dabgpu_mask_result *out);
 
+/* ---- DPD measurement: align the feedback capture, bin AM/AM and AM/PM, fit MemlessPoly ----------------------------------- *
+ * The numbers dabgpu_set_poly takes, from a block of transmitted samples (tx: complexf, format 0, or DABGPU_FMT_S16) and the
+ * matching capture of the amplifier's feedback path (rx: complexf), n samples each, without the IQ leaving the device.  The
+ * reference does this outside the modulator (python/dpd: ExtractStatistic.py, Model_Poly.py); no entry is named *_process.
+ * Three steps: cross-spectrum -> alignment (host), aligned statistics per amplitude bin, polynomial fit (host).
+ * dabgpu_dpd_xspectrum_dev / dabgpu_dpd_xspectrum: a Welch cross-spectrum in the spectrum monitor's geometry -- segments of
+ *   2048 samples at a hop of 1024, rectangular window; segment i of tx is samples 1024 i ... 1024 i + 2047, of rx the same
+ *   range shifted by rx_offset; a segment whose rx range leaves the buffer is not used.  Per bin (FFT order) S += TX conj(RX),
+ *   P_tx += |TX|^2, P_rx += |RX|^2: fp32 transforms and products, float64 sums, no floating-point atomics (the sums repeat
+ *   bit for bit; they agree to float64 reordering across run geometries).  Every call starts the sums over.
+ *   dabgpu_get_dpd_xspectrum waits and returns S (2048 complex doubles, re / im interleaved), P_tx, P_rx and the number of
+ *   segments used (any pointer may be NULL).
+ * dabgpu_dpd_solve_alignment: host only, no context.  c = inverse DFT of conj(S); lag = the l in -1024 ... 1023 of the largest
+ *   |c[l]|; tau in (-1, 1) maximises |sum_k conj(S[k]) e^{j w_k (lag + tau)}|, w_k = 2 pi f_k / 2048 with f_k the signed bin
+ *   number, found to better than 1e-9 in float64 (a scan at 1/32 sample, then bisection on the derivative of that power,
+ *   which a search on the power itself cannot reach: it is flat to 1e-8 around its maximum); gain = sum_k S[k] e^{-j w_k (lag + tau)} /
+ *   sum P_rx, the least-squares gain that maps the aligned rx onto tx; coherence = |sum_k S[k] e^{-j w_k (lag + tau)}|^2 /
+ *   (sum P_tx sum P_rx).  rx[i + lag + tau] belongs to tx[i].
+ * dabgpu_dpd_align_dev / dabgpu_dpd_align: two cross-spectrum passes and two solves.  Pass 1 at offset 0 gives the integer
+ *   lag, refused with a message when |lag| > DABGPU_DPD_MAX_LAG; pass 2 at rx_offset = lag gives tau, gain and coherence (and
+ *   moves lag by one where pass 1 landed next to the peak).  Waits for the device: the result is host data.
+ * dabgpu_dpd_delay_taps: host only.  taps[j] = sinc(j - 15 - tau) kaiser(j - 15 - tau), Kaiser window with beta = 10 over
+ *   +-16 samples around the sinc's peak, so that sum_j taps[j] x[i + j - 15] is x at i + tau; tau = 0 gives the unit impulse at tap 15 exactly.
+ *   |tau| < 1.
+ * dabgpu_dpd_measure_dev / dabgpu_dpd_measure: the statistics.  The aligned rx sample of tx sample i is
+ *   r = gain * sum_{j=0..31} taps[j] rx[i + lag + j - 15] (taps of al->tau, fp32); al = NULL means lag 0, tau 0, gain 1.
+ *   Sample i is used if and only if all 32 taps lie inside rx, whatever tau is.  a2 = re re + im im of the tx sample in fp32,
+ *   each operation rounded (no fused multiply-add); its bin is b = #{ j >= 1 : edge2[j] <= a2 } with edge2[j] the fp32
+ *   rounding of (j peak / n_bins)^2 formed in float64; n_bins is 1 ... DABGPU_DPD_MAX_BINS (the reference uses 64).  a2 >=
+ *   edge2[n_bins] counts as overflow and lands in no bin.  Two differences from ExtractStatistic.py: its strict inequalities
+ *   on both sides drop a sample that sits exactly on an edge, here it belongs to the bin above; and it keeps only the first
+ *   ES_n_per_bin samples of a bin in arrival order, which has no meaning on a device -- here every sample counts.
+ *   Per bin: n, sum |t|, sum |r|, sum phi, sum |r|^2, sum phi^2 with phi = atan2(Im(r conj t), Re(r conj t)).  Each term is
+ *   rounded once to an integer -- |t| and |r| in units of peak 2^-24, |r|^2 in units of peak^2 2^-24, phi in units of 2^-24
+ *   rad, phi^2 in units of 2^-24 rad^2 -- and integers are added: the sums are the same bits for every repetition and every
+ *   run geometry.  |r| is clamped at 16 peak, so no term passes 2^32, and the sums hold at most 2^31 samples: a call whose n
+ *   would take the samples offered since the sums started over past 2^31 is refused.  accumulate 0 starts the sums over;
+ *   otherwise the call adds to them and must use the peak and n_bins they were formed with.
+ * dabgpu_get_dpd_stats: waits; counts, the sums as doubles in their natural units, the raw integers (raw[b][0..5] = n,
+ *   sum |t|, sum |r|, sum phi, sum |r|^2, sum phi^2), overflow, samples_used (overflow included), peak, n_bins.
+ * dabgpu_reset_dpd: sums to zero, peak and n_bins forgotten.
+ * dabgpu_dpd_fit_poly: host only, no context.  Bins with n >= min_count are used; per bin t = mean |t|, r = mean |r|, p = mean
+ *   phi.  DABGPU_DPD_BASIS_MAGSQ (the default) is indirect learning for the predistorter this library runs, which evaluates both
+ *   polynomials in |x|^2 (src/MemlessPoly.cpp:244-258): t ~ sum am[i] r^(2i+1), p ~ sum pm[i] r^(2i); MemlessPoly applies
+ *   -sum pm, so am and pm go to dabgpu_set_poly as they are.  DABGPU_DPD_BASIS_REFERENCE restates Model_Poly.py, which fits
+ *   powers of the amplitude and therefore does NOT fit MemlessPoly: tx = sum c_i rx^i (i = 1 ... 5), phase = sum c_i tx^i
+ *   (i = 0 ... 4), tx the bin CENTRE (ExtractStatistic._tx_value_per_bin), phase zero where tx < tx_min, over the leading run
+ *   of bins with n >= min_count (the reference's crop rule with "full" replaced), tx / rx / phase rounded to fp32 as the
+ *   arrays Model_Poly.train takes are, and every power rounded to fp32 as `sig ** i` on those arrays is: the correctly
+ *   rounded power, which numpy's plain float32 power gives.  (numpy's AVX-512 float32 power is off by up to an ulp per entry
+ *   and moves Model_Poly's own coefficients by some 1e-5 from machine to machine; the pin is against the former.)  Either way: columns scaled by the largest abscissa, Householder QR in float64, rows times
+ *   sqrt(n) when `weighted`.  out = prev + lr (fit - prev), applied ONCE (prev NULL: am 1 0 0 0 0, pm 0).  Model_Poly.train
+ *   applies its rate twice, so the reference's effective rate is lr^2; the two agree at lr = 1.  info (may be
+ *   NULL): bins used, max |R_kk| / min |R_kk| of each scaled system and each fit's rms residual.  Fewer than six usable
+ *   bins is refused.
+ * Refused with DABGPU_E_INVALID and a message before anything is queued: a tx format other than 0 / DABGPU_FMT_S16, a pointer
+ * not aligned to the sample size, a null pointer with samples, n_bins outside 1 ... 256, peak <= 0 or not finite, another peak
+ * or n_bins while accumulating, the sample cap, |al->lag| > DABGPU_DPD_MAX_LAG, |al->tau| >= 1, |rx_offset| > 2^40. */
+#define DABGPU_DPD_MAX_LAG 1000
+#define DABGPU_DPD_MAX_BINS 256
+#define DABGPU_DPD_BASIS_MAGSQ 0
+#define DABGPU_DPD_BASIS_REFERENCE 1
+typedef struct dabgpu_dpd_alignment {
+    int lag;
+    double tau;
+    double gain_re, gain_im;
+    double coherence;
+} dabgpu_dpd_alignment;
+typedef struct dabgpu_dpd_stats {
+    int n_bins;
+    float peak;
+    uint64_t overflow, samples_used;
+    uint64_t count[DABGPU_DPD_MAX_BINS];
+    double sum_tx[DABGPU_DPD_MAX_BINS], sum_rx[DABGPU_DPD_MAX_BINS], sum_phase[DABGPU_DPD_MAX_BINS];
+    double sum_rx2[DABGPU_DPD_MAX_BINS], sum_phase2[DABGPU_DPD_MAX_BINS];
+    int64_t raw[DABGPU_DPD_MAX_BINS][6];
+} dabgpu_dpd_stats;
+typedef struct dabgpu_dpd_fit_info {
+    int bins_used;
+    double cond_am, cond_pm;
+    double resid_am, resid_pm;
+} dabgpu_dpd_fit_info;
+DABGPU_API int dabgpu_dpd_xspectrum_dev(dabgpu_ctx *ctx, const void *d_tx, int tx_format, const void *d_rx, size_t n_samples,
+                                        long long rx_offset, void *stream);
+DABGPU_API int dabgpu_dpd_xspectrum(dabgpu_ctx *ctx, const void *tx, int tx_format, const void *rx, size_t n_samples,
+                                    long long rx_offset);
+DABGPU_API int dabgpu_get_dpd_xspectrum(dabgpu_ctx *ctx, double *s2048x2, double *p_tx2048, double *p_rx2048,
+                                        uint64_t *segments);
+DABGPU_API int dabgpu_dpd_solve_alignment(const double *s2048x2, const double *p_tx2048, const double *p_rx2048,
+                                          dabgpu_dpd_alignment *out);
+DABGPU_API int dabgpu_dpd_align_dev(dabgpu_ctx *ctx, const void *d_tx, int tx_format, const void *d_rx, size_t n_samples,
+                                    dabgpu_dpd_alignment *out, void *stream);
+DABGPU_API int dabgpu_dpd_align(dabgpu_ctx *ctx, const void *tx, int tx_format, const void *rx, size_t n_samples,
+                                dabgpu_dpd_alignment *out);
+DABGPU_API int dabgpu_dpd_delay_taps(double tau, float taps[32]);
+DABGPU_API int dabgpu_dpd_measure_dev(dabgpu_ctx *ctx, const void *d_tx, int tx_format, const void *d_rx, size_t n_samples,
+                                      const dabgpu_dpd_alignment *al, float peak, int n_bins, int accumulate, void *stream);
+DABGPU_API int dabgpu_dpd_measure(dabgpu_ctx *ctx, const void *tx, int tx_format, const void *rx, size_t n_samples,
+                                  const dabgpu_dpd_alignment *al, float peak, int n_bins, int accumulate);
+DABGPU_API int dabgpu_get_dpd_stats(dabgpu_ctx *ctx, dabgpu_dpd_stats *out);
+DABGPU_API int dabgpu_reset_dpd(dabgpu_ctx *ctx);
+/* diagnostics: segments per workgroup of dpd_xspectrum_kernel (0, the default: about 1024 workgroups, four segments or more
+ * each) and tx samples per workgroup of dpd_stats_kernel (a multiple of 256 up to 2048; 0, the default: 2048).  The
+ * cross-spectrum agrees to float64 reordering for every value, the statistics are the same bits. */
+DABGPU_API int dabgpu_debug_dpd_run_segments(dabgpu_ctx *ctx, int segments);
+DABGPU_API int dabgpu_debug_dpd_tile(dabgpu_ctx *ctx, int samples);
+DABGPU_API int dabgpu_dpd_fit_poly(const dabgpu_dpd_stats *stats, int basis, uint64_t min_count, int weighted, double tx_min,
+                                   const float prev_am[5], const float prev_pm[5], double lr_am, double lr_pm, float am[5],
+                                   float pm[5], dabgpu_dpd_fit_info *info);
+
 /* wait for everything queued on the context's own stream(s): every lane */
 DABGPU_API int dabgpu_synchronize(dabgpu_ctx *ctx);
 

@@ -47,6 +47,10 @@ EXPORTS = [
     "dabgpu_debug_demod_run_symbols",
     "dabgpu_spectrum_window", "dabgpu_spectrum", "dabgpu_spectrum_dev", "dabgpu_get_spectrum", "dabgpu_reset_spectrum",
     "dabgpu_set_spectrum_monitor", "dabgpu_debug_spectrum_run_segments", "dabgpu_spectrum_check_mask",
+    "dabgpu_dpd_xspectrum", "dabgpu_dpd_xspectrum_dev", "dabgpu_get_dpd_xspectrum", "dabgpu_dpd_solve_alignment",
+    "dabgpu_dpd_align", "dabgpu_dpd_align_dev", "dabgpu_dpd_delay_taps", "dabgpu_dpd_measure", "dabgpu_dpd_measure_dev",
+    "dabgpu_get_dpd_stats", "dabgpu_reset_dpd", "dabgpu_debug_dpd_run_segments", "dabgpu_debug_dpd_tile",
+    "dabgpu_dpd_fit_poly",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -102,6 +106,28 @@ class _SpectrumInfo(C.Structure):
 class _MaskResult(C.Structure):
     _fields_ = [("ref", C.c_double), ("worst_margin_db", C.c_double), ("worst_freq_hz", C.c_double),
                 ("n_violations", C.c_int), ("n_checked", C.c_int), ("oob_max_db", C.c_double), ("oob_freq_hz", C.c_double)]
+
+
+class _DpdAlignment(C.Structure):
+    _fields_ = [("lag", C.c_int), ("tau", C.c_double), ("gain_re", C.c_double), ("gain_im", C.c_double),
+                ("coherence", C.c_double)]
+
+
+DPD_MAX_BINS, DPD_MAX_LAG, DPD_TAPS = 256, 1000, 32
+DPD_BASIS = {"magsq": 0, "reference": 1}
+
+
+class _DpdStats(C.Structure):
+    _fields_ = [("n_bins", C.c_int), ("peak", C.c_float), ("overflow", C.c_uint64), ("samples_used", C.c_uint64),
+                ("count", C.c_uint64 * DPD_MAX_BINS), ("sum_tx", C.c_double * DPD_MAX_BINS),
+                ("sum_rx", C.c_double * DPD_MAX_BINS), ("sum_phase", C.c_double * DPD_MAX_BINS),
+                ("sum_rx2", C.c_double * DPD_MAX_BINS), ("sum_phase2", C.c_double * DPD_MAX_BINS),
+                ("raw", C.c_int64 * 6 * DPD_MAX_BINS)]
+
+
+class _DpdFitInfo(C.Structure):
+    _fields_ = [("bins_used", C.c_int), ("cond_am", C.c_double), ("cond_pm", C.c_double), ("resid_am", C.c_double),
+                ("resid_pm", C.c_double)]
 
 
 SPECTRUM_NFFT = 2048
@@ -242,6 +268,22 @@ def load_library():
     lib.dabgpu_set_spectrum_monitor.argtypes = [vp, C.c_int, C.c_int]
     lib.dabgpu_debug_spectrum_run_segments.argtypes = [vp, C.c_int]
     lib.dabgpu_spectrum_check_mask.argtypes = [dp, C.c_int, C.c_double, dp, dp, C.c_int, C.c_double, C.POINTER(_MaskResult)]
+    ll, fp, al = C.c_longlong, C.POINTER(C.c_float), C.POINTER(_DpdAlignment)
+    lib.dabgpu_dpd_xspectrum.argtypes = [vp, vp, C.c_int, vp, sz, ll]
+    lib.dabgpu_dpd_xspectrum_dev.argtypes = [vp, vp, C.c_int, vp, sz, ll, vp]
+    lib.dabgpu_get_dpd_xspectrum.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_uint64)]
+    lib.dabgpu_dpd_solve_alignment.argtypes = [dp, dp, dp, al]
+    lib.dabgpu_dpd_align.argtypes = [vp, vp, C.c_int, vp, sz, al]
+    lib.dabgpu_dpd_align_dev.argtypes = [vp, vp, C.c_int, vp, sz, al, vp]
+    lib.dabgpu_dpd_delay_taps.argtypes = [C.c_double, fp]
+    lib.dabgpu_dpd_measure.argtypes = [vp, vp, C.c_int, vp, sz, al, C.c_float, C.c_int, C.c_int]
+    lib.dabgpu_dpd_measure_dev.argtypes = [vp, vp, C.c_int, vp, sz, al, C.c_float, C.c_int, C.c_int, vp]
+    lib.dabgpu_get_dpd_stats.argtypes = [vp, C.POINTER(_DpdStats)]
+    lib.dabgpu_reset_dpd.argtypes = [vp]
+    lib.dabgpu_debug_dpd_run_segments.argtypes = [vp, C.c_int]
+    lib.dabgpu_debug_dpd_tile.argtypes = [vp, C.c_int]
+    lib.dabgpu_dpd_fit_poly.argtypes = [C.POINTER(_DpdStats), C.c_int, C.c_uint64, C.c_int, C.c_double, fp, fp, C.c_double,
+                                        C.c_double, fp, fp, C.POINTER(_DpdFitInfo)]
     _lib = lib
     return lib
 
@@ -283,6 +325,81 @@ def check_mask(raw, rate_hz, mask=(), oob_from_hz=OOB_FROM_HZ):
                                       lim.ctypes.data_as(dp), offs.size, float(oob_from_hz), C.byref(res)) != 0:
         raise DabGpuError(lib.dabgpu_last_error(None).decode())
     return {k: getattr(res, k) for k, _ in _MaskResult._fields_}
+
+
+def _alignment_dict(a):
+    return {"lag": int(a.lag), "tau": float(a.tau), "gain": complex(a.gain_re, a.gain_im), "coherence": float(a.coherence)}
+
+
+def _alignment_struct(al):
+    """None, or a dict with lag / tau / gain (as dpd_align returns it) -> (_DpdAlignment or None)"""
+    if al is None:
+        return None
+    g = complex(al.get("gain", 1.0))
+    return _DpdAlignment(int(al.get("lag", 0)), float(al.get("tau", 0.0)), g.real, g.imag, float(al.get("coherence", 0.0)))
+
+
+def dpd_solve_alignment(S, p_tx, p_rx):
+    """Host only: dabgpu_dpd_solve_alignment on a cross-spectrum (S: 2048 complex, p_tx / p_rx: 2048 real, FFT order).
+    Returns a dict: lag, tau, gain (complex), coherence; rx[i + lag + tau] belongs to tx[i]."""
+    lib = load_library()
+    s2 = np.ascontiguousarray(S, np.complex128).reshape(-1)
+    pt = np.ascontiguousarray(p_tx, np.float64).reshape(-1)
+    pr = np.ascontiguousarray(p_rx, np.float64).reshape(-1)
+    if s2.size != SPECTRUM_NFFT or pt.size != SPECTRUM_NFFT or pr.size != SPECTRUM_NFFT:
+        raise DabGpuError("dpd_solve_alignment: S, p_tx and p_rx hold 2048 bins each")
+    dp = C.POINTER(C.c_double)
+    a = _DpdAlignment()
+    if lib.dabgpu_dpd_solve_alignment(s2.view(np.float64).ctypes.data_as(dp), pt.ctypes.data_as(dp), pr.ctypes.data_as(dp),
+                                      C.byref(a)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return _alignment_dict(a)
+
+
+def dpd_delay_taps(tau):
+    """Host only: the 32 fp32 taps of the fractional-delay filter the statistics kernel runs on rx (Kaiser-windowed sinc,
+    beta = 10, centred on tap 15; tau = 0 is the unit impulse)."""
+    lib = load_library()
+    out = np.empty(DPD_TAPS, np.float32)
+    if lib.dabgpu_dpd_delay_taps(float(tau), out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return out
+
+
+def _stats_struct(stats):
+    st = _DpdStats()
+    n = int(stats["n_bins"])
+    if not 1 <= n <= DPD_MAX_BINS:
+        raise DabGpuError("dpd: n_bins is 1 ... 256")
+    st.n_bins, st.peak = n, float(stats["peak"])
+    for name in ("count", "sum_tx", "sum_rx", "sum_phase"):
+        v = np.asarray(stats[name]).reshape(-1)
+        if v.size < n:
+            raise DabGpuError("dpd: %s holds fewer than n_bins entries" % name)
+        arr = getattr(st, name)
+        for b in range(n):
+            arr[b] = int(v[b]) if name == "count" else float(v[b])
+    return st
+
+
+def dpd_fit_poly(stats, basis="magsq", min_count=1, weighted=True, tx_min=0.0, prev_am=None, prev_pm=None, lr_am=1.0,
+                 lr_pm=1.0):
+    """Host only: dabgpu_dpd_fit_poly on per-bin statistics (the dict Modulator.dpd_stats() returns, or any dict with
+    n_bins, peak, count, sum_tx, sum_rx, sum_phase).  basis "magsq" (the default) gives the coefficients set_poly takes;
+    "reference" restates the reference's Model_Poly.  Returns (am, pm, info)."""
+    lib = load_library()
+    st = _stats_struct(stats)
+    fp = C.POINTER(C.c_float)
+    am, pm = np.zeros(5, np.float32), np.zeros(5, np.float32)
+    pa = None if prev_am is None else np.ascontiguousarray(prev_am, np.float32).reshape(5)
+    pp = None if prev_pm is None else np.ascontiguousarray(prev_pm, np.float32).reshape(5)
+    info = _DpdFitInfo()
+    if lib.dabgpu_dpd_fit_poly(C.byref(st), DPD_BASIS[basis] if isinstance(basis, str) else int(basis), int(min_count),
+                               int(bool(weighted)), float(tx_min), None if pa is None else pa.ctypes.data_as(fp),
+                               None if pp is None else pp.ctypes.data_as(fp), float(lr_am), float(lr_pm),
+                               am.ctypes.data_as(fp), pm.ctypes.data_as(fp), C.byref(info)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return am, pm, {k: getattr(info, k) for k, _ in _DpdFitInfo._fields_}
 
 
 def fir_inverse_design(taps):
@@ -897,6 +1014,122 @@ class Modulator:
     def set_spectrum_run_segments(self, segments=0):
         """Diagnostic: segments per workgroup of the spectrum kernel (0: chosen from the input size)."""
         self._chk(self._lib.dabgpu_debug_spectrum_run_segments(self._h, int(segments)))
+
+    # ---- DPD measurement: tx against the amplifier's feedback capture (include/dabgpu.h, "DPD measurement") ----
+    @staticmethod
+    def _dpd_host_pair(tx, rx):
+        tx = np.ascontiguousarray(tx).reshape(-1)
+        rx = np.ascontiguousarray(rx).reshape(-1)
+        fmt = {np.dtype(np.complex64): 0, np.dtype(np.int16): 1}.get(tx.dtype)
+        if fmt is None or rx.dtype != np.complex64:
+            raise DabGpuError("dpd: tx is complex64 or int16 (interleaved re, im), rx is complex64")
+        if fmt and tx.size % 2:
+            raise DabGpuError("dpd: integer input is (re, im) pairs")
+        n = tx.size if fmt == 0 else tx.size // 2
+        if rx.size != n:
+            raise DabGpuError("dpd: tx and rx hold the same number of samples")
+        return tx, rx, fmt, n
+
+    def _dpd_dev_pair(self, d_tx, d_rx, n_samples):
+        import torch
+        fmt = {torch.complex64: 0, torch.int16: 1}.get(d_tx.dtype)
+        if fmt is None or d_rx.dtype != torch.complex64:
+            raise DabGpuError("dpd: tx is complex64 or int16 (interleaved re, im), rx is complex64")
+        if not d_tx.is_contiguous() or not d_rx.is_contiguous():
+            raise DabGpuError("dpd: the tensors must be contiguous")
+        if fmt and d_tx.numel() % 2:
+            raise DabGpuError("dpd: integer input is (re, im) pairs")
+        have = min(d_tx.numel() if fmt == 0 else d_tx.numel() // 2, d_rx.numel())
+        n = have if n_samples is None else int(n_samples)
+        if n > have:
+            raise DabGpuError("dpd: n_samples exceeds a tensor")
+        return fmt, n
+
+    def dpd_xspectrum(self, tx, rx, rx_offset=0):
+        """Host path: the Welch cross-spectrum of tx (complex64 or int16 pairs) and rx (complex64), rx segments shifted by
+        rx_offset.  Returns dpd_xspectrum_result()."""
+        tx, rx, fmt, n = self._dpd_host_pair(tx, rx)
+        self._chk(self._lib.dabgpu_dpd_xspectrum(self._h, tx.ctypes.data if n else None, fmt, rx.ctypes.data if n else None,
+                                                 n, int(rx_offset)))
+        return self.dpd_xspectrum_result()
+
+    def dpd_xspectrum_dev(self, d_tx, d_rx, rx_offset=0, stream=None, n_samples=None):
+        """Device path on torch tensors, asynchronous on the stream as chain_dev; the result: dpd_xspectrum_result()."""
+        fmt, n = self._dpd_dev_pair(d_tx, d_rx, n_samples)
+        s = self._stream_handle(d_tx, stream)
+        self._chk(self._lib.dabgpu_dpd_xspectrum_dev(self._h, d_tx.data_ptr() if n else None, fmt,
+                                                     d_rx.data_ptr() if n else None, n, int(rx_offset), s))
+        if not s:
+            self.synchronize()
+
+    def dpd_xspectrum_result(self):
+        """Waits: S (2048 complex128: sum of TX conj(RX), FFT order), p_tx, p_rx (float64) and the segments used."""
+        S = np.empty(SPECTRUM_NFFT, np.complex128)
+        pt, pr = np.empty(SPECTRUM_NFFT, np.float64), np.empty(SPECTRUM_NFFT, np.float64)
+        seg = C.c_uint64()
+        dp = C.POINTER(C.c_double)
+        self._chk(self._lib.dabgpu_get_dpd_xspectrum(self._h, S.view(np.float64).ctypes.data_as(dp), pt.ctypes.data_as(dp),
+                                                     pr.ctypes.data_as(dp), C.byref(seg)))
+        return {"S": S, "p_tx": pt, "p_rx": pr, "segments": int(seg.value)}
+
+    def dpd_align(self, tx, rx):
+        """Host path: integer lag, sub-sample delay, gain and coherence of rx against tx (two cross-spectrum passes).
+        Returns a dict: lag, tau, gain (complex), coherence."""
+        tx, rx, fmt, n = self._dpd_host_pair(tx, rx)
+        a = _DpdAlignment()
+        self._chk(self._lib.dabgpu_dpd_align(self._h, tx.ctypes.data if n else None, fmt, rx.ctypes.data if n else None, n,
+                                             C.byref(a)))
+        return _alignment_dict(a)
+
+    def dpd_align_dev(self, d_tx, d_rx, stream=None, n_samples=None):
+        """Device path of dpd_align; waits for the stream, because the result is host data."""
+        fmt, n = self._dpd_dev_pair(d_tx, d_rx, n_samples)
+        a = _DpdAlignment()
+        self._chk(self._lib.dabgpu_dpd_align_dev(self._h, d_tx.data_ptr() if n else None, fmt, d_rx.data_ptr() if n else None,
+                                                 n, C.byref(a), self._stream_handle(d_tx, stream)))
+        return _alignment_dict(a)
+
+    def dpd_measure(self, tx, rx, alignment=None, peak=1.0, n_bins=64, accumulate=False):
+        """Host path: the aligned amplitude-bin statistics of the pair into the context's sums (dpd_stats()).  alignment: the
+        dict dpd_align returns (None: lag 0, tau 0, gain 1)."""
+        tx, rx, fmt, n = self._dpd_host_pair(tx, rx)
+        al = _alignment_struct(alignment)
+        self._chk(self._lib.dabgpu_dpd_measure(self._h, tx.ctypes.data if n else None, fmt, rx.ctypes.data if n else None, n,
+                                               None if al is None else C.byref(al), float(peak), int(n_bins),
+                                               int(bool(accumulate))))
+
+    def dpd_measure_dev(self, d_tx, d_rx, alignment=None, peak=1.0, n_bins=64, accumulate=False, stream=None, n_samples=None):
+        """Device path of dpd_measure, asynchronous on the stream as chain_dev."""
+        fmt, n = self._dpd_dev_pair(d_tx, d_rx, n_samples)
+        al = _alignment_struct(alignment)
+        s = self._stream_handle(d_tx, stream)
+        self._chk(self._lib.dabgpu_dpd_measure_dev(self._h, d_tx.data_ptr() if n else None, fmt,
+                                                   d_rx.data_ptr() if n else None, n, None if al is None else C.byref(al),
+                                                   float(peak), int(n_bins), int(bool(accumulate)), s))
+        if not s:
+            self.synchronize()
+
+    def dpd_stats(self):
+        """Waits: n_bins, peak, overflow, samples_used, and per bin count, sum_tx, sum_rx, sum_phase, sum_rx2, sum_phase2
+        (float64) and raw (int64, n_bins x 6: the integers the device added)."""
+        st = _DpdStats()
+        self._chk(self._lib.dabgpu_get_dpd_stats(self._h, C.byref(st)))
+        n = int(st.n_bins)
+        d = {"n_bins": n, "peak": float(st.peak), "overflow": int(st.overflow), "samples_used": int(st.samples_used),
+             "count": np.array(st.count[:n], np.uint64).astype(np.int64)}
+        for name in ("sum_tx", "sum_rx", "sum_phase", "sum_rx2", "sum_phase2"):
+            d[name] = np.array(getattr(st, name)[:n], np.float64)
+        d["raw"] = np.ctypeslib.as_array(st.raw).reshape(DPD_MAX_BINS, 6)[:n].copy()
+        return d
+
+    def reset_dpd(self):
+        self._chk(self._lib.dabgpu_reset_dpd(self._h))
+
+    def set_dpd_geometry(self, run_segments=0, tile=0):
+        """Diagnostic: segments per workgroup of the cross-spectrum kernel and tx samples per workgroup of the statistics
+        kernel (0: the defaults)."""
+        self._chk(self._lib.dabgpu_debug_dpd_run_segments(self._h, int(run_segments)))
+        self._chk(self._lib.dabgpu_debug_dpd_tile(self._h, int(tile)))
 
     def synchronize(self):
         """Wait for everything the context has queued, on every lane."""

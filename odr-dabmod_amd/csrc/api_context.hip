@@ -99,6 +99,51 @@ size_t tf_samples(const Geometry &g)
     return (size_t)g.null_size + (size_t)g.nb_symbols * (size_t)g.sym_size;
 }
 
+// Least squares min |A x - b| by Householder QR in float64.  A: m x n, column-major, m >= n; A and b are overwritten (R in
+// A's upper triangle, Q^T b in b, so that b[n .. m) are the residual's components).  rmin / rmax: the smallest and largest
+// |R_kk|, whose ratio estimates the condition number.  False when a column is (numerically) dependent.
+bool householder_lstsq(std::vector<double> &A, std::vector<double> &b, int m, int n, std::vector<double> &x, double *rmin,
+                       double *rmax)
+{
+    std::vector<double> v(m);
+    for (int k = 0; k < n; ++k) {
+        double *ck = &A[(size_t)k * m];
+        double nrm = 0.0;
+        for (int i = k; i < m; ++i) nrm += ck[i] * ck[i];
+        nrm = std::sqrt(nrm);
+        if (nrm == 0.0) return false;
+        const double alpha = ck[k] > 0.0 ? -nrm : nrm;
+        for (int i = k; i < m; ++i) v[i] = ck[i];
+        v[k] -= alpha;
+        double vv = 0.0;
+        for (int i = k; i < m; ++i) vv += v[i] * v[i];
+        if (vv == 0.0) return false;
+        auto reflect = [&](double *x) {
+            double dot = 0.0;
+            for (int i = k; i < m; ++i) dot += v[i] * x[i];
+            const double f = 2.0 * dot / vv;
+            for (int i = k; i < m; ++i) x[i] -= f * v[i];
+        };
+        for (int j = k + 1; j < n; ++j) reflect(&A[(size_t)j * m]);
+        reflect(b.data());
+        ck[k] = alpha;
+    }
+    x.assign(n, 0.0);
+    double lo = INFINITY, hi = 0.0;
+    for (int k = n - 1; k >= 0; --k) {
+        double acc = b[k];
+        for (int j = k + 1; j < n; ++j) acc -= A[(size_t)j * m + k] * x[j];
+        const double d = A[(size_t)k * m + k];
+        if (std::fabs(d) < 1e-300) return false;
+        x[k] = acc / d;
+        lo = std::min(lo, std::fabs(d));
+        hi = std::max(hi, std::fabs(d));
+    }
+    if (rmin) *rmin = lo;
+    if (rmax) *rmax = hi;
+    return true;
+}
+
 // Inverse of the FIR filter on the occupied carriers, for the equalised-boundary variant of the frame kernel
 // (tf_kernel<..., EQ>, tf_kernel.h): real g[0 .. L) with
 //     x[n] = sum_j g[j] z[n - (j - c)]      (z = x filtered cyclically, z[n] = sum_j taps[j] x[n + j]),
@@ -141,37 +186,8 @@ bool design_inverse_filter(const std::vector<float> &taps, int N, int K, std::ve
             col[2 * r + 1] = w * std::sin(a);
         }
     }
-    std::vector<double> v(m);
-    for (int k = 0; k < n; ++k) {
-        double *ck = &A[(size_t)k * m];
-        double nrm = 0.0;
-        for (int i = k; i < m; ++i) nrm += ck[i] * ck[i];
-        nrm = std::sqrt(nrm);
-        if (nrm == 0.0) return false;
-        const double alpha = ck[k] > 0.0 ? -nrm : nrm;
-        for (int i = k; i < m; ++i) v[i] = ck[i];
-        v[k] -= alpha;
-        double vv = 0.0;
-        for (int i = k; i < m; ++i) vv += v[i] * v[i];
-        if (vv == 0.0) return false;
-        auto reflect = [&](double *x) {
-            double dot = 0.0;
-            for (int i = k; i < m; ++i) dot += v[i] * x[i];
-            const double f = 2.0 * dot / vv;
-            for (int i = k; i < m; ++i) x[i] -= f * v[i];
-        };
-        for (int j = k + 1; j < n; ++j) reflect(&A[(size_t)j * m]);
-        reflect(b.data());
-        ck[k] = alpha;
-    }
-    std::vector<double> g(n);
-    for (int k = n - 1; k >= 0; --k) {
-        double acc = b[k];
-        for (int j = k + 1; j < n; ++j) acc -= A[(size_t)j * m + k] * g[j];
-        const double d = A[(size_t)k * m + k];
-        if (std::fabs(d) < 1e-300) return false;
-        g[k] = acc / d;
-    }
+    std::vector<double> g;
+    if (!householder_lstsq(A, b, m, n, g)) return false;
     // what the kernel will use: the fp32 taps; fit over the occupied bins and the noise gain
     g_out.assign((size_t)L + 1, 0.0f);
     double norm2 = 0.0;
@@ -531,7 +547,8 @@ void dabgpu_destroy(dabgpu_ctx *c)
                       &c->d_cfr_counts, &c->d_cfr_mer, &c->d_cfr_papr, &c->d_cfr_tmp,
                       &c->d_fe_prbs, &c->d_fe_units, &c->d_fe_owner, &c->d_fe_hist, &c->d_fe_tmp, &c->d_fe_fic, &c->d_fe_eti,
                       &c->d_fe_seed, &c->d_demod_stats, &c->d_demod_bits, &c->d_demod_ref,
-                      &c->d_spec_tw, &c->d_spec_win, &c->d_spec_rows, &c->d_spec_acc, &c->d_spec_in})
+                      &c->d_spec_tw, &c->d_spec_win, &c->d_spec_rows, &c->d_spec_acc, &c->d_spec_in,
+                      &c->d_dpd_tw, &c->d_dpd_rows, &c->d_dpd_xacc, &c->d_dpd_sums, &c->d_dpd_edge, &c->d_dpd_tx, &c->d_dpd_rx})
         b->release();
     for (auto &sl : c->slot) {
         sl.d_eti.release();

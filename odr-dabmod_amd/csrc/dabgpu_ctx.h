@@ -11,6 +11,8 @@
 //                     that rides on a chain call
 //   api_spectrum.hip  the spectrum monitor (spectrum.hip): Welch power spectrum of any sample buffer, stand-alone and behind a
 //                     chain call; the window tables and the mask check (host only)
+//   api_dpd.hip       the DPD measurement (dpd.hip): cross-spectrum and aligned amplitude-bin statistics of a tx / feedback
+//                     pair; alignment solve, delay taps and polynomial fit (host only)
 //   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
 //                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
 #pragma once
@@ -186,6 +188,18 @@ struct dabgpu_ctx {
     double spec_rate_hz = 0.0;
     hipStream_t spec_stream = nullptr;
     int spec_run_segments = 0;            // dabgpu_debug_spectrum_run_segments: segments per workgroup, 0 = by the input size
+    // The DPD measurement (api_dpd.hip): the 2048-entry twiddle table (the context's own in Mode I), the cross-spectrum's rows
+    // and sums (4 x 2048 float64 and the segment count), the statistics' integer sums (256 bins x 6 figures, overflow, samples
+    // used), the squared bin edges and the host-pointer entries' staging.  dpd_peak / dpd_bins: what the sums were formed
+    // with (0: none yet); dpd_offered: samples offered since they started over (the cap).
+    dabgpu_api::DevBuf d_dpd_tw, d_dpd_rows, d_dpd_xacc, d_dpd_sums, d_dpd_edge, d_dpd_tx, d_dpd_rx;
+    bool dpd_ready = false;
+    float dpd_peak = 0.f;
+    int dpd_bins = 0;
+    unsigned long long dpd_offered = 0;
+    hipStream_t dpd_stream = nullptr;
+    int dpd_run_segments = 0;             // dabgpu_debug_dpd_run_segments
+    int dpd_tile = 0;                     // dabgpu_debug_dpd_tile
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII
     bool tables_valid = false;            // apply_settings has uploaded every table group once
     unsigned long long tii_seg_epoch = 0; // 1 while the cached segment matches the settings (apply_settings zeroes it), and its stage mask
@@ -331,6 +345,9 @@ template <typename T> hipError_t upload(DevBuf &b, const std::vector<T> &v, hipS
 }
 
 bool design_inverse_filter(const std::vector<float> &taps, int N, int K, std::vector<float> &g_out, double *fit_out);
+// least squares by Householder QR in float64 (A: m x n column-major; A and b are overwritten)
+bool householder_lstsq(std::vector<double> &A, std::vector<double> &b, int m, int n, std::vector<double> &x,
+                       double *rmin = nullptr, double *rmax = nullptr);
 int apply_settings(dabgpu_ctx *c);
 Tables tables_of(dabgpu_ctx *c);
 GainParams gain_of(const dabgpu_ctx *c);

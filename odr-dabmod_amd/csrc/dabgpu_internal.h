@@ -190,6 +190,42 @@ struct SpectrumArgs {
 };
 void spectrum_runs(long long n_segments, int forced, int *n_runs, int *segs_per_run);
 hipError_t launch_spectrum(const SpectrumArgs &a, hipStream_t s);
+// dpd.hip: the predistortion measurement (dabgpu_dpd_*).  The cross-spectrum uses the spectrum kernel's geometry (segments of
+// SPECTRUM_NFFT samples at a hop of half that, rectangular window, runs of segments, rows and a reduce in workgroup order).
+enum { DPD_TAPS = 32, DPD_TAP_CENTRE = 15, DPD_MAX_BINS = 256, DPD_TILE_MAX = 2048, DPD_FIGURES = 6 };
+struct DpdXspecArgs {
+    const void *tx;           // cf32 (fmt 0) or s16 pairs (fmt 1)
+    int fmt;
+    const float2 *rx;         // cf32; segment i of rx is samples 1024 i + rx_offset ... + 2047
+    long long rx_offset;
+    long long seg_first;      // the first segment whose rx range lies inside the buffer, and how many follow it (the
+    long long n_segments;     //   segments used form one range: launch_dpd_xspectrum forms it, every lane sees the same)
+    int n_runs, segs_per_run; // (spectrum_runs)
+    const float2 *twiddle;    // exp(+2 pi i m / 2048), 2048 entries
+    double *rows;             // scratch, n_runs x 4 x 2048: Re S, Im S, P_tx, P_rx, bins in FFT order
+    double *acc;              // 4 x 2048 sums, then the segment count as one unsigned long long
+};
+// the range of segments of an n-sample pair whose rx range (shifted by rx_offset) lies inside the buffer
+void dpd_segments(size_t n, long long rx_offset, long long *first, long long *count);
+// (n_samples: of either buffer; the launch checks the range of segments in `a` against it)
+hipError_t launch_dpd_xspectrum(const DpdXspecArgs &a, size_t n_samples, hipStream_t s);
+struct DpdStatsArgs {
+    const void *tx;           // cf32 (fmt 0) or s16 pairs (fmt 1)
+    int fmt;
+    const float2 *rx;
+    long long n, lag;         // samples in either buffer; the aligned rx sample of i is centred on rx[i + lag]
+    long long i_first, i_end; // the samples used: all 32 taps inside rx (launch_dpd_stats forms the range, dpd_used_range)
+    long long tile_first;     // the tile of workgroup 0 (launch_dpd_stats: the tile that holds i_first)
+    float h[DPD_TAPS];        // fractional-delay taps (dabgpu_dpd_delay_taps)
+    float g_re, g_im;         // complex gain on the filtered rx sample
+    float peak;               // amplitudes are counted in units of peak 2^-24
+    int n_bins;
+    const float *edge2;       // n_bins + 1 squared bin edges, fp32
+    int tile;                 // samples per workgroup: a multiple of 256, at most DPD_TILE_MAX
+    unsigned long long *sums; // DPD_MAX_BINS x DPD_FIGURES integers, then overflow and samples used
+};
+void dpd_used_range(long long n, long long lag, long long *i_first, long long *i_end);
+hipError_t launch_dpd_stats(DpdStatsArgs a, hipStream_t s);
 // f-4 TII: the sparse symbol (stand-alone stage), and its addition to a stream whose null symbol is blank
 hipError_t launch_tii(const float2 *in, const uint8_t *acp, int K, int old_variant, int insert, float2 *out,
                       hipStream_t s);

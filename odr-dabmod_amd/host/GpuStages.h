@@ -471,6 +471,9 @@ public:
     const MonitorTotals &monitor_totals() const { return m_mon_last; }
     // Settings::spectrum: waits for the chain's work; all zero before the first frame, or with the spectrum monitor off
     SpectrumTotals spectrum_totals();
+    // the library context behind the chain, for the C-ABI's measurement entries that take buffers of the caller's
+    // (dabgpu_dpd_*: include/dabgpu.h, "DPD measurement"); owned by the chain
+    dabgpu_ctx *context() const { return m_ctx.get(); }
     ~DabGpuChain() override;
     // the RemoteControllables to enrol (rcs.enrol(p), lib/RemoteControl.h:141); owned by the chain
     std::vector<RemoteControllable *> remote_controllables() const;

@@ -46,6 +46,15 @@
 //                        the occupied band (+-768 kHz); stderr gets the segments and the out-of-band maximum (from --oob-from
 //                        HZ, default 970000) with its frequency.  The output file is the one without the option.  With
 //                        --contexts N the contexts' sums are added.  Not with --bits-only or --separate-converter.
+//   --dpd-feedback RXFILE --dpd-out COEFFILE [--dpd-bins N] [--dpd-min-count N]
+//                        the DPD measurement (include/dabgpu.h, "DPD measurement"): RXFILE holds complexf samples of the
+//                        amplifier's feedback path, sample i belonging to sample i of this run's output stream up to an unknown
+//                        delay (|delay| <= 1000 samples).  The first batch written gives the alignment (stderr: lag, tau, gain,
+//                        coherence) and the peak (its largest |t|); every batch is measured into one set of sums; after the
+//                        run the polynomial is fitted (DABGPU_DPD_BASIS_MAGSQ, weighted) and written to COEFFILE in
+//                        MemlessPoly's coefficient file format 1, which --poly reads back.  Output complexf or s16 at any
+//                        rate; not with --contexts above 1, --bits-only or --separate-converter.  Exit status 4 when the fit
+//                        is refused.  N bins (default 64), bins with fewer than --dpd-min-count samples (default 10) unused.
 //   --mask MASKFILE      with --spectrum: "offset_hz limit_db" per line (# starts a comment), offsets increasing; the limit is
 //                        piecewise linear in dB between the points (dabgpu_spectrum_check_mask).  stderr gets the worst margin
 //                        and where it lies; exit status 3 when a bin lies above the mask (2 stays the monitor's).
@@ -61,6 +70,8 @@
 #include "GpuStages.h"
 #include "dabgpu.h"
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -86,6 +97,7 @@ namespace {
                          "       [--gpu-frontend]   ETI -> coded bits on the device as well (not with --contexts above 1, --bits-only,\n"
                          "                        --separate-converter)\n"
                          "       [--monitor]   decode every frame written on the device; totals on stderr, exit 2 on a bit error\n"
+                         "       [--dpd-feedback RXFILE --dpd-out COEFFILE [--dpd-bins N] [--dpd-min-count N]]   fit MemlessPoly from a feedback capture\n"
                          "       [--spectrum FILE [--mask MASKFILE] [--oob-from HZ]]   power spectrum of everything written, per bin into FILE;\n"
                          "                        exit 3 when it lies above the mask (lines of: offset_hz limit_db)\n"
                          "       [--state-out FILE] [--state-in FILE]   with --gpu-frontend: leave / take up the stream's state\n");
@@ -152,6 +164,9 @@ int main(int argc, char **argv)
     std::string state_in, state_out;
     std::string spectrum_path, mask_path;
     double oob_from = 970000.0;
+    std::string dpd_rx_path, dpd_out_path;
+    int dpd_bins = 64;
+    unsigned long dpd_min_count = 10;
     try {
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
@@ -196,6 +211,10 @@ int main(int argc, char **argv)
             else if (a == "--spectrum") { spectrum_path = val(); gs.spectrum = true; }
             else if (a == "--mask") mask_path = val();
             else if (a == "--oob-from") oob_from = std::stod(val());
+            else if (a == "--dpd-feedback") dpd_rx_path = val();
+            else if (a == "--dpd-out") dpd_out_path = val();
+            else if (a == "--dpd-bins") dpd_bins = std::atoi(val().c_str());
+            else if (a == "--dpd-min-count") dpd_min_count = std::stoul(val());
             else if (a == "--state-in") state_in = val();
             else if (a == "--state-out") state_out = val();
             else if (a == "--contexts") {
@@ -232,6 +251,27 @@ int main(int argc, char **argv)
         if (!mask_path.empty() && !gs.spectrum) {
             std::fprintf(stderr, "dabmod_file: --mask needs --spectrum\n");
             return 2;
+        }
+        const bool dpd = !dpd_rx_path.empty();
+        if (dpd_rx_path.empty() != dpd_out_path.empty()) {
+            std::fprintf(stderr, "dabmod_file: --dpd-feedback and --dpd-out go together\n");
+            return 2;
+        }
+        if (dpd && (contexts > 1 || bits_only || separate_converter || (format != "complexf" && format != "s16"))) {
+            std::fprintf(stderr, "dabmod_file: --dpd-feedback does not go with %s\n",
+                         contexts > 1 ? "--contexts above 1: one context holds the sums"
+                         : bits_only  ? "--bits-only: nothing is modulated"
+                         : separate_converter ? "--separate-converter: the chain's own output is what is measured"
+                                              : "u8 / s8 output: the transmitted samples are complexf or s16");
+            return 2;
+        }
+        std::ifstream dpd_rx;
+        if (dpd) {
+            dpd_rx.open(dpd_rx_path, std::ios::binary);
+            if (!dpd_rx) {
+                std::fprintf(stderr, "dabmod_file: cannot read %s\n", dpd_rx_path.c_str());
+                return 1;
+            }
         }
         std::vector<double> mask_offs, mask_limit;
         if (!mask_path.empty()) {
@@ -302,6 +342,35 @@ int main(int argc, char **argv)
             mon.n_bits += t.n_bits;
             mon.sum_mer_db += t.sum_mer_db;
         };
+        // --dpd-feedback: the bytes just written against as many samples of RXFILE (short at its end: the common part)
+        dabgpu_dpd_alignment dpd_al{};
+        float dpd_peak = 0.f;
+        bool dpd_aligned = false;
+        std::vector<char> dpd_buf;
+        auto dpd_feed = [&](DabGpuChain *ch, const void *p, size_t bytes) {
+            if (!dpd) return;
+            const int fmt = format == "s16" ? DABGPU_FMT_S16 : 0;
+            size_t n = bytes / (fmt ? 4 : 8);
+            dpd_buf.resize(n * 8);
+            dpd_rx.read(dpd_buf.data(), static_cast<std::streamsize>(dpd_buf.size()));
+            n = std::min(n, static_cast<size_t>(dpd_rx.gcount()) / 8);
+            if (!n) return;
+            auto chk = [&](int rc) { if (rc) throw std::runtime_error(std::string("--dpd-feedback: ") + dabgpu_last_error(ch->context())); };
+            if (!dpd_aligned) {
+                chk(dabgpu_dpd_align(ch->context(), p, fmt, dpd_buf.data(), n, &dpd_al));
+                double peak2 = 0.0;
+                for (size_t i = 0; i < n; ++i) {
+                    const double re = fmt ? static_cast<const int16_t *>(p)[2 * i] : static_cast<const float *>(p)[2 * i];
+                    const double im = fmt ? static_cast<const int16_t *>(p)[2 * i + 1] : static_cast<const float *>(p)[2 * i + 1];
+                    peak2 = std::max(peak2, re * re + im * im);
+                }
+                dpd_peak = std::nextafter(static_cast<float>(std::sqrt(peak2)), INFINITY);     // (the largest sample lands in the last bin)
+                dpd_aligned = true;
+                std::fprintf(stderr, "dabmod_file: dpd: lag %d tau %.6f gain %.6f%+.6fj coherence %.6f peak %.6g\n", dpd_al.lag, dpd_al.tau,
+                             dpd_al.gain_re, dpd_al.gain_im, dpd_al.coherence, static_cast<double>(dpd_peak));
+            }
+            chk(dabgpu_dpd_measure(ch->context(), p, fmt, dpd_buf.data(), n, &dpd_al, dpd_peak, dpd_bins, 1));
+        };
         // the oldest batch in flight, in stream order: batch j lives on chain j mod N
         auto drain_one = [&]() {
             DabGpuChain *ch = chain_of(n_collected++);
@@ -311,6 +380,7 @@ int main(int argc, char **argv)
             n_out += n / ch->output_bytes_per_frame();
             if (format != "complexf") clipped += ch->get_num_clipped_samples();
             out.write(static_cast<const char *>(p), static_cast<std::streamsize>(n));
+            dpd_feed(ch, p, n);
             --in_flight;
         };
         // two batches in flight per chain; the owning chain starts from the state behind the frame before its batch
@@ -437,6 +507,7 @@ int main(int argc, char **argv)
                     clipped += chain->get_num_clipped_samples();
                 }
                 out.write(static_cast<const char *>(o->getData()), static_cast<std::streamsize>(o->getLength()));
+                dpd_feed(chain.get(), o->getData(), o->getLength());
             }
             if (got < 0) {
                 std::fprintf(stderr, "dabmod_file: error while reading %s\n", in_path.c_str());
@@ -513,6 +584,38 @@ int main(int argc, char **argv)
                              res.worst_margin_db, res.worst_freq_hz, res.n_violations, res.n_checked);
                 mask_violations = res.n_violations;
             }
+        }
+        if (dpd) {
+            if (!dpd_aligned) {
+                std::fprintf(stderr, "dabmod_file: --dpd-feedback: nothing was measured (no output, or an empty feedback file)\n");
+                return 1;
+            }
+            dabgpu_dpd_stats st;
+            if (dabgpu_get_dpd_stats(chain->context(), &st) != 0)
+                throw std::runtime_error(std::string("--dpd-feedback: ") + dabgpu_last_error(chain->context()));
+            float am[5], pm[5];
+            dabgpu_dpd_fit_info fi;
+            if (dabgpu_dpd_fit_poly(&st, DABGPU_DPD_BASIS_MAGSQ, dpd_min_count, 1, 0.0, nullptr, nullptr, 1.0, 1.0, am, pm, &fi) != 0) {
+                std::fprintf(stderr, "dabmod_file: dpd: the fit is refused: %s\n", dabgpu_last_error(nullptr));
+                return 4;
+            }
+            // (FormatConverter's s16 is the complexf value truncated: amplitudes of s16 output are in the units of the stream the
+            // predistorter runs on, so the coefficients hold for either format)
+            std::FILE *cf = std::fopen(dpd_out_path.c_str(), "w");
+            if (!cf) {
+                std::fprintf(stderr, "dabmod_file: cannot write %s\n", dpd_out_path.c_str());
+                return 1;
+            }
+            std::fprintf(cf, "1\n5\n");
+            for (int i = 0; i < 5; ++i) std::fprintf(cf, "%.9g\n", static_cast<double>(am[i]));
+            for (int i = 0; i < 5; ++i) std::fprintf(cf, "%.9g\n", static_cast<double>(pm[i]));
+            if (std::fclose(cf) != 0) {
+                std::fprintf(stderr, "dabmod_file: cannot write %s\n", dpd_out_path.c_str());
+                return 1;
+            }
+            std::fprintf(stderr, "dabmod_file: dpd: %llu samples in %d bins (%llu above the peak), %d bins fitted, residual am %.3g pm %.3g -> %s\n",
+                         static_cast<unsigned long long>(st.samples_used), st.n_bins, static_cast<unsigned long long>(st.overflow),
+                         fi.bins_used, fi.resid_am, fi.resid_pm, dpd_out_path.c_str());
         }
         if (gs.monitor && mon.bit_errors) return 2;
         if (mask_violations) return 3;
