@@ -651,6 +651,10 @@ DABGPU_API int dabgpu_set_spectrum_monitor(dabgpu_ctx *ctx, int enable, int wind
  * four segments or more each).  At most 65536 workgroups whatever is asked.  The sums agree to float64 reordering for every
  * value; exists so that a test can walk the run geometry. */
 DABGPU_API int dabgpu_debug_spectrum_run_segments(dabgpu_ctx *ctx, int segments);
+/* dabgpu_debug_resampler_run_hops -- diagnostic: hops per workgroup of every resampler kernel; 0 (the default) = by the call size. */
+DABGPU_API int dabgpu_debug_resampler_run_hops(dabgpu_ctx *ctx, int hops);
+/* dabgpu_debug_resampler_last_launch -- diagnostic: hops per workgroup and workgroups of the context's most recent resampler launch (0, 0: none yet). */
+DABGPU_API int dabgpu_debug_resampler_last_launch(dabgpu_ctx *ctx, int *hops, unsigned *grid);
 /* dabgpu_spectrum_check_mask -- host only, no context, no device: a spectrum against a mask.  Bin k of nfft lies at f_k = (k < nfft/2 ? k : k - nfft) rate_hz
  * / nfft.  ref = mean of raw over the bins with 0 < |f_k| <= 768 kHz (the occupied band in all four modes); level_k =
  * 10 log10(raw[k] / ref).  The mask is n_points (offs_hz, limit_db) pairs with offs_hz strictly increasing: the limit at |f_k| is

@@ -50,7 +50,7 @@ EXPORTS = [
     "dabgpu_dpd_xspectrum", "dabgpu_dpd_xspectrum_dev", "dabgpu_get_dpd_xspectrum", "dabgpu_dpd_solve_alignment",
     "dabgpu_dpd_align", "dabgpu_dpd_align_dev", "dabgpu_dpd_delay_taps", "dabgpu_dpd_measure", "dabgpu_dpd_measure_dev",
     "dabgpu_get_dpd_stats", "dabgpu_reset_dpd", "dabgpu_debug_dpd_run_segments", "dabgpu_debug_dpd_tile",
-    "dabgpu_dpd_fit_poly",
+    "dabgpu_dpd_fit_poly", "dabgpu_debug_resampler_run_hops", "dabgpu_debug_resampler_last_launch",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -267,6 +267,8 @@ def load_library():
     lib.dabgpu_reset_spectrum.argtypes = [vp]
     lib.dabgpu_set_spectrum_monitor.argtypes = [vp, C.c_int, C.c_int]
     lib.dabgpu_debug_spectrum_run_segments.argtypes = [vp, C.c_int]
+    lib.dabgpu_debug_resampler_run_hops.argtypes = [vp, C.c_int]
+    lib.dabgpu_debug_resampler_last_launch.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_uint)]
     lib.dabgpu_spectrum_check_mask.argtypes = [dp, C.c_int, C.c_double, dp, dp, C.c_int, C.c_double, C.POINTER(_MaskResult)]
     ll, fp, al = C.c_longlong, C.POINTER(C.c_float), C.POINTER(_DpdAlignment)
     lib.dabgpu_dpd_xspectrum.argtypes = [vp, vp, C.c_int, vp, sz, ll]
@@ -1010,6 +1012,16 @@ class Modulator:
             d["psd"] = raw / (d["segments"] * d["sum_w2"]) if d["segments"] and d["sum_w2"] else np.zeros_like(raw)
         d["freqs"] = spectrum_freqs(d["rate_hz"]) if d["rate_hz"] else None
         return d
+
+    def set_resampler_run_hops(self, hops=0):
+        """Diagnostic: consecutive hops per workgroup of every resampler kernel (0: chosen from the call size)."""
+        self._chk(self._lib.dabgpu_debug_resampler_run_hops(self._h, int(hops)))
+
+    def resampler_last_launch(self):
+        """Diagnostic: (hops per workgroup, workgroups) of the context's most recent resampler launch; (0, 0) before the first."""
+        hops, grid = C.c_int(), C.c_uint()
+        self._chk(self._lib.dabgpu_debug_resampler_last_launch(self._h, C.byref(hops), C.byref(grid)))
+        return int(hops.value), int(grid.value)
 
     def set_spectrum_run_segments(self, segments=0):
         """Diagnostic: segments per workgroup of the spectrum kernel (0: chosen from the input size)."""

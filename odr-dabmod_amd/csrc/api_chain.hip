@@ -113,15 +113,18 @@ int run_resampler(dabgpu_ctx *c, const float2 *d_in, size_t total, float2 *d_out
     a.M = (int)c->rs_M;
     a.tw_s = (const float2 *)c->d_rs_tw_s.p;
     a.tw_l = (const float2 *)c->d_rs_tw_l.p;
+    a.run_hops = c->rs_run_hops;
     // new halo = last two hops of the concatenation [halo | in]: the x2 / x4 kernel of Mode I writes it itself, into the
     // other buffer (launches of one stream are in order: the next call reads what this one wrote)
     if (resampler_writes_halo(a)) {
         a.halo_out = halo_next;
         HIPCHK(c, launch_resampler(a, s));
+        resampler_last_launch(&c->rs_last_hops, &c->rs_last_grid);
         c->rs_halo_cur ^= 1;
         return DABGPU_OK;
     }
     HIPCHK(c, launch_resampler(a, s));
+    resampler_last_launch(&c->rs_last_hops, &c->rs_last_grid);
     if (nhops >= 2) {
         HIPCHK(c, hipMemcpyAsync(halo, d_in + (nhops - 2) * hin, 2 * hin * sizeof(float2),
                                  hipMemcpyDeviceToDevice, s));

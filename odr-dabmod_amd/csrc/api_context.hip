@@ -700,6 +700,23 @@ int dabgpu_set_resampler(dabgpu_ctx *c, size_t in_rate, size_t out_rate)
     return DABGPU_OK;
 }
 
+int dabgpu_debug_resampler_run_hops(dabgpu_ctx *c, int hops)
+{
+    if (!c) return DABGPU_E_INVALID;
+    if (hops < 0) return fail(c, DABGPU_E_INVALID, "Resampler: hops per run: a positive number, or 0 = by the call size");
+    c->rs_run_hops = hops;
+    return DABGPU_OK;
+}
+
+int dabgpu_debug_resampler_last_launch(dabgpu_ctx *c, int *hops, unsigned *grid)
+{
+    if (!c) return DABGPU_E_INVALID;
+    if (!hops || !grid) return fail(c, DABGPU_E_INVALID, "null argument");
+    *hops = c->rs_last_hops;
+    *grid = c->rs_last_grid;
+    return DABGPU_OK;
+}
+
 int dabgpu_debug_trace(dabgpu_ctx *c, int enable)
 {
     if (!c) return DABGPU_E_INVALID;

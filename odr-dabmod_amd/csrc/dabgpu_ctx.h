@@ -137,6 +137,9 @@ struct dabgpu_ctx {
     int rs_halo_cur = 0;                  // which of the two halo buffers holds the state the next call reads
     size_t rs_L = 1, rs_M = 1;
     float rs_factor = 1.f;
+    int rs_last_hops = 0;                 // dabgpu_debug_resampler_last_launch: the most recent resampler launch of this context
+    unsigned rs_last_grid = 0;
+    int rs_run_hops = 0;                  // dabgpu_debug_resampler_run_hops: hops per workgroup, 0 = by the call size
     // scratch
     dabgpu_api::DevBuf d_a, d_b, d_c, d_in, d_out, d_count, d_fmt, d_clip;
     dabgpu_api::DevBuf d_car;             // CIC equaliser on: the carriers between the front kernel and the from-carriers chain

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "resampler_runs.h"
+
 namespace dabgpu {
 
 constexpr int kMaxTaps = 128;        // fused (spectral) FIR of the frame kernel
@@ -286,9 +288,14 @@ struct ResamplerArgs {
     int L, M;
     const float2 *tw_s;     // nin / M entries exp(+2 pi i m / (nin / M))
     const float2 *tw_l;     // L entries exp(+2 pi i m / L)
+    int run_hops;           // hops per workgroup, forced (dabgpu_debug_resampler_run_hops); 0: by the call size (resampler_runs.h)
 };
 hipError_t launch_resampler(const ResamplerArgs &a, hipStream_t s);
 bool resampler_has_s16(const ResamplerArgs &a);
+// the geometry of the calling thread's most recent resampler launch (the launchers note it; run_resampler keeps it in the context
+// for dabgpu_debug_resampler_last_launch)
+void note_resampler_launch(int hops_per_run, unsigned grid);
+void resampler_last_launch(int *hops_per_run, unsigned *grid);
 bool resampler_writes_halo(const ResamplerArgs &a);   // the kernel this geometry runs honours halo_out
 
 }  // namespace dabgpu

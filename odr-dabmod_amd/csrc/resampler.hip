@@ -556,8 +556,9 @@ template <int LOGNIN> hipError_t launch_resampler_n(const ResamplerArgs &a, hipS
     // runs of hops: every run starts with one dual forward transform (half a hop's work).  Long streams
     // get runs of 96 hops (one Mode-I frame); short ones are cut finer so that the launch still covers the
     // chip (>= 512 workgroups when there are that many pairs of hops) -- latency, not efficiency, counts there
-    int hpr = (int)std::max<size_t>(2, std::min<size_t>(96, a.nhops / 512));
-    const dim3 grid((unsigned)((a.nhops + hpr - 1) / hpr)), block(NIN / 8);
+    // (resampler_runs.h has the formula; a.run_hops > 0 -- dabgpu_debug_resampler_run_hops -- takes its place)
+    const int hpr = resampler_run_hops(a.nhops, false, a.run_hops);
+    const dim3 grid(resampler_run_grid(a.nhops, hpr)), block(NIN / 8);
     const size_t lds = 2 * (size_t)(NIN + NIN / 8) * 16 + (2 + 56) * sizeof(float2) + (size_t)(NIN / 2) * sizeof(float);
     const bool poly = a.poly != nullptr;
     switch (Q) {
@@ -566,8 +567,9 @@ template <int LOGNIN> hipError_t launch_resampler_n(const ResamplerArgs &a, hipS
             if constexpr (LOGNIN == 12) {
                 // Mode I (the BASELINE config 4 shape, and x2): hop-independent radix-16 kernel, two 256-lane workgroups per CU.
                 // No run prologue, so short streams are cut into single hops; long ones into runs of 24 (four runs per frame)
-                const int hpr16 = (int)std::max<size_t>(1, std::min<size_t>(24, a.nhops / 1536));
-                const dim3 grid16((unsigned)((a.nhops + hpr16 - 1) / hpr16)), block16(256);
+                const int hpr16 = resampler_run_hops(a.nhops, true, a.run_hops);
+                const dim3 grid16(resampler_run_grid(a.nhops, hpr16)), block16(256);
+                note_resampler_launch(hpr16, grid16.x);
                 const size_t lds16 = (size_t)(2 * Fft16::LDS_ELEMS + 256 + 8) * sizeof(float2) + (size_t)(NIN / 2) * sizeof(float);
                 // (more than 64 KiB of dynamic LDS has to be asked for)
 #define RS16_LAUNCH(P, F, QQ)                                                                                          \
@@ -587,10 +589,12 @@ template <int LOGNIN> hipError_t launch_resampler_n(const ResamplerArgs &a, hipS
 #undef RS16_LAUNCH
             } else if (Q == 2) {
                 if (a.clipped) return hipErrorInvalidValue;
+                note_resampler_launch(hpr, grid.x);
                 if (poly) DABGPU_LAUNCH((resampler_kernel<LOGNIN, 2, true>), grid, block, lds, s, a, hpr);
                 else DABGPU_LAUNCH((resampler_kernel<LOGNIN, 2, false>), grid, block, lds, s, a, hpr);
             } else {
                 if (a.clipped) return hipErrorInvalidValue;
+                note_resampler_launch(hpr, grid.x);
                 if (poly) DABGPU_LAUNCH((resampler_kernel<LOGNIN, 4, true>), grid, block, lds, s, a, hpr);
                 else DABGPU_LAUNCH((resampler_kernel<LOGNIN, 4, false>), grid, block, lds, s, a, hpr);
             }
@@ -601,6 +605,10 @@ template <int LOGNIN> hipError_t launch_resampler_n(const ResamplerArgs &a, hipS
 }
 
 }  // namespace
+
+namespace { thread_local int g_last_hops = 0; thread_local unsigned g_last_grid = 0; }
+void note_resampler_launch(int hops_per_run, unsigned grid) { g_last_hops = hops_per_run; g_last_grid = grid; }
+void resampler_last_launch(int *hops_per_run, unsigned *grid) { *hops_per_run = g_last_hops; *grid = g_last_grid; }
 
 // the kernel that leaves the next call's halo behind itself (resampler16_kernel): x2 and x4 at nin = 4096 (Mode I)
 bool resampler_writes_halo(const ResamplerArgs &a)

@@ -336,8 +336,9 @@ template <typename K> hipError_t allow_lds(K kernel, size_t lds)
 template <int LOGNIN, int LOGS> hipError_t launch_resampler_rational(const ResamplerArgs &a, hipStream_t s)
 {
     constexpr int NIN = 1 << LOGNIN;
-    const int hpr = (int)std::max<size_t>(2, std::min<size_t>(96, a.nhops / 512));
-    const dim3 grid((unsigned)((a.nhops + hpr - 1) / hpr)), block(NIN / 8 < 64 ? 64 : NIN / 8);
+    const int hpr = resampler_run_hops(a.nhops, false, a.run_hops);
+    const dim3 grid(resampler_run_grid(a.nhops, hpr)), block(NIN / 8 < 64 ? 64 : NIN / 8);
+    note_resampler_launch(hpr, grid.x);
     int cl_in_lds = 0;
     const size_t lds = rational_lds_bytes<LOGNIN>(a.L, &cl_in_lds);
     hipError_t e;
@@ -354,8 +355,9 @@ template <int LOGNIN, int LOGS> hipError_t launch_resampler_rational(const Resam
 template <int LOGNIN, int LOGS> hipError_t launch_resampler_lane(const ResamplerArgs &a, hipStream_t s)
 {
     constexpr int NIN = 1 << LOGNIN;
-    const int hpr = (int)std::max<size_t>(2, std::min<size_t>(96, a.nhops / 512));
-    const dim3 grid((unsigned)((a.nhops + hpr - 1) / hpr)), block(NIN / 8 < 64 ? 64 : NIN / 8);
+    const int hpr = resampler_run_hops(a.nhops, false, a.run_hops);
+    const dim3 grid(resampler_run_grid(a.nhops, hpr)), block(NIN / 8 < 64 ? 64 : NIN / 8);
+    note_resampler_launch(hpr, grid.x);
     const size_t lds = rational_lds_bytes<LOGNIN>(0, nullptr);
     hipError_t e = allow_lds(resampler_lane_kernel<LOGNIN, LOGS>, lds);
     if (e != hipSuccess) return e;
