@@ -601,6 +601,49 @@ DABGPU_API int dabgpu_set_monitor(dabgpu_ctx *ctx, int enable, int early);
  * 0 (the default) = chosen from the batch size.  Same bits for every value; exists so that a test can walk the run geometry. */
 DABGPU_API int dabgpu_debug_demod_run_symbols(dabgpu_ctx *ctx, int symbols);
 
+/* ---- the channel decoder: coded bits -> the ETI payload, per-unit corrected bits and payload bit errors -------------------- *
+ * What a DAB receiver runs behind the demodulator, on the device: the time de-interleaver, depuncturing, the K = 7 Viterbi
+ * decoder (hard decisions) and the energy dispersal -- the two kernels of the front-end backwards, from the very tables
+ * dabgpu_frontend_configure uploads.  The reference has no receiver; these entries replace nothing of its flowgraph.  No
+ * synchronisation, no soft decisions, no ETI header or FIG reconstruction.
+ * Input: n_tf transmission frames of coded bits in the chain's input layout (what dabgpu_frontend_process writes and
+ *   dabgpu_demod returns), at most max_frames per call, four-byte aligned on the device.
+ * Output: n = n_tf x (4 | 1 | 1 | 2) images of 6144 bytes.  An image holds the decoded FIC and sub-channel payload at their
+ *   places in the ETI frame (fic_offset, the sub-channels' offsets) and zeros everywhere else: headers, EOF and TIST are not
+ *   reconstructed.
+ * Stream state: the time interleaver spreads a frame over sixteen, so the context keeps the last fifteen received rows (the
+ *   punctured FIC of an ETI frame followed by its CIF) on the device, zero after dabgpu_frontend_configure (the layout is new)
+ *   and after dabgpu_decode_reset; dabgpu_frontend_reset does not touch them.  The decoder is a delay line of fifteen ETI
+ *   frames: a call that brings rows e ... e + n - 1 of a stream returns ETI frames e - 15 ... e + n - 16.  Outputs with a
+ *   negative index are the lead-in: zero bytes, valid = 0, all counts 0.  THE LAST FIFTEEN FRAMES OF A FINITE STREAM ARE NEVER
+ *   RETURNED: the transmitter has not sent all of their bits yet.  The calls carry stream state, so they stay on lane 0 in
+ *   call order, like the front-end's.  There is no state blob and no seed for this history (out of scope here): a stream
+ *   is decoded from its start, or the first fifteen outputs after a reset are discarded by the caller.
+ * d_ref_eti / ref_eti (may be NULL): n x 6144 bytes, row i the ETI frame output i should equal; the differing payload bits
+ *   are counted per unit (headers and padding are not compared).
+ * Per (output, unit) figures, all integers, the same for every call geometry: corrected = the final path metric = received
+ *   coded bits that disagree with the decoded codeword; coded_bits = transmitted bits of the unit; bit_errors / n_bits against
+ *   the reference payload (0 / 0 without one).  dabgpu_get_decode_stats: output `frame` of the most recent call, after waiting
+ *   for it; unit -1 = the whole frame (sums), 0 = the FIC, 1 + i = sub-channel i in STC order.
+ * Refused before anything is queued, the history untouched: front-end not configured; a layout in which two sub-channels cover
+ *   one capacity unit (DABGPU_E_INVALID: the front-end lets the last one win, the other's bits were never transmitted);
+ *   n_tf = 0; n_tf above max_frames and out_cap below n x 6144 (DABGPU_E_CAPACITY; *out_bytes receives the size).
+ * dabgpu_decode_check_layout: host only, no context, no device: DABGPU_E_INVALID and the message (dabgpu_last_error(NULL), per
+ *   thread) for a layout the decoder refuses. */
+typedef struct dabgpu_decode_stats {
+    uint32_t valid; /* 0: lead-in output (stream index < 0) */
+    uint64_t corrected, coded_bits;
+    uint64_t bit_errors, n_bits;
+} dabgpu_decode_stats;
+DABGPU_API int dabgpu_decode_check_layout(const dabgpu_fe_layout *layout);
+/* zero history, layout kept; waits for the context */
+DABGPU_API int dabgpu_decode_reset(dabgpu_ctx *ctx);
+DABGPU_API int dabgpu_decode_dev(dabgpu_ctx *ctx, const void *d_bits, size_t n_tf, void *d_eti_out, size_t out_cap,
+                                 const void *d_ref_eti, size_t *out_bytes, void *stream);
+DABGPU_API int dabgpu_decode(dabgpu_ctx *ctx, const uint8_t *bits, size_t n_tf, uint8_t *eti_out, size_t out_cap,
+                             const uint8_t *ref_eti, size_t *out_bytes);
+DABGPU_API int dabgpu_get_decode_stats(dabgpu_ctx *ctx, size_t frame, int unit, dabgpu_decode_stats *out);
+
 /* ---- the spectrum monitor: Welch power spectrum of any sample buffer, mask check ----------------------------------------- *
  * The other half of what a transmitter operator watches: the out-of-band shoulders FIRFilter exists for, which CFR, the
  * predistorter, the guard window and the integer formats all trade against MER.  The reference has no such stage; these

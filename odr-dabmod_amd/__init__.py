@@ -51,6 +51,7 @@ EXPORTS = [
     "dabgpu_dpd_align", "dabgpu_dpd_align_dev", "dabgpu_dpd_delay_taps", "dabgpu_dpd_measure", "dabgpu_dpd_measure_dev",
     "dabgpu_get_dpd_stats", "dabgpu_reset_dpd", "dabgpu_debug_dpd_run_segments", "dabgpu_debug_dpd_tile",
     "dabgpu_dpd_fit_poly", "dabgpu_debug_resampler_run_hops", "dabgpu_debug_resampler_last_launch",
+    "dabgpu_decode_check_layout", "dabgpu_decode_reset", "dabgpu_decode_dev", "dabgpu_decode", "dabgpu_get_decode_stats",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -96,6 +97,11 @@ class _CfrStats(C.Structure):
 class _DemodStats(C.Structure):
     _fields_ = [("sum_signal", C.c_double), ("sum_quadrature", C.c_double), ("bit_errors", C.c_uint64),
                 ("n_bits", C.c_uint64), ("min_margin", C.c_double)]
+
+
+class _DecodeStats(C.Structure):
+    _fields_ = [("valid", C.c_uint32), ("corrected", C.c_uint64), ("coded_bits", C.c_uint64), ("bit_errors", C.c_uint64),
+                ("n_bits", C.c_uint64)]
 
 
 class _SpectrumInfo(C.Structure):
@@ -259,6 +265,11 @@ def load_library():
     lib.dabgpu_demod_check_early.argtypes = [C.c_int, C.c_int]
     lib.dabgpu_set_monitor.argtypes = [vp, C.c_int, C.c_int]
     lib.dabgpu_debug_demod_run_symbols.argtypes = [vp, C.c_int]
+    lib.dabgpu_decode_check_layout.argtypes = [C.POINTER(_FeLayout)]
+    lib.dabgpu_decode_reset.argtypes = [vp]
+    lib.dabgpu_decode_dev.argtypes = [vp, vp, sz, vp, sz, vp, szp, vp]
+    lib.dabgpu_decode.argtypes = [vp, vp, sz, vp, sz, vp, szp]
+    lib.dabgpu_get_decode_stats.argtypes = [vp, sz, C.c_int, C.POINTER(_DecodeStats)]
     dp = C.POINTER(C.c_double)
     lib.dabgpu_spectrum_window.argtypes = [C.c_int, C.POINTER(C.c_float)]
     lib.dabgpu_spectrum.argtypes = [vp, vp, C.c_int, sz, C.c_int, C.c_int]
@@ -296,6 +307,31 @@ def demod_check_early(mode, early):
     lib = load_library()
     if lib.dabgpu_demod_check_early(int(mode), int(early)) != 0:
         raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def decode_check_layout(frame):
+    """Host only (needs the library, no device): raises DabGpuError when the layout of this ETI frame is one the front-end
+    refuses, or one the channel decoder refuses (two sub-channels on one capacity unit)."""
+    lib = load_library()
+    frame = np.ascontiguousarray(frame, np.uint8).reshape(-1)
+    if frame.size != ETI_FRAME_BYTES:
+        raise DabGpuError("frontend: ETI frames are 6144 bytes")
+    lay = _FeLayout()
+    if lib.dabgpu_frontend_describe(frame.ctypes.data, C.byref(lay)) != 0 or lib.dabgpu_decode_check_layout(C.byref(lay)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def decode_reference(eti, e, n):
+    """The reference rows of a decode() call: the call that brings ETI frames e ... e + n - 1 of the stream `eti`
+    ((frames, 6144) uint8) returns frames e - 15 ... e + n - 16, so row i is frame e + i - 15 -- zero where that lies before
+    the start of the stream (the lead-in outputs, which are not compared)."""
+    eti = np.ascontiguousarray(eti, np.uint8).reshape(-1, ETI_FRAME_BYTES)
+    ref = np.zeros((n, ETI_FRAME_BYTES), np.uint8)
+    for i in range(n):
+        k = e + i - FE_HISTORY_FRAMES
+        if 0 <= k < eti.shape[0]:
+            ref[i] = eti[k]
+    return ref
 
 
 def spectrum_window(window):
@@ -955,6 +991,51 @@ class Modulator:
     def set_demod_run_symbols(self, symbols=0):
         """Diagnostic: data symbols per workgroup of the receiver's kernel (0: chosen from the batch size)."""
         self._chk(self._lib.dabgpu_debug_demod_run_symbols(self._h, int(symbols)))
+
+    # ---- the channel decoder: coded bits -> the ETI payload (include/dabgpu.h, "the channel decoder") ----
+    def decode(self, bits, ref_eti=None):
+        """Host path: whole transmission frames of coded bits (the chain's input layout) -> (eti_images, stats).  eti_images:
+        (n, 6144) uint8, the decoded FIC and sub-channel payload at their places, zeros elsewhere; output i of the call
+        that brings rows e ... is ETI frame e + i - 15 of the stream (decode_reference).  ref_eti: (n, 6144), counted
+        against.  stats: decode_stats(i) per output."""
+        bits = np.ascontiguousarray(bits, np.uint8).reshape(-1)
+        per = self.geometry["tf_input_bytes"]
+        if bits.size % per:
+            raise DabGpuError("decode: input size not valid (whole transmission frames of coded bits)")
+        n_tf = bits.size // per
+        n = n_tf * CIFS_PER_FRAME[self.geometry["mode"]]
+        ref = None
+        if ref_eti is not None:
+            ref = np.ascontiguousarray(ref_eti, np.uint8).reshape(-1)
+            if ref.size != n * ETI_FRAME_BYTES:
+                raise DabGpuError("decode: the reference is one 6144-byte ETI frame per output")
+        out = np.empty(max(n, 1) * ETI_FRAME_BYTES, np.uint8)
+        ob = C.c_size_t()
+        self._chk(self._lib.dabgpu_decode(self._h, bits.ctypes.data, n_tf, out.ctypes.data, out.nbytes,
+                                          ref.ctypes.data if ref is not None else None, C.byref(ob)))
+        return out[:ob.value].reshape(n, ETI_FRAME_BYTES), [self.decode_stats(i) for i in range(n)]
+
+    def decode_dev(self, d_bits, n_tf, d_eti_out, d_ref_eti=None, stream=None):
+        """Device path on torch uint8 tensors, asynchronous on the stream (as chain_dev); the figures: decode_stats."""
+        s = self._stream_handle(d_bits, stream)
+        ob = C.c_size_t()
+        self._chk(self._lib.dabgpu_decode_dev(self._h, d_bits.data_ptr(), n_tf, d_eti_out.data_ptr(),
+                                              d_eti_out.numel() * d_eti_out.element_size(),
+                                              d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob), s))
+        if not s:
+            self.synchronize()
+        return ob.value
+
+    def decode_reset(self):
+        """Zero decoder history (the start of a received stream), layout kept.  Waits."""
+        self._chk(self._lib.dabgpu_decode_reset(self._h))
+
+    def decode_stats(self, frame, unit=-1):
+        """Output `frame` of the most recent decode() / decode_dev() (waits for it): valid, corrected, coded_bits,
+        bit_errors, n_bits.  unit -1: the whole frame; 0: the FIC; 1 + i: sub-channel i in STC order."""
+        st = _DecodeStats()
+        self._chk(self._lib.dabgpu_get_decode_stats(self._h, frame, int(unit), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in _DecodeStats._fields_}
 
     # ---- the spectrum monitor: Welch power spectrum of any sample buffer (include/dabgpu.h, "the spectrum monitor") ----
     def spectrum(self, iq, window=2, accumulate=False):

@@ -377,7 +377,7 @@ int dabgpu_frontend_configure(dabgpu_ctx *c, const uint8_t *frame)
     c->fe_header.assign(frame + 5, frame + 8 + 4 * L.nst);
     c->fe_header[1] &= 0x18;
     c->fe_configured = true;
-    return DABGPU_OK;
+    return decode_configure(c);                                      // (the channel decoder's history belongs to the layout too)
 }
 
 int dabgpu_frontend_reset(dabgpu_ctx *c)

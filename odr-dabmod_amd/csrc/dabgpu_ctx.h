@@ -13,6 +13,8 @@
 //                     chain call; the window tables and the mask check (host only)
 //   api_dpd.hip       the DPD measurement (dpd.hip): cross-spectrum and aligned amplitude-bin statistics of a tx / feedback
 //                     pair; alignment solve, delay taps and polynomial fit (host only)
+//   api_decode.hip    the channel decoder (decode.hip): coded bits -> ETI payload, its history of fifteen received rows, the
+//                     per-unit figures; the layout check (host only)
 //   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
 //                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
 #pragma once
@@ -203,6 +205,18 @@ struct dabgpu_ctx {
     hipStream_t dpd_stream = nullptr;
     int dpd_run_segments = 0;             // dabgpu_debug_dpd_run_segments
     int dpd_tile = 0;                     // dabgpu_debug_dpd_tile
+    // The channel decoder (api_decode.hip, decode.hip).  d_dec_rows is the stream state: [15 + n][fic_out + 6912] received rows,
+    // punctured FIC | CIF of one ETI frame each, rows 0 ... 14 = the last fifteen of the stream (zero after configure / reset:
+    // dec_zero_pending asks the next call to zero them).  dec_pos: rows received since then (outputs before row 15 are the
+    // lead-in).  dec_slot: where each unit's survivor words start inside one output's share of d_dec_surv.  The records of
+    // the most recent call, the stream they are complete on and the host-pointer entry's staging follow.
+    dabgpu_api::DevBuf d_dec_rows, d_dec_tmp, d_dec_slot, d_dec_surv, d_dec_stats, d_dec_in, d_dec_out, d_dec_ref;
+    std::vector<uint32_t> dec_slot;
+    std::string dec_refusal;              // not empty: the configured layout is not decoded (two sub-channels on one capacity unit)
+    unsigned long long dec_pos = 0;
+    bool dec_zero_pending = true;
+    size_t dec_frames = 0, dec_first_valid = 0;
+    hipStream_t dec_stream = nullptr;
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII
     bool tables_valid = false;            // apply_settings has uploaded every table group once
     unsigned long long tii_seg_epoch = 0; // 1 while the cached segment matches the settings (apply_settings zeroes it), and its stage mask
@@ -417,6 +431,11 @@ int run_chain(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, void *d_out_v
 const char *monitor_refusal(const dabgpu_ctx *c, const ChainPlan &p);
 extern const char *const kMonitorNoSubmit;
 int run_monitor(dabgpu_ctx *c, const ChainPlan &p, const void *d_bits, const void *d_iq, hipStream_t s);
+
+// ---- api_decode.hip
+// dabgpu_frontend_configure's last step: the decoder's view of the new layout (survivor slots, the overlap refusal) and a zero
+// history; the context is idle
+int decode_configure(dabgpu_ctx *c);
 
 // ---- api_spectrum.hip
 // The spectrum monitor (dabgpu_set_spectrum_monitor) on a chain call from coded bits: behind run_chain (and run_monitor) on

@@ -269,6 +269,31 @@ struct FeArgs {
 hipError_t launch_fe_encode(const FeArgs &a, hipStream_t s);
 hipError_t launch_fe_assemble(const FeArgs &a, hipStream_t s);
 
+// The channel decoder (decode.hip): the front-end backwards, from the tables the front-end uploads.  A received row is the
+// punctured FIC of one ETI frame followed by its CIF (fic_out + kFeCifBytes bytes); `rows` holds the fifteen rows before the
+// call (the decoder's history) and the call's n rows behind them.  Output i of a call is decoded from rows i ... i + 15.
+constexpr int kDecThreads = 64;           // one wave: lane = state of the K = 7 code
+constexpr int kDecMaxSteps = 48 * 1024;   // trellis steps of one unit the kernel's LDS holds (a frame's payload gives < 48 294)
+struct DecUnitStats {                     // per (output, unit); plain stores, every record of a launch is written
+    uint32_t corrected, coded_bits, bit_errors, n_bits;
+};
+struct DecArgs {
+    const uint8_t *bits;                  // n_tf transmission frames in the chain's input layout (dword aligned)
+    uint8_t *rows;                        // (kFeHistory + n_out) x (fic_out + kFeCifBytes)
+    const uint8_t *prbs;
+    const FeUnit *units;
+    const uint32_t *slot;                 // n_units + 1: where a unit's survivor words start inside an output's scratch
+    unsigned long long *surv;             // n_out x slot[n_units] survivor words
+    uint8_t *out;                         // n_out x 6144, zeroed before the launch
+    const uint8_t *ref;                   // nullptr, or n_out x 6144
+    DecUnitStats *stats;                  // n_out x n_units
+    int n_out, n_units, cifs, fic_out;
+    int sym_bytes;                        // the steps of the layout's longest unit, rounded up to 64: the workgroup's LDS
+    int first_valid;                      // outputs before this one lie before the start of the stream: nothing is decoded
+};
+hipError_t launch_dec_rows(const DecArgs &a, hipStream_t s);
+hipError_t launch_dec_decode(const DecArgs &a, hipStream_t s);
+
 // Resampler (reference src/Resampler.cpp:131-195), power-of-two FFT sizes.
 struct ResamplerArgs {
     int nin, nout;          // FFT sizes (e.g. 4096 -> 16384)

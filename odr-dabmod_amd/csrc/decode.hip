@@ -1,0 +1,196 @@
+// decode.hip -- the channel decoder on the device: the chain's coded bits -> the ETI payload.  frontend.hip backwards, from the
+// tables dabgpu_frontend_configure uploads (FeUnit, the dispersal sequence).  The reference has no receiver: nothing here
+// replaces a class of its flowgraph.  Two launches per call:
+//   dec_rows_kernel    one lane per input dword: the transmission frame layout (the FICs of its ETI frames, then their CIFs)
+//                      into rows of one ETI frame each, punctured FIC | CIF, behind the fifteen rows of history.
+//   dec_decode_kernel  one wave per (output ETI frame, unit).  The time interleaver undone (delay_mask of frontend.hip forward
+//                      in time: 16 rows OR-ed per dword), depuncturing into one byte per trellis step (received nibble |
+//                      transmitted mask << 4), the K = 7 Viterbi decoder with lane = state, traceback, energy dispersal.
+// Hard decisions, Hamming metrics in uint32, no normalisation.  The rules a CPU model has to follow to give the same bits
+// (tests/decode_model.py): state 0 starts at 0, every other state at 1 << 24; of the two predecessors of a state the one whose
+// oldest bit is 0 survives unless the other's metric is strictly smaller; traceback starts at state 0 behind the tail.
+// Predecessor metrics come through ds_bpermute (two per step): DESIGN.md 4.10 says why.
+#include "dabgpu_internal.h"
+
+namespace dabgpu {
+
+namespace {
+
+constexpr int kDecRowWords = kFeCifBytes / 4;
+
+// (frontend.hip) bit 0x80 >> b of an even byte belongs to the frame delayed by {0,8,4,12,2,10,6,14}[b], of an odd byte by one
+// more: the mask a delay has on a little-endian dword of two (even, odd) byte pairs
+__device__ __forceinline__ uint32_t delay_mask(int d)
+{
+    const int h = d >> 1, b = ((h & 1) << 2) | (h & 2) | (h >> 2);
+    const uint32_t m = 0x80u >> b;
+    return (d & 1) ? m * 0x01000100u : m * 0x00010001u;
+}
+
+// the inverse of frontend.hip's keep_bits: the `kept` bits of acc (right-aligned, first bit highest) at the places the
+// pattern keeps, MSB first
+__device__ __forceinline__ uint32_t spread_bits(uint32_t acc, uint32_t pattern, uint32_t kept)
+{
+    uint32_t w = 0, n = kept;
+#pragma unroll
+    for (int b = 31; b >= 0; --b)
+        if ((pattern >> b) & 1u) w |= ((acc >> --n) & 1u) << b;
+    return w;
+}
+
+__global__ __launch_bounds__(256) void dec_rows_kernel(DecArgs a, size_t total)
+{
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const uint32_t fic_row = (uint32_t)a.fic_out / 4, fic_words = (uint32_t)a.cifs * fic_row;
+    const uint32_t tf_words = fic_words + (uint32_t)a.cifs * kDecRowWords, row_words = fic_row + kDecRowWords;
+    const size_t tf = idx / tf_words;
+    const uint32_t w = (uint32_t)(idx % tf_words);
+    uint32_t k, at;
+    if (w < fic_words) {
+        k = w / fic_row;
+        at = w % fic_row;
+    } else {
+        k = (w - fic_words) / kDecRowWords;
+        at = fic_row + (w - fic_words) % kDecRowWords;
+    }
+    ((uint32_t *)a.rows)[((size_t)kFeHistory + tf * a.cifs + k) * row_words + at] = ((const uint32_t *)a.bits)[idx];
+}
+
+__global__ __launch_bounds__(kDecThreads) void dec_decode_kernel(DecArgs a)
+{
+    // the unit's punctured bits as a stream in words whose MSB is the first bit (later: the decoded bytes); one byte per step,
+    // as many as the layout's longest unit has (a.sym_bytes: the launch sizes the workgroup's LDS by it)
+    __shared__ uint32_t s_pun[kDecRowWords + 2];
+    extern __shared__ uint32_t s_sym[];
+    const int lane = threadIdx.x;
+    const int f = blockIdx.x / a.n_units, ui = blockIdx.x % a.n_units;
+    const FeUnit &u = a.units[ui];
+    DecUnitStats *st = a.stats + (size_t)f * a.n_units + ui;
+    if (f < a.first_valid) {
+        if (lane == 0) *st = DecUnitStats{0, 0, 0, 0};
+        return;
+    }
+    const uint32_t in_bytes = u.in_bytes, out_words = u.out_bytes / 4;
+    const uint32_t row_words = (uint32_t)a.fic_out / 4 + kDecRowWords;
+    const uint32_t T = 8 * in_bytes + 6;
+
+    // ---- the unit's punctured bytes of output frame f: the FIC from row f, a sub-channel through the time interleaver
+    const uint32_t *row = (const uint32_t *)a.rows + (size_t)f * row_words;
+    if (u.owner < 0) {
+        for (uint32_t d = lane; d < out_words; d += kDecThreads) s_pun[d] = __builtin_bswap32(row[d]);
+    } else {
+        const uint32_t *src = row + (uint32_t)a.fic_out / 4 + u.dst_off / 4;
+        for (uint32_t d = lane; d < out_words; d += kDecThreads) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v |= src[(size_t)k * row_words + d] & delay_mask(k);
+            s_pun[d] = __builtin_bswap32(v);
+        }
+    }
+    if (lane < 2) s_pun[out_words + lane] = 0;
+    __syncthreads();
+
+    // ---- depuncture: one lane per 4-byte group of the mother code's output (8 steps); group in_bytes is the tail
+    for (uint32_t i = lane; i <= in_bytes; i += kDecThreads) {
+        uint32_t r = 0;
+        while (r < u.nseg && i >= u.g0[r + 1]) ++r;
+        const uint32_t pattern = u.pat[r], kept = __popc(pattern);
+        uint32_t w = 0;
+        if (kept) {
+            const uint32_t at = u.base[r] + (i - u.g0[r]) * kept;
+            const unsigned long long v = ((unsigned long long)s_pun[at >> 5] << 32) | s_pun[(at >> 5) + 1];
+            w = spread_bits((uint32_t)((v << (at & 31u)) >> (64 - kept)), pattern, kept);
+        }
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            lo |= (((w >> (28 - 4 * k)) & 0xfu) | (((pattern >> (28 - 4 * k)) & 0xfu) << 4)) << (8 * k);
+            hi |= (((w >> (12 - 4 * k)) & 0xfu) | (((pattern >> (12 - 4 * k)) & 0xfu) << 4)) << (8 * k);
+        }
+        s_sym[2 * i] = lo;
+        s_sym[2 * i + 1] = hi;
+    }
+    __syncthreads();
+
+    // ---- forward pass.  State = the last six input bits, newest at bit 0; the step into state s with oldest bit o has the
+    // encoder's window (o << 6) | s.  Every generator reads the oldest bit: the two expected nibbles are complements.
+    const uint32_t e0 = ((__popc(lane & 0x6d) & 1u) << 3) | ((__popc(lane & 0x4f) & 1u) << 2) | ((__popc(lane & 0x53) & 1u) << 1) |
+                        (__popc(lane & 0x6d) & 1u);
+    const int from0 = (lane >> 1) * 4, from1 = (32 + (lane >> 1)) * 4;
+    uint32_t metric = lane ? 1u << 24 : 0u;
+    unsigned long long *surv = a.surv + (size_t)f * a.slot[a.n_units] + a.slot[ui];
+    const uint8_t *sym = (const uint8_t *)s_sym;
+    const uint32_t chunks = (T + 63) / 64;
+    for (uint32_t c = 0; c < chunks; ++c) {
+        const int symv = sym[c * 64 + lane];
+        const int nk = (int)min(64u, T - c * 64);
+        unsigned long long mine = 0;
+        for (int k = 0; k < nk; ++k) {
+            const uint32_t r = (uint32_t)__builtin_amdgcn_readlane(symv, k);
+            const uint32_t m = r >> 4, x0 = (e0 ^ r) & m, x1 = x0 ^ m;
+            const uint32_t a0 = (uint32_t)__builtin_amdgcn_ds_bpermute(from0, (int)metric) + __popc(x0);
+            const uint32_t a1 = (uint32_t)__builtin_amdgcn_ds_bpermute(from1, (int)metric) + __popc(x1);
+            const bool other = a1 < a0;
+            metric = other ? a1 : a0;
+            const unsigned long long word = __ballot(other);
+            if (lane == k) mine = word;                  // (lane k keeps step k's word)
+        }
+        surv[c * 64 + lane] = mine;                      // 512 coalesced bytes
+    }
+    const uint32_t corrected = (uint32_t)__builtin_amdgcn_readlane((int)metric, 0);
+
+    // ---- traceback from state 0 behind the tail: the state in a scalar, the words of 64 steps one per lane (each lane reads
+    // back the very word it stored); bit k of `bits` is the input bit of step 64 c + k
+    uint8_t *dec = (uint8_t *)s_pun;
+    uint32_t state = 0;
+    for (uint32_t c = chunks; c-- > 0;) {
+        const unsigned long long mine = surv[c * 64 + lane];
+        const int nk = (int)min(64u, T - c * 64);
+        unsigned long long bits = 0;
+        for (int k = nk - 1; k >= 0; --k) {
+            const unsigned long long word = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mine >> 32), k) << 32) |
+                                            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mine, k);
+            bits |= (unsigned long long)(state & 1u) << k;
+            state = ((uint32_t)((word >> state) & 1u) << 5) | (state >> 1);
+        }
+        // eight payload bytes, first bit highest (the tail's six steps lie behind byte in_bytes - 1)
+        const uint32_t at = c * 8 + lane;
+        if (lane < 8 && at < in_bytes) dec[at] = (uint8_t)(__brev((uint32_t)(bits >> (8 * (lane & 7))) & 0xffu) >> 24);
+    }
+    __syncthreads();
+
+    // ---- energy dispersal, the payload at its place in the frame, the count against the reference
+    uint8_t *out = a.out + (size_t)f * 6144 + u.in_off;
+    const uint8_t *ref = a.ref ? a.ref + (size_t)f * 6144 + u.in_off : nullptr;
+    uint32_t errors = 0;
+    for (uint32_t i = lane; i < in_bytes; i += kDecThreads) {
+        const uint8_t v = dec[i] ^ a.prbs[i];
+        out[i] = v;
+        if (ref) errors += __popc((uint32_t)(v ^ ref[i]));
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) errors += __shfl_xor(errors, off);
+    if (lane == 0) *st = DecUnitStats{corrected, u.base[u.nseg] + 12u, errors, ref ? 8 * in_bytes : 0u};
+}
+
+}  // namespace
+
+hipError_t launch_dec_rows(const DecArgs &a, hipStream_t s)
+{
+    if (a.n_out <= 0) return hipSuccess;
+    if (a.n_out % a.cifs || a.fic_out % 4) return hipErrorInvalidValue;
+    const size_t total = (size_t)a.n_out * (size_t)(a.fic_out + kFeCifBytes) / 4;
+    DABGPU_LAUNCH(dec_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, total);
+    return hipGetLastError();
+}
+
+hipError_t launch_dec_decode(const DecArgs &a, hipStream_t s)
+{
+    if (a.n_out <= 0 || a.n_units <= 0) return hipSuccess;
+    if (a.sym_bytes <= 0 || a.sym_bytes % 64 || a.sym_bytes > kDecMaxSteps) return hipErrorInvalidValue;
+    DABGPU_LAUNCH(dec_decode_kernel, dim3((unsigned)a.n_out * (unsigned)a.n_units), dim3(kDecThreads), (size_t)a.sym_bytes + 8, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace dabgpu

@@ -40,6 +40,13 @@
 //                        device against the coded bits it was made from.  After the run: frames, bit errors, worst and mean MER
 //                        on stderr; exit status 2 when a bit error was counted.  The output file is the one without the option.
 //                        Native-rate complexf / s16 output; with --batch the batches run one at a time.
+//   --loopback           with --gpu-frontend: the whole loop closed on the device.  After each batch its IQ is demodulated
+//                        (dabgpu_demod, the window where --monitor puts it) and the coded bits are decoded (dabgpu_decode: time
+//                        de-interleaver, Viterbi, energy dispersal) against the ETI frames the program read, which it keeps in
+//                        a ring of fifteen: the decoder returns a frame fifteen frames after its first bits went out, and
+//                        never returns the last fifteen of the file.  After the run: frames compared, FIC and MSC payload
+//                        bit errors, corrected channel bits and coded bits on stderr; exit status 2 on any payload bit error.
+//                        Native-rate complexf / s16 output; not with --state-in (the decoder's history is not in the file).
 //   --spectrum FILE      the spectrum monitor behind every GPU call (DabGpuChain::Settings::spectrum): a Welch power spectrum of
 //                        everything written -- any rate, any format -- 2048 bins, Blackman-Harris window.  After the run FILE
 //                        holds one "offset_hz level_db" line per bin in ascending frequency, level relative to the mean over
@@ -96,6 +103,8 @@ namespace {
                          "                        N > 1 not with --bits-only or --separate-converter)\n"
                          "       [--gpu-frontend]   ETI -> coded bits on the device as well (not with --contexts above 1, --bits-only,\n"
                          "                        --separate-converter)\n"
+                         "       [--loopback]   with --gpu-frontend: demodulate and channel-decode every batch on the device against the ETI\n"
+                         "                        frames read; totals on stderr, exit 2 on a payload bit error\n"
                          "       [--monitor]   decode every frame written on the device; totals on stderr, exit 2 on a bit error\n"
                          "       [--dpd-feedback RXFILE --dpd-out COEFFILE [--dpd-bins N] [--dpd-min-count N]]   fit MemlessPoly from a feedback capture\n"
                          "       [--spectrum FILE [--mask MASKFILE] [--oob-from HZ]]   power spectrum of everything written, per bin into FILE;\n"
@@ -160,7 +169,7 @@ int main(int argc, char **argv)
     size_t batch = 1;
     bool reference_latency = false;
     long contexts = 1;
-    bool gpu_frontend = false;
+    bool gpu_frontend = false, loopback = false;
     std::string state_in, state_out;
     std::string spectrum_path, mask_path;
     double oob_from = 970000.0;
@@ -208,6 +217,7 @@ int main(int argc, char **argv)
             else if (a == "--reference-gain") gs.referenceGainRounding = true;
             else if (a == "--gpu-frontend") gpu_frontend = true;
             else if (a == "--monitor") gs.monitor = true;
+            else if (a == "--loopback") loopback = true;
             else if (a == "--spectrum") { spectrum_path = val(); gs.spectrum = true; }
             else if (a == "--mask") mask_path = val();
             else if (a == "--oob-from") oob_from = std::stod(val());
@@ -234,6 +244,15 @@ int main(int argc, char **argv)
                                         "the stream state a chain is seeded with"
                          : bits_only  ? "--bits-only: the coded bits stay on the device"
                                       : "--separate-converter: the streaming path converts inside the chain");
+            return 2;
+        }
+
+        if (loopback && (!gpu_frontend || gs.outputRate != 2048000 || (format != "complexf" && format != "s16") || !state_in.empty())) {
+            std::fprintf(stderr, "dabmod_file: --loopback does not go with %s\n",
+                         !gpu_frontend ? "the CPU front-end (it needs --gpu-frontend): the decoder reads the layout the device front-end holds"
+                         : gs.outputRate != 2048000 ? "--rate: the receiver takes the native rate"
+                         : !state_in.empty() ? "--state-in: the decoder's history is not part of the state file"
+                                             : "u8 / s8 output: the receiver takes complexf or s16");
             return 2;
         }
 
@@ -371,12 +390,58 @@ int main(int argc, char **argv)
             }
             chk(dabgpu_dpd_measure(ch->context(), p, fmt, dpd_buf.data(), n, &dpd_al, dpd_peak, dpd_bins, 1));
         };
+        // --loopback: the ETI frames handed to the device that the decoder has not returned yet, oldest first (loop_first: the
+        // stream index of the oldest; at most fifteen stay behind a batch), the decoder's position, and the totals
+        std::deque<std::vector<uint8_t>> loop_eti;
+        uint64_t loop_first = 0, loop_pos = 0;
+        struct { unsigned long long frames = 0, fic_errors = 0, msc_errors = 0, n_bits = 0, corrected = 0, coded_bits = 0; } loop;
+        std::vector<uint8_t> loop_bits, loop_out, loop_ref;
+        int loop_early = -1;
+        size_t loop_cifs = 1;
+        auto loopback_batch = [&](DabGpuChain *ch, const void *p, size_t bytes) {
+            dabgpu_ctx *c = ch->context();
+            auto chk = [&](int rc) { if (rc) throw std::runtime_error(std::string("--loopback: ") + dabgpu_last_error(c)); };
+            if (loop_early < 0) {
+                // where --monitor puts the window: behind FIRFilter's look-ahead and the guard window's overlap
+                loop_early = static_cast<int>(gs.ofdmWindowOverlap);
+                for (RemoteControllable *rc : ch->remote_controllables())
+                    if (rc->get_rc_name() == "firfilter") loop_early += std::stoi(rc->get_parameter("ntaps")) - 1;
+            }
+            const size_t n_frames = bytes / ch->output_bytes_per_frame(), n = n_frames * loop_cifs;
+            loop_bits.resize(n_frames * ch->input_bytes_per_frame());
+            loop_out.resize(n * 6144);
+            loop_ref.assign(n * 6144, 0);
+            chk(dabgpu_demod(c, p, format == "s16" ? DABGPU_FMT_S16 : 0, n_frames, loop_early, loop_bits.data(), nullptr));
+            // output i is frame loop_pos + i - 15 of the stream
+            for (size_t i = 0; i < n; ++i)
+                if (loop_pos + i >= 15) std::memcpy(&loop_ref[i * 6144], loop_eti.at(loop_pos + i - 15 - loop_first).data(), 6144);
+            size_t ob = 0;
+            chk(dabgpu_decode(c, loop_bits.data(), n_frames, loop_out.data(), loop_out.size(), loop_ref.data(), &ob));
+            for (size_t i = 0; i < n; ++i) {
+                dabgpu_decode_stats all{}, fic{};
+                chk(dabgpu_get_decode_stats(c, i, -1, &all));
+                chk(dabgpu_get_decode_stats(c, i, 0, &fic));
+                if (!all.valid) continue;
+                ++loop.frames;
+                loop.fic_errors += fic.bit_errors;
+                loop.msc_errors += all.bit_errors - fic.bit_errors;
+                loop.n_bits += all.n_bits;
+                loop.corrected += all.corrected;
+                loop.coded_bits += all.coded_bits;
+            }
+            loop_pos += n;
+            while (loop_first + 15 < loop_pos) {
+                loop_eti.pop_front();
+                ++loop_first;
+            }
+        };
         // the oldest batch in flight, in stream order: batch j lives on chain j mod N
         auto drain_one = [&]() {
             DabGpuChain *ch = chain_of(n_collected++);
             const void *p = nullptr;
             const size_t n = ch->collect(&p);
             add_monitor(ch);
+            if (loopback) loopback_batch(ch, p, n);
             n_out += n / ch->output_bytes_per_frame();
             if (format != "complexf") clipped += ch->get_num_clipped_samples();
             out.write(static_cast<const char *>(p), static_cast<std::streamsize>(n));
@@ -403,6 +468,11 @@ int main(int argc, char **argv)
             if (in_flight == 2) drain_one();
             ++n_batches;
             chain->submit_eti(pending_eti.data(), frames * cifs);
+            if (loopback) {
+                loop_cifs = cifs;
+                for (size_t k = 0; k < frames * cifs; ++k)
+                    loop_eti.emplace_back(pending_eti.begin() + k * 6144, pending_eti.begin() + (k + 1) * 6144);
+            }
             pending_eti.erase(pending_eti.begin(), pending_eti.begin() + frames * cifs * 6144);
             n_submitted += frames;
             ++in_flight;
@@ -541,6 +611,11 @@ int main(int argc, char **argv)
                          mon.frames, static_cast<unsigned long long>(mon.bit_errors), static_cast<unsigned long long>(mon.n_bits),
                          mon.worst_mer_db, mon.frames ? mon.sum_mer_db / static_cast<double>(mon.frames) : 0.0);
         }
+        if (loopback) {
+            std::fprintf(stderr, "dabmod_file: loopback: %llu frames compared, %llu FIC and %llu MSC payload bit errors in %llu bits, "
+                                 "%llu corrected channel bits in %llu coded bits\n",
+                         loop.frames, loop.fic_errors, loop.msc_errors, loop.n_bits, loop.corrected, loop.coded_bits);
+        }
         int mask_violations = 0;
         if (gs.spectrum) {
             // the contexts' sums added: one spectrum of the whole file
@@ -618,6 +693,7 @@ int main(int argc, char **argv)
                          fi.bins_used, fi.resid_am, fi.resid_pm, dpd_out_path.c_str());
         }
         if (gs.monitor && mon.bit_errors) return 2;
+        if (loopback && (loop.fic_errors || loop.msc_errors)) return 2;
         if (mask_violations) return 3;
         return 0;
     } catch (const std::exception &e) {
