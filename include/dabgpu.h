@@ -586,6 +586,20 @@ DABGPU_API int dabgpu_demod_dev(dabgpu_ctx *ctx, const void *d_iq, int format, s
 DABGPU_API int dabgpu_demod(dabgpu_ctx *ctx, const void *iq, int format, size_t n_frames, int early, uint8_t *bits_out,
                             const uint8_t *ref_bits);
 DABGPU_API int dabgpu_get_demod_stats(dabgpu_ctx *ctx, size_t frame, dabgpu_demod_stats *out);
+/* Soft output: the same call with one int8 metric per coded bit besides (d_soft_out / soft_out, not NULL, four-byte aligned on
+ * the device); bits, reference count and per-frame figures exactly as above (same kernel, same sums, dabgpu_get_demod_stats).
+ * Layout: n_frames x 8 tf_input_bytes.  Soft 8 p + b of a frame belongs to bit 0x80 >> b of byte p of the coded-bit layout:
+ *   per block the I softs in interleaver-undone order, then the Q softs.  soft > 0: the bit is more likely 1; soft < 0: more
+ *   likely 0; 0 says nothing.
+ * Scale, per data symbol s over its K carriers: P = sum_k |d_k|^2, q = 64 sqrt(2) / sqrt(P / K),
+ *   soft_I = clamp(rint(-Re d_k q), -127, 127), soft_Q likewise from Im d_k; all zero when P = 0.  A clean, flat symbol gives
+ *   +-64.  Per symbol on purpose: independent of the per-symbol gain (as the MER figure is), the carriers' relative reliability
+ *   is kept, and no second pass over the frame is needed.  P is added in a fixed order: the softs repeat bit for bit and do not
+ *   depend on the run geometry (dabgpu_debug_demod_run_symbols).  Same `early` rule and the same refusals as dabgpu_demod*. */
+DABGPU_API int dabgpu_demod_soft_dev(dabgpu_ctx *ctx, const void *d_iq, int format, size_t n_frames, int early,
+                                     void *d_soft_out, void *d_bits_out, const void *d_ref_bits, void *stream);
+DABGPU_API int dabgpu_demod_soft(dabgpu_ctx *ctx, const void *iq, int format, size_t n_frames, int early, int8_t *soft_out,
+                                 uint8_t *bits_out, const uint8_t *ref_bits);
 /* host only, no context, no device: the range test of `early` for a transmission mode (1..4; 0 = IV), with the message the
  * entries above give (dabgpu_last_error(NULL), per thread) */
 DABGPU_API int dabgpu_demod_check_early(int mode, int early);
@@ -605,7 +619,7 @@ DABGPU_API int dabgpu_debug_demod_run_symbols(dabgpu_ctx *ctx, int symbols);
  * What a DAB receiver runs behind the demodulator, on the device: the time de-interleaver, depuncturing, the K = 7 Viterbi
  * decoder (hard decisions) and the energy dispersal -- the two kernels of the front-end backwards, from the very tables
  * dabgpu_frontend_configure uploads.  The reference has no receiver; these entries replace nothing of its flowgraph.  No
- * synchronisation, no soft decisions, no ETI header or FIG reconstruction.
+ * synchronisation, no ETI header or FIG reconstruction; soft decisions: dabgpu_decode_soft* below.
  * Input: n_tf transmission frames of coded bits in the chain's input layout (what dabgpu_frontend_process writes and
  *   dabgpu_demod returns), at most max_frames per call, four-byte aligned on the device.
  * Output: n = n_tf x (4 | 1 | 1 | 2) images of 6144 bytes.  An image holds the decoded FIC and sub-channel payload at their
@@ -643,6 +657,36 @@ DABGPU_API int dabgpu_decode_dev(dabgpu_ctx *ctx, const void *d_bits, size_t n_t
 DABGPU_API int dabgpu_decode(dabgpu_ctx *ctx, const uint8_t *bits, size_t n_tf, uint8_t *eti_out, size_t out_cap,
                              const uint8_t *ref_eti, size_t *out_bytes);
 DABGPU_API int dabgpu_get_decode_stats(dabgpu_ctx *ctx, size_t frame, int unit, dabgpu_decode_stats *out);
+/* The soft decoder: the same calls on soft metrics.  Input: n_tf x 8 tf_input_bytes int8 in the layout dabgpu_demod_soft writes
+ * (soft 8 p + b belongs to bit 0x80 >> b of byte p; > 0: more likely 1).  Any int8 is accepted; -128 counts with magnitude 128.
+ * Stream state of its own: fifteen soft rows of 8 (fic_out + 6912) bytes, allocated at the first soft call, zero after
+ *   dabgpu_frontend_configure and dabgpu_decode_reset, independent of the hard decoder's history -- hard and soft calls may be
+ *   mixed on one context, and each stream sees only its own rows.  The same delay line of fifteen ETI frames, the same lead-in
+ *   outputs, the same refusals before anything is queued, the same lane.
+ * Metric, in integers.  With e_i the expected bit and r_i the soft of a branch's four code bits (0 where the bit was not
+ *   transmitted): cost = sum_i max(0, (1 - 2 e_i) r_i), the magnitude of every soft whose sign contradicts the branch; the
+ *   complementary branch costs sum |r_i| - cost.  State 0 starts at 0, every other state at 1 << 30.  uint32 without
+ *   normalisation: at most 4 x 128 = 512 per step over fewer than 48 294 steps stays below 2^32 (even doubled).  Tie rule and
+ *   traceback are the hard decoder's: the predecessor whose oldest bit is 0 survives unless the other is strictly smaller;
+ *   traceback starts from state 0 behind the tail.  On softs that are +-1 the decisions are the hard decoder's, ties included.
+ * Per (output, unit) figures, all integers, the same for every call geometry:
+ *   metric      final metric of state 0 = sum |soft| over the received bits that contradict the decoded codeword
+ *   contra_sum  that sum formed a second way, from the decoded bits encoded again: always equal to metric
+ *   soft_sum    sum |soft| over the unit's transmitted bits
+ *   corrected   transmitted bits with a non-zero soft whose sign contradicts the re-encoded codeword
+ *   erasures    transmitted bits with soft 0
+ *   coded_bits, bit_errors, n_bits as dabgpu_decode_stats */
+typedef struct dabgpu_decode_soft_stats {
+    uint32_t valid; /* 0: lead-in output (stream index < 0) */
+    uint64_t metric, contra_sum, soft_sum;
+    uint64_t corrected, erasures, coded_bits;
+    uint64_t bit_errors, n_bits;
+} dabgpu_decode_soft_stats;
+DABGPU_API int dabgpu_decode_soft_dev(dabgpu_ctx *ctx, const void *d_soft, size_t n_tf, void *d_eti_out, size_t out_cap,
+                                      const void *d_ref_eti, size_t *out_bytes, void *stream);
+DABGPU_API int dabgpu_decode_soft(dabgpu_ctx *ctx, const int8_t *soft, size_t n_tf, uint8_t *eti_out, size_t out_cap,
+                                  const uint8_t *ref_eti, size_t *out_bytes);
+DABGPU_API int dabgpu_get_decode_soft_stats(dabgpu_ctx *ctx, size_t frame, int unit, dabgpu_decode_soft_stats *out);
 
 /* ---- the spectrum monitor: Welch power spectrum of any sample buffer, mask check ----------------------------------------- *
  * The other half of what a transmitter operator watches: the out-of-band shoulders FIRFilter exists for, which CFR, the

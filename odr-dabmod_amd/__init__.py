@@ -52,6 +52,7 @@ EXPORTS = [
     "dabgpu_get_dpd_stats", "dabgpu_reset_dpd", "dabgpu_debug_dpd_run_segments", "dabgpu_debug_dpd_tile",
     "dabgpu_dpd_fit_poly", "dabgpu_debug_resampler_run_hops", "dabgpu_debug_resampler_last_launch",
     "dabgpu_decode_check_layout", "dabgpu_decode_reset", "dabgpu_decode_dev", "dabgpu_decode", "dabgpu_get_decode_stats",
+    "dabgpu_demod_soft", "dabgpu_demod_soft_dev", "dabgpu_decode_soft", "dabgpu_decode_soft_dev", "dabgpu_get_decode_soft_stats",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -97,6 +98,12 @@ class _CfrStats(C.Structure):
 class _DemodStats(C.Structure):
     _fields_ = [("sum_signal", C.c_double), ("sum_quadrature", C.c_double), ("bit_errors", C.c_uint64),
                 ("n_bits", C.c_uint64), ("min_margin", C.c_double)]
+
+
+class _DecodeSoftStats(C.Structure):
+    _fields_ = [("valid", C.c_uint32), ("metric", C.c_uint64), ("contra_sum", C.c_uint64), ("soft_sum", C.c_uint64),
+                ("corrected", C.c_uint64), ("erasures", C.c_uint64), ("coded_bits", C.c_uint64), ("bit_errors", C.c_uint64),
+                ("n_bits", C.c_uint64)]
 
 
 class _DecodeStats(C.Structure):
@@ -270,6 +277,11 @@ def load_library():
     lib.dabgpu_decode_dev.argtypes = [vp, vp, sz, vp, sz, vp, szp, vp]
     lib.dabgpu_decode.argtypes = [vp, vp, sz, vp, sz, vp, szp]
     lib.dabgpu_get_decode_stats.argtypes = [vp, sz, C.c_int, C.POINTER(_DecodeStats)]
+    lib.dabgpu_demod_soft.argtypes = [vp, vp, C.c_int, sz, C.c_int, vp, vp, vp]
+    lib.dabgpu_demod_soft_dev.argtypes = [vp, vp, C.c_int, sz, C.c_int, vp, vp, vp, vp]
+    lib.dabgpu_decode_soft_dev.argtypes = [vp, vp, sz, vp, sz, vp, szp, vp]
+    lib.dabgpu_decode_soft.argtypes = [vp, vp, sz, vp, sz, vp, szp]
+    lib.dabgpu_get_decode_soft_stats.argtypes = [vp, sz, C.c_int, C.POINTER(_DecodeSoftStats)]
     dp = C.POINTER(C.c_double)
     lib.dabgpu_spectrum_window.argtypes = [C.c_int, C.POINTER(C.c_float)]
     lib.dabgpu_spectrum.argtypes = [vp, vp, C.c_int, sz, C.c_int, C.c_int]
@@ -972,6 +984,48 @@ class Modulator:
         if not s:
             self.synchronize()
 
+    def demod_soft(self, iq, early=0, ref_bits=None, want_bits=False):
+        """demod() with soft output: -> soft (n_frames x 8 tf_input_bytes int8; soft 8 p + b belongs to bit 0x80 >> b of byte
+        p, > 0: more likely 1, a clean flat symbol gives +-64), or (soft, bits) with want_bits=True.  The per-frame figures
+        are monitor_stats(frame), as after demod()."""
+        iq = np.ascontiguousarray(iq)
+        fmt = self._iq_format(iq.dtype)
+        per = self.geometry["tf_samples"] * (2 if fmt else 1)
+        if iq.size == 0 or iq.size % per:
+            raise DabGpuError("demod: input size not valid (whole transmission frames at the native rate)")
+        n = iq.size // per
+        nb = self.geometry["tf_input_bytes"]
+        soft = np.empty((n, 8 * nb), np.int8)
+        out = np.empty((n, nb), np.uint8) if want_bits else None
+        ref = None
+        if ref_bits is not None:
+            ref = np.ascontiguousarray(ref_bits, np.uint8).reshape(-1)
+            if ref.size != n * nb:
+                raise DabGpuError("demod: reference bits do not match the frames")
+        self._chk(self._lib.dabgpu_demod_soft(self._h, iq.ctypes.data, fmt, n, int(early), soft.ctypes.data,
+                                              out.ctypes.data if want_bits else None, ref.ctypes.data if ref is not None else None))
+        return (soft, out) if want_bits else soft
+
+    def demod_soft_dev(self, d_iq, n_frames, d_soft_out, early=0, d_bits_out=None, d_ref_bits=None, stream=None):
+        """demod_dev() with soft output: d_soft_out is int8, n_frames x 8 tf_input_bytes."""
+        import torch
+        fmt = 0 if d_iq.dtype == torch.complex64 else (FORMATS["s16"][0] if d_iq.dtype == torch.int16 else -1)
+        if fmt < 0:
+            raise DabGpuError("demod: input is complex64 or int16 (interleaved re, im)")
+        if d_iq.numel() != n_frames * self.geometry["tf_samples"] * (2 if fmt else 1):
+            raise DabGpuError("demod: input size not valid (whole transmission frames at the native rate)")
+        if d_soft_out is None or d_soft_out.numel() * d_soft_out.element_size() != 8 * n_frames * self.geometry["tf_input_bytes"]:
+            raise DabGpuError("demod: the soft buffer is n_frames x 8 tf_input_bytes int8")
+        for tns in (d_bits_out, d_ref_bits):
+            if tns is not None and tns.numel() * tns.element_size() != n_frames * self.geometry["tf_input_bytes"]:
+                raise DabGpuError("demod: bit buffers are n_frames x tf_input_bytes")
+        s = self._stream_handle(d_iq, stream)
+        self._chk(self._lib.dabgpu_demod_soft_dev(self._h, d_iq.data_ptr(), fmt, n_frames, int(early), d_soft_out.data_ptr(),
+                                                  d_bits_out.data_ptr() if d_bits_out is not None else None,
+                                                  d_ref_bits.data_ptr() if d_ref_bits is not None else None, s))
+        if not s:
+            self.synchronize()
+
     def set_monitor(self, enable, early=-1):
         """Demodulate every native-rate chain call's output against its own coded bits (off by default); early < 0: from
         the call's filter and window.  The figures: monitor_stats(frame)."""
@@ -1025,6 +1079,47 @@ class Modulator:
         if not s:
             self.synchronize()
         return ob.value
+
+    def decode_soft(self, soft, ref_eti=None):
+        """decode() on soft metrics: whole transmission frames of int8 softs in demod_soft()'s layout (8 per coded byte; any
+        int8, -128 counts with magnitude 128) -> (eti_images, stats), stats: decode_soft_stats(i) per output.  A stream of its
+        own beside decode()'s: the two histories do not see each other."""
+        soft = np.ascontiguousarray(soft, np.int8).reshape(-1)
+        per = 8 * self.geometry["tf_input_bytes"]
+        if soft.size % per:
+            raise DabGpuError("decode: input size not valid (whole transmission frames of soft metrics)")
+        n_tf = soft.size // per
+        n = n_tf * CIFS_PER_FRAME[self.geometry["mode"]]
+        ref = None
+        if ref_eti is not None:
+            ref = np.ascontiguousarray(ref_eti, np.uint8).reshape(-1)
+            if ref.size != n * ETI_FRAME_BYTES:
+                raise DabGpuError("decode: the reference is one 6144-byte ETI frame per output")
+        out = np.empty(max(n, 1) * ETI_FRAME_BYTES, np.uint8)
+        ob = C.c_size_t()
+        self._chk(self._lib.dabgpu_decode_soft(self._h, soft.ctypes.data, n_tf, out.ctypes.data, out.nbytes,
+                                               ref.ctypes.data if ref is not None else None, C.byref(ob)))
+        return out[:ob.value].reshape(n, ETI_FRAME_BYTES), [self.decode_soft_stats(i) for i in range(n)]
+
+    def decode_soft_dev(self, d_soft, n_tf, d_eti_out, d_ref_eti=None, stream=None):
+        """Device path on torch tensors (int8 softs, uint8 images), asynchronous on the stream; the figures: decode_soft_stats."""
+        if d_soft.numel() * d_soft.element_size() != 8 * n_tf * self.geometry["tf_input_bytes"]:
+            raise DabGpuError("decode: input size not valid (whole transmission frames of soft metrics)")
+        s = self._stream_handle(d_soft, stream)
+        ob = C.c_size_t()
+        self._chk(self._lib.dabgpu_decode_soft_dev(self._h, d_soft.data_ptr(), n_tf, d_eti_out.data_ptr(),
+                                                   d_eti_out.numel() * d_eti_out.element_size(),
+                                                   d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob), s))
+        if not s:
+            self.synchronize()
+        return ob.value
+
+    def decode_soft_stats(self, frame, unit=-1):
+        """Output `frame` of the most recent decode_soft() / decode_soft_dev() (waits for it): valid, metric, contra_sum (always
+        equal to metric), soft_sum, corrected, erasures, coded_bits, bit_errors, n_bits.  unit as decode_stats."""
+        st = _DecodeSoftStats()
+        self._chk(self._lib.dabgpu_get_decode_soft_stats(self._h, frame, int(unit), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in _DecodeSoftStats._fields_}
 
     def decode_reset(self):
         """Zero decoder history (the start of a received stream), layout kept.  Waits."""

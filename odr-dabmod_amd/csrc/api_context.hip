@@ -546,11 +546,11 @@ void dabgpu_destroy(dabgpu_ctx *c)
                       &c->d_acp, &c->d_tii_car, &c->d_tii_frame, &c->d_gain1, &c->d_gains, &c->d_cic,
                       &c->d_cfr_counts, &c->d_cfr_mer, &c->d_cfr_papr, &c->d_cfr_tmp,
                       &c->d_fe_prbs, &c->d_fe_units, &c->d_fe_owner, &c->d_fe_hist, &c->d_fe_tmp, &c->d_fe_fic, &c->d_fe_eti,
-                      &c->d_fe_seed, &c->d_demod_stats, &c->d_demod_bits, &c->d_demod_ref,
+                      &c->d_fe_seed, &c->d_demod_stats, &c->d_demod_bits, &c->d_demod_ref, &c->d_demod_soft,
                       &c->d_spec_tw, &c->d_spec_win, &c->d_spec_rows, &c->d_spec_acc, &c->d_spec_in,
                       &c->d_dpd_tw, &c->d_dpd_rows, &c->d_dpd_xacc, &c->d_dpd_sums, &c->d_dpd_edge, &c->d_dpd_tx, &c->d_dpd_rx,
                       &c->d_dec_rows, &c->d_dec_tmp, &c->d_dec_slot, &c->d_dec_surv, &c->d_dec_stats, &c->d_dec_in, &c->d_dec_out,
-                      &c->d_dec_ref})
+                      &c->d_dec_ref, &c->d_decs_rows, &c->d_decs_tmp, &c->d_decs_stats, &c->d_decs_in})
         b->release();
     for (auto &sl : c->slot) {
         sl.d_eti.release();

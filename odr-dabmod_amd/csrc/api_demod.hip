@@ -14,8 +14,9 @@ namespace {
 const char *const kEarlyRange = "demod: early must lie inside the cyclic prefix (0 ... sym_size - spacing)";
 
 // zero records, one launch; on `s`.  d_iq: n_frames x tf_samples samples of `format` (0 = cf32, DABGPU_FMT_S16).
+// d_soft: nullptr (the hard kernel), or n_frames x 8 tf_input_bytes int8 (the soft kernel: the same bits and sums besides).
 int queue_demod(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *d_bits_out, const void *d_ref,
-                hipStream_t s)
+                hipStream_t s, void *d_soft = nullptr)
 {
     HIPCHK(c, c->d_demod_stats.reserve(std::max<size_t>(n_frames, 1) * sizeof(DemodFrameStats)));
     HIPCHK(c, hipMemsetAsync(c->d_demod_stats.p, 0, n_frames * sizeof(DemodFrameStats), s));
@@ -31,6 +32,7 @@ int queue_demod(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, in
     a.bits_out = (uint8_t *)d_bits_out;
     a.ref_bits = (const uint8_t *)d_ref;
     a.stats = (DemodFrameStats *)c->d_demod_stats.p;
+    a.soft_out = (int8_t *)d_soft;
     HIPCHK(c, launch_demod(a, s));
     c->demod_frames = n_frames;
     c->demod_has_ref = d_ref != nullptr;
@@ -107,6 +109,43 @@ int dabgpu_demod(dabgpu_ctx *c, const void *iq, int format, size_t n_frames, int
     if ((rc = dabgpu_demod_dev(c, c->d_out.p, format, n_frames, early, bits_out ? c->d_demod_bits.p : nullptr,
                                ref_bits ? c->d_demod_ref.p : nullptr, c->stream)))
         return rc;
+    return io.out(bits_out, c->d_demod_bits.p, bits_out ? bit_bytes : 0);
+}
+
+int dabgpu_demod_soft_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *d_soft_out,
+                          void *d_bits_out, const void *d_ref_bits, void *stream)
+{
+    CTXCHK(c);
+    int rc = apply_settings(c);
+    if (rc) return rc;
+    if ((rc = check_demod(c, d_iq, format, n_frames, early, d_bits_out, d_ref_bits))) return rc;
+    if (!d_soft_out) return fail(c, DABGPU_E_INVALID, "null argument");
+    if ((uintptr_t)d_soft_out & 3u) return fail(c, DABGPU_E_INVALID, "demod: buffers must be aligned to four bytes");
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;
+    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
+    return queue_demod(c, d_iq, format, n_frames, early, d_bits_out, d_ref_bits, s, d_soft_out);
+}
+
+int dabgpu_demod_soft(dabgpu_ctx *c, const void *iq, int format, size_t n_frames, int early, int8_t *soft_out, uint8_t *bits_out,
+                      const uint8_t *ref_bits)
+{
+    CTXCHK(c);
+    int rc = check_demod(c, iq, format, n_frames, early, nullptr, nullptr);
+    if (rc) return rc;
+    if (!soft_out) return fail(c, DABGPU_E_INVALID, "null argument");
+    if ((rc = dabgpu_synchronize(c))) return rc;
+    const size_t iq_bytes = n_frames * tf_samples(c->g) * (format ? 4 : sizeof(float2));
+    const size_t bit_bytes = n_frames * tf_in_bytes(c->g);
+    HostIO io(c);
+    if ((rc = io.in(c->d_out, iq, iq_bytes))) return rc;
+    if (ref_bits && (rc = io.in(c->d_demod_ref, ref_bits, bit_bytes))) return rc;
+    if (bits_out) HIPCHK(c, c->d_demod_bits.reserve(std::max<size_t>(bit_bytes, 16)));
+    HIPCHK(c, c->d_demod_soft.reserve(std::max<size_t>(8 * bit_bytes, 16)));
+    if ((rc = dabgpu_demod_soft_dev(c, c->d_out.p, format, n_frames, early, c->d_demod_soft.p, bits_out ? c->d_demod_bits.p : nullptr,
+                                    ref_bits ? c->d_demod_ref.p : nullptr, c->stream)))
+        return rc;
+    if (n_frames && (rc = io.out(soft_out, c->d_demod_soft.p, 8 * bit_bytes))) return rc;
     return io.out(bits_out, c->d_demod_bits.p, bits_out ? bit_bytes : 0);
 }
 

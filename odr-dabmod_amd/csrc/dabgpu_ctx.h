@@ -179,7 +179,7 @@ struct dabgpu_ctx {
     hipStream_t cfr_last_stream = nullptr;
     // The receiver (api_demod.hip): the records of the most recent dabgpu_demod* call or monitored chain call, the stream
     // they are complete on, and the staging of the host-pointer entry.  Monitored calls stay on lane 0: one set.
-    dabgpu_api::DevBuf d_demod_stats, d_demod_bits, d_demod_ref;
+    dabgpu_api::DevBuf d_demod_stats, d_demod_bits, d_demod_ref, d_demod_soft;
     size_t demod_frames = 0;
     bool demod_has_ref = false;
     hipStream_t demod_stream = nullptr;
@@ -217,6 +217,14 @@ struct dabgpu_ctx {
     bool dec_zero_pending = true;
     size_t dec_frames = 0, dec_first_valid = 0;
     hipStream_t dec_stream = nullptr;
+    // The soft decoder (dabgpu_decode_soft*): a stream of its own beside the hard one -- fifteen rows of 8 x (fic_out + 6912)
+    // int8 metrics, its own position, records and staging; layout, refusal, slots and survivor scratch are shared (both stay
+    // on lane 0).  Zeroed with the hard history (configure, dabgpu_decode_reset).
+    dabgpu_api::DevBuf d_decs_rows, d_decs_tmp, d_decs_stats, d_decs_in;
+    unsigned long long decs_pos = 0;
+    bool decs_zero_pending = true;
+    size_t decs_frames = 0, decs_first_valid = 0;
+    hipStream_t decs_stream = nullptr;
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII
     bool tables_valid = false;            // apply_settings has uploaded every table group once
     unsigned long long tii_seg_epoch = 0; // 1 while the cached segment matches the settings (apply_settings zeroes it), and its stage mask

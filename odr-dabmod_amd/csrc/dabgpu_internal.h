@@ -173,6 +173,7 @@ struct DemodArgs {
     uint8_t *bits_out;        // nullptr, or n_frames x (nb_symbols - 1) * K / 4 bytes, dword aligned
     const uint8_t *ref_bits;  // nullptr, or the same shape: differing bits are counted
     DemodFrameStats *stats;   // n_frames records
+    int8_t *soft_out;         // nullptr (the hard kernel), or n_frames x (nb_symbols - 1) * 2 K soft metrics, dword aligned
 };
 void demod_runs(const Geometry &g, size_t n_frames, int forced, int *runs_per_frame, int *syms_per_run);
 hipError_t launch_demod(const DemodArgs &a, hipStream_t s);
@@ -293,6 +294,26 @@ struct DecArgs {
 };
 hipError_t launch_dec_rows(const DecArgs &a, hipStream_t s);
 hipError_t launch_dec_decode(const DecArgs &a, hipStream_t s);
+// The soft decoder: the same on int8 metrics, one per coded bit (rows eight times as long); survivor scratch and slots shared
+struct DecSoftUnitStats {                 // per (output, unit); plain stores, every record of a launch is written
+    uint32_t metric, contra_sum, soft_sum, corrected, erasures, coded_bits, bit_errors, n_bits;
+};
+struct DecSoftArgs {
+    const int8_t *soft;                   // n_tf x 8 tf_input_bytes (dword aligned)
+    int8_t *rows;                         // (kFeHistory + n_out) x 8 (fic_out + kFeCifBytes)
+    const uint8_t *prbs;
+    const FeUnit *units;
+    const uint32_t *slot;
+    unsigned long long *surv;
+    uint8_t *out;                         // n_out x 6144, zeroed before the launch
+    const uint8_t *ref;                   // nullptr, or n_out x 6144
+    DecSoftUnitStats *stats;              // n_out x n_units
+    int n_out, n_units, cifs, fic_out;
+    int lds_bytes;                        // 8 x out_bytes of the layout's largest unit: the punctured softs a workgroup stages
+    int first_valid;
+};
+hipError_t launch_dec_soft_rows(const DecSoftArgs &a, hipStream_t s);
+hipError_t launch_dec_soft_decode(const DecSoftArgs &a, hipStream_t s);
 
 // Resampler (reference src/Resampler.cpp:131-195), power-of-two FFT sizes.
 struct ResamplerArgs {

@@ -174,6 +174,194 @@ __global__ __launch_bounds__(kDecThreads) void dec_decode_kernel(DecArgs a)
     if (lane == 0) *st = DecUnitStats{corrected, u.base[u.nseg] + 12u, errors, ref ? 8 * in_bytes : 0u};
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The soft decoder (dabgpu_decode_soft*): the same two launches on int8 metrics, one per coded bit (soft > 0: the bit is more
+// likely 1; 0 says nothing; -128 counts with magnitude 128), eight bytes where the hard decoder has one.
+//   dec_soft_rows_kernel    one lane per dword of softs, the hard rows kernel's index rule on rows eight times as long.
+//   dec_soft_decode_kernel  one wave per (output, unit), lane = state.  The unit's PUNCTURED softs are staged in LDS (at most
+//                           864 CU x 64 = 55 296 B; the depunctured ones, four bytes per step, would not fit), the time
+//                           interleaver undone by a byte gather over sixteen rows.  Depuncturing happens per 64-step chunk:
+//                           lane k forms the four softs of step 64 c + k (0 where the pattern drops the bit) in one dword and
+//                           their magnitudes' sum, and the step loop reads both by v_readlane.
+// Metric: with e_i the branch's expected bit and r_i the soft, cost = sum max(0, (1 - 2 e_i) r_i) = (sum |r_i| + sum (1 - 2 e_i)
+// r_i) / 2 -- one signed 4 x int8 dot product per state and the step's scalar total; the complementary branch costs total - cost.
+// State 0 starts at 0, every other state at 1 << 30; uint32 without normalisation (at most 512 per step, fewer than 48 294
+// steps).  Tie rule and traceback are the hard decoder's.  Behind the traceback the decoded bits are encoded again, one lane
+// per 4-byte group, against the softs in LDS: the contradicting bits, their magnitudes (= the final metric), the erasures.
+__device__ __forceinline__ uint32_t dec_mother_code(uint32_t prev, uint32_t byte)     // (frontend.hip: mother_code)
+{
+    const uint32_t s = ((prev & 0x3fu) << 8) | byte;
+    uint32_t w = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t win = (s >> (7 - k)) & 0x7fu;
+        w = (w << 4) | ((__popc(win & 0x6du) & 1u) << 3) | ((__popc(win & 0x4fu) & 1u) << 2) | ((__popc(win & 0x53u) & 1u) << 1) |
+            (__popc(win & 0x6du) & 1u);
+    }
+    return w;
+}
+
+__global__ __launch_bounds__(256) void dec_soft_rows_kernel(DecSoftArgs a, size_t total)
+{
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const uint32_t fic_row = 2u * (uint32_t)a.fic_out, fic_words = (uint32_t)a.cifs * fic_row, cif_row = 8u * kDecRowWords;
+    const uint32_t tf_words = fic_words + (uint32_t)a.cifs * cif_row, row_words = fic_row + cif_row;
+    const size_t tf = idx / tf_words;
+    const uint32_t w = (uint32_t)(idx % tf_words);
+    uint32_t k, at;
+    if (w < fic_words) {
+        k = w / fic_row;
+        at = w % fic_row;
+    } else {
+        k = (w - fic_words) / cif_row;
+        at = fic_row + (w - fic_words) % cif_row;
+    }
+    ((uint32_t *)a.rows)[((size_t)kFeHistory + tf * a.cifs + k) * row_words + at] = ((const uint32_t *)a.soft)[idx];
+}
+
+__global__ __launch_bounds__(kDecThreads) void dec_soft_decode_kernel(DecSoftArgs a)
+{
+    __shared__ uint32_t s_dec[kDecRowWords + 2];         // the decoded bytes, before the energy dispersal
+    extern __shared__ uint32_t s_soft[];               // the unit's punctured softs: 8 x out_bytes (a.lds_bytes)
+    const int lane = threadIdx.x;
+    const int f = blockIdx.x / a.n_units, ui = blockIdx.x % a.n_units;
+    const FeUnit &u = a.units[ui];
+    DecSoftUnitStats *st = a.stats + (size_t)f * a.n_units + ui;
+    if (f < a.first_valid) {
+        if (lane == 0) *st = DecSoftUnitStats{0, 0, 0, 0, 0, 0, 0, 0};
+        return;
+    }
+    const uint32_t in_bytes = u.in_bytes, soft_words = 2u * u.out_bytes;
+    const size_t row_bytes = 8 * ((size_t)a.fic_out + kFeCifBytes);
+    const uint32_t T = 8 * in_bytes + 6;
+
+    // ---- the unit's punctured softs of output frame f.  Soft 8 p + b of a sub-channel lies in the row delayed by
+    // {0,8,4,12,2,10,6,14}[b] + (p & 1) (delay_mask): dword d holds bits 4 (d & 1) ... of byte p = d >> 1
+    const int8_t *row = a.rows + (size_t)f * row_bytes;
+    if (u.owner < 0) {
+        for (uint32_t d = lane; d < soft_words; d += kDecThreads) s_soft[d] = ((const uint32_t *)row)[d];
+    } else {
+        const uint8_t *src = (const uint8_t *)row + 8 * ((size_t)a.fic_out + u.dst_off);
+        for (uint32_t d = lane; d < soft_words; d += kDecThreads) {
+            const uint32_t first = 2u * (d & 1u) + ((d >> 1) & 1u);
+            const uint8_t *at = src + 4 * (size_t)d;
+            s_soft[d] = (uint32_t)at[(first + 0) * row_bytes] | ((uint32_t)at[(first + 8) * row_bytes + 1] << 8) |
+                        ((uint32_t)at[(first + 4) * row_bytes + 2] << 16) | ((uint32_t)at[(first + 12) * row_bytes + 3] << 24);
+        }
+    }
+    __syncthreads();
+
+    // ---- forward pass (dec_decode_kernel's, on signed metrics).  sgn: 1 - 2 e_i per code bit of the branch from the
+    // predecessor whose oldest bit is 0, first code bit in the lowest byte
+    const int8_t *soft = (const int8_t *)s_soft;
+    const uint32_t e0 = ((__popc(lane & 0x6d) & 1u) << 3) | ((__popc(lane & 0x4f) & 1u) << 2) | ((__popc(lane & 0x53) & 1u) << 1) |
+                        (__popc(lane & 0x6d) & 1u);
+    const uint32_t sgn = ((e0 & 8u) ? 0xffu : 1u) | (((e0 & 4u) ? 0xffu : 1u) << 8) | (((e0 & 2u) ? 0xffu : 1u) << 16) |
+                         (((e0 & 1u) ? 0xffu : 1u) << 24);
+    const int from0 = (lane >> 1) * 4, from1 = (32 + (lane >> 1)) * 4;
+    uint32_t metric = lane ? 1u << 30 : 0u;
+    unsigned long long *surv = a.surv + (size_t)f * a.slot[a.n_units] + a.slot[ui];
+    const uint32_t chunks = (T + 63) / 64;
+    for (uint32_t c = 0; c < chunks; ++c) {
+        const uint32_t t = c * 64 + lane;
+        uint32_t pk = 0, tot = 0;
+        if (t < T) {
+            const uint32_t i = t >> 3;
+            uint32_t r = 0;
+            while (r < u.nseg && i >= u.g0[r + 1]) ++r;
+            const uint32_t pattern = u.pat[r], kept = __popc(pattern);
+            const uint32_t at = u.base[r] + (i - u.g0[r]) * kept;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t pb = 31u - (4u * (t & 7u) + j);
+                if ((pattern >> pb) & 1u) {
+                    const int v = soft[at + __popcll((unsigned long long)pattern >> (pb + 1))];
+                    pk |= ((uint32_t)v & 0xffu) << (8 * j);
+                    tot += (uint32_t)abs(v);
+                }
+            }
+        }
+        const int nk = (int)min(64u, T - c * 64);
+        unsigned long long mine = 0;
+        for (int k = 0; k < nk; ++k) {
+            const int r = __builtin_amdgcn_readlane((int)pk, k);
+            const int tt = __builtin_amdgcn_readlane((int)tot, k);
+            const int dot = __builtin_amdgcn_sdot4((int)sgn, r, 0, false);
+            const uint32_t c0 = (uint32_t)(tt + dot) >> 1, c1 = (uint32_t)tt - c0;
+            const uint32_t a0 = (uint32_t)__builtin_amdgcn_ds_bpermute(from0, (int)metric) + c0;
+            const uint32_t a1 = (uint32_t)__builtin_amdgcn_ds_bpermute(from1, (int)metric) + c1;
+            const bool other = a1 < a0;
+            metric = other ? a1 : a0;
+            const unsigned long long word = __ballot(other);
+            if (lane == k) mine = word;
+        }
+        surv[c * 64 + lane] = mine;
+    }
+    const uint32_t final_metric = (uint32_t)__builtin_amdgcn_readlane((int)metric, 0);
+
+    // ---- traceback (dec_decode_kernel's)
+    uint8_t *dec = (uint8_t *)s_dec;
+    uint32_t state = 0;
+    for (uint32_t c = chunks; c-- > 0;) {
+        const unsigned long long mine = surv[c * 64 + lane];
+        const int nk = (int)min(64u, T - c * 64);
+        unsigned long long bits = 0;
+        for (int k = nk - 1; k >= 0; --k) {
+            const unsigned long long word = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mine >> 32), k) << 32) |
+                                            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mine, k);
+            bits |= (unsigned long long)(state & 1u) << k;
+            state = ((uint32_t)((word >> state) & 1u) << 5) | (state >> 1);
+        }
+        const uint32_t at = c * 8 + lane;
+        if (lane < 8 && at < in_bytes) dec[at] = (uint8_t)(__brev((uint32_t)(bits >> (8 * (lane & 7))) & 0xffu) >> 24);
+    }
+    __syncthreads();
+
+    // ---- the decoded bits encoded again, against the softs: one lane per 4-byte group of the mother code (group in_bytes: the tail)
+    uint32_t corrected = 0, contra = 0, soft_sum = 0, erasures = 0;
+    for (uint32_t i = lane; i <= in_bytes; i += kDecThreads) {
+        const uint32_t w = dec_mother_code(i ? dec[i - 1] : 0u, i < in_bytes ? dec[i] : 0u);
+        uint32_t r = 0;
+        while (r < u.nseg && i >= u.g0[r + 1]) ++r;
+        const uint32_t pattern = u.pat[r], kept = __popc(pattern);
+        uint32_t at = u.base[r] + (i - u.g0[r]) * kept;
+        for (int b = 31; b >= 0; --b) {
+            if (!((pattern >> b) & 1u)) continue;
+            const int v = soft[at++];
+            const uint32_t mag = (uint32_t)abs(v);
+            soft_sum += mag;
+            if (v == 0) {
+                ++erasures;
+            } else if ((v > 0) != (bool)((w >> b) & 1u)) {
+                ++corrected;
+                contra += mag;
+            }
+        }
+    }
+
+    // ---- energy dispersal, the payload at its place in the frame, the count against the reference
+    uint8_t *out = a.out + (size_t)f * 6144 + u.in_off;
+    const uint8_t *ref = a.ref ? a.ref + (size_t)f * 6144 + u.in_off : nullptr;
+    uint32_t errors = 0;
+    for (uint32_t i = lane; i < in_bytes; i += kDecThreads) {
+        const uint8_t v = dec[i] ^ a.prbs[i];
+        out[i] = v;
+        if (ref) errors += __popc((uint32_t)(v ^ ref[i]));
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        errors += __shfl_xor(errors, off);
+        corrected += __shfl_xor(corrected, off);
+        contra += __shfl_xor(contra, off);
+        soft_sum += __shfl_xor(soft_sum, off);
+        erasures += __shfl_xor(erasures, off);
+    }
+    if (lane == 0)
+        *st = DecSoftUnitStats{final_metric, contra, soft_sum, corrected, erasures, u.base[u.nseg] + 12u, errors, ref ? 8 * in_bytes : 0u};
+}
+
 }  // namespace
 
 hipError_t launch_dec_rows(const DecArgs &a, hipStream_t s)
@@ -190,6 +378,23 @@ hipError_t launch_dec_decode(const DecArgs &a, hipStream_t s)
     if (a.n_out <= 0 || a.n_units <= 0) return hipSuccess;
     if (a.sym_bytes <= 0 || a.sym_bytes % 64 || a.sym_bytes > kDecMaxSteps) return hipErrorInvalidValue;
     DABGPU_LAUNCH(dec_decode_kernel, dim3((unsigned)a.n_out * (unsigned)a.n_units), dim3(kDecThreads), (size_t)a.sym_bytes + 8, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_dec_soft_rows(const DecSoftArgs &a, hipStream_t s)
+{
+    if (a.n_out <= 0) return hipSuccess;
+    if (a.n_out % a.cifs || a.fic_out % 4) return hipErrorInvalidValue;
+    const size_t total = (size_t)a.n_out * (size_t)(a.fic_out + kFeCifBytes) * 2;
+    DABGPU_LAUNCH(dec_soft_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, total);
+    return hipGetLastError();
+}
+
+hipError_t launch_dec_soft_decode(const DecSoftArgs &a, hipStream_t s)
+{
+    if (a.n_out <= 0 || a.n_units <= 0) return hipSuccess;
+    if (a.lds_bytes <= 0 || a.lds_bytes % 4 || a.lds_bytes > 8 * kFeCifBytes) return hipErrorInvalidValue;
+    DABGPU_LAUNCH(dec_soft_decode_kernel, dim3((unsigned)a.n_out * (unsigned)a.n_units), dim3(kDecThreads), (size_t)a.lds_bytes, s, a);
     return hipGetLastError();
 }
 

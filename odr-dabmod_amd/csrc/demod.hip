@@ -18,13 +18,23 @@ namespace {
 // Carrier position k (bins 1 ... K/2 -> k = bin - 1, bins N - K/2 ... -> k = bin - N + K) is bit n = src_carrier[k] of the
 // block: I half then Q half, K/8 bytes each, MSB first.  The lanes OR their bits into one LDS image of the
 // block; the first K/16 lanes store it as dwords and count the bits that differ from the reference block.
-template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_kernel(DemodArgs a)
+//
+// SOFT (dabgpu_demod_soft*): besides all of the above, one int8 metric per coded bit -- clamp(rint(-Re d q)), clamp(rint(-Im d
+// q)) with q = 64 sqrt(2) / sqrt(P / K), P = the symbol's sum of |d|^2.  P is added in a FIXED order (the lane's six terms, an
+// xor butterfly inside the wave, the waves in wave order through LDS), so the bytes repeat bit for bit and do not depend on
+// the run geometry.  The softs go to an LDS image of the block by byte writes (soft n of the I half, K + n of the Q half: one
+// writer each) and leave as 3 T dwords, three per lane, contiguous across the lanes.  The hard instantiations carry none of it.
+template <int LOGN, bool SOFT> __device__ __forceinline__ void demod_body(const DemodArgs &a)
 {
     typedef Fft<LOGN> F;
     constexpr int N = F::N, T = F::T, K = 3 * N / 4, WORDS = K / 16;
     static_assert(WORDS <= T, "one lane per dword of the block");
+    static_assert(2 * K == 12 * T, "three soft dwords per lane");
+    constexpr int NW = (T + 63) / 64, WL = T < 64 ? T : 64;
     __shared__ cf xbuf[2 * F::LDS_ELEMS];
     __shared__ uint32_t blk[WORDS];
+    __shared__ uint32_t sblk[SOFT ? 3 * T : 1];
+    __shared__ float red_p[SOFT ? NW : 1];
     __shared__ double red_s[T], red_q[T];
     __shared__ float red_m[T];
     __shared__ unsigned red_e[T];
@@ -44,7 +54,7 @@ template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_kernel
     // the lane's six carriers: slot, and where the carrier's two bits go in the LDS image (word, bit inside the word)
     // (slot 0 of lane 0 is the DC bin: its first carrier is bin 3T, slot 3; selected by value, never by a register index)
     constexpr int rr[6] = {0, 1, 2, 5, 6, 7};
-    int iword[6], qword[6];
+    int iword[6], qword[6], nsoft[SOFT ? 6 : 1];
     unsigned shift[6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
@@ -56,6 +66,7 @@ template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_kernel
         qword[c] = qb >> 2;
         // (K/8 is a multiple of four bytes in every mode: the byte's place inside its word is the same in both halves)
         shift[c] = 8u * ((unsigned)ib & 3u) + (7u - ((unsigned)n & 7u));
+        if constexpr (SOFT) nsoft[c] = n;
     }
 
     const size_t first = (size_t)a.g.null_size + (size_t)(a.g.sym_size - N - a.early);      // window of symbol 1
@@ -83,6 +94,7 @@ template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_kernel
     if (t == 0) prev[0] = v[3];
 
     const size_t block_words = (size_t)frame * (size_t)nblocks * WORDS;
+    uint32_t *soft_out = SOFT ? reinterpret_cast<uint32_t *>(a.soft_out) + (size_t)frame * (size_t)nblocks * (3 * T) : nullptr;
     double acc_s = 0., acc_q = 0.;
     float worst = 1.0f;                    // min over the lane's decisions of min(|Re d|, |Im d|)^2 / |d|^2
     unsigned errors = 0u;
@@ -90,11 +102,13 @@ template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_kernel
         load(b + 2, v);
         F::template run<-1, true, cf, false>(v, xbuf, par, tw, t);
         float ps = 0.f, pq = 0.f;
+        float sre[SOFT ? 6 : 1], sim[SOFT ? 6 : 1];
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
             const cf z = (c == 0 && t == 0) ? v[3] : v[rr[c]], p = prev[c];
             const float dre = fmaf(z.x, p.x, z.y * p.y), dim = fmaf(z.y, p.x, -(z.x * p.y));      // z conj(p)
             prev[c] = z;
+            if constexpr (SOFT) { sre[c] = dre; sim[c] = dim; }
             const unsigned I = dre < 0.f ? 1u : 0u, Q = dim < 0.f ? 1u : 0u;
             if (I) atomicOr(&blk[iword[c]], 1u << shift[c]);
             if (Q) atomicOr(&blk[qword[c]], 1u << shift[c]);
@@ -108,7 +122,30 @@ template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_kernel
         }
         acc_s += (double)ps;
         acc_q += (double)pq;
+        if constexpr (SOFT) {
+            // the symbol's power: the butterfly leaves the same sum in every lane of the wave (a + b = b + a exactly)
+            float pw = ps;
+#pragma unroll
+            for (int off = WL / 2; off >= 1; off >>= 1) pw += __shfl_xor(pw, off, WL);
+            if ((t & 63) == 0) red_p[t >> 6] = pw;
+        }
         lds_barrier();
+        if constexpr (SOFT) {
+            float P = red_p[0];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) P += red_p[w];
+            const float q = P > 0.f ? 90.50966799187809f / sqrtf(P / (float)K) : 0.f;
+            int8_t *sb = reinterpret_cast<int8_t *>(sblk);
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+                sb[nsoft[c]] = (int8_t)(int)fminf(fmaxf(rintf(-sre[c] * q), -127.f), 127.f);
+                sb[K + nsoft[c]] = (int8_t)(int)fminf(fmaxf(rintf(-sim[c] * q), -127.f), 127.f);
+            }
+            lds_barrier();
+            uint32_t *dst = soft_out + (size_t)b * (3 * T);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) dst[t + T * j] = sblk[t + T * j];
+        }
         if (t < WORDS) {
             const uint32_t w = blk[t];
             blk[t] = 0u;                   // (the next symbol's ORs come behind the barriers of its transform)
@@ -144,6 +181,9 @@ template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_kernel
     }
 }
 
+template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_kernel(DemodArgs a) { demod_body<LOGN, false>(a); }
+template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_soft_kernel(DemodArgs a) { demod_body<LOGN, true>(a); }
+
 }  // namespace
 
 // (demod_runs: how a frame's data symbols are split into runs -- forced: symbols per run, 0 = by the batch size.  A run costs
@@ -170,6 +210,16 @@ hipError_t launch_demod(const DemodArgs &a, hipStream_t s)
         (a.fmt != 0 && a.fmt != 1) || a.g.K != 3 * a.g.N / 4)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)a.n_frames * (unsigned)a.runs_per_frame);
+    if (a.soft_out) {
+        switch (a.g.logN) {
+        case 8: DABGPU_LAUNCH(demod_soft_kernel<8>, grid, dim3(Fft<8>::T), 0, s, a); break;
+        case 9: DABGPU_LAUNCH(demod_soft_kernel<9>, grid, dim3(Fft<9>::T), 0, s, a); break;
+        case 10: DABGPU_LAUNCH(demod_soft_kernel<10>, grid, dim3(Fft<10>::T), 0, s, a); break;
+        case 11: DABGPU_LAUNCH(demod_soft_kernel<11>, grid, dim3(Fft<11>::T), 0, s, a); break;
+        default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     switch (a.g.logN) {
     case 8: DABGPU_LAUNCH(demod_kernel<8>, grid, dim3(Fft<8>::T), 0, s, a); break;
     case 9: DABGPU_LAUNCH(demod_kernel<9>, grid, dim3(Fft<9>::T), 0, s, a); break;

@@ -47,6 +47,10 @@
 //                        never returns the last fifteen of the file.  After the run: frames compared, FIC and MSC payload
 //                        bit errors, corrected channel bits and coded bits on stderr; exit status 2 on any payload bit error.
 //                        Native-rate complexf / s16 output; not with --state-in (the decoder's history is not in the file).
+//   --soft               with --loopback: soft decisions -- dabgpu_demod_soft (one int8 metric per coded bit) and
+//                        dabgpu_decode_soft in place of the hard pair, the same bookkeeping and exit status.  The summary line
+//                        adds the path metric over the sum of the metrics' magnitudes, and the erasures.  On the modulator's
+//                        own clean output the metric is 0: the option makes the path reachable from the program.
 //   --spectrum FILE      the spectrum monitor behind every GPU call (DabGpuChain::Settings::spectrum): a Welch power spectrum of
 //                        everything written -- any rate, any format -- 2048 bins, Blackman-Harris window.  After the run FILE
 //                        holds one "offset_hz level_db" line per bin in ascending frequency, level relative to the mean over
@@ -105,6 +109,7 @@ namespace {
                          "                        --separate-converter)\n"
                          "       [--loopback]   with --gpu-frontend: demodulate and channel-decode every batch on the device against the ETI\n"
                          "                        frames read; totals on stderr, exit 2 on a payload bit error\n"
+                         "       [--soft]   with --loopback: soft decisions (int8 metrics, soft Viterbi) in place of hard ones\n"
                          "       [--monitor]   decode every frame written on the device; totals on stderr, exit 2 on a bit error\n"
                          "       [--dpd-feedback RXFILE --dpd-out COEFFILE [--dpd-bins N] [--dpd-min-count N]]   fit MemlessPoly from a feedback capture\n"
                          "       [--spectrum FILE [--mask MASKFILE] [--oob-from HZ]]   power spectrum of everything written, per bin into FILE;\n"
@@ -169,7 +174,7 @@ int main(int argc, char **argv)
     size_t batch = 1;
     bool reference_latency = false;
     long contexts = 1;
-    bool gpu_frontend = false, loopback = false;
+    bool gpu_frontend = false, loopback = false, soft = false;
     std::string state_in, state_out;
     std::string spectrum_path, mask_path;
     double oob_from = 970000.0;
@@ -218,6 +223,7 @@ int main(int argc, char **argv)
             else if (a == "--gpu-frontend") gpu_frontend = true;
             else if (a == "--monitor") gs.monitor = true;
             else if (a == "--loopback") loopback = true;
+            else if (a == "--soft") soft = true;
             else if (a == "--spectrum") { spectrum_path = val(); gs.spectrum = true; }
             else if (a == "--mask") mask_path = val();
             else if (a == "--oob-from") oob_from = std::stod(val());
@@ -253,6 +259,11 @@ int main(int argc, char **argv)
                          : gs.outputRate != 2048000 ? "--rate: the receiver takes the native rate"
                          : !state_in.empty() ? "--state-in: the decoder's history is not part of the state file"
                                              : "u8 / s8 output: the receiver takes complexf or s16");
+            return 2;
+        }
+
+        if (soft && !loopback) {
+            std::fprintf(stderr, "dabmod_file: --soft does not go without --loopback: it chooses the decisions of that loop\n");
             return 2;
         }
 
@@ -394,8 +405,12 @@ int main(int argc, char **argv)
         // stream index of the oldest; at most fifteen stay behind a batch), the decoder's position, and the totals
         std::deque<std::vector<uint8_t>> loop_eti;
         uint64_t loop_first = 0, loop_pos = 0;
-        struct { unsigned long long frames = 0, fic_errors = 0, msc_errors = 0, n_bits = 0, corrected = 0, coded_bits = 0; } loop;
+        struct {
+            unsigned long long frames = 0, fic_errors = 0, msc_errors = 0, n_bits = 0, corrected = 0, coded_bits = 0;
+            unsigned long long metric = 0, soft_sum = 0, erasures = 0;      // --soft
+        } loop;
         std::vector<uint8_t> loop_bits, loop_out, loop_ref;
+        std::vector<int8_t> loop_soft;
         int loop_early = -1;
         size_t loop_cifs = 1;
         auto loopback_batch = [&](DabGpuChain *ch, const void *p, size_t bytes) {
@@ -411,16 +426,36 @@ int main(int argc, char **argv)
             loop_bits.resize(n_frames * ch->input_bytes_per_frame());
             loop_out.resize(n * 6144);
             loop_ref.assign(n * 6144, 0);
-            chk(dabgpu_demod(c, p, format == "s16" ? DABGPU_FMT_S16 : 0, n_frames, loop_early, loop_bits.data(), nullptr));
+            if (soft) {
+                loop_soft.resize(8 * loop_bits.size());
+                chk(dabgpu_demod_soft(c, p, format == "s16" ? DABGPU_FMT_S16 : 0, n_frames, loop_early, loop_soft.data(), nullptr, nullptr));
+            } else {
+                chk(dabgpu_demod(c, p, format == "s16" ? DABGPU_FMT_S16 : 0, n_frames, loop_early, loop_bits.data(), nullptr));
+            }
             // output i is frame loop_pos + i - 15 of the stream
             for (size_t i = 0; i < n; ++i)
                 if (loop_pos + i >= 15) std::memcpy(&loop_ref[i * 6144], loop_eti.at(loop_pos + i - 15 - loop_first).data(), 6144);
             size_t ob = 0;
-            chk(dabgpu_decode(c, loop_bits.data(), n_frames, loop_out.data(), loop_out.size(), loop_ref.data(), &ob));
+            if (soft) chk(dabgpu_decode_soft(c, loop_soft.data(), n_frames, loop_out.data(), loop_out.size(), loop_ref.data(), &ob));
+            else chk(dabgpu_decode(c, loop_bits.data(), n_frames, loop_out.data(), loop_out.size(), loop_ref.data(), &ob));
             for (size_t i = 0; i < n; ++i) {
                 dabgpu_decode_stats all{}, fic{};
-                chk(dabgpu_get_decode_stats(c, i, -1, &all));
-                chk(dabgpu_get_decode_stats(c, i, 0, &fic));
+                if (soft) {
+                    dabgpu_decode_soft_stats sa{}, sf{};
+                    chk(dabgpu_get_decode_soft_stats(c, i, -1, &sa));
+                    chk(dabgpu_get_decode_soft_stats(c, i, 0, &sf));
+                    all.valid = sa.valid; all.corrected = sa.corrected; all.coded_bits = sa.coded_bits;
+                    all.bit_errors = sa.bit_errors; all.n_bits = sa.n_bits;
+                    fic.bit_errors = sf.bit_errors;
+                    if (sa.valid) {
+                        loop.metric += sa.metric;
+                        loop.soft_sum += sa.soft_sum;
+                        loop.erasures += sa.erasures;
+                    }
+                } else {
+                    chk(dabgpu_get_decode_stats(c, i, -1, &all));
+                    chk(dabgpu_get_decode_stats(c, i, 0, &fic));
+                }
                 if (!all.valid) continue;
                 ++loop.frames;
                 loop.fic_errors += fic.bit_errors;
@@ -615,6 +650,9 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "dabmod_file: loopback: %llu frames compared, %llu FIC and %llu MSC payload bit errors in %llu bits, "
                                  "%llu corrected channel bits in %llu coded bits\n",
                          loop.frames, loop.fic_errors, loop.msc_errors, loop.n_bits, loop.corrected, loop.coded_bits);
+            if (soft)
+                std::fprintf(stderr, "dabmod_file: loopback: soft decisions, metric %llu / soft_sum %llu, %llu erasures\n", loop.metric,
+                             loop.soft_sum, loop.erasures);
         }
         int mask_violations = 0;
         if (gs.spectrum) {
