@@ -4,6 +4,7 @@
 // Everything lives in an anonymous namespace: each .hip file that includes it gets its own copy.
 #pragma once
 #include "dabgpu_internal.h"
+#include "fft_planes.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -562,6 +563,122 @@ template <int LOGN> struct Fft {
             }
             uedge = csub(csub(e[0], y2), mul_i<S>(csub(y1, y3)));
         }
+    }
+
+    // ---- split-plane exchanges (N = 2048, single transforms, one buffer; fft_planes.h) ----------------------------------------
+    // The same four stages as run<S, false, cf, true> -- the same butterflies on the same twiddle values in the same order, so the
+    // same floats -- with another lane holding each element between the stages: every exchange writes plane[slot][lane], real and
+    // imaginary parts apart, and gathers eight (last stage: four) adjacent dwords of a row.  On the LDS path a wave's exchange is
+    // then 16 ds_write_addtid_b32 (2 cycles each: no address register, one data dword) + 4 ds_read_b128 (4 each) = 48 cycles where
+    // 8 ds_write_b64 (6 each) + 8 ds_read_b64 (2 each) are 64; all of it conflict-free (tools/fft_planes_check.cpp).
+    // The lane of the caller works on first-stage index fftp::in_index(lane) and leaves with x[lane + T m] like run().
+
+    // twiddles of stages 3 and 4 (stage 2 reads the LDS table): the layout of load_twiddles<true>, the lane's indices from the maps
+    static DEV void load_twiddles_planes(const cf *__restrict__ wtab, int t, cf *tw)
+    {
+        static_assert(LOGN != 11 || (NR8 == 3 && RF == 4 && NTW == 20), "8 . 8 . 8 . 4");
+        const int base = fftp::tw3_index(t) * (N / 512);
+#pragma unroll
+        for (int r = 1; r < 8; ++r) tw[7 + r - 1] = wtab[(r * base) & (N - 1)];
+        int n = 14;
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int r = 1; r < RF; ++r) tw[n++] = wtab[(r * (t + T * b)) & (N - 1)];
+    }
+
+    // one exchange's sixteen stores: v[slot] of this lane to row `slot`, column = the lane's index in the workgroup.  m0base: LDS
+    // byte address of the wave's first column in row 0 of the real plane (a scalar).  M0 is set inside the statement -- nothing is
+    // assumed of it before, nothing relies on it after (the compiler keeps nothing there in these kernels: no LDS-direct loads, no
+    // indirect register indexing, no message sends).  One wait state between a scalar write of M0 and an add-TID LDS instruction.
+    static DEV void planes_write(const cf *v, unsigned m0base)
+    {
+        static_assert(fftp::kPitch * 4 == 1040 && fftp::kPlane * 4 == 8320, "the immediates below");
+        asm volatile("s_mov_b32 m0, %16\n\t"
+                     "s_nop 0\n\t"
+                     "ds_write_addtid_b32 %0 offset:0\n\t"
+                     "ds_write_addtid_b32 %1 offset:8320\n\t"
+                     "ds_write_addtid_b32 %2 offset:1040\n\t"
+                     "ds_write_addtid_b32 %3 offset:9360\n\t"
+                     "ds_write_addtid_b32 %4 offset:2080\n\t"
+                     "ds_write_addtid_b32 %5 offset:10400\n\t"
+                     "ds_write_addtid_b32 %6 offset:3120\n\t"
+                     "ds_write_addtid_b32 %7 offset:11440\n\t"
+                     "ds_write_addtid_b32 %8 offset:4160\n\t"
+                     "ds_write_addtid_b32 %9 offset:12480\n\t"
+                     "ds_write_addtid_b32 %10 offset:5200\n\t"
+                     "ds_write_addtid_b32 %11 offset:13520\n\t"
+                     "ds_write_addtid_b32 %12 offset:6240\n\t"
+                     "ds_write_addtid_b32 %13 offset:14560\n\t"
+                     "ds_write_addtid_b32 %14 offset:7280\n\t"
+                     "ds_write_addtid_b32 %15 offset:15600"
+                     :: "v"(v[0].x), "v"(v[0].y), "v"(v[1].x), "v"(v[1].y), "v"(v[2].x), "v"(v[2].y), "v"(v[3].x), "v"(v[3].y),
+                        "v"(v[4].x), "v"(v[4].y), "v"(v[5].x), "v"(v[5].y), "v"(v[6].x), "v"(v[6].y), "v"(v[7].x), "v"(v[7].y),
+                        "s"(m0base)
+                     : "memory");
+    }
+    // eight adjacent columns of one row into v[0 .. 7]: two 16-byte reads per plane
+    static DEV void planes_read8(cf *v, const float *re)
+    {
+        const float *im = re + fftp::kPlane;
+        const float4 a0 = *reinterpret_cast<const float4 *>(re), a1 = *reinterpret_cast<const float4 *>(re + 4);
+        const float4 b0 = *reinterpret_cast<const float4 *>(im), b1 = *reinterpret_cast<const float4 *>(im + 4);
+        v[0] = mk(a0.x, b0.x); v[1] = mk(a0.y, b0.y); v[2] = mk(a0.z, b0.z); v[3] = mk(a0.w, b0.w);
+        v[4] = mk(a1.x, b1.x); v[5] = mk(a1.y, b1.y); v[6] = mk(a1.z, b1.z); v[7] = mk(a1.w, b1.w);
+    }
+    template <int S>
+    static DEV void run_planes(cf *v, cf *lds, const cf *tw, int t, const cf *tw8, PhaseTimer *pt = nullptr)
+    {
+        static_assert(LOGN == 11 && N == fftp::kN && T == fftp::kT, "the maps are those of the 2048-point transform");
+#define DABGPU_STAMP(PH) do { if (pt) pt->stamp(PH); } while (0)
+        const float *re = reinterpret_cast<const float *>(lds);
+        const unsigned m0base = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(uintptr_t)lds + 4u * ((unsigned)t & ~63u)));
+        int n = 7;
+        cf w[7];
+#pragma unroll
+        for (int r = 0; r < 7; ++r) w[r] = twid<S>(tw8[r * 8 + fftp::tw2_index(t)]);     // (ahead of the exchange, as in run)
+        dft8<S>(v);
+        DABGPU_STAMP(PH_BUTTERFLY);
+        planes_write(v, m0base);
+        xbarrier();
+        planes_read8(v, re + fftp::read1(t));
+        xbarrier();
+        DABGPU_STAMP(PH_EXCHANGE);
+        twiddle_dft8<S>(v, w);
+        DABGPU_STAMP(PH_BUTTERFLY);
+        planes_write(v, m0base);
+        xbarrier();
+        planes_read8(v, re + fftp::read2(t));
+        xbarrier();
+        DABGPU_STAMP(PH_EXCHANGE);
+        stage_twiddles<S>(tw, n, w);
+        twiddle_dft8<S>(v, w);
+        DABGPU_STAMP(PH_BUTTERFLY);
+        planes_write(v, m0base);
+        xbarrier();
+        {
+            // inputs c = 0 .. 3 of butterfly beta sit in v[beta + 2 c]
+            const float *r0 = re + fftp::read3(t), *r1 = r0 + fftp::kRead3Second;
+            const float4 a0 = *reinterpret_cast<const float4 *>(r0), b0 = *reinterpret_cast<const float4 *>(r0 + fftp::kPlane);
+            const float4 a1 = *reinterpret_cast<const float4 *>(r1), b1 = *reinterpret_cast<const float4 *>(r1 + fftp::kPlane);
+            v[0] = mk(a0.x, b0.x); v[2] = mk(a0.y, b0.y); v[4] = mk(a0.z, b0.z); v[6] = mk(a0.w, b0.w);
+            v[1] = mk(a1.x, b1.x); v[3] = mk(a1.y, b1.y); v[5] = mk(a1.z, b1.z); v[7] = mk(a1.w, b1.w);
+        }
+        xbarrier();
+        DABGPU_STAMP(PH_EXCHANGE);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const cf w1 = twid<S>(tw[n]), w2 = twid<S>(tw[n + 1]), w3 = twid<S>(tw[n + 2]);
+            n += 3;
+            // (products folded into the first layer's sums, as in run)
+            const cf x0 = v[b], x1 = cmul(v[b + 2], w1);
+            const cf s0 = cfma(x0, v[b + 4], w2), s2 = cfma(x1, v[b + 6], w3);
+            const cf s1 = twice_minus(x0, s0), d3 = twice_minus(x1, s2);
+            v[b] = cadd(s0, s2); v[b + 4] = csub(s0, s2);
+            v[b + 2] = caddi<S>(s1, d3); v[b + 6] = csubi<S>(s1, d3);
+        }
+        DABGPU_STAMP(PH_BUTTERFLY);
+#undef DABGPU_STAMP
     }
 
 };

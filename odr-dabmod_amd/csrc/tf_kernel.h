@@ -145,6 +145,11 @@ void tf_kernel(const TfArgs a)
     const bool lane_on = (HALVES || T >= 64) ? true : t < T;  // only N=256 (T=32) without HALVES runs with idle lanes (the block is max(T, 64) lanes)
     const unsigned long long on_mask = (HALVES || T >= 64) ? ~0ull : ((1ull << (T & 63)) - 1ull);   // the same as a wave mask
     const int tt = lane_on ? t : 0;
+    // PLANES (tf_layout.h): the transform's exchanges run through split planes and the lane works on another first-stage index --
+    // ti below, for everything on the INPUT side (carriers, filter response, bit positions, differential state, the partner of the
+    // gain statistic); behind the transform lane t holds samples t + T m whichever exchange it took.  Otherwise ti == tt.
+    constexpr bool PLANES = VAR.planes;
+    const int ti = PLANES ? fftp::in_index(tt) : tt;
     auto hoff = [&](int n) __attribute__((always_inline)) -> int { return HALVES ? half * n : 0; };   // the frame's copy of a buffer
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -156,7 +161,7 @@ void tf_kernel(const TfArgs a)
     // occupies the SIMD twice as long), 8-byte exchanges, and registers for a fourth wave per SIMD
     // (the default filter length only: the run-time tap count's boundary loop does not fit the 128 registers)
     constexpr bool CFR_SEQ = VAR.cfr_seq;
-    constexpr int kXElems = VAR.dual ? 2 * F::LDS_ELEMS : (DBUF ? 2 : 1) * F::LDS_ELEMS;
+    constexpr int kXElems = PLANES ? fftp::kElems : VAR.dual ? 2 * F::LDS_ELEMS : (DBUF ? 2 : 1) * F::LDS_ELEMS;
     double *red = reinterpret_cast<double *>(fbuf + NH * kXElems);  // 16 doubles
     fbuf += hoff(kXElems);
     // FIR boundary samples: two buffers [tail of symbol s (C) | head of symbol s+1 (C)], contiguous so
@@ -280,11 +285,12 @@ void tf_kernel(const TfArgs a)
 
     // ---- per-lane constants ------------------------------------------------
     cf tw[F::NTW > 0 ? F::NTW : 1];
-    F::template load_twiddles<true>(a.t.twiddle, tt, tw);
+    if constexpr (PLANES) F::load_twiddles_planes(a.t.twiddle, tt, tw);
+    else F::template load_twiddles<true>(a.t.twiddle, tt, tw);
 
     // the lane's 6 active first-stage inputs: r = {0|3,1,2,5,6,7}; bin = t + T*r
     // interleaved position k: bins 1..K/2 -> k = bin-1 ; bins N-K/2.. -> k = bin-N+K
-    const int r0 = (tt == 0) ? 3 : 0;
+    const int r0 = (ti == 0) ? 3 : 0;
     int kpos[6];
     cf hk[6];
     cf hk8[CFR && FIR ? 8 : 1];      // CFR: the corrected spectrum is dense, all eight bins of the lane are filtered
@@ -292,7 +298,7 @@ void tf_kernel(const TfArgs a)
         const int rr[6] = {r0, 1, 2, 5, 6, 7};
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
-            const int bin = tt + T * rr[c];
+            const int bin = ti + T * rr[c];
             kpos[c] = (bin <= K / 2) ? bin - 1 : bin - N + K;
             if (FIR) hk[c] = a.t.fir_h[bin];
         }
@@ -311,7 +317,7 @@ void tf_kernel(const TfArgs a)
     // in the lane that holds them -- carriers (5, 4, 3) at bits (12, 16, 20), lane 0 (which pairs with itself and has
     // bin 3T in slot 0): carriers (3, 5, 4).
     unsigned P = 0u;
-    unsigned fpos[6] = {0u, 4u, 8u, tt == 0 ? 12u : 20u, tt == 0 ? 20u : 16u, tt == 0 ? 16u : 12u};
+    unsigned fpos[6] = {0u, 4u, 8u, ti == 0 ? 12u : 20u, ti == 0 ? 20u : 16u, ti == 0 ? 16u : 12u};
     const uint8_t *fbits = nullptr;
     if (FROM_BITS) {
         fbits = a.bits + (size_t)frame * (size_t)(G::nb_symbols - 1) * (size_t)(K / 4);
@@ -1217,7 +1223,8 @@ void tf_kernel(const TfArgs a)
                 // carriers lives in lane T - t (lane 0 pairs with itself): exchange one packed word.
                 phw[tt] = P >> 12;                        // fields (-k0, -k1, -k2) of this lane
                 lds_barrier();
-                const unsigned o = phw[(T - tt) & (T - 1)];
+                // (PLANES: carrier -k lives in the lane whose first-stage index is T - ti; that read is conflict-free as well)
+                const unsigned o = phw[PLANES ? fftp::in_partner(tt) : ((T - tt) & (T - 1))];
                 // Every carrier of a symbol has the same phase parity (each block adds an odd number of eighths
                 // to all of them), so a pair's phase sum is an even number of eighths and its cosine is +1, 0 or -1:
                 // S = #(sum = 0 mod 4 quarter turns) - #(sum = 2 mod 4).  Both phases of a pair carry the symbol's
@@ -1293,7 +1300,8 @@ void tf_kernel(const TfArgs a)
             }
             place(val, v);
             pt.stamp(PH_INPUT);
-            F::template run<+1, DBUF, cf, true>(v, fbuf, fpar, tw, tt, tw8_l, &pt);
+            if constexpr (PLANES) F::template run_planes<+1>(v, fbuf, tw, tt, tw8_l, &pt);
+            else F::template run<+1, DBUF, cf, true>(v, fbuf, fpar, tw, tt, tw8_l, &pt);
             if constexpr (CFR_LEAN) {
                 cfr_symbol(v, z, nullptr, s, !lookahead);
             } else if (CFR) {

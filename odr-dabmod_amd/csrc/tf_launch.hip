@@ -26,7 +26,9 @@ size_t tf_lds_bytes(int logN, unsigned flags, int nt, int overlap, int ntaps)
                                    flags & TF_GVAR, tf_ofmt(flags), flags & TF_WINDOW, eq);
     const bool cfr_lean = v.cfr_lean, dbuf = v.dbuf, dual = v.dual;
     const size_t nh = v.halves ? 2 : 1;          // (two frames per workgroup: every per-frame buffer twice)
-    size_t b = dual ? (N + N / 8) * 2 * sizeof(float2) : (dbuf ? 2 : 1) * (N + N / 8) * sizeof(float2);
+    size_t b = v.planes ? (size_t)fftp::kBytes
+               : dual   ? (N + N / 8) * 2 * sizeof(float2)
+                        : (dbuf ? 2 : 1) * (N + N / 8) * sizeof(float2);
     b += 16 * sizeof(double);
     if (flags & TF_GAIN) b += ((flags & TF_FROM_BITS) ? 1 : 6) * (N / 8) * sizeof(uint32_t);   // phase words / paired bins
     const bool wf = (flags & TF_WINDOW) && (flags & TF_FIR) && !eq;

@@ -2,6 +2,7 @@
 // (tf_launch.hip: tf_lds_bytes) has to agree with.
 #pragma once
 #include "dabgpu_internal.h"
+#include "fft_planes.h"
 
 namespace dabgpu {
 // LDS of the equalised-boundary variants (see tf_kernel), in complex slots: two windows of the previous filtered symbol and
@@ -30,6 +31,9 @@ struct TfVariant {
                         // from a register window (four outputs x twelve taps per lane); its sample buffers carry four slots of padding
     bool pair;          // Mode I equalised-boundary kernels (round 6): the coded bits are prefetched two symbols' blocks at a time -- four
                         // block slots in LDS instead of two -- so that the wait behind the previous iteration's stores comes every other symbol
+    bool planes;        // Mode I equalised-boundary kernels with complexf output, no windowing (the headline chain, with and without
+                        // TII): the transform's exchanges go through split re / im planes (fft_planes.h, Fft::run_planes) -- 16.6 kB
+                        // of exchange buffer instead of 18.4, the lane works on first-stage index fftp::in_index(lane)
     int waves_per_simd; // asked of the register allocator (HIP: the second __launch_bounds__ argument)
 };
 constexpr TfVariant tf_variant(int logn, bool from_bits, bool gain, bool guard, bool fir, int nt, bool cfr, bool gvar,
@@ -44,6 +48,7 @@ constexpr TfVariant tf_variant(int logn, bool from_bits, bool gain, bool guard, 
     v.bwin = logn != 11 && fir && nt == 45 && !cfr && !win && !eq;
     v.halves = logn == 8 && from_bits && guard && fir && nt == 45 && !cfr && !gvar && ofmt == 0 && !win && !eq;
     v.pair = eq && logn == 11;
+    v.planes = eq && logn == 11 && ofmt == 0 && !win;
     // EQ: 4 (128 VGPRs, 29 KB of LDS: four workgroups per CU); modes II - IV: 3 (their one- and two-wave workgroups are limited by
     //   the windows' LDS before that, and at 128 registers they spill)
     // CFR: 4 where it is built lean, 3 on the other coded-bits chains with the guard interval that keep one transform live, else 2
