@@ -560,7 +560,7 @@ DABGPU_API int dabgpu_chain_seed_eti_dev(dabgpu_ctx *ctx, const void *d_eti_lead
  * The modulator's output decoded back on the device: per OFDM symbol the forward transform over the window that ends `early`
  * samples before the end of the symbol, differential demodulation against the symbol before, hard QPSK decisions, the
  * frequency interleaver undone -- ETSI EN 300 401 14.5 - 14.7 backwards.  The reference has no receiver; these entries replace
- * nothing of its flowgraph.  No synchronisation and no channel estimate: the input is whole transmission frames as a chain
+ * nothing of its flowgraph.  No synchronisation (since built: dabgpu_sync* below) and no channel estimate: the input is whole transmission frames as a chain
  * call without the Resampler writes them (tf_samples each), complexf (format 0) or DABGPU_FMT_S16; u8 / s8 are not taken.
  * `early` (0 ... sym_size - spacing, the data symbols' cyclic prefix; anything else is DABGPU_E_INVALID) moves the window away
  * from what FIRFilter's look-ahead and the guard window's overlap leave at the end of a symbol: ntaps - 1 for a filtered
@@ -615,11 +615,67 @@ DABGPU_API int dabgpu_set_monitor(dabgpu_ctx *ctx, int enable, int early);
  * 0 (the default) = chosen from the batch size.  Same bits for every value; exists so that a test can walk the run geometry. */
 DABGPU_API int dabgpu_debug_demod_run_symbols(dabgpu_ctx *ctx, int symbols);
 
+/* ---- the synchroniser: frame starts and carrier offset of a capture, frames for the receiver ------------------------------- *
+ * The stage in front of dabgpu_demod*: a native-rate capture that starts at an arbitrary sample and sits a few carrier spacings
+ * off (a feedback or monitoring receiver's, as dabgpu_dpd_* takes them) -> where its transmission frames start, the carrier
+ * frequency offset of each, and the frames rotated back and cut out, so that capture -> sync -> demod(_soft) -> decode(_soft)
+ * runs on the device.  The reference has no receiver; these entries replace nothing of its flowgraph.
+ * Input: n_samples at the native rate, complexf (format 0) or DABGPU_FMT_S16.  With N = spacing, K = carriers, L = nb_symbols,
+ * null = null_size, sym = sym_size, CP = sym - N, tf = tf_samples, B = N / 32, NB = floor(null / B), P[k] the phase reference
+ * symbol on carrier k:
+ *   1. block power     p[b] = sum_{j < B} |x[b B + j]|^2 over the whole blocks of the first tf + null samples
+ *   2. coarse start    S[b] = p[b] + ... + p[b + NB - 1]; b* = the first b in 0 ... tf / B - 1 with the lowest S;
+ *                      coarse_0 = b* B.  Frame k is a candidate when coarse_k = coarse_0 + k tf has coarse_k + tf <= n_samples,
+ *                      at most max_frames (the context's) of them.  null_depth = (S[b*] / NB) / mean(p): 0 for exact-zero nulls
+ *   3. fractional offset, per candidate: gamma = sum_s sum_{i = 2 B}^{CP - 2 B - 1} x[a_s + i] conj(x[a_s + i + N]),
+ *                      a_s = coarse_k + null + s sym, s < L;  eps = -arg(gamma) / 2 pi in [-1/2, 1/2)
+ *   4. integer offset  R = FFT_N(x[w0 + i] e^{-j 2 pi eps i / N}), w0 = coarse_k + null + CP;  for m = -max_shift ... max_shift
+ *                      D(m) = sum_k R[k + 1 + m] conj(R[k + m]) conj(P[k + 1] conj(P[k])) over the pairs k, k + 1 both occupied;
+ *                      shift = the first m with the largest |D|^2 (a timing error only rotates D)
+ *   5. fine start      C[k] = R[k + shift] conj(P[k]) on the occupied carriers, c = N IFFT_N(C), l* = the first index of the
+ *                      largest |c|^2, taken as l* - N from N / 2 on;  start = coarse_k + l*;
+ *                      quality = |c[l*]|^2 / (K sum |C|^2): at most 1, 1 for a clean flat single path
+ *   6. per frame       start, shift, eps, cfo_hz = (shift + eps) 2 048 000 / N, quality, null_depth,
+ *                      valid = (start >= 0 and start + tf <= n_samples)
+ *   7. extraction      out[k][i] = x[start_k + i] e^{j phi_i}, i < tf, complexf;  phi_i = 2 pi ((i step mod 2^64) >> 32) / 2^32,
+ *                      step = rint(-(shift + eps) / N 2^64): an integer phase, nothing accumulates over a frame.  Frames that
+ *                      are not valid are zeros.
+ * The coarse start lands at or after the true start, by less than B: a capture needs a tail behind its last frame for that
+ * frame to be a candidate.  Near eps = +-1/2 consecutive frames may report (12, +0.4998) and (13, -0.4999): ONLY shift + eps
+ * IS MEANINGFUL.  Every sum and search runs in a fixed order: a call on the same samples gives the same bytes, ties go to the
+ * first index.  The extracted frames start on the strongest path; demodulate them with `early` inside the cyclic prefix
+ * (CP / 2 leaves room on either side).
+ * dabgpu_sync_dev: device pointer (aligned to a sample), asynchronous on `stream` (NULL: the context's own stream, behind every
+ *   lane); no host round trip between its kernels.  dabgpu_sync: the host-pointer form.  dabgpu_get_sync_result: waits for the
+ *   most recent of them, as dabgpu_get_demod_stats does; *n_frames = the candidates, min(*n_frames, cap) records to `out`.
+ * dabgpu_sync_extract_dev / dabgpu_sync_extract: step 7 with the records of the most recent dabgpu_sync* call on the context,
+ *   straight from device memory (same stream, or ordered behind it by the caller).  The output holds
+ *   min(max_frames, n_samples / tf) frames of tf complexf samples, eight-byte aligned; those beyond the candidates are zeros too.
+ * Refused with DABGPU_E_INVALID and a message before anything is queued: a format other than 0 / DABGPU_FMT_S16, a null or
+ *   misaligned pointer, n_samples < 2 tf + null (no whole frame is guaranteed in less), max_shift outside 0 ... 31 (31 =
+ *   (N - K) / 2 - 1 in Mode III), an extraction without a dabgpu_sync* call on the same n_samples before it.
+ * dabgpu_sync_check: host only, no context, no device: the shape refusals for a mode (1..4; 0 = IV), message via
+ *   dabgpu_last_error(NULL).
+ * Out of scope: sampling-clock offset, fractional-sample timing, multipath beyond the strongest path, tracking across calls,
+ *   resampled (non-native-rate) captures, u8 / s8. */
+typedef struct dabgpu_sync_frame {
+    int64_t start;
+    int shift, valid;
+    double eps, cfo_hz, quality, null_depth;
+} dabgpu_sync_frame;
+DABGPU_API int dabgpu_sync_dev(dabgpu_ctx *ctx, const void *d_iq, int format, size_t n_samples, int max_shift, void *stream);
+DABGPU_API int dabgpu_sync(dabgpu_ctx *ctx, const void *iq, int format, size_t n_samples, int max_shift);
+DABGPU_API int dabgpu_get_sync_result(dabgpu_ctx *ctx, size_t *n_frames, dabgpu_sync_frame *out, size_t cap);
+DABGPU_API int dabgpu_sync_extract_dev(dabgpu_ctx *ctx, const void *d_iq, int format, size_t n_samples, void *d_frames_out,
+                                       void *stream);
+DABGPU_API int dabgpu_sync_extract(dabgpu_ctx *ctx, const void *iq, int format, size_t n_samples, void *frames_out);
+DABGPU_API int dabgpu_sync_check(int mode, size_t n_samples, int max_shift);
+
 /* ---- the channel decoder: coded bits -> the ETI payload, per-unit corrected bits and payload bit errors -------------------- *
  * What a DAB receiver runs behind the demodulator, on the device: the time de-interleaver, depuncturing, the K = 7 Viterbi
  * decoder (hard decisions) and the energy dispersal -- the two kernels of the front-end backwards, from the very tables
  * dabgpu_frontend_configure uploads.  The reference has no receiver; these entries replace nothing of its flowgraph.  No
- * synchronisation, no ETI header or FIG reconstruction; soft decisions: dabgpu_decode_soft* below.
+ * synchronisation (since built: dabgpu_sync* above), no ETI header or FIG reconstruction; soft decisions: dabgpu_decode_soft* below.
  * Input: n_tf transmission frames of coded bits in the chain's input layout (what dabgpu_frontend_process writes and
  *   dabgpu_demod returns), at most max_frames per call, four-byte aligned on the device.
  * Output: n = n_tf x (4 | 1 | 1 | 2) images of 6144 bytes.  An image holds the decoded FIC and sub-channel payload at their

@@ -53,6 +53,7 @@ EXPORTS = [
     "dabgpu_dpd_fit_poly", "dabgpu_debug_resampler_run_hops", "dabgpu_debug_resampler_last_launch",
     "dabgpu_decode_check_layout", "dabgpu_decode_reset", "dabgpu_decode_dev", "dabgpu_decode", "dabgpu_get_decode_stats",
     "dabgpu_demod_soft", "dabgpu_demod_soft_dev", "dabgpu_decode_soft", "dabgpu_decode_soft_dev", "dabgpu_get_decode_soft_stats",
+    "dabgpu_sync_dev", "dabgpu_sync", "dabgpu_get_sync_result", "dabgpu_sync_extract_dev", "dabgpu_sync_extract", "dabgpu_sync_check",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -98,6 +99,11 @@ class _CfrStats(C.Structure):
 class _DemodStats(C.Structure):
     _fields_ = [("sum_signal", C.c_double), ("sum_quadrature", C.c_double), ("bit_errors", C.c_uint64),
                 ("n_bits", C.c_uint64), ("min_margin", C.c_double)]
+
+
+class _SyncFrame(C.Structure):
+    _fields_ = [("start", C.c_int64), ("shift", C.c_int), ("valid", C.c_int), ("eps", C.c_double), ("cfo_hz", C.c_double),
+                ("quality", C.c_double), ("null_depth", C.c_double)]
 
 
 class _DecodeSoftStats(C.Structure):
@@ -272,6 +278,12 @@ def load_library():
     lib.dabgpu_demod_check_early.argtypes = [C.c_int, C.c_int]
     lib.dabgpu_set_monitor.argtypes = [vp, C.c_int, C.c_int]
     lib.dabgpu_debug_demod_run_symbols.argtypes = [vp, C.c_int]
+    lib.dabgpu_sync_dev.argtypes = [vp, vp, C.c_int, sz, C.c_int, vp]
+    lib.dabgpu_sync.argtypes = [vp, vp, C.c_int, sz, C.c_int]
+    lib.dabgpu_get_sync_result.argtypes = [vp, szp, C.POINTER(_SyncFrame), sz]
+    lib.dabgpu_sync_extract_dev.argtypes = [vp, vp, C.c_int, sz, vp, vp]
+    lib.dabgpu_sync_extract.argtypes = [vp, vp, C.c_int, sz, vp]
+    lib.dabgpu_sync_check.argtypes = [C.c_int, sz, C.c_int]
     lib.dabgpu_decode_check_layout.argtypes = [C.POINTER(_FeLayout)]
     lib.dabgpu_decode_reset.argtypes = [vp]
     lib.dabgpu_decode_dev.argtypes = [vp, vp, sz, vp, sz, vp, szp, vp]
@@ -318,6 +330,16 @@ def demod_check_early(mode, early):
     data symbols, with the message demod() / set_monitor() give."""
     lib = load_library()
     if lib.dabgpu_demod_check_early(int(mode), int(early)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def sync_check(mode, n_samples, max_shift=31):
+    """Host only (needs the library, no device): raises DabGpuError when sync() would refuse a capture of n_samples in this mode
+    or this max_shift, with the message it gives."""
+    lib = load_library()
+    if int(n_samples) < 0:
+        raise DabGpuError("sync: n_samples must not be negative")
+    if lib.dabgpu_sync_check(int(mode), int(n_samples), int(max_shift)) != 0:
         raise DabGpuError(lib.dabgpu_last_error(None).decode())
 
 
@@ -487,6 +509,7 @@ class Modulator:
         self._lib.dabgpu_get_geometry(self._h, C.byref(g))
         self.geometry = {n: getattr(g, n) for n, _ in _Geometry._fields_}
         self.device = device
+        self.max_frames = int(max_frames)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1045,6 +1068,81 @@ class Modulator:
     def set_demod_run_symbols(self, symbols=0):
         """Diagnostic: data symbols per workgroup of the receiver's kernel (0: chosen from the batch size)."""
         self._chk(self._lib.dabgpu_debug_demod_run_symbols(self._h, int(symbols)))
+
+    # ---- the synchroniser: frame starts and carrier offset of a capture (include/dabgpu.h, "the synchroniser") ----
+    def _sync_host(self, iq):
+        iq = np.ascontiguousarray(iq)
+        if iq.dtype == np.complex64:
+            return iq.reshape(-1), 0, iq.size
+        if iq.dtype == np.int16 and iq.size % 2 == 0:
+            return iq.reshape(-1), FORMATS["s16"][0], iq.size // 2
+        raise DabGpuError("sync: input format is complex64 or int16 (interleaved re, im)")
+
+    @staticmethod
+    def _sync_tensor(d_iq):
+        import torch
+        if d_iq.dtype == torch.complex64:
+            return 0, d_iq.numel()
+        if d_iq.dtype == torch.int16 and d_iq.numel() % 2 == 0:
+            return FORMATS["s16"][0], d_iq.numel() // 2
+        if d_iq.dtype in (torch.uint8, torch.int8):
+            return FORMATS["u8" if d_iq.dtype == torch.uint8 else "s8"][0], d_iq.numel() // 2      # (the library refuses them)
+        raise DabGpuError("sync: input format is complex64 or int16 (interleaved re, im)")
+
+    def sync_slots(self, n_samples):
+        """Frames an extraction of an n_samples capture writes: min(max_frames, n_samples // tf_samples)."""
+        return min(self.max_frames, int(n_samples) // self.geometry["tf_samples"])
+
+    def sync(self, iq, max_shift=31):
+        """Host path: a native-rate capture (complex64, or int16 interleaved re, im) -> sync_result()."""
+        iq, fmt, n = self._sync_host(iq)
+        self._chk(self._lib.dabgpu_sync(self._h, iq.ctypes.data, fmt, n, int(max_shift)))
+        return self.sync_result()
+
+    def sync_dev(self, d_iq, max_shift=31, stream=None):
+        """Device path on a torch tensor (complex64, or int16 pairs), asynchronous on the stream as chain_dev; the records
+        are sync_result(), the frames sync_extract_dev()."""
+        fmt, n = self._sync_tensor(d_iq)
+        s = self._stream_handle(d_iq, stream)
+        self._chk(self._lib.dabgpu_sync_dev(self._h, d_iq.data_ptr(), fmt, n, int(max_shift), s))
+        if not s:
+            self.synchronize()
+
+    def sync_result(self):
+        """The candidate frames of the most recent sync() / sync_dev() (waits for it): a list of dicts start, shift, valid, eps,
+        cfo_hz, quality, null_depth.  Near eps = +-1/2 only shift + eps is meaningful."""
+        n = C.c_size_t()
+        cap = max(self.max_frames, 1)
+        recs = (_SyncFrame * cap)()
+        self._chk(self._lib.dabgpu_get_sync_result(self._h, C.byref(n), recs, cap))
+        return [{k: getattr(recs[i], k) for k, _ in _SyncFrame._fields_} for i in range(min(n.value, cap))]
+
+    def sync_result_bytes(self):
+        """The same records as the bytes the device wrote (n_frames x 48)."""
+        n = C.c_size_t()
+        cap = max(self.max_frames, 1)
+        recs = (_SyncFrame * cap)()
+        self._chk(self._lib.dabgpu_get_sync_result(self._h, C.byref(n), recs, cap))
+        return bytes(recs)[:min(n.value, cap) * C.sizeof(_SyncFrame)]
+
+    def sync_extract(self, iq):
+        """Host path: the capture the most recent sync() was given -> (sync_slots, tf_samples) complex64, every valid frame
+        rotated back by its offset and cut out at its start; frames that are not valid are zeros."""
+        iq, fmt, n = self._sync_host(iq)
+        out = np.empty((self.sync_slots(n), self.geometry["tf_samples"]), np.complex64)
+        self._chk(self._lib.dabgpu_sync_extract(self._h, iq.ctypes.data, fmt, n, out.ctypes.data))
+        return out
+
+    def sync_extract_dev(self, d_iq, d_frames_out, stream=None):
+        """Device path: d_frames_out is complex64, sync_slots(n_samples) x tf_samples."""
+        import torch
+        fmt, n = self._sync_tensor(d_iq)
+        if d_frames_out.dtype != torch.complex64 or d_frames_out.numel() != self.sync_slots(n) * self.geometry["tf_samples"]:
+            raise DabGpuError("sync_extract: the output is complex64, sync_slots(n_samples) x tf_samples")
+        s = self._stream_handle(d_iq, stream)
+        self._chk(self._lib.dabgpu_sync_extract_dev(self._h, d_iq.data_ptr(), fmt, n, d_frames_out.data_ptr(), s))
+        if not s:
+            self.synchronize()
 
     # ---- the channel decoder: coded bits -> the ETI payload (include/dabgpu.h, "the channel decoder") ----
     def decode(self, bits, ref_eti=None):

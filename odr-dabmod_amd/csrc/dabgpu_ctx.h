@@ -15,6 +15,8 @@
 //                     pair; alignment solve, delay taps and polynomial fit (host only)
 //   api_decode.hip    the channel decoder (decode.hip): coded bits -> ETI payload, its history of fifteen received rows, the
 //                     per-unit figures; the layout check (host only)
+//   api_sync.hip      the synchroniser (sync.hip): frame starts and carrier offset of a capture, the frames extracted for the
+//                     receiver; the shape check (host only)
 //   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
 //                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
 #pragma once
@@ -225,6 +227,12 @@ struct dabgpu_ctx {
     bool decs_zero_pending = true;
     size_t decs_frames = 0, decs_first_valid = 0;
     hipStream_t decs_stream = nullptr;
+    // The synchroniser (api_sync.hip, sync.hip): head and frame records of the most recent dabgpu_sync* call (what
+    // dabgpu_sync_extract* reads, straight from device memory), the block powers, the stream they are complete on, what the
+    // call was given (0 samples: none yet) and the host-pointer entries' staging.
+    dabgpu_api::DevBuf d_sync, d_sync_power, d_sync_in, d_sync_out;
+    size_t sync_n = 0, sync_slots = 0;
+    hipStream_t sync_stream = nullptr;
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII
     bool tables_valid = false;            // apply_settings has uploaded every table group once
     unsigned long long tii_seg_epoch = 0; // 1 while the cached segment matches the settings (apply_settings zeroes it), and its stage mask

@@ -177,6 +177,35 @@ struct DemodArgs {
 };
 void demod_runs(const Geometry &g, size_t n_frames, int forced, int *runs_per_frame, int *syms_per_run);
 hipError_t launch_demod(const DemodArgs &a, hipStream_t s);
+// sync.hip: the synchroniser (dabgpu_sync*): frame starts and carrier offset of a native-rate capture, and the frames extracted
+constexpr int kSyncMaxShift = 31;         // integer carrier offsets searched: -max_shift ... max_shift, at most this
+struct SyncHead {                         // written by the coarse kernel
+    long long coarse0;                    // b* B: the coarse start of candidate 0
+    int count;                            // candidate frames: coarse0 + (k + 1) tf <= n, at most `slots`
+    int reserved;
+    double null_depth;
+    double reserved2;
+};
+struct SyncFrame {                        // one per candidate, the layout of dabgpu_sync_frame; zeroed before the launch
+    long long start;
+    int shift, valid;
+    double eps, cfo_hz, quality, null_depth;
+};
+struct SyncArgs {
+    Geometry g;
+    Tables t;                 // twiddle, phase_q
+    const void *iq;           // n samples: cf32 (fmt 0) or s16 pairs (fmt 1 = DABGPU_FMT_S16)
+    int fmt;
+    long long n;
+    int max_shift;
+    int slots;                // frame records (and frames of an extraction): min(max_frames, n / tf)
+    float *power;             // nblk block powers (scratch)
+    int nblk;                 // whole blocks of N / 32 samples in the first min(n, tf + null) samples
+    SyncHead *head;
+    SyncFrame *frames;
+};
+hipError_t launch_sync(const SyncArgs &a, hipStream_t s);
+hipError_t launch_sync_extract(const SyncArgs &a, float2 *out, hipStream_t s);
 // spectrum.hip: Welch periodogram of one sample buffer (dabgpu_spectrum*, the spectrum monitor): segments of SPECTRUM_NFFT
 // samples at a hop of half that, in every transmission mode
 enum { SPECTRUM_NFFT = 2048, kSpectrumMaxRuns = 1 << 16 };

@@ -1,0 +1,347 @@
+// sync.hip -- the synchroniser in front of the receiver: a native-rate capture that starts at an arbitrary sample and sits a few
+// carrier spacings off -> where its transmission frames start, their carrier frequency offset, and the frames themselves as
+// dabgpu_demod* takes them.  Written from ETSI EN 300 401 (14.3: null symbol and phase reference symbol) and the textbook
+// estimators: energy of the null symbol, cyclic-prefix correlation (fractional offset), differential correlation against the
+// phase reference symbol (integer offset), its channel impulse response (fine start).  The reference has no receiver.
+// Four kernels, no host round trip between them: block power, coarse start (one workgroup), one workgroup per candidate frame
+// for everything else, and the extraction.  Every sum and every search runs in a FIXED order -- the lane's own terms, an xor
+// butterfly inside the wave, the waves in wave order through LDS (demod_soft_kernel's rule) -- so a result repeats bit for bit
+// and ties go to the first index.  No floating-point atomics.
+#include "device_common.h"
+
+namespace dabgpu {
+namespace {
+
+DEV cf ld_iq(const void *iq, int fmt, long long i)
+{
+    if (fmt == 0) return reinterpret_cast<const float2 *>(iq)[i];
+    const uint32_t w = reinterpret_cast<const uint32_t *>(iq)[i];       // s16 pair: re in the low half
+    return mk((float)(short)(w & 0xffffu), (float)(short)(w >> 16));
+}
+
+// exp(2 pi j f), f = the upper 32 bits of a 64-bit turn accumulator / 2^32.  Range reduction in integers: the nearest quarter
+// turn comes off exactly, what is left (|.| <= 1/8 turn, 30 bits) is rounded to fp32 once (2^-27 half turns: 2.4e-8 rad).
+DEV cf turn_phase(unsigned long long acc)
+{
+    const uint32_t hi = (uint32_t)(acc >> 32);
+    const uint32_t q = (hi + 0x20000000u) >> 30;
+    const int r = (int)(hi - (q << 30));
+    float s, c;
+    sincospif((float)r * 4.656612873077393e-10f, &s, &c);               // r 2^-31 half turns
+    switch (q & 3u) {
+    case 0: return mk(c, s);
+    case 1: return mk(-s, c);
+    case 2: return mk(-c, -s);
+    default: return mk(s, -c);
+    }
+}
+// rint(turns per sample 2^64) as the accumulator's step (|turns| < 1/4: fits the signed conversion)
+DEV unsigned long long turn_step(double turns) { return (unsigned long long)(long long)rint(turns * 18446744073709551616.0); }
+
+DEV cf mul_quarter(cf z, unsigned q)                                    // z i^q
+{
+    switch (q & 3u) {
+    case 0: return z;
+    case 1: return mk(-z.y, z.x);
+    case 2: return mk(-z.x, -z.y);
+    default: return mk(z.y, -z.x);
+    }
+}
+
+// ---- workgroup reductions in a fixed order: butterfly over the WL lanes of a wave, then the NW waves in wave order ----------
+template <int WL, typename V> DEV V wave_sum_w(V x)
+{
+#pragma unroll
+    for (int off = WL / 2; off >= 1; off >>= 1) x += __shfl_xor(x, off, WL);
+    return x;
+}
+template <int NW, int WL, typename V> DEV V group_sum(V x, V *red, int t)
+{
+    x = wave_sum_w<WL>(x);
+    if ((t & 63) == 0) red[t >> 6] = x;
+    lds_barrier();
+    V s = red[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) s += red[w];
+    lds_barrier();
+    return s;
+}
+// the first index of the extreme value: MAX (largest) or the smallest; (v, i) pairs, a lower index wins a tie
+template <bool MAX, typename V> DEV bool better(V v, int i, V v0, int i0)
+{
+    return (MAX ? v > v0 : v < v0) || (v == v0 && i < i0);
+}
+template <bool MAX, int NW, int WL, typename V> DEV void group_arg(V &v, int &i, V *red_v, int *red_i, int t)
+{
+#pragma unroll
+    for (int off = WL / 2; off >= 1; off >>= 1) {
+        const V ov = __shfl_xor(v, off, WL);
+        const int oi = __shfl_xor(i, off, WL);
+        if (better<MAX>(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+    if ((t & 63) == 0) { red_v[t >> 6] = v; red_i[t >> 6] = i; }
+    lds_barrier();
+    v = red_v[0]; i = red_i[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w)
+        if (better<MAX>(red_v[w], red_i[w], v, i)) { v = red_v[w]; i = red_i[w]; }
+    lds_barrier();
+}
+
+// ---- 1. block power: p[b] = sum of |x|^2 over the B samples of block b; one sample per lane, the butterfly over B lanes -----
+template <int B> __global__ __launch_bounds__(256) void sync_power_kernel(SyncArgs a)
+{
+    const long long i = (long long)blockIdx.x * 256 + (long long)threadIdx.x;
+    const bool in = i < (long long)a.nblk * B;                          // (whole groups of B lanes: nblk B is a multiple of B)
+    float e = 0.f;
+    if (in) {
+        const cf x = ld_iq(a.iq, a.fmt, i);
+        e = fmaf(x.x, x.x, x.y * x.y);
+    }
+    e = wave_sum_w<B>(e);
+    if (in && ((int)threadIdx.x & (B - 1)) == 0) a.power[i / B] = e;
+}
+
+// ---- 2. coarse start: S[b] = p[b] + ... + p[b + NB - 1] (added afresh for every b: sums of exact zeros stay zero), the first b
+// with the lowest S among the windows inside the buffer, the candidate count and the null depth.  One workgroup.
+constexpr int kCoarseThreads = 1024;
+__global__ __launch_bounds__(kCoarseThreads) void sync_coarse_kernel(SyncArgs a)
+{
+    constexpr int NW = kCoarseThreads / 64;
+    __shared__ double red_d[NW];
+    __shared__ int red_i[NW];
+    const int t = (int)threadIdx.x;
+    const int B = a.g.N / 32, NB = a.g.null_size / B;
+    const long long tf = (long long)a.g.null_size + (long long)a.g.nb_symbols * a.g.sym_size;
+    const int nwin = min((int)(tf / B), a.nblk - NB + 1);
+
+    double total = 0.;
+    for (int b = t; b < a.nblk; b += kCoarseThreads) total += (double)a.power[b];
+    total = group_sum<NW, 64>(total, red_d, t);
+
+    double best = __builtin_huge_val();
+    int bb = 0x7fffffff;
+    for (int b = t; b < nwin; b += kCoarseThreads) {
+        double s = 0.;
+        for (int j = 0; j < NB; ++j) s += (double)a.power[b + j];
+        if (s < best) { best = s; bb = b; }
+    }
+    group_arg<false, NW, 64>(best, bb, red_d, red_i, t);
+    if (t == 0) {
+        SyncHead h{};
+        if (nwin >= 1) {
+            h.coarse0 = (long long)bb * B;
+            int count = 0;
+            while (count < a.slots && h.coarse0 + (long long)(count + 1) * tf <= a.n) ++count;
+            h.count = count;
+            const double mean = total / (double)a.nblk;
+            h.null_depth = mean > 0. ? best / (double)NB / mean : 0.;
+        }
+        *a.head = h;
+    }
+}
+
+// ---- 3 - 6. one workgroup of N/8 lanes per candidate frame ----------------------------------------------------------------
+// position of carrier k (k = 1 ... K/2, -K/2 ... -1) in Tables::phase_q: the frame kernel's order, positive carriers first
+template <int K> DEV int carrier_pos(int k) { return k > 0 ? k - 1 : k + K; }
+
+template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void sync_frame_kernel(SyncArgs a)
+{
+    typedef Fft<LOGN> F;
+    constexpr int N = F::N, T = F::T, K = 3 * N / 4, B = N / 32;
+    constexpr int NW = (T + 63) / 64, WL = T < 64 ? T : 64;
+    constexpr int MAXM = 2 * kSyncMaxShift + 1;
+    constexpr int PAIRS = K - 2, PER = (PAIRS + T - 1) / T;             // carrier pairs k, k + 1 both occupied; per lane
+    __shared__ cf xbuf[2 * F::LDS_ELEMS];
+    __shared__ cf bins[N];
+    __shared__ cf red_D[MAXM * NW];
+    __shared__ float d2[MAXM];
+    __shared__ double red_d[NW];
+    __shared__ float red_f[NW];
+    __shared__ int red_i[NW];
+
+    const int t = (int)threadIdx.x;
+    const int slot = (int)blockIdx.x;
+    const SyncHead head = *a.head;
+    if (slot >= head.count) return;                                     // (its record stays zero: the API zeroes them all)
+    const int L = a.g.nb_symbols, null = a.g.null_size, sym = a.g.sym_size, CP = sym - N;
+    const long long tf = (long long)null + (long long)L * sym;
+    const long long ck = head.coarse0 + (long long)slot * tf;           // ck + tf <= n: every read below lies inside the frame
+
+    cf tw[F::NTW > 0 ? F::NTW : 1];
+    F::template load_twiddles<false>(a.t.twiddle, t, tw);
+
+    // 3. fractional offset: gamma = sum over the symbols' cyclic prefixes, 2 B samples left out on either side
+    const int W = CP - 4 * B, terms = L * W;
+    double gr = 0., gi = 0.;
+    for (int j = t; j < terms; j += T) {
+        const int s = j / W, i = j - s * W + 2 * B;
+        const long long at = ck + null + (long long)s * sym + i;
+        const cf x = ld_iq(a.iq, a.fmt, at), y = ld_iq(a.iq, a.fmt, at + N);
+        gr += (double)x.x * (double)y.x + (double)x.y * (double)y.y;    // x conj(y)
+        gi += (double)x.y * (double)y.x - (double)x.x * (double)y.y;
+    }
+    gr = group_sum<NW, WL>(gr, red_d, t);
+    gi = group_sum<NW, WL>(gi, red_d, t);
+    double eps = -atan2(gi, gr) * 0.15915494309189535;                 // -arg / 2 pi, in [-1/2, 1/2)
+    if (eps >= 0.5) eps -= 1.0;
+
+    // 4. integer offset: the phase reference symbol's window, derotated by eps, transformed; bins kept in LDS
+    cf v[8];
+    {
+        const unsigned long long step = turn_step(-eps / (double)N);
+        const long long w0 = ck + null + CP;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int i = t + T * m;
+            v[m] = cmul(ld_iq(a.iq, a.fmt, w0 + i), turn_phase((unsigned long long)i * step));
+        }
+    }
+    int par = 0;
+    F::template run<-1, true, cf, false>(v, xbuf, par, tw, t);
+#pragma unroll
+    for (int m = 0; m < 8; ++m) bins[t + T * m] = v[m];
+    // the lane's carrier pairs: first carrier and the quarter turns of conj(P[k + 1] conj(P[k]))
+    int pk[PER];
+    unsigned prot[PER];
+    bool pon[PER];
+#pragma unroll
+    for (int c = 0; c < PER; ++c) {
+        const int p = t + T * c;
+        pon[c] = p < PAIRS;
+        const int k = !pon[c] ? 1 : (p < K / 2 - 1 ? p + 1 : p - (K - 1));     // 1 ... K/2 - 1, then -K/2 ... -2
+        pk[c] = k;
+        prot[c] = ((unsigned)a.t.phase_q[carrier_pos<K>(k)] - (unsigned)a.t.phase_q[carrier_pos<K>(k + 1)]) & 3u;
+    }
+    lds_barrier();
+    const int M = a.max_shift, nm = 2 * M + 1;
+    for (int mi = 0; mi < nm; ++mi) {
+        const int m = mi - M;
+        cf acc = mk(0.f, 0.f);
+#pragma unroll
+        for (int c = 0; c < PER; ++c) {
+            const int b0 = (pk[c] + m) & (N - 1);
+            const cf r0 = bins[b0], r1 = bins[(b0 + 1) & (N - 1)];
+            const cf z = mul_quarter(mk(fmaf(r1.x, r0.x, r1.y * r0.y), fmaf(r1.y, r0.x, -(r1.x * r0.y))), prot[c]);
+            if (pon[c]) acc = cadd(acc, z);
+        }
+        acc.x = wave_sum_w<WL>(acc.x);
+        acc.y = wave_sum_w<WL>(acc.y);
+        if ((t & 63) == 0) red_D[mi * NW + (t >> 6)] = acc;
+    }
+    lds_barrier();
+    for (int mi = t; mi < nm; mi += T) {
+        cf D = red_D[mi * NW];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) D = cadd(D, red_D[mi * NW + w]);
+        d2[mi] = fmaf(D.x, D.x, D.y * D.y);
+    }
+    lds_barrier();
+    int mstar = -M;
+    {
+        float bestd = d2[0];
+        for (int mi = 1; mi < nm; ++mi)
+            if (d2[mi] > bestd) { bestd = d2[mi]; mstar = mi - M; }
+    }
+
+    // 5. fine start: C = bins shifted by m*, times conj(P), on the occupied carriers; c = N IFFT(C); its first largest |c|^2
+    float pc = 0.f;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        const int b = t + T * m;
+        const int k = b <= N / 2 ? b : b - N;
+        const bool occ = k != 0 && k >= -K / 2 && k <= K / 2;
+        const cf r = bins[(b + mstar) & (N - 1)];
+        const unsigned q = a.t.phase_q[carrier_pos<K>(occ ? k : 1)];
+        v[m] = occ ? mul_quarter(r, 0u - q) : mk(0.f, 0.f);
+        if (occ) pc = fmaf(r.x, r.x, fmaf(r.y, r.y, pc));
+    }
+    pc = group_sum<NW, WL>(pc, red_f, t);
+    F::template run<1, true, cf, false>(v, xbuf, par, tw, t);
+    float peak = -1.f;
+    int lstar = 0;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        const float c2 = fmaf(v[m].x, v[m].x, v[m].y * v[m].y);
+        if (c2 > peak) { peak = c2; lstar = t + T * m; }
+    }
+    group_arg<true, NW, WL>(peak, lstar, red_f, red_i, t);
+
+    // 6. the record
+    if (t == 0) {
+        SyncFrame f{};
+        f.start = ck + (lstar < N / 2 ? lstar : lstar - N);
+        f.shift = mstar;
+        f.valid = (f.start >= 0 && f.start + tf <= a.n) ? 1 : 0;
+        f.eps = eps;
+        f.cfo_hz = ((double)mstar + eps) * 2048000.0 / (double)N;
+        f.quality = pc > 0.f ? (double)peak / ((double)K * (double)pc) : 0.;
+        f.null_depth = head.null_depth;
+        a.frames[slot] = f;
+    }
+}
+
+// ---- 7. extraction: out[k][i] = x[start_k + i] e^{j phi_i}, phi from the 64-bit integer step; zeros for what is not valid ----
+template <int FMT> __global__ __launch_bounds__(256) void sync_extract_kernel(SyncArgs a, float2 *out)
+{
+    const long long tf = (long long)a.g.null_size + (long long)a.g.nb_symbols * a.g.sym_size;
+    const long long i = (long long)blockIdx.x * 256 + (long long)threadIdx.x;
+    const int slot = (int)blockIdx.y;
+    if (i >= tf) return;
+    cf y = mk(0.f, 0.f);
+    if (slot < a.head->count) {
+        const SyncFrame f = a.frames[slot];
+        if (f.valid) {                                                  // start >= 0 and start + tf <= n
+            const unsigned long long step = turn_step(-((double)f.shift + f.eps) / (double)a.g.N);
+            y = cmul(ld_iq(a.iq, FMT, f.start + i), turn_phase((unsigned long long)i * step));
+        }
+    }
+    out[(long long)slot * tf + i] = y;
+}
+
+bool sync_args_ok(const SyncArgs &a)
+{
+    const long long tf = (long long)a.g.null_size + (long long)a.g.nb_symbols * a.g.sym_size;
+    const int B = a.g.N / 32;
+    return (a.fmt == 0 || a.fmt == 1) && a.g.K == 3 * a.g.N / 4 && a.g.logN >= 8 && a.g.logN <= 11 && a.iq && a.head &&
+           a.frames && a.slots >= 1 && a.n >= 2 * tf + a.g.null_size && a.max_shift >= 0 && a.max_shift <= kSyncMaxShift &&
+           a.nblk == (int)(std::min<long long>(a.n, tf + a.g.null_size) / B);
+}
+
+}  // namespace
+
+hipError_t launch_sync(const SyncArgs &a, hipStream_t s)
+{
+    if (!sync_args_ok(a) || !a.power) return hipErrorInvalidValue;
+    const int B = a.g.N / 32;
+    const dim3 pgrid((unsigned)(((long long)a.nblk * B + 255) / 256));
+    switch (a.g.logN) {
+    case 8: DABGPU_LAUNCH(sync_power_kernel<8>, pgrid, dim3(256), 0, s, a); break;
+    case 9: DABGPU_LAUNCH(sync_power_kernel<16>, pgrid, dim3(256), 0, s, a); break;
+    case 10: DABGPU_LAUNCH(sync_power_kernel<32>, pgrid, dim3(256), 0, s, a); break;
+    default: DABGPU_LAUNCH(sync_power_kernel<64>, pgrid, dim3(256), 0, s, a); break;
+    }
+    DABGPU_LAUNCH(sync_coarse_kernel, dim3(1), dim3(kCoarseThreads), 0, s, a);
+    const dim3 grid((unsigned)a.slots);
+    switch (a.g.logN) {
+    case 8: DABGPU_LAUNCH(sync_frame_kernel<8>, grid, dim3(Fft<8>::T), 0, s, a); break;
+    case 9: DABGPU_LAUNCH(sync_frame_kernel<9>, grid, dim3(Fft<9>::T), 0, s, a); break;
+    case 10: DABGPU_LAUNCH(sync_frame_kernel<10>, grid, dim3(Fft<10>::T), 0, s, a); break;
+    default: DABGPU_LAUNCH(sync_frame_kernel<11>, grid, dim3(Fft<11>::T), 0, s, a); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_sync_extract(const SyncArgs &a, float2 *out, hipStream_t s)
+{
+    if (!sync_args_ok(a) || !out) return hipErrorInvalidValue;
+    const long long tf = (long long)a.g.null_size + (long long)a.g.nb_symbols * a.g.sym_size;
+    const dim3 grid((unsigned)((tf + 255) / 256), (unsigned)a.slots);
+    if (a.fmt == 0)
+        DABGPU_LAUNCH(sync_extract_kernel<0>, grid, dim3(256), 0, s, a, out);
+    else
+        DABGPU_LAUNCH(sync_extract_kernel<1>, grid, dim3(256), 0, s, a, out);
+    return hipGetLastError();
+}
+
+}  // namespace dabgpu
