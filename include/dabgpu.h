@@ -926,6 +926,77 @@ DABGPU_API int dabgpu_dpd_fit_poly(const dabgpu_dpd_stats *stats, int basis, uin
                                    const float prev_am[5], const float prev_pm[5], double lr_am, double lr_pm, float am[5],
                                    float pm[5], dabgpu_dpd_fit_info *info);
 
+/* ---- the channel: sparse multipath, a Doppler rotation per path, seeded Gaussian noise, on a sample stream ------------------ *
+ * The stage between the modulator's IQ and the receiver (dabgpu_sync*, dabgpu_demod*): what a channel emulator next to a
+ * modulator does, on samples that are on the device already.  The reference has no such stage; these entries replace nothing
+ * of its flowgraph.  The output is a function of the input stream, the settings, the seed and the absolute sample position
+ * alone: a stream cut into calls of any lengths gives the bytes of one call.
+ * Let a = position + i be the absolute index of sample i of a call; `position` counts the samples the stream has taken since
+ * the last dabgpu_channel_reset (0 before the first), x[.] is the input stream, zero before the reset:
+ *   y[a] = sum_{p < n_paths} g_p e^{j 2 pi theta_p(a)} x[a - d_p]  +  sigma (n_re(a) + j n_im(a))
+ * Paths: 0 <= n_paths <= DABGPU_CH_MAX_PATHS.  d_p = delay, an integer number of samples, 0 ... DABGPU_CH_MAX_DELAY (2047: 1 ms
+ *   at the native rate, longer than every guard interval -- Mode I's is 504 samples).  g_p = gain_re + j gain_im, fp32; it
+ *   carries the path's initial phase.
+ * Doppler: step_p = rint(doppler_hz / rate_hz 2^64) as a two's-complement 64-bit integer (both float64, the quotient first;
+ *   |doppler_hz| < rate_hz / 2, rate_hz > 0: 2 048 000 for the native rate, the output rate for a resampled chain);
+ *   theta_p(a) = (the upper 32 bits of a step_p mod 2^64) / 2^32: an integer phase, nothing accumulates along the stream.  The
+ *   rotation is e^{j 2 pi theta}: the nearest quarter turn comes off theta exactly in integers, the rest (at most 1/8 turn, 30
+ *   bits) is rounded to fp32 once and goes through sincospif -- dabgpu_sync_extract's rotation.  A carrier offset is the same
+ *   Doppler on every path.
+ * Path sum, in fp32, complex products as (re re - im im, re im + im re) with one fused multiply-add each:
+ *   S0 = the sum of g_p x[a - d_p] over the paths with step_p = 0, in their given order, starting from zero (such a path
+ *        multiplies by g_p alone);
+ *   S1 = the sum of (g_p e^{j 2 pi theta_p(a)}) x[a - d_p] over the paths with step_p != 0, in their given order, starting
+ *        from zero;  y = (S0 + S1) + sigma n, the last step one fused multiply-add per component, left out when sigma = 0.
+ * Noise: Philox4x32-10 (Salmon et al., SC11) with the key (seed mod 2^32, seed >> 32) and the counter (c mod 2^32, c >> 32, 0,
+ *   0), c = a >> 1.  Of its four output words w0 ... w3 an even a takes (wa, wb) = (w0, w1), an odd a (w2, w3).
+ *   u = ((wa >> 9) + 0.5) 2^-23 (exact in fp32, never 0 or 1);  r = sqrtf(-2 logf(u));
+ *   n_re + j n_im = r (cos, sin)(2 pi wb / 2^32), the angle reduced exactly as above.
+ *   The components are unit Gaussians CUT OFF at sqrt(48 ln 2) = 5.77 (u >= 2^-24).  sigma >= 0 is fp32 and absolute, per
+ *   component; with sigma = 0 no generator runs.
+ * Formats: input complexf (format 0) or DABGPU_FMT_S16 (a value becomes its float on load, as in dabgpu_demod*); output
+ *   complexf or DABGPU_FMT_S16 -- dabgpu_format_process's conversion of the complexf result byte for byte (saturating,
+ *   toward zero), without a clip count.  u8 / s8 are refused.
+ * State: the last 2047 input samples, kept as floats, and `position`.  Calls may mix the two input formats.
+ * dabgpu_channel_check: host only, no context, no device: the refusals of the settings, message via dabgpu_last_error(NULL).
+ * dabgpu_set_channel: installs a configuration; history and position stay.  It takes effect at the next call and is ordered
+ *   behind the calls queued before it (the path table travels with each launch).
+ * dabgpu_channel_reset: zero history, the stream continues at `position` (the next call zeroes it, on its own stream).
+ * dabgpu_get_channel_position: waits for the most recent call, as dabgpu_get_sync_result does.
+ * dabgpu_channel_dev: device pointers (aligned to a sample), asynchronous on `stream` (NULL: the context's own stream, behind
+ *   every lane); two launches, no host round trip.  The calls carry stream state: the caller keeps them in order.
+ *   dabgpu_channel: the host-pointer form.
+ * Refused with DABGPU_E_INVALID and a message before anything is queued (position, history and the output untouched): a null
+ *   pointer or one not aligned to a sample, n_samples = 0 (or above 2^40), input and output ranges that overlap, a format
+ *   other than the two, more than 64 paths, a delay above 2047, a gain or sigma that is not finite, sigma < 0, rate_hz <= 0,
+ *   |doppler_hz| >= rate_hz / 2, a call before any dabgpu_set_channel.
+ * Out of scope: fractional-sample delays, sampling-clock offset, correlated (Jakes) fading inside the kernel (the caller
+ *   composes it from paths: a sum of sinusoids per delay), u8 / s8. */
+#define DABGPU_CH_MAX_PATHS 64
+#define DABGPU_CH_MAX_DELAY 2047
+typedef struct dabgpu_channel_path {
+    uint32_t delay;
+    float gain_re, gain_im;
+    double doppler_hz;
+} dabgpu_channel_path;
+typedef struct dabgpu_channel_config {
+    uint32_t n_paths;
+    float sigma;
+    uint64_t seed;
+    double rate_hz;
+    dabgpu_channel_path paths[DABGPU_CH_MAX_PATHS];
+} dabgpu_channel_config;
+DABGPU_API int dabgpu_channel_check(const dabgpu_channel_config *cfg);
+DABGPU_API int dabgpu_set_channel(dabgpu_ctx *ctx, const dabgpu_channel_config *cfg);
+DABGPU_API int dabgpu_channel_reset(dabgpu_ctx *ctx, uint64_t position);
+DABGPU_API int dabgpu_get_channel_position(dabgpu_ctx *ctx, uint64_t *position);
+DABGPU_API int dabgpu_channel_dev(dabgpu_ctx *ctx, const void *d_in, int in_format, size_t n_samples, void *d_out,
+                                  int out_format, void *stream);
+DABGPU_API int dabgpu_channel(dabgpu_ctx *ctx, const void *in, int in_format, size_t n_samples, void *out, int out_format);
+/* Diagnostic: samples per workgroup of the channel's kernel (rounded up to a multiple of 4); 0 (the default) = chosen from the
+ * call size.  Same bytes for every value; exists so that a test can walk the run geometry. */
+DABGPU_API int dabgpu_debug_channel_run_samples(dabgpu_ctx *ctx, int samples);
+
 /* wait for everything queued on the context's own stream(s): every lane */
 DABGPU_API int dabgpu_synchronize(dabgpu_ctx *ctx);
 

@@ -54,6 +54,8 @@ EXPORTS = [
     "dabgpu_decode_check_layout", "dabgpu_decode_reset", "dabgpu_decode_dev", "dabgpu_decode", "dabgpu_get_decode_stats",
     "dabgpu_demod_soft", "dabgpu_demod_soft_dev", "dabgpu_decode_soft", "dabgpu_decode_soft_dev", "dabgpu_get_decode_soft_stats",
     "dabgpu_sync_dev", "dabgpu_sync", "dabgpu_get_sync_result", "dabgpu_sync_extract_dev", "dabgpu_sync_extract", "dabgpu_sync_check",
+    "dabgpu_channel_check", "dabgpu_set_channel", "dabgpu_channel_reset", "dabgpu_get_channel_position", "dabgpu_channel_dev",
+    "dabgpu_channel", "dabgpu_debug_channel_run_samples",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -104,6 +106,18 @@ class _DemodStats(C.Structure):
 class _SyncFrame(C.Structure):
     _fields_ = [("start", C.c_int64), ("shift", C.c_int), ("valid", C.c_int), ("eps", C.c_double), ("cfo_hz", C.c_double),
                 ("quality", C.c_double), ("null_depth", C.c_double)]
+
+
+CH_MAX_PATHS, CH_MAX_DELAY = 64, 2047
+
+
+class _ChannelPath(C.Structure):
+    _fields_ = [("delay", C.c_uint32), ("gain_re", C.c_float), ("gain_im", C.c_float), ("doppler_hz", C.c_double)]
+
+
+class _ChannelConfig(C.Structure):
+    _fields_ = [("n_paths", C.c_uint32), ("sigma", C.c_float), ("seed", C.c_uint64), ("rate_hz", C.c_double),
+                ("paths", _ChannelPath * CH_MAX_PATHS)]
 
 
 class _DecodeSoftStats(C.Structure):
@@ -284,6 +298,13 @@ def load_library():
     lib.dabgpu_sync_extract_dev.argtypes = [vp, vp, C.c_int, sz, vp, vp]
     lib.dabgpu_sync_extract.argtypes = [vp, vp, C.c_int, sz, vp]
     lib.dabgpu_sync_check.argtypes = [C.c_int, sz, C.c_int]
+    lib.dabgpu_channel_check.argtypes = [C.POINTER(_ChannelConfig)]
+    lib.dabgpu_set_channel.argtypes = [vp, C.POINTER(_ChannelConfig)]
+    lib.dabgpu_channel_reset.argtypes = [vp, C.c_uint64]
+    lib.dabgpu_get_channel_position.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.dabgpu_channel_dev.argtypes = [vp, vp, C.c_int, sz, vp, C.c_int, vp]
+    lib.dabgpu_channel.argtypes = [vp, vp, C.c_int, sz, vp, C.c_int]
+    lib.dabgpu_debug_channel_run_samples.argtypes = [vp, C.c_int]
     lib.dabgpu_decode_check_layout.argtypes = [C.POINTER(_FeLayout)]
     lib.dabgpu_decode_reset.argtypes = [vp]
     lib.dabgpu_decode_dev.argtypes = [vp, vp, sz, vp, sz, vp, szp, vp]
@@ -341,6 +362,57 @@ def sync_check(mode, n_samples, max_shift=31):
         raise DabGpuError("sync: n_samples must not be negative")
     if lib.dabgpu_sync_check(int(mode), int(n_samples), int(max_shift)) != 0:
         raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def _channel_config(paths, sigma, seed, rate_hz):
+    """The C structure of a channel configuration; what cannot be written into it is refused here, with the library's words."""
+    paths = list(paths)
+    if len(paths) > CH_MAX_PATHS:
+        raise DabGpuError("channel: at most 64 paths (DABGPU_CH_MAX_PATHS)")
+    cfg = _ChannelConfig()
+    cfg.n_paths, cfg.sigma, cfg.seed, cfg.rate_hz = len(paths), float(sigma), int(seed) & (2 ** 64 - 1), float(rate_hz)
+    for i, (delay, gain, doppler_hz) in enumerate(paths):
+        if not 0 <= int(delay) <= CH_MAX_DELAY:
+            raise DabGpuError("channel: a path's delay is 0 ... 2047 samples (DABGPU_CH_MAX_DELAY)")
+        g = np.complex64(gain)
+        cfg.paths[i].delay, cfg.paths[i].gain_re, cfg.paths[i].gain_im = int(delay), float(g.real), float(g.imag)
+        cfg.paths[i].doppler_hz = float(doppler_hz)
+    return cfg
+
+
+def channel_check(paths, sigma=0.0, seed=0, rate_hz=2048000.0):
+    """Host only (needs the library, no device): raises DabGpuError when set_channel() would refuse these settings, with the
+    message it gives.  paths: (delay, gain, doppler_hz) tuples, the gain complex."""
+    lib = load_library()
+    cfg = _channel_config(paths, sigma, seed, rate_hz)
+    if lib.dabgpu_channel_check(C.byref(cfg)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def channel_sigma(power, cn_db):
+    """The channel's sigma (per component) that puts a signal of mean power `power` at C/N cn_db: sqrt(power / 10^(cn_db / 10) / 2)."""
+    return float(np.sqrt(float(power) / 10.0 ** (float(cn_db) / 10.0) / 2.0))
+
+
+def rayleigh_paths(delays, powers_db, doppler_hz, n_sinusoids, seed):
+    """Host only: a sum-of-sinusoids fading profile as a path list for set_channel().  Per delay, n_sinusoids paths of equal
+    power (together 10^(powers_db / 10)), Doppler doppler_hz cos(alpha_k) with alpha_k = 2 pi (k + u) / n_sinusoids, u and the
+    phases drawn from numpy's RandomState(seed).  A convenience: no statistical claim is made for it."""
+    delays, powers_db = [int(d) for d in delays], [float(p) for p in powers_db]
+    n_sinusoids = int(n_sinusoids)
+    if len(delays) != len(powers_db) or n_sinusoids < 1:
+        raise DabGpuError("rayleigh_paths: one power per delay, at least one sinusoid")
+    if len(delays) * n_sinusoids > CH_MAX_PATHS:
+        raise DabGpuError("channel: at most 64 paths (DABGPU_CH_MAX_PATHS)")
+    rs = np.random.RandomState(int(seed))
+    paths = []
+    for d, p_db in zip(delays, powers_db):
+        amp = np.sqrt(10.0 ** (p_db / 10.0) / n_sinusoids)
+        alpha = 2.0 * np.pi * (np.arange(n_sinusoids) + rs.uniform()) / n_sinusoids
+        phase = rs.uniform(0.0, 2.0 * np.pi, n_sinusoids)
+        for k in range(n_sinusoids):
+            paths.append((d, complex(amp * np.exp(1j * phase[k])), float(doppler_hz) * float(np.cos(alpha[k]))))
+    return paths
 
 
 def decode_check_layout(frame):
@@ -1141,6 +1213,60 @@ class Modulator:
             raise DabGpuError("sync_extract: the output is complex64, sync_slots(n_samples) x tf_samples")
         s = self._stream_handle(d_iq, stream)
         self._chk(self._lib.dabgpu_sync_extract_dev(self._h, d_iq.data_ptr(), fmt, n, d_frames_out.data_ptr(), s))
+        if not s:
+            self.synchronize()
+
+    # ---- the channel emulator: paths, Doppler and seeded noise on a sample stream (include/dabgpu.h, "the channel") ----
+    def set_channel(self, paths, sigma=0.0, seed=0, rate_hz=2048000.0):
+        """Install a channel: paths are (delay, gain, doppler_hz) tuples, the gain complex; sigma is absolute, per component
+        (channel_sigma).  History and position stay; takes effect at the next call."""
+        cfg = _channel_config(paths, sigma, seed, rate_hz)
+        self._chk(self._lib.dabgpu_set_channel(self._h, C.byref(cfg)))
+
+    def channel_reset(self, position=0):
+        """Zero history; the stream continues at `position`."""
+        self._chk(self._lib.dabgpu_channel_reset(self._h, int(position) & (2 ** 64 - 1)))
+
+    def channel_position(self):
+        """Samples the stream has taken since the last reset, plus the reset's position (waits for the most recent call)."""
+        pos = C.c_uint64()
+        self._chk(self._lib.dabgpu_get_channel_position(self._h, C.byref(pos)))
+        return int(pos.value)
+
+    def set_channel_run_samples(self, samples=0):
+        """Diagnostic: samples per workgroup of the channel's kernel (0: chosen from the call size)."""
+        self._chk(self._lib.dabgpu_debug_channel_run_samples(self._h, int(samples)))
+
+    def channel(self, iq, out="complexf"):
+        """Host path: the next samples of the stream (complex64, or int16 interleaved re, im) through the channel ->
+        complex64, or int16 pairs with out="s16"."""
+        iq = np.ascontiguousarray(iq)
+        if iq.dtype == np.complex64:
+            fmt, n = 0, iq.size
+        elif iq.dtype == np.int16 and iq.size % 2 == 0:
+            fmt, n = FORMATS["s16"][0], iq.size // 2
+        else:
+            raise DabGpuError("channel: input format is complex64 or int16 (interleaved re, im)")
+        if out not in ("complexf", "s16"):
+            raise DabGpuError("channel: formats are complexf (0) or DABGPU_FMT_S16")
+        y = np.empty(n, np.complex64) if out == "complexf" else np.empty(2 * n, np.int16)
+        # (an empty array has no buffer worth the name: the library refuses n_samples = 0 on whatever pointer it gets)
+        self._chk(self._lib.dabgpu_channel(self._h, iq.ctypes.data, fmt, n, y.ctypes.data, 0 if out == "complexf" else FORMATS["s16"][0]))
+        return y
+
+    def channel_dev(self, d_in, d_out, stream=None):
+        """Device path on torch tensors (complex64, or int16 pairs; contiguous, the same number of samples), asynchronous on
+        the stream as chain_dev."""
+        import torch
+        for t in (d_in, d_out):
+            if t.dtype not in (torch.complex64, torch.int16) or (t.dtype == torch.int16 and t.numel() % 2):
+                raise DabGpuError("channel: tensors are complex64 or int16 (interleaved re, im)")
+        fi, n = self._sync_tensor(d_in)
+        fo, m = self._sync_tensor(d_out)
+        if n != m or not d_in.is_contiguous() or not d_out.is_contiguous():
+            raise DabGpuError("channel: input and output are contiguous and hold the same number of samples")
+        s = self._stream_handle(d_in, stream)
+        self._chk(self._lib.dabgpu_channel_dev(self._h, d_in.data_ptr(), fi, n, d_out.data_ptr(), fo, s))
         if not s:
             self.synchronize()
 

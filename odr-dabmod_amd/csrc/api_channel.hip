@@ -1,0 +1,162 @@
+// api_channel.hip -- the channel emulator of channel.hip behind the C-ABI: a sparse, time-varying multipath channel with seeded
+// Gaussian noise on a sample stream (dabgpu_set_channel, dabgpu_channel / _dev), the stream's history and position
+// (dabgpu_channel_reset, dabgpu_get_channel_position) and the settings check (dabgpu_channel_check, host only).  The reference
+// has no such stage: nothing here replaces a plugin of its flowgraph, which is why no entry is named *_process.
+#include "dabgpu_ctx.h"
+
+using namespace dabgpu;
+using namespace dabgpu_api;
+
+static_assert(DABGPU_CH_MAX_PATHS == kChMaxPaths && DABGPU_CH_MAX_DELAY == kChMaxDelay, "the header's limits are the kernel's");
+
+namespace {
+constexpr size_t kHistBytes = (size_t)kChMaxDelay * sizeof(float2);
+const char *const kMisaligned = "channel: buffers must be aligned to a sample (eight bytes complexf, four bytes s16)";
+
+// the refusals that depend on the settings alone (dabgpu_channel_check: no context, no device); nullptr = fine
+const char *settings_refusal(const dabgpu_channel_config *cfg)
+{
+    if (!cfg) return "null argument";
+    if (cfg->n_paths > (uint32_t)kChMaxPaths) return "channel: at most 64 paths (DABGPU_CH_MAX_PATHS)";
+    if (!std::isfinite(cfg->sigma)) return "channel: gains and sigma must be finite";
+    if (cfg->sigma < 0.f) return "channel: sigma must not be negative";
+    if (!(cfg->rate_hz > 0.0) || !std::isfinite(cfg->rate_hz)) return "channel: rate_hz must be positive";
+    for (uint32_t p = 0; p < cfg->n_paths; ++p) {
+        const dabgpu_channel_path &q = cfg->paths[p];
+        if (q.delay > (uint32_t)kChMaxDelay) return "channel: a path's delay is 0 ... 2047 samples (DABGPU_CH_MAX_DELAY)";
+        if (!std::isfinite(q.gain_re) || !std::isfinite(q.gain_im)) return "channel: gains and sigma must be finite";
+        if (!(std::fabs(q.doppler_hz) < cfg->rate_hz / 2)) return "channel: |doppler_hz| must be below rate_hz / 2";
+    }
+    return nullptr;
+}
+
+// rint(doppler_hz / rate_hz 2^64) as a two's-complement 64-bit integer (|.| < 2^63: the signed conversion is defined)
+unsigned long long doppler_step(double doppler_hz, double rate_hz)
+{
+    return (unsigned long long)(long long)std::rint(doppler_hz / rate_hz * 18446744073709551616.0);
+}
+
+size_t sample_bytes(int format) { return format ? 4 : sizeof(float2); }
+
+int check_call(dabgpu_ctx *c, const void *in, int in_format, size_t n_samples, const void *out, int out_format)
+{
+    if (!c->ch_configured) return fail(c, DABGPU_E_INVALID, "channel: no configuration (no dabgpu_set_channel call yet)");
+    if ((in_format != 0 && in_format != DABGPU_FMT_S16) || (out_format != 0 && out_format != DABGPU_FMT_S16))
+        return fail(c, DABGPU_E_INVALID, "channel: formats are complexf (0) or DABGPU_FMT_S16");
+    if (!in || !out) return fail(c, DABGPU_E_INVALID, "null argument");
+    if (((uintptr_t)in & (in_format ? 3u : 7u)) || ((uintptr_t)out & (out_format ? 3u : 7u))) return fail(c, DABGPU_E_INVALID, kMisaligned);
+    if (n_samples == 0) return fail(c, DABGPU_E_INVALID, "channel: n_samples must not be 0");
+    if (n_samples > ((size_t)1 << 40)) return fail(c, DABGPU_E_INVALID, "channel: n_samples must not exceed 2^40");
+    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + n_samples * sample_bytes(in_format);
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + n_samples * sample_bytes(out_format);
+    if (i0 < o1 && o0 < i1) return fail(c, DABGPU_E_INVALID, "channel: input and output must not overlap");
+    return DABGPU_OK;
+}
+}  // namespace
+
+extern "C" {
+int dabgpu_channel_check(const dabgpu_channel_config *cfg)
+{
+    if (const char *why = settings_refusal(cfg)) return fail(nullptr, DABGPU_E_INVALID, why);
+    return DABGPU_OK;
+}
+
+int dabgpu_set_channel(dabgpu_ctx *c, const dabgpu_channel_config *cfg)
+{
+    CTXCHK(c);
+    if (const char *why = settings_refusal(cfg)) return fail(c, DABGPU_E_INVALID, why);
+    ChannelArgs a{};
+    a.sigma = cfg->sigma;
+    a.seed_lo = (uint32_t)cfg->seed;
+    a.seed_hi = (uint32_t)(cfg->seed >> 32);
+    // the paths that do not rotate first, either group in the given order (the two sums of the definition)
+    for (int rotating = 0; rotating < 2; ++rotating) {
+        for (uint32_t p = 0; p < cfg->n_paths; ++p) {
+            const dabgpu_channel_path &q = cfg->paths[p];
+            const unsigned long long step = doppler_step(q.doppler_hz, cfg->rate_hz);
+            if ((step != 0) != (rotating != 0)) continue;
+            ChannelPath &d = a.path[a.n_paths++];
+            d.delay = q.delay;
+            d.gr = q.gain_re;
+            d.gi = q.gain_im;
+            d.step = step;
+        }
+        if (!rotating) a.n_static = a.n_paths;
+    }
+    c->ch_args = a;
+    c->ch_configured = true;
+    return DABGPU_OK;
+}
+
+int dabgpu_channel_reset(dabgpu_ctx *c, uint64_t position)
+{
+    CTXCHK(c);
+    c->ch_zero_pending = true;            // (the next call zeroes the history on its own stream, in front of its kernels)
+    c->ch_position = position;
+    return DABGPU_OK;
+}
+
+int dabgpu_get_channel_position(dabgpu_ctx *c, uint64_t *position)
+{
+    CTXCHK(c);
+    if (!position) return fail(c, DABGPU_E_INVALID, "null argument");
+    HIPCHK(c, hipStreamSynchronize(c->ch_stream ? c->ch_stream : c->stream));
+    *position = c->ch_position;
+    return DABGPU_OK;
+}
+
+int dabgpu_debug_channel_run_samples(dabgpu_ctx *c, int samples)
+{
+    CTXCHK(c);
+    if (samples < 0) return fail(c, DABGPU_E_INVALID, "channel: samples per workgroup must not be negative (0 = chosen)");
+    c->ch_run_samples = samples;
+    return DABGPU_OK;
+}
+
+int dabgpu_channel_dev(dabgpu_ctx *c, const void *d_in, int in_format, size_t n_samples, void *d_out, int out_format, void *stream)
+{
+    CTXCHK(c);
+    int rc = check_call(c, d_in, in_format, n_samples, d_out, out_format);
+    if (rc) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;       // (d_in: a chain call's output on any lane)
+    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
+    HIPCHK(c, c->d_ch_hist.reserve(2 * kHistBytes));
+    float2 *cur = (float2 *)((char *)c->d_ch_hist.p + (size_t)c->ch_hist_cur * kHistBytes);
+    float2 *next = (float2 *)((char *)c->d_ch_hist.p + (size_t)(c->ch_hist_cur ^ 1) * kHistBytes);
+    if (c->ch_zero_pending) {
+        HIPCHK(c, hipMemsetAsync(cur, 0, kHistBytes, s));
+        c->ch_zero_pending = false;
+    }
+    ChannelArgs a = c->ch_args;
+    a.in = d_in;
+    a.out = d_out;
+    a.hist = cur;
+    a.n = (long long)n_samples;
+    a.position = c->ch_position;
+    a.in_fmt = in_format ? 1 : 0;
+    a.out_fmt = out_format ? 1 : 0;
+    a.run = channel_run(n_samples, c->ch_run_samples);
+    HIPCHK(c, launch_channel(a, s));
+    HIPCHK(c, launch_channel_history(d_in, a.in_fmt, a.n, cur, next, s));
+    c->ch_hist_cur ^= 1;
+    c->ch_position += n_samples;
+    c->ch_stream = s;
+    return DABGPU_OK;
+}
+
+int dabgpu_channel(dabgpu_ctx *c, const void *in, int in_format, size_t n_samples, void *out, int out_format)
+{
+    CTXCHK(c);
+    int rc = check_call(c, in, in_format, n_samples, out, out_format);
+    if (rc) return rc;
+    if ((rc = dabgpu_synchronize(c))) return rc;
+    const size_t out_bytes = n_samples * sample_bytes(out_format);
+    HostIO io(c);
+    if ((rc = io.in(c->d_ch_in, in, n_samples * sample_bytes(in_format)))) return rc;
+    HIPCHK(c, c->d_ch_out.reserve(std::max<size_t>(out_bytes, 16)));
+    if ((rc = dabgpu_channel_dev(c, c->d_ch_in.p, in_format, n_samples, c->d_ch_out.p, out_format, c->stream))) return rc;
+    return io.out(out, c->d_ch_out.p, out_bytes);
+}
+
+}  // extern "C"

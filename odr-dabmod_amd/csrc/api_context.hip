@@ -551,7 +551,8 @@ void dabgpu_destroy(dabgpu_ctx *c)
                       &c->d_dpd_tw, &c->d_dpd_rows, &c->d_dpd_xacc, &c->d_dpd_sums, &c->d_dpd_edge, &c->d_dpd_tx, &c->d_dpd_rx,
                       &c->d_dec_rows, &c->d_dec_tmp, &c->d_dec_slot, &c->d_dec_surv, &c->d_dec_stats, &c->d_dec_in, &c->d_dec_out,
                       &c->d_dec_ref, &c->d_decs_rows, &c->d_decs_tmp, &c->d_decs_stats, &c->d_decs_in,
-                      &c->d_sync, &c->d_sync_power, &c->d_sync_in, &c->d_sync_out})
+                      &c->d_sync, &c->d_sync_power, &c->d_sync_in, &c->d_sync_out,
+                      &c->d_ch_hist, &c->d_ch_in, &c->d_ch_out})
         b->release();
     for (auto &sl : c->slot) {
         sl.d_eti.release();

@@ -17,6 +17,8 @@
 //                     per-unit figures; the layout check (host only)
 //   api_sync.hip      the synchroniser (sync.hip): frame starts and carrier offset of a capture, the frames extracted for the
 //                     receiver; the shape check (host only)
+//   api_channel.hip   the channel emulator (channel.hip): paths, Doppler and seeded noise on a sample stream, its history and
+//                     position; the settings check (host only)
 //   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
 //                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
 #pragma once
@@ -233,6 +235,18 @@ struct dabgpu_ctx {
     dabgpu_api::DevBuf d_sync, d_sync_power, d_sync_in, d_sync_out;
     size_t sync_n = 0, sync_slots = 0;
     hipStream_t sync_stream = nullptr;
+    // The channel emulator (api_channel.hip, channel.hip).  d_ch_hist: two histories of kChMaxDelay float samples, the stream
+    // state; ch_hist_cur: the one the next call reads (a call writes the other and swaps).  ch_zero_pending: the next call
+    // zeroes it first (after dabgpu_channel_reset, and before the first call).  ch_position: samples the stream has taken.
+    // ch_args: the installed configuration as the kernel takes it (paths that do not rotate first, either group in the
+    // given order); ch_stream: the stream the most recent call went to.
+    dabgpu_api::DevBuf d_ch_hist, d_ch_in, d_ch_out;
+    dabgpu::ChannelArgs ch_args{};
+    bool ch_configured = false, ch_zero_pending = true;
+    int ch_hist_cur = 0;
+    unsigned long long ch_position = 0;
+    hipStream_t ch_stream = nullptr;
+    int ch_run_samples = 0;               // dabgpu_debug_channel_run_samples: samples per workgroup, 0 = by the call size
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII
     bool tables_valid = false;            // apply_settings has uploaded every table group once
     unsigned long long tii_seg_epoch = 0; // 1 while the cached segment matches the settings (apply_settings zeroes it), and its stage mask

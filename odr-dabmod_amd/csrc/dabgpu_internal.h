@@ -206,6 +206,34 @@ struct SyncArgs {
 };
 hipError_t launch_sync(const SyncArgs &a, hipStream_t s);
 hipError_t launch_sync_extract(const SyncArgs &a, float2 *out, hipStream_t s);
+// channel.hip: the channel emulator (dabgpu_channel*): sparse multipath, a Doppler rotation per path, seeded Gaussian noise
+constexpr int kChMaxPaths = 64;           // DABGPU_CH_MAX_PATHS
+constexpr int kChMaxDelay = 2047;         // DABGPU_CH_MAX_DELAY: the history holds this many input samples
+constexpr int kChLane = 4;                // consecutive samples per lane
+constexpr int kChTile = 256 * kChLane;    // samples per workgroup and pass
+struct ChannelPath {
+    uint32_t delay;
+    float gr, gi;
+    uint32_t reserved;
+    unsigned long long step;              // rint(doppler_hz / rate_hz 2^64), two's complement
+};
+struct ChannelArgs {                      // by value in the kernel arguments: a new configuration is ordered behind what is queued
+    const void *in;                       // n samples, in_fmt 0 (complexf) or 1 (s16 pairs)
+    void *out;                            // n samples, out_fmt likewise
+    const float2 *hist;                   // kChMaxDelay samples: hist[kChMaxDelay + j] = sample j < 0 of this call
+    long long n;
+    unsigned long long position;          // absolute index of sample 0
+    int in_fmt, out_fmt;
+    int n_static, n_paths;                // path[0 ... n_static - 1]: step = 0; path[n_static ... n_paths - 1]: step != 0
+    int run;                              // samples per workgroup, a multiple of kChLane
+    float sigma;
+    uint32_t seed_lo, seed_hi;
+    ChannelPath path[kChMaxPaths];
+};
+int channel_run(size_t n, int forced);
+hipError_t launch_channel(const ChannelArgs &a, hipStream_t s);
+// the history behind a call: next[j] = sample n - kChMaxDelay + j of the call, from `in` or (calls shorter than it) from `cur`
+hipError_t launch_channel_history(const void *in, int in_fmt, long long n, const float2 *cur, float2 *next, hipStream_t s);
 // spectrum.hip: Welch periodogram of one sample buffer (dabgpu_spectrum*, the spectrum monitor): segments of SPECTRUM_NFFT
 // samples at a hop of half that, in every transmission mode
 enum { SPECTRUM_NFFT = 2048, kSpectrumMaxRuns = 1 << 16 };

@@ -51,6 +51,15 @@
 //                        dabgpu_decode_soft in place of the hard pair, the same bookkeeping and exit status.  The summary line
 //                        adds the path metric over the sum of the metrics' magnitudes, and the erasures.  On the modulator's
 //                        own clean output the metric is 0: the option makes the path reachable from the program.
+//   --channel-cn DB      with --loopback: the channel emulator (dabgpu_channel) between the batch's IQ and the demodulator: Gaussian
+//                        noise DB below the mean power of the first batch's samples behind the null symbol (computed once),
+//                        from --channel-seed N (default 0); one stream position runs across the batches.  --channel-echo
+//                        DELAY,DB,PHASE (repeatable) adds a path behind the direct one: DELAY samples late, DB relative to it,
+//                        PHASE radians.  Echoes inside the guard interval need no synchroniser -- the window is where --monitor
+//                        puts it -- so a DELAY above the cyclic prefix less that window's lead is refused (at the first batch,
+//                        when the filter's length is known: exit status 1, as every failure of the run).  No carrier offset
+//                        here (that takes the synchroniser across batch boundaries).  The summary adds C/N, seed and paths; the
+//                        output file is the one without the options; exit statuses as --loopback's.
 //   --spectrum FILE      the spectrum monitor behind every GPU call (DabGpuChain::Settings::spectrum): a Welch power spectrum of
 //                        everything written -- any rate, any format -- 2048 bins, Blackman-Harris window.  After the run FILE
 //                        holds one "offset_hz level_db" line per bin in ascending frequency, level relative to the mean over
@@ -110,6 +119,8 @@ namespace {
                          "       [--loopback]   with --gpu-frontend: demodulate and channel-decode every batch on the device against the ETI\n"
                          "                        frames read; totals on stderr, exit 2 on a payload bit error\n"
                          "       [--soft]   with --loopback: soft decisions (int8 metrics, soft Viterbi) in place of hard ones\n"
+                         "       [--channel-cn DB [--channel-seed N] [--channel-echo DELAY,DB,PHASE]...]   with --loopback: noise and echoes\n"
+                         "           between the IQ and the demodulator (the channel emulator)\n"
                          "       [--monitor]   decode every frame written on the device; totals on stderr, exit 2 on a bit error\n"
                          "       [--dpd-feedback RXFILE --dpd-out COEFFILE [--dpd-bins N] [--dpd-min-count N]]   fit MemlessPoly from a feedback capture\n"
                          "       [--spectrum FILE [--mask MASKFILE] [--oob-from HZ]]   power spectrum of everything written, per bin into FILE;\n"
@@ -175,6 +186,11 @@ int main(int argc, char **argv)
     bool reference_latency = false;
     long contexts = 1;
     bool gpu_frontend = false, loopback = false, soft = false;
+    bool channel = false;
+    double channel_cn = 0.0;
+    unsigned long long channel_seed = 0;
+    struct Echo { unsigned delay; double db, phase; };
+    std::vector<Echo> channel_echoes;
     std::string state_in, state_out;
     std::string spectrum_path, mask_path;
     double oob_from = 970000.0;
@@ -224,6 +240,13 @@ int main(int argc, char **argv)
             else if (a == "--monitor") gs.monitor = true;
             else if (a == "--loopback") loopback = true;
             else if (a == "--soft") soft = true;
+            else if (a == "--channel-cn") { channel_cn = std::stod(val()); channel = true; }
+            else if (a == "--channel-seed") channel_seed = std::stoull(val());
+            else if (a == "--channel-echo") {
+                Echo e{};
+                if (std::sscanf(val().c_str(), "%u,%lf,%lf", &e.delay, &e.db, &e.phase) != 3) usage();
+                channel_echoes.push_back(e);
+            }
             else if (a == "--spectrum") { spectrum_path = val(); gs.spectrum = true; }
             else if (a == "--mask") mask_path = val();
             else if (a == "--oob-from") oob_from = std::stod(val());
@@ -264,6 +287,16 @@ int main(int argc, char **argv)
 
         if (soft && !loopback) {
             std::fprintf(stderr, "dabmod_file: --soft does not go without --loopback: it chooses the decisions of that loop\n");
+            return 2;
+        }
+
+        if ((channel || channel_seed || !channel_echoes.empty()) && !(loopback && channel)) {
+            std::fprintf(stderr, "dabmod_file: --channel-seed and --channel-echo go with --channel-cn, and that with --loopback: the "
+                                 "channel sits between the IQ and that loop's demodulator\n");
+            return 2;
+        }
+        if (channel_echoes.size() + 1 > DABGPU_CH_MAX_PATHS) {
+            std::fprintf(stderr, "dabmod_file: --channel-echo: at most %d echoes\n", DABGPU_CH_MAX_PATHS - 1);
             return 2;
         }
 
@@ -411,6 +444,8 @@ int main(int argc, char **argv)
         } loop;
         std::vector<uint8_t> loop_bits, loop_out, loop_ref;
         std::vector<int8_t> loop_soft;
+        std::vector<uint8_t> loop_rx;             // --channel-cn: the batch behind the channel, in the output's format
+        double channel_sigma = -1.0;              //   < 0: not installed yet (the first batch sets the level)
         int loop_early = -1;
         size_t loop_cifs = 1;
         auto loopback_batch = [&](DabGpuChain *ch, const void *p, size_t bytes) {
@@ -423,6 +458,47 @@ int main(int argc, char **argv)
                     if (rc->get_rc_name() == "firfilter") loop_early += std::stoi(rc->get_parameter("ntaps")) - 1;
             }
             const size_t n_frames = bytes / ch->output_bytes_per_frame(), n = n_frames * loop_cifs;
+            const int loop_fmt = format == "s16" ? DABGPU_FMT_S16 : 0;
+            if (channel) {
+                dabgpu_geometry g{};
+                chk(dabgpu_get_geometry(c, &g));
+                if (channel_sigma < 0.0) {
+                    const int reach = g.sym_size - g.spacing - loop_early;
+                    for (const Echo &e : channel_echoes)
+                        if (static_cast<long>(e.delay) > reach)
+                            throw std::runtime_error("--channel-echo: a delay of " + std::to_string(e.delay) + " samples lies beyond the cyclic "
+                                                     "prefix less the window's lead (" + std::to_string(reach) + "): that takes the synchroniser");
+                    // mean power of the first batch's samples behind the null symbol
+                    double sum = 0.0;
+                    for (size_t f = 0; f < n_frames; ++f)
+                        for (size_t i = static_cast<size_t>(g.null_size); i < g.tf_samples; ++i) {
+                            const size_t at = 2 * (f * g.tf_samples + i);
+                            const double re = loop_fmt ? static_cast<const int16_t *>(p)[at] : static_cast<const float *>(p)[at];
+                            const double im = loop_fmt ? static_cast<const int16_t *>(p)[at + 1] : static_cast<const float *>(p)[at + 1];
+                            sum += re * re + im * im;
+                        }
+                    const double power = sum / static_cast<double>(n_frames * (g.tf_samples - static_cast<size_t>(g.null_size)));
+                    channel_sigma = std::sqrt(power / std::pow(10.0, channel_cn / 10.0) / 2.0);
+                    dabgpu_channel_config cc{};
+                    cc.n_paths = static_cast<uint32_t>(1 + channel_echoes.size());
+                    cc.sigma = static_cast<float>(channel_sigma);
+                    cc.seed = channel_seed;
+                    cc.rate_hz = 2048000.0;
+                    cc.paths[0].gain_re = 1.0f;
+                    for (size_t k = 0; k < channel_echoes.size(); ++k) {
+                        const Echo &e = channel_echoes[k];
+                        const double amp = std::pow(10.0, e.db / 20.0);
+                        cc.paths[k + 1].delay = e.delay;
+                        cc.paths[k + 1].gain_re = static_cast<float>(amp * std::cos(e.phase));
+                        cc.paths[k + 1].gain_im = static_cast<float>(amp * std::sin(e.phase));
+                    }
+                    chk(dabgpu_set_channel(c, &cc));
+                    chk(dabgpu_channel_reset(c, 0));
+                }
+                loop_rx.resize(bytes);
+                chk(dabgpu_channel(c, p, loop_fmt, n_frames * g.tf_samples, loop_rx.data(), loop_fmt));
+                p = loop_rx.data();
+            }
             loop_bits.resize(n_frames * ch->input_bytes_per_frame());
             loop_out.resize(n * 6144);
             loop_ref.assign(n * 6144, 0);
@@ -650,6 +726,9 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "dabmod_file: loopback: %llu frames compared, %llu FIC and %llu MSC payload bit errors in %llu bits, "
                                  "%llu corrected channel bits in %llu coded bits\n",
                          loop.frames, loop.fic_errors, loop.msc_errors, loop.n_bits, loop.corrected, loop.coded_bits);
+            if (channel)
+                std::fprintf(stderr, "dabmod_file: loopback: channel: C/N %.1f dB, seed %llu, %zu path%s, sigma %g\n", channel_cn, channel_seed,
+                             1 + channel_echoes.size(), channel_echoes.empty() ? "" : "s", channel_sigma);
             if (soft)
                 std::fprintf(stderr, "dabmod_file: loopback: soft decisions, metric %llu / soft_sum %llu, %llu erasures\n", loop.metric,
                              loop.soft_sum, loop.erasures);
