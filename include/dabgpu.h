@@ -997,6 +997,71 @@ DABGPU_API int dabgpu_channel(dabgpu_ctx *ctx, const void *in, int in_format, si
  * call size.  Same bytes for every value; exists so that a test can walk the run geometry. */
 DABGPU_API int dabgpu_debug_channel_run_samples(dabgpu_ctx *ctx, int samples);
 
+/* ---- the TII analyser: transmitters, levels and delays from the null symbols of whole frames -------------------------------- *
+ * Reads what dabgpu_set_tii puts into a signal: which (comb, pattern) the null symbols carry, how strong every comb is and
+ * when it arrives -- of one transmitter, or of the several of a single-frequency network in one monitoring capture.  The
+ * reference has no receiver; these entries replace nothing of its flowgraph.
+ * Input: n_frames whole transmission frames at the native rate, each tf_samples long and starting at its frame start -- what a
+ * chain call without the Resampler writes, or dabgpu_sync_extract* -- complexf (format 0) or DABGPU_FMT_S16 (a value becomes
+ * its float on load).  Modes I and II only (no other carries TII), 2 <= n_frames <= max_frames.
+ * With N = spacing, K = carriers, null = null_size, P[k] the phase reference symbol on carrier k, carrier k on bin k mod N, and
+ * `early` as dabgpu_demod* means it (the window ends `early` samples before the end of the null symbol; 0 ... null - N):
+ *   Cells      (c, b), c = 0 ... 23 (the comb), b = 0 ... 7 (the pattern bit), cell index 8 c + b.  First carriers, EN 300 401
+ *              14.8.1 as carrier numbers of the standard: Mode I  k(c, b, g) = {-768, -384, 1, 385}[g] + 2 c + 48 b, g = 0 ... 3;
+ *              Mode II  k(c, b) = -192 + 2 c + 48 b for b < 4 and -191 + 2 c + 48 b for b >= 4 (one g).  Every first carrier has
+ *              its pair carrier k + 1.  Pattern p is row p of a_b(p): the 70 eight-bit words of weight four in ascending
+ *              order, b = 0 the most significant bit.
+ *   Per frame  R = DFT_N(x[null - early - N ... null - early)) on the cells' carriers, in float64: R[k] = sum_n x[n]
+ *              e^{-j 2 pi ((k n) mod N) / N}, n in order, fused multiply-adds, the twiddles float64 (a clean capture's unset
+ *              cells are 1e-14 of the set ones: an fp32 transform's own rounding would be the floor).  In float64, g in order:
+ *              E_f(c, b) = sum_g (|R[k]|^2 + |R[k + 1]|^2),  G_f(c, b) = sum_g R[k + 1] conj(R[k]) conj(q_k),
+ *              q_k = 1 (new variant) or P[k + 1] conj(P[k]) (old variant).
+ *   Parity     total[p] = sum over the cells of (sum of E_f over the frames f = p mod 2, in frame order);  parity = 0 if
+ *              total[0] >= total[1], else 1.  Only the n_used frames f = parity mod 2 are used: E(c, b) and G(c, b) are the
+ *              sums of E_f and G_f over them, in frame order.
+ *   Floor      floor = the 96th smallest of the 192 E(c, b) (a cell's rank: the cells smaller, or equal with a lower index).
+ *   Decision   thr = max(min_ratio floor, min_rel max E), in float64;  cell (c, b) is set when E >= thr and E > 0.  A comb with
+ *              at least one set cell is an entry; entries are in comb order.  mask = the set bits, b as 0x80 >> b;  n_set;
+ *              pattern = the table index of mask when n_set = 4, else -1 (two transmitters on one comb, or a faint one, report
+ *              the mask only);  energy = (sum of the set cells' E, b in order) / n_used.
+ *   Coarse     tau1 = -arg(sum over the set b of G(c, b), b in order) N / 2 pi (float64 atan2), in samples from the window;
+ *              delay_coarse = tau1 - early.  Unambiguous within +-N / 2.
+ *   Fine       s = N / 16384 samples (1/8 in Mode I, 1/32 in Mode II);  u_j = rint(tau1 / s) + j, j = -128 ... 127;
+ *              H_f[k] = R_f[k] conj(T[k]) (R_f rounded to fp32) on the carriers of the entry's set cells, T[k] = P[k] on a first carrier and on its
+ *              pair carrier T[k + 1] = P[k] (new variant) or P[k + 1] (old variant);
+ *              S_j = sum_f |sum_k H_f[k] e^{j 2 pi ((k u_j) mod 16384) / 16384}|^2, the inner sum in fp32 (fused multiply-adds,
+ *              the phase an exact integer turn) over the carriers in ascending k, the outer in float64 over the used frames in
+ *              order;  j* = the first j with the largest S;  delay = u_j* s - early;
+ *              runner_up = (the largest S_j with |j - j*| > 16384 / N) / S_j*, 0 when S_j* = 0.
+ *              A comb's carriers lie on a lattice of 48 carriers, so S repeats almost unchanged every N / 48 samples; only the
+ *              pair carriers resolve that, and coarsely: hence the two stages and the window of +-N / 128 samples.
+ * delay = 0: the useful part of the null symbol starts at sample null - N of the frame.  A chain with FIRFilter reads -22 (its
+ *   look-ahead, the 22 samples dabgpu_sync* reports as well).  Delays of two entries differ by the transmitters' distance in time.
+ * As emitted -- bit-exact to the reference -- a Mode II signal configured with pattern p reads here, by the standard, as the
+ *   pattern with bits b and b + 4 exchanged (comb 3, pattern 5 reads as comb 3, pattern 32); Mode I reads as configured.
+ *   INTEGRATION.md F has the cause.
+ * Every sum and search runs in a fixed order (the lane's own terms in index order, an xor butterfly in the wave, the waves in
+ *   wave order; ties go to the first index; no floating-point atomics): a call on the same samples gives the same bytes.
+ * dabgpu_tii_scan_dev: device pointer (aligned to a sample), asynchronous on `stream` (NULL: the context's own stream, behind
+ *   every lane); three launches, no host round trip.  dabgpu_tii_scan: the host-pointer form.
+ * dabgpu_get_tii_scan: waits for the most recent of them, as dabgpu_get_sync_result does; the head, and min(cap, 24) entry
+ *   slots to `out`.  The result has a fixed layout: the head (40 bytes), then 24 slots of 48 bytes, zeros behind n_entries.
+ * Refused with DABGPU_E_INVALID and a message before anything is queued (the previous result stays): Mode III or IV,
+ *   n_frames < 2 or > max_frames, early outside 0 ... null - N, min_ratio not finite or < 1, min_rel outside [0, 1), a format
+ *   other than 0 / DABGPU_FMT_S16, a null or misaligned pointer.
+ * dabgpu_tii_scan_check: host only, no context, no device: the refusals of mode (1..4; 0 = IV), n_frames (>= 2; max_frames is
+ *   the context's) and the settings, message via dabgpu_last_error(NULL).
+ * Out of scope: coherent accumulation across frames, more than one pattern per comb resolved, sampling-clock offset, u8 / s8,
+ *   resampled captures. */
+typedef struct dabgpu_tii_scan_config { int early, old_variant; float min_ratio, min_rel; } dabgpu_tii_scan_config;
+typedef struct dabgpu_tii_scan_head   { int n_used, parity, n_entries, reserved; double floor, total[2]; } dabgpu_tii_scan_head;
+typedef struct dabgpu_tii_entry       { int comb, pattern, mask, n_set; double energy, delay_coarse, delay, runner_up; } dabgpu_tii_entry;
+DABGPU_API int dabgpu_tii_scan_dev(dabgpu_ctx *ctx, const void *d_frames, int format, size_t n_frames,
+                                   const dabgpu_tii_scan_config *cfg, void *stream);
+DABGPU_API int dabgpu_tii_scan(dabgpu_ctx *ctx, const void *frames, int format, size_t n_frames, const dabgpu_tii_scan_config *cfg);
+DABGPU_API int dabgpu_get_tii_scan(dabgpu_ctx *ctx, dabgpu_tii_scan_head *head, dabgpu_tii_entry *out, size_t cap);
+DABGPU_API int dabgpu_tii_scan_check(int mode, size_t n_frames, const dabgpu_tii_scan_config *cfg);
+
 /* wait for everything queued on the context's own stream(s): every lane */
 DABGPU_API int dabgpu_synchronize(dabgpu_ctx *ctx);
 

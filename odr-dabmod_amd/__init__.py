@@ -56,6 +56,7 @@ EXPORTS = [
     "dabgpu_sync_dev", "dabgpu_sync", "dabgpu_get_sync_result", "dabgpu_sync_extract_dev", "dabgpu_sync_extract", "dabgpu_sync_check",
     "dabgpu_channel_check", "dabgpu_set_channel", "dabgpu_channel_reset", "dabgpu_get_channel_position", "dabgpu_channel_dev",
     "dabgpu_channel", "dabgpu_debug_channel_run_samples",
+    "dabgpu_tii_scan_dev", "dabgpu_tii_scan", "dabgpu_get_tii_scan", "dabgpu_tii_scan_check",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -108,6 +109,21 @@ class _SyncFrame(C.Structure):
                 ("quality", C.c_double), ("null_depth", C.c_double)]
 
 
+class _TiiScanConfig(C.Structure):
+    _fields_ = [("early", C.c_int), ("old_variant", C.c_int), ("min_ratio", C.c_float), ("min_rel", C.c_float)]
+
+
+class _TiiScanHead(C.Structure):
+    _fields_ = [("n_used", C.c_int), ("parity", C.c_int), ("n_entries", C.c_int), ("reserved", C.c_int),
+                ("floor", C.c_double), ("total", C.c_double * 2)]
+
+
+class _TiiEntry(C.Structure):
+    _fields_ = [("comb", C.c_int), ("pattern", C.c_int), ("mask", C.c_int), ("n_set", C.c_int), ("energy", C.c_double),
+                ("delay_coarse", C.c_double), ("delay", C.c_double), ("runner_up", C.c_double)]
+
+
+TII_SLOTS = 24
 CH_MAX_PATHS, CH_MAX_DELAY = 64, 2047
 
 
@@ -305,6 +321,10 @@ def load_library():
     lib.dabgpu_channel_dev.argtypes = [vp, vp, C.c_int, sz, vp, C.c_int, vp]
     lib.dabgpu_channel.argtypes = [vp, vp, C.c_int, sz, vp, C.c_int]
     lib.dabgpu_debug_channel_run_samples.argtypes = [vp, C.c_int]
+    lib.dabgpu_tii_scan_dev.argtypes = [vp, vp, C.c_int, sz, C.POINTER(_TiiScanConfig), vp]
+    lib.dabgpu_tii_scan.argtypes = [vp, vp, C.c_int, sz, C.POINTER(_TiiScanConfig)]
+    lib.dabgpu_get_tii_scan.argtypes = [vp, C.POINTER(_TiiScanHead), C.POINTER(_TiiEntry), sz]
+    lib.dabgpu_tii_scan_check.argtypes = [C.c_int, sz, C.POINTER(_TiiScanConfig)]
     lib.dabgpu_decode_check_layout.argtypes = [C.POINTER(_FeLayout)]
     lib.dabgpu_decode_reset.argtypes = [vp]
     lib.dabgpu_decode_dev.argtypes = [vp, vp, sz, vp, sz, vp, szp, vp]
@@ -361,6 +381,23 @@ def sync_check(mode, n_samples, max_shift=31):
     if int(n_samples) < 0:
         raise DabGpuError("sync: n_samples must not be negative")
     if lib.dabgpu_sync_check(int(mode), int(n_samples), int(max_shift)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def _tii_scan_config(early, old_variant, min_ratio, min_rel):
+    cfg = _TiiScanConfig()
+    cfg.early, cfg.old_variant, cfg.min_ratio, cfg.min_rel = int(early), int(bool(old_variant)), float(min_ratio), float(min_rel)
+    return cfg
+
+
+def tii_scan_check(mode, n_frames, early, old_variant=False, min_ratio=12.0, min_rel=1e-3):
+    """Host only (needs the library, no device): raises DabGpuError when tii_scan() would refuse these settings in this mode,
+    with the message it gives (n_frames against max_frames is the context's to check)."""
+    lib = load_library()
+    if int(n_frames) < 0:
+        raise DabGpuError("tii_scan: n_frames must lie in 2 ... max_frames")
+    cfg = _tii_scan_config(early, old_variant, min_ratio, min_rel)
+    if lib.dabgpu_tii_scan_check(int(mode), int(n_frames), C.byref(cfg)) != 0:
         raise DabGpuError(lib.dabgpu_last_error(None).decode())
 
 
@@ -1269,6 +1306,48 @@ class Modulator:
         self._chk(self._lib.dabgpu_channel_dev(self._h, d_in.data_ptr(), fi, n, d_out.data_ptr(), fo, s))
         if not s:
             self.synchronize()
+
+    # ---- the TII analyser: transmitters, levels and delays of whole frames (include/dabgpu.h, "the TII analyser") ----
+    def tii_scan(self, frames, early, old_variant=False, min_ratio=12.0, min_rel=1e-3):
+        """Host path: whole transmission frames at the native rate (complex64, or int16 interleaved re, im) ->
+        tii_scan_result()."""
+        iq, fmt, n = self._sync_host(frames)
+        tf = self.geometry["tf_samples"]
+        if n % tf:
+            raise DabGpuError("tii_scan: the input is whole transmission frames (tf_samples each)")
+        cfg = _tii_scan_config(early, old_variant, min_ratio, min_rel)
+        self._chk(self._lib.dabgpu_tii_scan(self._h, iq.ctypes.data, fmt, n // tf, C.byref(cfg)))
+        return self.tii_scan_result()
+
+    def tii_scan_dev(self, d_frames, n_frames, early, old_variant=False, min_ratio=12.0, min_rel=1e-3, stream=None):
+        """Device path on a torch tensor (complex64, or int16 pairs) that holds n_frames whole frames, asynchronous on the
+        stream as chain_dev; the result: tii_scan_result()."""
+        fmt, n = self._sync_tensor(d_frames)
+        if int(n_frames) < 0 or n < int(n_frames) * self.geometry["tf_samples"] or not d_frames.is_contiguous():
+            raise DabGpuError("tii_scan: the tensor is contiguous and holds n_frames whole transmission frames")
+        cfg = _tii_scan_config(early, old_variant, min_ratio, min_rel)
+        s = self._stream_handle(d_frames, stream)
+        self._chk(self._lib.dabgpu_tii_scan_dev(self._h, d_frames.data_ptr(), fmt, int(n_frames), C.byref(cfg), s))
+        if not s:
+            self.synchronize()
+
+    def _tii_scan_raw(self):
+        head, recs = _TiiScanHead(), (_TiiEntry * TII_SLOTS)()
+        self._chk(self._lib.dabgpu_get_tii_scan(self._h, C.byref(head), recs, TII_SLOTS))
+        return head, recs
+
+    def tii_scan_result(self):
+        """The most recent tii_scan() / tii_scan_dev() (waits for it): (head, entries) -- head: a dict n_used, parity,
+        n_entries, floor, total; entries: one dict per comb with a set cell, in comb order: comb, pattern (-1: not four
+        cells), mask, n_set, energy, delay_coarse, delay, runner_up.  Delays are in samples."""
+        head, recs = self._tii_scan_raw()
+        h = dict(n_used=head.n_used, parity=head.parity, n_entries=head.n_entries, floor=head.floor, total=list(head.total))
+        return h, [{k: getattr(recs[i], k) for k, _ in _TiiEntry._fields_} for i in range(min(head.n_entries, TII_SLOTS))]
+
+    def tii_scan_result_bytes(self):
+        """The same result as the bytes the device wrote: the head (40), then 24 entry slots of 48, zeros behind n_entries."""
+        head, recs = self._tii_scan_raw()
+        return bytes(head) + bytes(recs)
 
     # ---- the channel decoder: coded bits -> the ETI payload (include/dabgpu.h, "the channel decoder") ----
     def decode(self, bits, ref_eti=None):

@@ -19,6 +19,8 @@
 //                     receiver; the shape check (host only)
 //   api_channel.hip   the channel emulator (channel.hip): paths, Doppler and seeded noise on a sample stream, its history and
 //                     position; the settings check (host only)
+//   api_tii_scan.hip  the TII analyser (tii_scan.hip): transmitters, levels and delays from the null symbols of whole frames;
+//                     the settings check (host only)
 //   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
 //                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
 #pragma once
@@ -247,6 +249,12 @@ struct dabgpu_ctx {
     unsigned long long ch_position = 0;
     hipStream_t ch_stream = nullptr;
     int ch_run_samples = 0;               // dabgpu_debug_channel_run_samples: samples per workgroup, 0 = by the call size
+    // The TII analyser (api_tii_scan.hip, tii_scan.hip).  d_tii_scan: head, 24 entry slots and the entries' grid centres of
+    // the most recent dabgpu_tii_scan* call; d_tii_rows / d_tii_bins: per-frame cell sums and occupied bins (scratch);
+    // d_tii_in: the host-pointer entry's staging; tii_scan_done: a call has been queued; tii_scan_stream: where.
+    dabgpu_api::DevBuf d_tii_scan, d_tii_rows, d_tii_bins, d_tii_in;
+    bool tii_scan_done = false;
+    hipStream_t tii_scan_stream = nullptr;
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII
     bool tables_valid = false;            // apply_settings has uploaded every table group once
     unsigned long long tii_seg_epoch = 0; // 1 while the cached segment matches the settings (apply_settings zeroes it), and its stage mask

@@ -234,6 +234,34 @@ int channel_run(size_t n, int forced);
 hipError_t launch_channel(const ChannelArgs &a, hipStream_t s);
 // the history behind a call: next[j] = sample n - kChMaxDelay + j of the call, from `in` or (calls shorter than it) from `cur`
 hipError_t launch_channel_history(const void *in, int in_fmt, long long n, const float2 *cur, float2 *next, hipStream_t s);
+// tii_scan.hip: the TII analyser (dabgpu_tii_scan*): which (comb, pattern) the null symbols of whole frames carry, the level
+// and the delay of every comb
+constexpr int kTiiCombs = 24;             // combs, and entry slots of a result
+constexpr int kTiiCells = 192;            // cells (c, b): 24 combs x 8 pattern bits, cell (c, b) at 8 c + b
+constexpr int kTiiGrid = 16384;           // the fine delay's grid: N / 16384 samples
+struct TiiScanHead {                      // the layout of dabgpu_tii_scan_head; written by the decide kernel
+    int n_used, parity, n_entries, reserved;
+    double floor, total[2];
+};
+struct TiiEntry {                         // the layout of dabgpu_tii_entry; zeroed before the launch
+    int comb, pattern, mask, n_set;
+    double energy, delay_coarse, delay, runner_up;
+};
+struct TiiScanArgs {
+    Geometry g;
+    Tables t;                 // twiddle, phase_q
+    const void *iq;           // n_frames x tf samples: cf32 (fmt 0) or s16 pairs (fmt 1 = DABGPU_FMT_S16)
+    int fmt;
+    int n_frames;
+    int early, old_variant;
+    float min_ratio, min_rel;
+    double *rows;             // scratch, n_frames x 3 x kTiiCells: E_f, Re G_f, Im G_f
+    float2 *bins;             // scratch, n_frames x K: the occupied bins of every frame's null symbol
+    TiiScanHead *head;
+    TiiEntry *entries;        // kTiiCombs slots
+    int *centre;              // kTiiCombs: rint(tau1 / s) of every entry, from the decide kernel to the delay kernel
+};
+hipError_t launch_tii_scan(const TiiScanArgs &a, hipStream_t s);
 // spectrum.hip: Welch periodogram of one sample buffer (dabgpu_spectrum*, the spectrum monitor): segments of SPECTRUM_NFFT
 // samples at a hop of half that, in every transmission mode
 enum { SPECTRUM_NFFT = 2048, kSpectrumMaxRuns = 1 << 16 };

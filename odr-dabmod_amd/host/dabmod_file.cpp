@@ -78,6 +78,12 @@
 //   --mask MASKFILE      with --spectrum: "offset_hz limit_db" per line (# starts a comment), offsets increasing; the limit is
 //                        piecewise linear in dB between the points (dabgpu_spectrum_check_mask).  stderr gets the worst margin
 //                        and where it lies; exit status 3 when a bin lies above the mask (2 stays the monitor's).
+//   --tii-scan           the TII analyser (dabgpu_tii_scan; include/dabgpu.h, "the TII analyser") on the last batch of two frames
+//                        or more that was written, the window where --monitor puts it, min_ratio 12, min_rel 1e-3.  stderr gets
+//                        the head and one line per entry (comb, pattern, mask, level, delay); exit status 2 when --tii is given
+//                        and the entries are not exactly the one configured -- the comb, and the pattern as the standard reads
+//                        it: in Mode II the configured pattern with bits b and b + 4 exchanged.  Native-rate
+//                        complexf / s16 output with --batch 2 or more; not with --bits-only or --separate-converter.
 //   --state-out FILE     with --gpu-frontend: after the last frame, write where the stream stands -- the number of ETI frames
 //                        modulated since FP = 0 and both stream-state blobs (DabGpuChain::get_stream_state /
 //                        frontend_state) -- so that another run continues it
@@ -125,6 +131,7 @@ namespace {
                          "       [--dpd-feedback RXFILE --dpd-out COEFFILE [--dpd-bins N] [--dpd-min-count N]]   fit MemlessPoly from a feedback capture\n"
                          "       [--spectrum FILE [--mask MASKFILE] [--oob-from HZ]]   power spectrum of everything written, per bin into FILE;\n"
                          "                        exit 3 when it lies above the mask (lines of: offset_hz limit_db)\n"
+                         "       [--tii-scan]   with --batch 2 or more: read the TII of the last batch; exit 2 when it is not the one --tii configures\n"
                          "       [--state-out FILE] [--state-in FILE]   with --gpu-frontend: leave / take up the stream's state\n");
     std::exit(2);
 }
@@ -197,6 +204,7 @@ int main(int argc, char **argv)
     std::string dpd_rx_path, dpd_out_path;
     int dpd_bins = 64;
     unsigned long dpd_min_count = 10;
+    bool tii_scan = false;
     try {
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
@@ -254,6 +262,7 @@ int main(int argc, char **argv)
             else if (a == "--dpd-out") dpd_out_path = val();
             else if (a == "--dpd-bins") dpd_bins = std::atoi(val().c_str());
             else if (a == "--dpd-min-count") dpd_min_count = std::stoul(val());
+            else if (a == "--tii-scan") tii_scan = true;
             else if (a == "--state-in") state_in = val();
             else if (a == "--state-out") state_out = val();
             else if (a == "--contexts") {
@@ -303,6 +312,16 @@ int main(int argc, char **argv)
         if (gs.monitor && (bits_only || separate_converter)) {
             std::fprintf(stderr, "dabmod_file: --monitor does not go with %s\n",
                          bits_only ? "--bits-only: nothing is modulated" : "--separate-converter: the chain's own output is what is decoded");
+            return 2;
+        }
+
+        if (tii_scan && (gs.outputRate != 2048000 || (format != "complexf" && format != "s16") || bits_only || separate_converter || batch < 2)) {
+            std::fprintf(stderr, "dabmod_file: --tii-scan does not go with %s\n",
+                         gs.outputRate != 2048000 ? "--rate: the analyser takes the native rate"
+                         : bits_only  ? "--bits-only: nothing is modulated"
+                         : separate_converter ? "--separate-converter: the chain's own output is what is scanned"
+                         : batch < 2  ? "--batch below 2: the last batch is scanned, and a scan takes two frames or more"
+                                      : "u8 / s8 output: the analyser takes complexf or s16");
             return 2;
         }
 
@@ -546,6 +565,14 @@ int main(int argc, char **argv)
                 ++loop_first;
             }
         };
+        // --tii-scan: the last batch of two frames or more, as written, and the chain it came from
+        std::vector<uint8_t> tii_last;
+        DabGpuChain *tii_chain = nullptr;
+        auto tii_keep = [&](DabGpuChain *ch, const void *p, size_t bytes) {
+            if (!tii_scan || bytes / ch->output_bytes_per_frame() < 2) return;
+            tii_last.assign(static_cast<const uint8_t *>(p), static_cast<const uint8_t *>(p) + bytes);
+            tii_chain = ch;
+        };
         // the oldest batch in flight, in stream order: batch j lives on chain j mod N
         auto drain_one = [&]() {
             DabGpuChain *ch = chain_of(n_collected++);
@@ -557,6 +584,7 @@ int main(int argc, char **argv)
             if (format != "complexf") clipped += ch->get_num_clipped_samples();
             out.write(static_cast<const char *>(p), static_cast<std::streamsize>(n));
             dpd_feed(ch, p, n);
+            tii_keep(ch, p, n);
             --in_flight;
         };
         // two batches in flight per chain; the owning chain starts from the state behind the frame before its batch
@@ -809,8 +837,48 @@ int main(int argc, char **argv)
                          static_cast<unsigned long long>(st.samples_used), st.n_bins, static_cast<unsigned long long>(st.overflow),
                          fi.bins_used, fi.resid_am, fi.resid_pm, dpd_out_path.c_str());
         }
+        bool tii_mismatch = false;
+        if (tii_scan) {
+            if (!tii_chain) {
+                std::fprintf(stderr, "dabmod_file: --tii-scan: no batch of two frames or more was written, there is nothing to scan\n");
+                return 1;
+            }
+            dabgpu_ctx *c = tii_chain->context();
+            dabgpu_tii_scan_config cfg{};
+            cfg.early = static_cast<int>(gs.ofdmWindowOverlap);           // where --monitor puts the window
+            for (RemoteControllable *rc : tii_chain->remote_controllables())
+                if (rc->get_rc_name() == "firfilter") cfg.early += std::stoi(rc->get_parameter("ntaps")) - 1;
+            cfg.old_variant = gs.tiiConfig.old_variant ? 1 : 0;
+            cfg.min_ratio = 12.0f;
+            cfg.min_rel = 1e-3f;
+            const size_t n_frames = tii_last.size() / tii_chain->output_bytes_per_frame();
+            dabgpu_tii_scan_head head;
+            dabgpu_tii_entry ent[24];
+            if (dabgpu_tii_scan(c, tii_last.data(), format == "s16" ? DABGPU_FMT_S16 : 0, n_frames, &cfg) != 0 ||
+                dabgpu_get_tii_scan(c, &head, ent, 24) != 0)
+                throw std::runtime_error(std::string("--tii-scan: ") + dabgpu_last_error(c));
+            std::fprintf(stderr, "dabmod_file: tii: %zu frames scanned, %d used (parity %d), window %d samples early, floor %.3g, %d entr%s\n",
+                         n_frames, head.n_used, head.parity, cfg.early, head.floor, head.n_entries, head.n_entries == 1 ? "y" : "ies");
+            for (int i = 0; i < head.n_entries && i < 24; ++i)
+                std::fprintf(stderr, "dabmod_file: tii: comb %d pattern %d mask 0x%02x (%d cells) level %.2f dB delay %+.3f samples "
+                                     "(coarse %+.2f, runner-up %.3f)\n", ent[i].comb, ent[i].pattern, ent[i].mask, ent[i].n_set,
+                             10.0 * std::log10(ent[i].energy), ent[i].delay, ent[i].delay_coarse, ent[i].runner_up);
+            if (gs.tiiConfig.enable) {
+                // the pattern as the standard reads it: row p of the words of weight four, in Mode II with its halves exchanged
+                int word = 0, want = -1;
+                for (int w = 0, idx = 0; w < 256; ++w)
+                    if (__builtin_popcount(static_cast<unsigned>(w)) == 4 && idx++ == gs.tiiConfig.pattern) word = w;
+                if (gs.dabMode == 2) word = ((word & 0x0f) << 4) | (word >> 4);
+                for (int w = 0, idx = 0; w <= word; ++w)
+                    if (__builtin_popcount(static_cast<unsigned>(w)) == 4) want = idx++;
+                tii_mismatch = head.n_entries != 1 || ent[0].comb != gs.tiiConfig.comb || ent[0].pattern != want;
+                std::fprintf(stderr, "dabmod_file: tii: configured comb %d pattern %d, read by the standard as pattern %d: %s\n",
+                             gs.tiiConfig.comb, gs.tiiConfig.pattern, want, tii_mismatch ? "NOT what was read" : "read");
+            }
+        }
         if (gs.monitor && mon.bit_errors) return 2;
         if (loopback && (loop.fic_errors || loop.msc_errors)) return 2;
+        if (tii_mismatch) return 2;
         if (mask_violations) return 3;
         return 0;
     } catch (const std::exception &e) {
