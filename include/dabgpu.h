@@ -1062,6 +1062,75 @@ DABGPU_API int dabgpu_tii_scan(dabgpu_ctx *ctx, const void *frames, int format, 
 DABGPU_API int dabgpu_get_tii_scan(dabgpu_ctx *ctx, dabgpu_tii_scan_head *head, dabgpu_tii_entry *out, size_t cap);
 DABGPU_API int dabgpu_tii_scan_check(int mode, size_t n_frames, const dabgpu_tii_scan_config *cfg);
 
+/* ---- the channel estimator: impulse response and echoes from the phase reference symbols of whole frames ------------------- *
+ * Reads what dabgpu_set_channel puts into a signal, or what a single-frequency network and the air do: the paths a capture went
+ * through, their levels and delays, how much arrives later than the guard interval, and the response on every carrier.  The
+ * reference has no receiver; these entries replace nothing of its flowgraph.
+ * Input: n_frames whole transmission frames at the native rate, each tf_samples long and starting at its frame start -- what a
+ * chain call without the Resampler writes, or dabgpu_sync_extract* -- complexf (format 0) or DABGPU_FMT_S16 (a value becomes
+ * its float on load).  All four modes, 1 <= n_frames <= max_frames.
+ * With N = spacing, K = carriers, null = null_size, sym = sym_size, CP = sym - N, P[k] the phase reference symbol on carrier k,
+ * carrier k on bin k mod N, `early` in 0 ... CP and `window` 0 (rectangular) or 1 (Hann):
+ *   Transform  per frame f:  R_f = DFT_N(x_f[w0 ... w0 + N)), w0 = null + CP - early; the samples become float64 on load and the
+ *              transform runs in float64 (the profile's floor lies at 1e-6 ... 1e-5 of its peak: an fp32 transform's own
+ *              rounding would show in it).
+ *   Channel    H_f[k] = R_f[k mod N] conj(P[k]) on the occupied carriers k = -K/2 ... -1, 1 ... K/2, 0 elsewhere.
+ *   Weights    i = the position of k in ascending carrier order (k = -K/2 -> 0, k = -1 -> K/2 - 1, k = 1 -> K/2, k = K/2 ->
+ *              K - 1);  w_i = 1 (window 0) or 0.5 - 0.5 cos(2 pi (i + 0.5) / K) (window 1), in float64;  S_w = sum_i w_i.
+ *   Response   h_f[l] = (1 / S_w) sum_k w H_f[k] e^{+j 2 pi k l / N}, l = 0 ... N - 1, in float64.
+ *   Profile    pdp[l] = (1 / n_frames) sum_f |h_f[l]|^2, the frames in order -- non-coherent across frames: residual carrier
+ *              offset and Doppler turn the taps from frame to frame.  resp[b] = (1 / n_frames) sum_f |H_f[k]|^2 at bin
+ *              b = k mod N, unweighted, 0 on the unoccupied bins.
+ *   Floor      floor = the pdp value of rank N/2 - 1, zero-based (a value's rank: the values smaller, or equal with a lower
+ *              index).  peak = the largest pdp, peak_index = its first index.
+ *   Decision   threshold = max(min_ratio floor, min_rel peak).  Tap l is a peak when pdp[l] > 0, pdp[l] >= threshold,
+ *              pdp[l] > pdp[(l - 1) mod N] and pdp[l] >= pdp[(l + 1) mod N].  n_peaks counts them all.
+ *   Paths      the DABGPU_CIR_MAX_PATHS = 16 strongest peaks in descending power, a lower index first among equals.  index = l;
+ *              delay = (l, or l - N from N/2 on) - early;  fine = 0.5 (a - c) / (a - 2 b + c) with a, b, c = pdp at l - 1, l,
+ *              l + 1 (mod N), 0 when the denominator is 0;  power = b.
+ *   Figures    over the reported paths in their order, float64, d_i = delay_i + fine_i:  path_power = sum p_i;  mean_delay =
+ *              sum p_i d_i / sum p_i;  delay_spread = sqrt(sum p_i (d_i - mean_delay)^2 / sum p_i);  first_delay = the smallest
+ *              delay_i;  outside_guard = the share of path_power on paths with delay_i - first_delay > CP (all 0 without a
+ *              path).  total = sum_l pdp[l] in index order.  resp_mean (sum / K), resp_min, resp_max over the occupied bins in
+ *              ascending bin order, resp_min_bin / resp_max_bin the first bin of each extreme.
+ *              A zero input (peak = 0) gives zero everywhere, the two bins included, and no path.
+ * delay = 0: a path whose phase reference symbol's useful part starts at sample null + CP of the frame.  A chain with FIRFilter
+ *   reads -22 (its look-ahead, the 22 samples dabgpu_sync* and dabgpu_tii_scan* report as well); behind dabgpu_sync_extract* the
+ *   strongest path reads 0.  A delay is unambiguous within +-N / 2.
+ * Resolution: with the Hann weights two paths closer than about 3 N / K samples merge; with the rectangular ones every path
+ *   shows its side lobes, from -13 dB down, as peaks of their own.  With one frame a noise tap exceeds min_ratio floor with
+ *   probability about e^{-0.69 min_ratio} (|h|^2 of noise is exponentially distributed and the floor is its median): 1e-6 at
+ *   min_ratio 20, per tap -- hence 20 as the wrappers' default, and more where one frame is all there is.
+ * Every sum and search runs in a fixed order (the frames in order, total and the response's sum in index order, searches as an
+ *   xor butterfly in the wave and the waves in wave order; ties go to the first index; no floating-point atomics): a call on
+ *   the same samples gives the same bytes.
+ * dabgpu_cir_dev: device pointer (aligned to a sample), asynchronous on `stream` (NULL: the context's own stream, behind every
+ *   lane); two launches, no host round trip.  dabgpu_cir: the host-pointer form.
+ * dabgpu_get_cir: waits for the most recent of them, as dabgpu_get_tii_scan does; the head, and min(cap, 16) path slots to
+ *   `out`.  The result has a fixed layout, the same in every mode: the head (128 bytes), then 16 slots of 32 bytes, zeros behind
+ *   n_paths: 640 bytes.  dabgpu_get_cir_profile: pdp and resp of the same call, N doubles each; either may be NULL.
+ * Refused with DABGPU_E_INVALID and a message before anything is queued (the previous result stays): n_frames < 1 or >
+ *   max_frames, early outside 0 ... CP, window other than 0 / 1, min_ratio not finite or < 1, min_rel outside [0, 1), a format
+ *   other than 0 / DABGPU_FMT_S16, a null or misaligned pointer; a get before any call.
+ * dabgpu_cir_check: host only, no context, no device: the refusals of mode (1..4; 0 = IV), n_frames (>= 1; max_frames is the
+ *   context's) and the settings, message via dabgpu_last_error(NULL).
+ * Out of scope: coherent averaging across frames, Doppler per path, a delay finer than the three-point `fine`, sampling-clock
+ *   offset, u8 / s8, resampled captures, and weighting the soft metrics with resp (this measures what that would need). */
+#define DABGPU_CIR_MAX_PATHS 16
+typedef struct dabgpu_cir_config { int early, window; float min_ratio, min_rel; } dabgpu_cir_config;
+typedef struct dabgpu_cir_head {
+    int n_frames, n_peaks, n_paths, window, peak_index, resp_min_bin, resp_max_bin, reserved;
+    double floor, threshold, peak, total, path_power, mean_delay, delay_spread, first_delay, outside_guard, resp_mean, resp_min,
+        resp_max;
+} dabgpu_cir_head;                                                                                  /* 128 bytes */
+typedef struct dabgpu_cir_path { int index, reserved; double delay, fine, power; } dabgpu_cir_path; /* 32 bytes */
+DABGPU_API int dabgpu_cir_dev(dabgpu_ctx *ctx, const void *d_frames, int format, size_t n_frames, const dabgpu_cir_config *cfg,
+                              void *stream);
+DABGPU_API int dabgpu_cir(dabgpu_ctx *ctx, const void *frames, int format, size_t n_frames, const dabgpu_cir_config *cfg);
+DABGPU_API int dabgpu_get_cir(dabgpu_ctx *ctx, dabgpu_cir_head *head, dabgpu_cir_path *out, size_t cap);
+DABGPU_API int dabgpu_get_cir_profile(dabgpu_ctx *ctx, double *pdp, double *resp);
+DABGPU_API int dabgpu_cir_check(int mode, size_t n_frames, const dabgpu_cir_config *cfg);
+
 /* wait for everything queued on the context's own stream(s): every lane */
 DABGPU_API int dabgpu_synchronize(dabgpu_ctx *ctx);
 

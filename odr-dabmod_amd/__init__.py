@@ -57,6 +57,7 @@ EXPORTS = [
     "dabgpu_channel_check", "dabgpu_set_channel", "dabgpu_channel_reset", "dabgpu_get_channel_position", "dabgpu_channel_dev",
     "dabgpu_channel", "dabgpu_debug_channel_run_samples",
     "dabgpu_tii_scan_dev", "dabgpu_tii_scan", "dabgpu_get_tii_scan", "dabgpu_tii_scan_check",
+    "dabgpu_cir_dev", "dabgpu_cir", "dabgpu_get_cir", "dabgpu_get_cir_profile", "dabgpu_cir_check",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -124,6 +125,25 @@ class _TiiEntry(C.Structure):
 
 
 TII_SLOTS = 24
+
+
+class _CirConfig(C.Structure):
+    _fields_ = [("early", C.c_int), ("window", C.c_int), ("min_ratio", C.c_float), ("min_rel", C.c_float)]
+
+
+class _CirHead(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("n_frames", "n_peaks", "n_paths", "window", "peak_index", "resp_min_bin", "resp_max_bin",
+                                       "reserved")] + \
+               [(k, C.c_double) for k in ("floor", "threshold", "peak", "total", "path_power", "mean_delay", "delay_spread",
+                                          "first_delay", "outside_guard", "resp_mean", "resp_min", "resp_max")]
+
+
+class _CirPath(C.Structure):
+    _fields_ = [("index", C.c_int), ("reserved", C.c_int), ("delay", C.c_double), ("fine", C.c_double), ("power", C.c_double)]
+
+
+CIR_MAX_PATHS = 16
+CIR_RECTANGULAR, CIR_HANN = 0, 1
 CH_MAX_PATHS, CH_MAX_DELAY = 64, 2047
 
 
@@ -325,6 +345,11 @@ def load_library():
     lib.dabgpu_tii_scan.argtypes = [vp, vp, C.c_int, sz, C.POINTER(_TiiScanConfig)]
     lib.dabgpu_get_tii_scan.argtypes = [vp, C.POINTER(_TiiScanHead), C.POINTER(_TiiEntry), sz]
     lib.dabgpu_tii_scan_check.argtypes = [C.c_int, sz, C.POINTER(_TiiScanConfig)]
+    lib.dabgpu_cir_dev.argtypes = [vp, vp, C.c_int, sz, C.POINTER(_CirConfig), vp]
+    lib.dabgpu_cir.argtypes = [vp, vp, C.c_int, sz, C.POINTER(_CirConfig)]
+    lib.dabgpu_get_cir.argtypes = [vp, C.POINTER(_CirHead), C.POINTER(_CirPath), sz]
+    lib.dabgpu_get_cir_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.dabgpu_cir_check.argtypes = [C.c_int, sz, C.POINTER(_CirConfig)]
     lib.dabgpu_decode_check_layout.argtypes = [C.POINTER(_FeLayout)]
     lib.dabgpu_decode_reset.argtypes = [vp]
     lib.dabgpu_decode_dev.argtypes = [vp, vp, sz, vp, sz, vp, szp, vp]
@@ -398,6 +423,23 @@ def tii_scan_check(mode, n_frames, early, old_variant=False, min_ratio=12.0, min
         raise DabGpuError("tii_scan: n_frames must lie in 2 ... max_frames")
     cfg = _tii_scan_config(early, old_variant, min_ratio, min_rel)
     if lib.dabgpu_tii_scan_check(int(mode), int(n_frames), C.byref(cfg)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def _cir_config(early, window, min_ratio, min_rel):
+    cfg = _CirConfig()
+    cfg.early, cfg.window, cfg.min_ratio, cfg.min_rel = int(early), int(window), float(min_ratio), float(min_rel)
+    return cfg
+
+
+def cir_check(mode, n_frames, early, window=1, min_ratio=20.0, min_rel=1e-3):
+    """Host only (needs the library, no device): raises DabGpuError when cir() would refuse these settings in this mode, with
+    the message it gives (n_frames against max_frames is the context's to check)."""
+    lib = load_library()
+    if int(n_frames) < 0:
+        raise DabGpuError("cir: n_frames must lie in 1 ... max_frames")
+    cfg = _cir_config(early, window, min_ratio, min_rel)
+    if lib.dabgpu_cir_check(int(mode), int(n_frames), C.byref(cfg)) != 0:
         raise DabGpuError(lib.dabgpu_last_error(None).decode())
 
 
@@ -1348,6 +1390,56 @@ class Modulator:
         """The same result as the bytes the device wrote: the head (40), then 24 entry slots of 48, zeros behind n_entries."""
         head, recs = self._tii_scan_raw()
         return bytes(head) + bytes(recs)
+
+    # ---- the channel estimator: impulse response and echoes of whole frames (include/dabgpu.h, "the channel estimator") ----
+    def cir(self, frames, early, window=1, min_ratio=20.0, min_rel=1e-3):
+        """Host path: whole transmission frames at the native rate (complex64, or int16 interleaved re, im) -> cir_result()."""
+        iq, fmt, n = self._sync_host(frames)
+        tf = self.geometry["tf_samples"]
+        if n % tf:
+            raise DabGpuError("cir: the input is whole transmission frames (tf_samples each)")
+        cfg = _cir_config(early, window, min_ratio, min_rel)
+        self._chk(self._lib.dabgpu_cir(self._h, iq.ctypes.data, fmt, n // tf, C.byref(cfg)))
+        return self.cir_result()
+
+    def cir_dev(self, d_frames, n_frames, early, window=1, min_ratio=20.0, min_rel=1e-3, stream=None):
+        """Device path on a torch tensor (complex64, or int16 pairs) that holds n_frames whole frames, asynchronous on the
+        stream as chain_dev; the result: cir_result(), cir_profile()."""
+        fmt, n = self._sync_tensor(d_frames)
+        if int(n_frames) < 0 or n < int(n_frames) * self.geometry["tf_samples"] or not d_frames.is_contiguous():
+            raise DabGpuError("cir: the tensor is contiguous and holds n_frames whole transmission frames")
+        cfg = _cir_config(early, window, min_ratio, min_rel)
+        s = self._stream_handle(d_frames, stream)
+        self._chk(self._lib.dabgpu_cir_dev(self._h, d_frames.data_ptr(), fmt, int(n_frames), C.byref(cfg), s))
+        if not s:
+            self.synchronize()
+
+    def _cir_raw(self):
+        head, recs = _CirHead(), (_CirPath * CIR_MAX_PATHS)()
+        self._chk(self._lib.dabgpu_get_cir(self._h, C.byref(head), recs, CIR_MAX_PATHS))
+        return head, recs
+
+    def cir_result(self):
+        """The most recent cir() / cir_dev() (waits for it): (head, paths) -- head: a dict of the fields of dabgpu_cir_head;
+        paths: one dict per reported path in descending power: index, delay, fine, power.  Delays are in samples."""
+        head, recs = self._cir_raw()
+        h = {k: getattr(head, k) for k, _ in _CirHead._fields_ if k != "reserved"}
+        return h, [{k: getattr(recs[i], k) for k, _ in _CirPath._fields_ if k != "reserved"}
+                   for i in range(min(head.n_paths, CIR_MAX_PATHS))]
+
+    def cir_result_bytes(self):
+        """The same result as the bytes the device wrote: the head (128), then 16 path slots of 32, zeros behind n_paths."""
+        head, recs = self._cir_raw()
+        return bytes(head) + bytes(recs)
+
+    def cir_profile(self):
+        """(pdp, resp) of the most recent cir() / cir_dev() as float64 arrays of `spacing` values: the power delay profile per
+        tap and the response per bin (0 on the unoccupied bins)."""
+        n = self.geometry["spacing"]
+        pdp, resp = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        dp = C.POINTER(C.c_double)
+        self._chk(self._lib.dabgpu_get_cir_profile(self._h, pdp.ctypes.data_as(dp), resp.ctypes.data_as(dp)))
+        return pdp, resp
 
     # ---- the channel decoder: coded bits -> the ETI payload (include/dabgpu.h, "the channel decoder") ----
     def decode(self, bits, ref_eti=None):

@@ -553,7 +553,7 @@ void dabgpu_destroy(dabgpu_ctx *c)
                       &c->d_dec_ref, &c->d_decs_rows, &c->d_decs_tmp, &c->d_decs_stats, &c->d_decs_in,
                       &c->d_sync, &c->d_sync_power, &c->d_sync_in, &c->d_sync_out,
                       &c->d_ch_hist, &c->d_ch_in, &c->d_ch_out,
-                      &c->d_tii_scan, &c->d_tii_rows, &c->d_tii_bins, &c->d_tii_in})
+                      &c->d_tii_scan, &c->d_tii_rows, &c->d_tii_bins, &c->d_tii_in, &c->d_cir, &c->d_cir_rows, &c->d_cir_in})
         b->release();
     for (auto &sl : c->slot) {
         sl.d_eti.release();

@@ -21,6 +21,8 @@
 //                     position; the settings check (host only)
 //   api_tii_scan.hip  the TII analyser (tii_scan.hip): transmitters, levels and delays from the null symbols of whole frames;
 //                     the settings check (host only)
+//   api_cir.hip       the channel estimator (cir.hip): impulse response, echoes and the response on the carriers from the
+//                     phase reference symbols of whole frames; the settings check (host only)
 //   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
 //                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
 #pragma once
@@ -255,6 +257,12 @@ struct dabgpu_ctx {
     dabgpu_api::DevBuf d_tii_scan, d_tii_rows, d_tii_bins, d_tii_in;
     bool tii_scan_done = false;
     hipStream_t tii_scan_stream = nullptr;
+    // The channel estimator (api_cir.hip, cir.hip).  d_cir: head, 16 path slots, then the profile and the response (N doubles
+    // each) of the most recent dabgpu_cir* call; d_cir_rows: per-frame taps and bins (scratch, max_frames of them); d_cir_in:
+    // the host-pointer entry's staging; cir_done: a call has been queued; cir_stream: where.
+    dabgpu_api::DevBuf d_cir, d_cir_rows, d_cir_in;
+    bool cir_done = false;
+    hipStream_t cir_stream = nullptr;
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII
     bool tables_valid = false;            // apply_settings has uploaded every table group once
     unsigned long long tii_seg_epoch = 0; // 1 while the cached segment matches the settings (apply_settings zeroes it), and its stage mask

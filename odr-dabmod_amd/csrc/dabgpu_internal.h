@@ -262,6 +262,33 @@ struct TiiScanArgs {
     int *centre;              // kTiiCombs: rint(tau1 / s) of every entry, from the decide kernel to the delay kernel
 };
 hipError_t launch_tii_scan(const TiiScanArgs &a, hipStream_t s);
+// cir.hip: the channel estimator (dabgpu_cir*): the impulse response a capture's phase reference symbols went through, its
+// echoes with level and delay, and the response on the carriers
+constexpr int kCirMaxPaths = 16;          // DABGPU_CIR_MAX_PATHS: path slots of a result
+struct CirHead {                          // the layout of dabgpu_cir_head; written by the decide kernel
+    int n_frames, n_peaks, n_paths, window, peak_index, resp_min_bin, resp_max_bin, reserved;
+    double floor, threshold, peak, total, path_power, mean_delay, delay_spread, first_delay, outside_guard, resp_mean, resp_min,
+        resp_max;
+};
+struct CirPath {                          // the layout of dabgpu_cir_path; zeroed before the launch
+    int index, reserved;
+    double delay, fine, power;
+};
+struct CirArgs {
+    Geometry g;
+    Tables t;                 // phase_q
+    const void *iq;           // n_frames x tf samples: cf32 (fmt 0) or s16 pairs (fmt 1 = DABGPU_FMT_S16)
+    int fmt;
+    int n_frames;
+    int early, window;
+    float min_ratio, min_rel;
+    double sum_w;             // S_w: the sum of the K weights in ascending carrier order
+    double *rows;             // scratch, n_frames x 2 N: |h_f|^2 per tap, then |H_f|^2 per bin
+    CirHead *head;
+    CirPath *paths;           // kCirMaxPaths slots
+    double *pdp, *resp;       // N each
+};
+hipError_t launch_cir(const CirArgs &a, hipStream_t s);
 // spectrum.hip: Welch periodogram of one sample buffer (dabgpu_spectrum*, the spectrum monitor): segments of SPECTRUM_NFFT
 // samples at a hop of half that, in every transmission mode
 enum { SPECTRUM_NFFT = 2048, kSpectrumMaxRuns = 1 << 16 };

@@ -84,6 +84,14 @@
 //                        and the entries are not exactly the one configured -- the comb, and the pattern as the standard reads
 //                        it: in Mode II the configured pattern with bits b and b + 4 exchanged.  Native-rate
 //                        complexf / s16 output with --batch 2 or more; not with --bits-only or --separate-converter.
+//   --cir FILE           the channel estimator (dabgpu_cir; include/dabgpu.h, "the channel estimator") on the last batch that was
+//                        written, the window where --monitor puts it, Hann weights, min_ratio 20, min_rel 1e-3.  With
+//                        --loopback --channel-cn it is that batch behind the channel emulator instead, so --channel-echo
+//                        37,-6,1.0 --cir out.txt shows the echo it was given.  stderr gets the head and one line per path (delay,
+//                        level in dB below the strongest, fine); FILE one line per tap: "delay_samples level_db", the level
+//                        relative to the peak, in ascending delay.  A measurement, not a verdict: the exit status stays what
+//                        it is without the option.  Native-rate complexf / s16 output; not with --bits-only or
+//                        --separate-converter.
 //   --state-out FILE     with --gpu-frontend: after the last frame, write where the stream stands -- the number of ETI frames
 //                        modulated since FP = 0 and both stream-state blobs (DabGpuChain::get_stream_state /
 //                        frontend_state) -- so that another run continues it
@@ -132,6 +140,8 @@ namespace {
                          "       [--spectrum FILE [--mask MASKFILE] [--oob-from HZ]]   power spectrum of everything written, per bin into FILE;\n"
                          "                        exit 3 when it lies above the mask (lines of: offset_hz limit_db)\n"
                          "       [--tii-scan]   with --batch 2 or more: read the TII of the last batch; exit 2 when it is not the one --tii configures\n"
+                         "       [--cir FILE]   impulse response of the channel the last batch went through (with --loopback --channel-cn: the\n"
+                         "                        emulator's), per tap into FILE (lines of: delay_samples level_db), paths on stderr\n"
                          "       [--state-out FILE] [--state-in FILE]   with --gpu-frontend: leave / take up the stream's state\n");
     std::exit(2);
 }
@@ -205,6 +215,7 @@ int main(int argc, char **argv)
     int dpd_bins = 64;
     unsigned long dpd_min_count = 10;
     bool tii_scan = false;
+    std::string cir_path;
     try {
         for (int i = 3; i < argc; ++i) {
             const std::string a = argv[i];
@@ -263,6 +274,7 @@ int main(int argc, char **argv)
             else if (a == "--dpd-bins") dpd_bins = std::atoi(val().c_str());
             else if (a == "--dpd-min-count") dpd_min_count = std::stoul(val());
             else if (a == "--tii-scan") tii_scan = true;
+            else if (a == "--cir") cir_path = val();
             else if (a == "--state-in") state_in = val();
             else if (a == "--state-out") state_out = val();
             else if (a == "--contexts") {
@@ -322,6 +334,16 @@ int main(int argc, char **argv)
                          : separate_converter ? "--separate-converter: the chain's own output is what is scanned"
                          : batch < 2  ? "--batch below 2: the last batch is scanned, and a scan takes two frames or more"
                                       : "u8 / s8 output: the analyser takes complexf or s16");
+            return 2;
+        }
+
+        const bool cir = !cir_path.empty();
+        if (cir && (gs.outputRate != 2048000 || (format != "complexf" && format != "s16") || bits_only || separate_converter)) {
+            std::fprintf(stderr, "dabmod_file: --cir does not go with %s\n",
+                         gs.outputRate != 2048000 ? "--rate: the estimator takes the native rate"
+                         : bits_only  ? "--bits-only: nothing is modulated"
+                         : separate_converter ? "--separate-converter: the chain's own output is what is measured"
+                                      : "u8 / s8 output: the estimator takes complexf or s16");
             return 2;
         }
 
@@ -467,6 +489,14 @@ int main(int argc, char **argv)
         double channel_sigma = -1.0;              //   < 0: not installed yet (the first batch sets the level)
         int loop_early = -1;
         size_t loop_cifs = 1;
+        // --cir: the last batch, as written or (--loopback --channel-cn) as the channel emulator left it, and its chain
+        std::vector<uint8_t> cir_last;
+        DabGpuChain *cir_chain = nullptr;
+        auto cir_keep = [&](DabGpuChain *ch, const void *p, size_t bytes) {
+            if (!cir || bytes < ch->output_bytes_per_frame()) return;
+            cir_last.assign(static_cast<const uint8_t *>(p), static_cast<const uint8_t *>(p) + bytes);
+            cir_chain = ch;
+        };
         auto loopback_batch = [&](DabGpuChain *ch, const void *p, size_t bytes) {
             dabgpu_ctx *c = ch->context();
             auto chk = [&](int rc) { if (rc) throw std::runtime_error(std::string("--loopback: ") + dabgpu_last_error(c)); };
@@ -517,6 +547,7 @@ int main(int argc, char **argv)
                 loop_rx.resize(bytes);
                 chk(dabgpu_channel(c, p, loop_fmt, n_frames * g.tf_samples, loop_rx.data(), loop_fmt));
                 p = loop_rx.data();
+                cir_keep(ch, p, bytes);
             }
             loop_bits.resize(n_frames * ch->input_bytes_per_frame());
             loop_out.resize(n * 6144);
@@ -585,6 +616,7 @@ int main(int argc, char **argv)
             out.write(static_cast<const char *>(p), static_cast<std::streamsize>(n));
             dpd_feed(ch, p, n);
             tii_keep(ch, p, n);
+            if (!(loopback && channel)) cir_keep(ch, p, n);
             --in_flight;
         };
         // two batches in flight per chain; the owning chain starts from the state behind the frame before its batch
@@ -717,6 +749,7 @@ int main(int argc, char **argv)
                 }
                 out.write(static_cast<const char *>(o->getData()), static_cast<std::streamsize>(o->getLength()));
                 dpd_feed(chain.get(), o->getData(), o->getLength());
+                cir_keep(chain.get(), o->getData(), o->getLength());
             }
             if (got < 0) {
                 std::fprintf(stderr, "dabmod_file: error while reading %s\n", in_path.c_str());
@@ -874,6 +907,56 @@ int main(int argc, char **argv)
                 tii_mismatch = head.n_entries != 1 || ent[0].comb != gs.tiiConfig.comb || ent[0].pattern != want;
                 std::fprintf(stderr, "dabmod_file: tii: configured comb %d pattern %d, read by the standard as pattern %d: %s\n",
                              gs.tiiConfig.comb, gs.tiiConfig.pattern, want, tii_mismatch ? "NOT what was read" : "read");
+            }
+        }
+        if (cir) {
+            if (!cir_chain) {
+                std::fprintf(stderr, "dabmod_file: --cir: no frame was written, there is nothing to measure\n");
+                return 1;
+            }
+            dabgpu_ctx *c = cir_chain->context();
+            dabgpu_geometry g{};
+            dabgpu_cir_config cfg{};
+            cfg.early = static_cast<int>(gs.ofdmWindowOverlap);           // where --monitor puts the window
+            for (RemoteControllable *rc : cir_chain->remote_controllables())
+                if (rc->get_rc_name() == "firfilter") cfg.early += std::stoi(rc->get_parameter("ntaps")) - 1;
+            cfg.window = 1;
+            cfg.min_ratio = 20.0f;
+            cfg.min_rel = 1e-3f;
+            const size_t n_frames = cir_last.size() / cir_chain->output_bytes_per_frame();
+            dabgpu_cir_head head;
+            dabgpu_cir_path path[DABGPU_CIR_MAX_PATHS];
+            if (dabgpu_get_geometry(c, &g) != 0 ||
+                dabgpu_cir(c, cir_last.data(), format == "s16" ? DABGPU_FMT_S16 : 0, n_frames, &cfg) != 0 ||
+                dabgpu_get_cir(c, &head, path, DABGPU_CIR_MAX_PATHS) != 0)
+                throw std::runtime_error(std::string("--cir: ") + dabgpu_last_error(c));
+            std::vector<double> pdp(static_cast<size_t>(g.spacing));
+            if (dabgpu_get_cir_profile(c, pdp.data(), nullptr) != 0) throw std::runtime_error(std::string("--cir: ") + dabgpu_last_error(c));
+            std::fprintf(stderr, "dabmod_file: cir: %zu frames%s, window %d samples early, floor %.1f dB below the peak, %d peak%s, %d path%s, "
+                                 "mean delay %+.2f, delay spread %.2f samples, %.4f of the paths' power beyond the guard interval\n",
+                         n_frames, loopback && channel ? " behind the channel" : "", cfg.early,
+                         head.peak > 0.0 && head.floor > 0.0 ? 10.0 * std::log10(head.peak / head.floor) : 0.0, head.n_peaks,
+                         head.n_peaks == 1 ? "" : "s", head.n_paths, head.n_paths == 1 ? "" : "s", head.mean_delay, head.delay_spread,
+                         head.outside_guard);
+            for (int i = 0; i < head.n_paths && i < DABGPU_CIR_MAX_PATHS; ++i)
+                std::fprintf(stderr, "dabmod_file: cir: path delay %+.0f samples level %.2f dB fine %+.3f\n", path[i].delay,
+                             10.0 * std::log10(path[i].power / path[0].power), path[i].fine);
+            std::FILE *cf = std::fopen(cir_path.c_str(), "w");
+            if (!cf) {
+                std::fprintf(stderr, "dabmod_file: cannot write %s\n", cir_path.c_str());
+                return 1;
+            }
+            // one line per tap in ascending delay: taps N/2 ... N - 1 lie before tap 0
+            const int N = g.spacing;
+            for (int i = 0; i < N; ++i) {
+                const int l = (i + N / 2) % N;
+                const double level = head.peak > 0.0 && pdp[static_cast<size_t>(l)] > 0.0
+                                         ? 10.0 * std::log10(pdp[static_cast<size_t>(l)] / head.peak) : -400.0;
+                std::fprintf(cf, "%d %.3f\n", (l < N / 2 ? l : l - N) - cfg.early, level);
+            }
+            if (std::fclose(cf) != 0) {
+                std::fprintf(stderr, "dabmod_file: cannot write %s\n", cir_path.c_str());
+                return 1;
             }
         }
         if (gs.monitor && mon.bit_errors) return 2;
