@@ -1087,6 +1087,14 @@ class Modulator:
             torch.cuda.current_stream(tensor.device).synchronize()
         return h
 
+    def _dev_call(self, fn, tensor, stream, *args):
+        """The tail of a device wrapper of the receive-side stages: fn(handle, *args, stream handle), ordered as
+        _stream_handle describes."""
+        s = self._stream_handle(tensor, stream)
+        self._chk(fn(self._h, *args, s))
+        if not s:
+            self.synchronize()
+
     def chain_dev(self, d_bits, n_frames, stages, d_out, stream=None):
         """Device path on torch tensors (coded bits -> IQ)."""
         s = self._stream_handle(d_bits, stream)
@@ -1151,12 +1159,9 @@ class Modulator:
         for tns in (d_bits_out, d_ref_bits):
             if tns is not None and tns.numel() * tns.element_size() != n_frames * self.geometry["tf_input_bytes"]:
                 raise DabGpuError("demod: bit buffers are n_frames x tf_input_bytes")
-        s = self._stream_handle(d_iq, stream)
-        self._chk(self._lib.dabgpu_demod_dev(self._h, d_iq.data_ptr(), fmt, n_frames, int(early),
-                                             d_bits_out.data_ptr() if d_bits_out is not None else None,
-                                             d_ref_bits.data_ptr() if d_ref_bits is not None else None, s))
-        if not s:
-            self.synchronize()
+        self._dev_call(self._lib.dabgpu_demod_dev, d_iq, stream, d_iq.data_ptr(), fmt, n_frames, int(early),
+                       d_bits_out.data_ptr() if d_bits_out is not None else None,
+                       d_ref_bits.data_ptr() if d_ref_bits is not None else None)
 
     def demod_soft(self, iq, early=0, ref_bits=None, want_bits=False):
         """demod() with soft output: -> soft (n_frames x 8 tf_input_bytes int8; soft 8 p + b belongs to bit 0x80 >> b of byte
@@ -1193,12 +1198,9 @@ class Modulator:
         for tns in (d_bits_out, d_ref_bits):
             if tns is not None and tns.numel() * tns.element_size() != n_frames * self.geometry["tf_input_bytes"]:
                 raise DabGpuError("demod: bit buffers are n_frames x tf_input_bytes")
-        s = self._stream_handle(d_iq, stream)
-        self._chk(self._lib.dabgpu_demod_soft_dev(self._h, d_iq.data_ptr(), fmt, n_frames, int(early), d_soft_out.data_ptr(),
-                                                  d_bits_out.data_ptr() if d_bits_out is not None else None,
-                                                  d_ref_bits.data_ptr() if d_ref_bits is not None else None, s))
-        if not s:
-            self.synchronize()
+        self._dev_call(self._lib.dabgpu_demod_soft_dev, d_iq, stream, d_iq.data_ptr(), fmt, n_frames, int(early),
+                       d_soft_out.data_ptr(), d_bits_out.data_ptr() if d_bits_out is not None else None,
+                       d_ref_bits.data_ptr() if d_ref_bits is not None else None)
 
     def set_monitor(self, enable, early=-1):
         """Demodulate every native-rate chain call's output against its own coded bits (off by default); early < 0: from
@@ -1221,16 +1223,20 @@ class Modulator:
         self._chk(self._lib.dabgpu_debug_demod_run_symbols(self._h, int(symbols)))
 
     # ---- the synchroniser: frame starts and carrier offset of a capture (include/dabgpu.h, "the synchroniser") ----
-    def _sync_host(self, iq):
+    # (the capture helpers below serve every stage that takes one: `stage` starts their refusals)
+    @staticmethod
+    def _capture_host(stage, iq):
+        """-> (the capture as a flat contiguous array, its format, its samples)"""
         iq = np.ascontiguousarray(iq)
         if iq.dtype == np.complex64:
             return iq.reshape(-1), 0, iq.size
         if iq.dtype == np.int16 and iq.size % 2 == 0:
             return iq.reshape(-1), FORMATS["s16"][0], iq.size // 2
-        raise DabGpuError("sync: input format is complex64 or int16 (interleaved re, im)")
+        raise DabGpuError(stage + ": input format is complex64 or int16 (interleaved re, im)")
 
     @staticmethod
-    def _sync_tensor(d_iq):
+    def _capture_tensor(stage, d_iq):
+        """-> (the tensor's format, its samples)"""
         import torch
         if d_iq.dtype == torch.complex64:
             return 0, d_iq.numel()
@@ -1238,7 +1244,22 @@ class Modulator:
             return FORMATS["s16"][0], d_iq.numel() // 2
         if d_iq.dtype in (torch.uint8, torch.int8):
             return FORMATS["u8" if d_iq.dtype == torch.uint8 else "s8"][0], d_iq.numel() // 2      # (the library refuses them)
-        raise DabGpuError("sync: input format is complex64 or int16 (interleaved re, im)")
+        raise DabGpuError(stage + ": input format is complex64 or int16 (interleaved re, im)")
+
+    def _frames_host(self, stage, frames):
+        """A host capture of whole transmission frames -> (flat array, format, frames)"""
+        iq, fmt, n = self._capture_host(stage, frames)
+        tf = self.geometry["tf_samples"]
+        if n % tf:
+            raise DabGpuError(stage + ": the input is whole transmission frames (tf_samples each)")
+        return iq, fmt, n // tf
+
+    def _frames_tensor(self, stage, d_frames, n_frames):
+        """A contiguous tensor that holds n_frames whole transmission frames -> its format"""
+        fmt, n = self._capture_tensor(stage, d_frames)
+        if int(n_frames) < 0 or n < int(n_frames) * self.geometry["tf_samples"] or not d_frames.is_contiguous():
+            raise DabGpuError(stage + ": the tensor is contiguous and holds n_frames whole transmission frames")
+        return fmt
 
     def sync_slots(self, n_samples):
         """Frames an extraction of an n_samples capture writes: min(max_frames, n_samples // tf_samples)."""
@@ -1246,18 +1267,15 @@ class Modulator:
 
     def sync(self, iq, max_shift=31):
         """Host path: a native-rate capture (complex64, or int16 interleaved re, im) -> sync_result()."""
-        iq, fmt, n = self._sync_host(iq)
+        iq, fmt, n = self._capture_host("sync", iq)
         self._chk(self._lib.dabgpu_sync(self._h, iq.ctypes.data, fmt, n, int(max_shift)))
         return self.sync_result()
 
     def sync_dev(self, d_iq, max_shift=31, stream=None):
         """Device path on a torch tensor (complex64, or int16 pairs), asynchronous on the stream as chain_dev; the records
         are sync_result(), the frames sync_extract_dev()."""
-        fmt, n = self._sync_tensor(d_iq)
-        s = self._stream_handle(d_iq, stream)
-        self._chk(self._lib.dabgpu_sync_dev(self._h, d_iq.data_ptr(), fmt, n, int(max_shift), s))
-        if not s:
-            self.synchronize()
+        fmt, n = self._capture_tensor("sync", d_iq)
+        self._dev_call(self._lib.dabgpu_sync_dev, d_iq, stream, d_iq.data_ptr(), fmt, n, int(max_shift))
 
     def sync_result(self):
         """The candidate frames of the most recent sync() / sync_dev() (waits for it): a list of dicts start, shift, valid, eps,
@@ -1279,7 +1297,7 @@ class Modulator:
     def sync_extract(self, iq):
         """Host path: the capture the most recent sync() was given -> (sync_slots, tf_samples) complex64, every valid frame
         rotated back by its offset and cut out at its start; frames that are not valid are zeros."""
-        iq, fmt, n = self._sync_host(iq)
+        iq, fmt, n = self._capture_host("sync", iq)
         out = np.empty((self.sync_slots(n), self.geometry["tf_samples"]), np.complex64)
         self._chk(self._lib.dabgpu_sync_extract(self._h, iq.ctypes.data, fmt, n, out.ctypes.data))
         return out
@@ -1287,13 +1305,10 @@ class Modulator:
     def sync_extract_dev(self, d_iq, d_frames_out, stream=None):
         """Device path: d_frames_out is complex64, sync_slots(n_samples) x tf_samples."""
         import torch
-        fmt, n = self._sync_tensor(d_iq)
+        fmt, n = self._capture_tensor("sync", d_iq)
         if d_frames_out.dtype != torch.complex64 or d_frames_out.numel() != self.sync_slots(n) * self.geometry["tf_samples"]:
             raise DabGpuError("sync_extract: the output is complex64, sync_slots(n_samples) x tf_samples")
-        s = self._stream_handle(d_iq, stream)
-        self._chk(self._lib.dabgpu_sync_extract_dev(self._h, d_iq.data_ptr(), fmt, n, d_frames_out.data_ptr(), s))
-        if not s:
-            self.synchronize()
+        self._dev_call(self._lib.dabgpu_sync_extract_dev, d_iq, stream, d_iq.data_ptr(), fmt, n, d_frames_out.data_ptr())
 
     # ---- the channel emulator: paths, Doppler and seeded noise on a sample stream (include/dabgpu.h, "the channel") ----
     def set_channel(self, paths, sigma=0.0, seed=0, rate_hz=2048000.0):
@@ -1319,13 +1334,7 @@ class Modulator:
     def channel(self, iq, out="complexf"):
         """Host path: the next samples of the stream (complex64, or int16 interleaved re, im) through the channel ->
         complex64, or int16 pairs with out="s16"."""
-        iq = np.ascontiguousarray(iq)
-        if iq.dtype == np.complex64:
-            fmt, n = 0, iq.size
-        elif iq.dtype == np.int16 and iq.size % 2 == 0:
-            fmt, n = FORMATS["s16"][0], iq.size // 2
-        else:
-            raise DabGpuError("channel: input format is complex64 or int16 (interleaved re, im)")
+        iq, fmt, n = self._capture_host("channel", iq)
         if out not in ("complexf", "s16"):
             raise DabGpuError("channel: formats are complexf (0) or DABGPU_FMT_S16")
         y = np.empty(n, np.complex64) if out == "complexf" else np.empty(2 * n, np.int16)
@@ -1340,38 +1349,27 @@ class Modulator:
         for t in (d_in, d_out):
             if t.dtype not in (torch.complex64, torch.int16) or (t.dtype == torch.int16 and t.numel() % 2):
                 raise DabGpuError("channel: tensors are complex64 or int16 (interleaved re, im)")
-        fi, n = self._sync_tensor(d_in)
-        fo, m = self._sync_tensor(d_out)
+        fi, n = self._capture_tensor("channel", d_in)
+        fo, m = self._capture_tensor("channel", d_out)
         if n != m or not d_in.is_contiguous() or not d_out.is_contiguous():
             raise DabGpuError("channel: input and output are contiguous and hold the same number of samples")
-        s = self._stream_handle(d_in, stream)
-        self._chk(self._lib.dabgpu_channel_dev(self._h, d_in.data_ptr(), fi, n, d_out.data_ptr(), fo, s))
-        if not s:
-            self.synchronize()
+        self._dev_call(self._lib.dabgpu_channel_dev, d_in, stream, d_in.data_ptr(), fi, n, d_out.data_ptr(), fo)
 
     # ---- the TII analyser: transmitters, levels and delays of whole frames (include/dabgpu.h, "the TII analyser") ----
     def tii_scan(self, frames, early, old_variant=False, min_ratio=12.0, min_rel=1e-3):
         """Host path: whole transmission frames at the native rate (complex64, or int16 interleaved re, im) ->
         tii_scan_result()."""
-        iq, fmt, n = self._sync_host(frames)
-        tf = self.geometry["tf_samples"]
-        if n % tf:
-            raise DabGpuError("tii_scan: the input is whole transmission frames (tf_samples each)")
+        iq, fmt, n_frames = self._frames_host("tii_scan", frames)
         cfg = _tii_scan_config(early, old_variant, min_ratio, min_rel)
-        self._chk(self._lib.dabgpu_tii_scan(self._h, iq.ctypes.data, fmt, n // tf, C.byref(cfg)))
+        self._chk(self._lib.dabgpu_tii_scan(self._h, iq.ctypes.data, fmt, n_frames, C.byref(cfg)))
         return self.tii_scan_result()
 
     def tii_scan_dev(self, d_frames, n_frames, early, old_variant=False, min_ratio=12.0, min_rel=1e-3, stream=None):
         """Device path on a torch tensor (complex64, or int16 pairs) that holds n_frames whole frames, asynchronous on the
         stream as chain_dev; the result: tii_scan_result()."""
-        fmt, n = self._sync_tensor(d_frames)
-        if int(n_frames) < 0 or n < int(n_frames) * self.geometry["tf_samples"] or not d_frames.is_contiguous():
-            raise DabGpuError("tii_scan: the tensor is contiguous and holds n_frames whole transmission frames")
+        fmt = self._frames_tensor("tii_scan", d_frames, n_frames)
         cfg = _tii_scan_config(early, old_variant, min_ratio, min_rel)
-        s = self._stream_handle(d_frames, stream)
-        self._chk(self._lib.dabgpu_tii_scan_dev(self._h, d_frames.data_ptr(), fmt, int(n_frames), C.byref(cfg), s))
-        if not s:
-            self.synchronize()
+        self._dev_call(self._lib.dabgpu_tii_scan_dev, d_frames, stream, d_frames.data_ptr(), fmt, int(n_frames), C.byref(cfg))
 
     def _tii_scan_raw(self):
         head, recs = _TiiScanHead(), (_TiiEntry * TII_SLOTS)()
@@ -1394,25 +1392,17 @@ class Modulator:
     # ---- the channel estimator: impulse response and echoes of whole frames (include/dabgpu.h, "the channel estimator") ----
     def cir(self, frames, early, window=1, min_ratio=20.0, min_rel=1e-3):
         """Host path: whole transmission frames at the native rate (complex64, or int16 interleaved re, im) -> cir_result()."""
-        iq, fmt, n = self._sync_host(frames)
-        tf = self.geometry["tf_samples"]
-        if n % tf:
-            raise DabGpuError("cir: the input is whole transmission frames (tf_samples each)")
+        iq, fmt, n_frames = self._frames_host("cir", frames)
         cfg = _cir_config(early, window, min_ratio, min_rel)
-        self._chk(self._lib.dabgpu_cir(self._h, iq.ctypes.data, fmt, n // tf, C.byref(cfg)))
+        self._chk(self._lib.dabgpu_cir(self._h, iq.ctypes.data, fmt, n_frames, C.byref(cfg)))
         return self.cir_result()
 
     def cir_dev(self, d_frames, n_frames, early, window=1, min_ratio=20.0, min_rel=1e-3, stream=None):
         """Device path on a torch tensor (complex64, or int16 pairs) that holds n_frames whole frames, asynchronous on the
         stream as chain_dev; the result: cir_result(), cir_profile()."""
-        fmt, n = self._sync_tensor(d_frames)
-        if int(n_frames) < 0 or n < int(n_frames) * self.geometry["tf_samples"] or not d_frames.is_contiguous():
-            raise DabGpuError("cir: the tensor is contiguous and holds n_frames whole transmission frames")
+        fmt = self._frames_tensor("cir", d_frames, n_frames)
         cfg = _cir_config(early, window, min_ratio, min_rel)
-        s = self._stream_handle(d_frames, stream)
-        self._chk(self._lib.dabgpu_cir_dev(self._h, d_frames.data_ptr(), fmt, int(n_frames), C.byref(cfg), s))
-        if not s:
-            self.synchronize()
+        self._dev_call(self._lib.dabgpu_cir_dev, d_frames, stream, d_frames.data_ptr(), fmt, int(n_frames), C.byref(cfg))
 
     def _cir_raw(self):
         head, recs = _CirHead(), (_CirPath * CIR_MAX_PATHS)()
@@ -1466,13 +1456,10 @@ class Modulator:
 
     def decode_dev(self, d_bits, n_tf, d_eti_out, d_ref_eti=None, stream=None):
         """Device path on torch uint8 tensors, asynchronous on the stream (as chain_dev); the figures: decode_stats."""
-        s = self._stream_handle(d_bits, stream)
         ob = C.c_size_t()
-        self._chk(self._lib.dabgpu_decode_dev(self._h, d_bits.data_ptr(), n_tf, d_eti_out.data_ptr(),
-                                              d_eti_out.numel() * d_eti_out.element_size(),
-                                              d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob), s))
-        if not s:
-            self.synchronize()
+        self._dev_call(self._lib.dabgpu_decode_dev, d_bits, stream, d_bits.data_ptr(), n_tf, d_eti_out.data_ptr(),
+                       d_eti_out.numel() * d_eti_out.element_size(),
+                       d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob))
         return ob.value
 
     def decode_soft(self, soft, ref_eti=None):
@@ -1500,13 +1487,10 @@ class Modulator:
         """Device path on torch tensors (int8 softs, uint8 images), asynchronous on the stream; the figures: decode_soft_stats."""
         if d_soft.numel() * d_soft.element_size() != 8 * n_tf * self.geometry["tf_input_bytes"]:
             raise DabGpuError("decode: input size not valid (whole transmission frames of soft metrics)")
-        s = self._stream_handle(d_soft, stream)
         ob = C.c_size_t()
-        self._chk(self._lib.dabgpu_decode_soft_dev(self._h, d_soft.data_ptr(), n_tf, d_eti_out.data_ptr(),
-                                                   d_eti_out.numel() * d_eti_out.element_size(),
-                                                   d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob), s))
-        if not s:
-            self.synchronize()
+        self._dev_call(self._lib.dabgpu_decode_soft_dev, d_soft, stream, d_soft.data_ptr(), n_tf, d_eti_out.data_ptr(),
+                       d_eti_out.numel() * d_eti_out.element_size(),
+                       d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob))
         return ob.value
 
     def decode_soft_stats(self, frame, unit=-1):
@@ -1556,11 +1540,8 @@ class Modulator:
         n = have if n_samples is None else int(n_samples)
         if n > have:
             raise DabGpuError("spectrum: n_samples exceeds the tensor")
-        s = self._stream_handle(d_iq, stream)
-        self._chk(self._lib.dabgpu_spectrum_dev(self._h, d_iq.data_ptr() if n else None, fmt, n, int(window),
-                                                int(bool(accumulate)), s))
-        if not s:
-            self.synchronize()
+        self._dev_call(self._lib.dabgpu_spectrum_dev, d_iq, stream, d_iq.data_ptr() if n else None, fmt, n, int(window),
+                       int(bool(accumulate)))
 
     def set_spectrum_monitor(self, enable, window=2):
         """Every chain call's output, whatever its rate and format, goes into the Welch sums (off by default); they
@@ -1639,11 +1620,8 @@ class Modulator:
     def dpd_xspectrum_dev(self, d_tx, d_rx, rx_offset=0, stream=None, n_samples=None):
         """Device path on torch tensors, asynchronous on the stream as chain_dev; the result: dpd_xspectrum_result()."""
         fmt, n = self._dpd_dev_pair(d_tx, d_rx, n_samples)
-        s = self._stream_handle(d_tx, stream)
-        self._chk(self._lib.dabgpu_dpd_xspectrum_dev(self._h, d_tx.data_ptr() if n else None, fmt,
-                                                     d_rx.data_ptr() if n else None, n, int(rx_offset), s))
-        if not s:
-            self.synchronize()
+        self._dev_call(self._lib.dabgpu_dpd_xspectrum_dev, d_tx, stream, d_tx.data_ptr() if n else None, fmt,
+                       d_rx.data_ptr() if n else None, n, int(rx_offset))
 
     def dpd_xspectrum_result(self):
         """Waits: S (2048 complex128: sum of TX conj(RX), FFT order), p_tx, p_rx (float64) and the segments used."""
@@ -1685,12 +1663,9 @@ class Modulator:
         """Device path of dpd_measure, asynchronous on the stream as chain_dev."""
         fmt, n = self._dpd_dev_pair(d_tx, d_rx, n_samples)
         al = _alignment_struct(alignment)
-        s = self._stream_handle(d_tx, stream)
-        self._chk(self._lib.dabgpu_dpd_measure_dev(self._h, d_tx.data_ptr() if n else None, fmt,
-                                                   d_rx.data_ptr() if n else None, n, None if al is None else C.byref(al),
-                                                   float(peak), int(n_bins), int(bool(accumulate)), s))
-        if not s:
-            self.synchronize()
+        self._dev_call(self._lib.dabgpu_dpd_measure_dev, d_tx, stream, d_tx.data_ptr() if n else None, fmt,
+                       d_rx.data_ptr() if n else None, n, None if al is None else C.byref(al),
+                       float(peak), int(n_bins), int(bool(accumulate)))
 
     def dpd_stats(self):
         """Waits: n_bins, peak, overflow, samples_used, and per bin count, sum_tx, sum_rx, sum_phase, sum_rx2, sum_phase2

@@ -694,10 +694,9 @@ int dabgpu_carriers_process_dev(dabgpu_ctx *c, const void *d_bits, size_t n_fram
     if ((rc = check_out(c, need, out_cap, out_bytes))) return rc;
     if (n_frames == 0) return DABGPU_OK;
     if (!d_bits || !d_carriers) return fail(c, DABGPU_E_INVALID, "null argument");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    if ((rc = run_carriers(c, d_bits, n_frames, (float2 *)d_carriers, chain_cic(c), s))) return rc;
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
+    if ((rc = run_carriers(c, d_bits, n_frames, (float2 *)d_carriers, chain_cic(c), call.s))) return rc;
     if (n_frames & 1) c->tii_insert = !c->tii_insert;          // like a chain call (src/TII.cpp:241-242)
     return DABGPU_OK;
 }

@@ -11,7 +11,6 @@ static_assert(DABGPU_CH_MAX_PATHS == kChMaxPaths && DABGPU_CH_MAX_DELAY == kChMa
 
 namespace {
 constexpr size_t kHistBytes = (size_t)kChMaxDelay * sizeof(float2);
-const char *const kMisaligned = "channel: buffers must be aligned to a sample (eight bytes complexf, four bytes s16)";
 
 // the refusals that depend on the settings alone (dabgpu_channel_check: no context, no device); nullptr = fine
 const char *settings_refusal(const dabgpu_channel_config *cfg)
@@ -36,15 +35,13 @@ unsigned long long doppler_step(double doppler_hz, double rate_hz)
     return (unsigned long long)(long long)std::rint(doppler_hz / rate_hz * 18446744073709551616.0);
 }
 
-size_t sample_bytes(int format) { return format ? 4 : sizeof(float2); }
-
 int check_call(dabgpu_ctx *c, const void *in, int in_format, size_t n_samples, const void *out, int out_format)
 {
-    if (!c->ch_configured) return fail(c, DABGPU_E_INVALID, "channel: no configuration (no dabgpu_set_channel call yet)");
+    if (!c->channel.configured) return fail(c, DABGPU_E_INVALID, "channel: no configuration (no dabgpu_set_channel call yet)");
     if ((in_format != 0 && in_format != DABGPU_FMT_S16) || (out_format != 0 && out_format != DABGPU_FMT_S16))
         return fail(c, DABGPU_E_INVALID, "channel: formats are complexf (0) or DABGPU_FMT_S16");
     if (!in || !out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (((uintptr_t)in & (in_format ? 3u : 7u)) || ((uintptr_t)out & (out_format ? 3u : 7u))) return fail(c, DABGPU_E_INVALID, kMisaligned);
+    if (!sample_aligned(in, in_format) || !sample_aligned(out, out_format)) return fail_misaligned(c, "channel");
     if (n_samples == 0) return fail(c, DABGPU_E_INVALID, "channel: n_samples must not be 0");
     if (n_samples > ((size_t)1 << 40)) return fail(c, DABGPU_E_INVALID, "channel: n_samples must not exceed 2^40");
     const uintptr_t i0 = (uintptr_t)in, i1 = i0 + n_samples * sample_bytes(in_format);
@@ -83,16 +80,16 @@ int dabgpu_set_channel(dabgpu_ctx *c, const dabgpu_channel_config *cfg)
         }
         if (!rotating) a.n_static = a.n_paths;
     }
-    c->ch_args = a;
-    c->ch_configured = true;
+    c->channel.args = a;
+    c->channel.configured = true;
     return DABGPU_OK;
 }
 
 int dabgpu_channel_reset(dabgpu_ctx *c, uint64_t position)
 {
     CTXCHK(c);
-    c->ch_zero_pending = true;            // (the next call zeroes the history on its own stream, in front of its kernels)
-    c->ch_position = position;
+    c->channel.zero_pending = true;       // (the next call zeroes the history on its own stream, in front of its kernels)
+    c->channel.position = position;
     return DABGPU_OK;
 }
 
@@ -100,8 +97,8 @@ int dabgpu_get_channel_position(dabgpu_ctx *c, uint64_t *position)
 {
     CTXCHK(c);
     if (!position) return fail(c, DABGPU_E_INVALID, "null argument");
-    HIPCHK(c, hipStreamSynchronize(c->ch_stream ? c->ch_stream : c->stream));
-    *position = c->ch_position;
+    HIPCHK(c, wait_result(c, c->channel.stream));
+    *position = c->channel.position;
     return DABGPU_OK;
 }
 
@@ -109,7 +106,7 @@ int dabgpu_debug_channel_run_samples(dabgpu_ctx *c, int samples)
 {
     CTXCHK(c);
     if (samples < 0) return fail(c, DABGPU_E_INVALID, "channel: samples per workgroup must not be negative (0 = chosen)");
-    c->ch_run_samples = samples;
+    c->channel.run_samples = samples;
     return DABGPU_OK;
 }
 
@@ -118,30 +115,29 @@ int dabgpu_channel_dev(dabgpu_ctx *c, const void *d_in, int in_format, size_t n_
     CTXCHK(c);
     int rc = check_call(c, d_in, in_format, n_samples, d_out, out_format);
     if (rc) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;       // (d_in: a chain call's output on any lane)
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    HIPCHK(c, c->d_ch_hist.reserve(2 * kHistBytes));
-    float2 *cur = (float2 *)((char *)c->d_ch_hist.p + (size_t)c->ch_hist_cur * kHistBytes);
-    float2 *next = (float2 *)((char *)c->d_ch_hist.p + (size_t)(c->ch_hist_cur ^ 1) * kHistBytes);
-    if (c->ch_zero_pending) {
-        HIPCHK(c, hipMemsetAsync(cur, 0, kHistBytes, s));
-        c->ch_zero_pending = false;
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
+    HIPCHK(c, c->channel.hist.reserve(2 * kHistBytes));
+    float2 *cur = (float2 *)((char *)c->channel.hist.p + (size_t)c->channel.hist_cur * kHistBytes);
+    float2 *next = (float2 *)((char *)c->channel.hist.p + (size_t)(c->channel.hist_cur ^ 1) * kHistBytes);
+    if (c->channel.zero_pending) {
+        HIPCHK(c, hipMemsetAsync(cur, 0, kHistBytes, call.s));
+        c->channel.zero_pending = false;
     }
-    ChannelArgs a = c->ch_args;
+    ChannelArgs a = c->channel.args;
     a.in = d_in;
     a.out = d_out;
     a.hist = cur;
     a.n = (long long)n_samples;
-    a.position = c->ch_position;
+    a.position = c->channel.position;
     a.in_fmt = in_format ? 1 : 0;
     a.out_fmt = out_format ? 1 : 0;
-    a.run = channel_run(n_samples, c->ch_run_samples);
-    HIPCHK(c, launch_channel(a, s));
-    HIPCHK(c, launch_channel_history(d_in, a.in_fmt, a.n, cur, next, s));
-    c->ch_hist_cur ^= 1;
-    c->ch_position += n_samples;
-    c->ch_stream = s;
+    a.run = channel_run(n_samples, c->channel.run_samples);
+    HIPCHK(c, launch_channel(a, call.s));
+    HIPCHK(c, launch_channel_history(d_in, a.in_fmt, a.n, cur, next, call.s));
+    c->channel.hist_cur ^= 1;
+    c->channel.position += n_samples;
+    c->channel.stream = call.s;
     return DABGPU_OK;
 }
 
@@ -153,10 +149,10 @@ int dabgpu_channel(dabgpu_ctx *c, const void *in, int in_format, size_t n_sample
     if ((rc = dabgpu_synchronize(c))) return rc;
     const size_t out_bytes = n_samples * sample_bytes(out_format);
     HostIO io(c);
-    if ((rc = io.in(c->d_ch_in, in, n_samples * sample_bytes(in_format)))) return rc;
-    HIPCHK(c, c->d_ch_out.reserve(std::max<size_t>(out_bytes, 16)));
-    if ((rc = dabgpu_channel_dev(c, c->d_ch_in.p, in_format, n_samples, c->d_ch_out.p, out_format, c->stream))) return rc;
-    return io.out(out, c->d_ch_out.p, out_bytes);
+    if ((rc = io.in(c->channel.in, in, n_samples * sample_bytes(in_format)))) return rc;
+    HIPCHK(c, c->channel.out.reserve(std::max<size_t>(out_bytes, 16)));
+    if ((rc = dabgpu_channel_dev(c, c->channel.in.p, in_format, n_samples, c->channel.out.p, out_format, c->stream))) return rc;
+    return io.out(out, c->channel.out.p, out_bytes);
 }
 
 }  // extern "C"

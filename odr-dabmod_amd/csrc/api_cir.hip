@@ -34,12 +34,7 @@ const char *settings_refusal(const Geometry &g, size_t n_frames, size_t max_fram
 int check_cir(dabgpu_ctx *c, const void *frames, int format, size_t n_frames, const dabgpu_cir_config *cfg, bool device)
 {
     if (const char *why = settings_refusal(c->g, n_frames, (size_t)c->max_frames, cfg)) return fail(c, DABGPU_E_INVALID, why);
-    if (format != 0 && format != DABGPU_FMT_S16)
-        return fail(c, DABGPU_E_INVALID, "cir: input format is complexf (0) or DABGPU_FMT_S16");
-    if (!frames) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (device && ((uintptr_t)frames & (format ? 3u : 7u)))
-        return fail(c, DABGPU_E_INVALID, "cir: buffers must be aligned to a sample (eight bytes complexf, four bytes s16)");
-    return DABGPU_OK;
+    return check_capture(c, "cir", frames, format, device);
 }
 
 // S_w: the K weights in ascending carrier order, in float64
@@ -58,14 +53,13 @@ int dabgpu_cir_dev(dabgpu_ctx *c, const void *d_frames, int format, size_t n_fra
     int rc = check_cir(c, d_frames, format, n_frames, cfg, true);
     if (rc) return rc;
     if ((rc = apply_settings(c))) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;       // (d_frames: a chain call's output on any lane)
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
     const size_t N = (size_t)c->g.N;
-    HIPCHK(c, c->d_cir.reserve(kResultBytes + 2 * N * sizeof(double)));
-    HIPCHK(c, c->d_cir_rows.reserve((size_t)c->max_frames * 2 * N * sizeof(double)));
-    c->cir_done = false;                                              // (a failed launch leaves no result behind)
-    HIPCHK(c, hipMemsetAsync(c->d_cir.p, 0, kResultBytes, s));
+    HIPCHK(c, c->cir.result.reserve(kResultBytes + 2 * N * sizeof(double)));
+    HIPCHK(c, c->cir.rows.reserve((size_t)c->max_frames * 2 * N * sizeof(double)));
+    c->cir.done = false;                                              // (a failed launch leaves no result behind)
+    HIPCHK(c, hipMemsetAsync(c->cir.result.p, 0, kResultBytes, call.s));
     CirArgs a{};
     a.g = c->g;
     a.t = tables_of(c);
@@ -77,50 +71,45 @@ int dabgpu_cir_dev(dabgpu_ctx *c, const void *d_frames, int format, size_t n_fra
     a.min_ratio = cfg->min_ratio;
     a.min_rel = cfg->min_rel;
     a.sum_w = weight_sum(c->g.K, cfg->window);
-    a.rows = (double *)c->d_cir_rows.p;
-    a.head = (CirHead *)c->d_cir.p;
-    a.paths = (CirPath *)((char *)c->d_cir.p + kHeadBytes);
-    a.pdp = (double *)((char *)c->d_cir.p + kResultBytes);
+    a.rows = (double *)c->cir.rows.p;
+    a.head = (CirHead *)c->cir.result.p;
+    a.paths = (CirPath *)((char *)c->cir.result.p + kHeadBytes);
+    a.pdp = (double *)((char *)c->cir.result.p + kResultBytes);
     a.resp = a.pdp + N;
-    HIPCHK(c, launch_cir(a, s));
-    c->cir_done = true;
-    c->cir_stream = s;
+    HIPCHK(c, launch_cir(a, call.s));
+    c->cir.done = true;
+    c->cir.stream = call.s;
     return DABGPU_OK;
 }
 
 int dabgpu_cir(dabgpu_ctx *c, const void *frames, int format, size_t n_frames, const dabgpu_cir_config *cfg)
 {
     CTXCHK(c);
-    int rc = check_cir(c, frames, format, n_frames, cfg, false);
-    if (rc) return rc;
-    if ((rc = dabgpu_synchronize(c))) return rc;
-    HostIO io(c);
-    if ((rc = io.in(c->d_cir_in, frames, n_frames * tf_samples(c->g) * (format ? 4 : sizeof(float2))))) return rc;
-    if ((rc = dabgpu_cir_dev(c, c->d_cir_in.p, format, n_frames, cfg, c->stream))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return DABGPU_OK;
+    if (int rc = check_cir(c, frames, format, n_frames, cfg, false)) return rc;
+    return capture_from_host(c, c->cir.in, frames, n_frames * tf_samples(c->g) * sample_bytes(format),
+                             [&](const void *d_frames) { return dabgpu_cir_dev(c, d_frames, format, n_frames, cfg, c->stream); });
 }
 
 int dabgpu_get_cir(dabgpu_ctx *c, dabgpu_cir_head *head, dabgpu_cir_path *out, size_t cap)
 {
     CTXCHK(c);
     if (!head || (cap && !out)) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (!c->cir_done) return fail(c, DABGPU_E_INVALID, "no channel estimate (no dabgpu_cir* call yet)");
-    HIPCHK(c, hipStreamSynchronize(c->cir_stream ? c->cir_stream : c->stream));
-    HIPCHK(c, hipMemcpy(head, c->d_cir.p, kHeadBytes, hipMemcpyDeviceToHost));
+    if (!c->cir.done) return fail(c, DABGPU_E_INVALID, "no channel estimate (no dabgpu_cir* call yet)");
+    HIPCHK(c, wait_result(c, c->cir.stream));
+    HIPCHK(c, hipMemcpy(head, c->cir.result.p, kHeadBytes, hipMemcpyDeviceToHost));
     const size_t m = std::min<size_t>(cap, kCirMaxPaths);             // (whole slots: zeros behind n_paths)
-    if (m) HIPCHK(c, hipMemcpy(out, (const char *)c->d_cir.p + kHeadBytes, m * sizeof(CirPath), hipMemcpyDeviceToHost));
+    if (m) HIPCHK(c, hipMemcpy(out, (const char *)c->cir.result.p + kHeadBytes, m * sizeof(CirPath), hipMemcpyDeviceToHost));
     return DABGPU_OK;
 }
 
 int dabgpu_get_cir_profile(dabgpu_ctx *c, double *pdp, double *resp)
 {
     CTXCHK(c);
-    if (!c->cir_done) return fail(c, DABGPU_E_INVALID, "no channel estimate (no dabgpu_cir* call yet)");
-    HIPCHK(c, hipStreamSynchronize(c->cir_stream ? c->cir_stream : c->stream));
+    if (!c->cir.done) return fail(c, DABGPU_E_INVALID, "no channel estimate (no dabgpu_cir* call yet)");
+    HIPCHK(c, wait_result(c, c->cir.stream));
     const size_t bytes = (size_t)c->g.N * sizeof(double);
-    if (pdp) HIPCHK(c, hipMemcpy(pdp, (const char *)c->d_cir.p + kResultBytes, bytes, hipMemcpyDeviceToHost));
-    if (resp) HIPCHK(c, hipMemcpy(resp, (const char *)c->d_cir.p + kResultBytes + bytes, bytes, hipMemcpyDeviceToHost));
+    if (pdp) HIPCHK(c, hipMemcpy(pdp, (const char *)c->cir.result.p + kResultBytes, bytes, hipMemcpyDeviceToHost));
+    if (resp) HIPCHK(c, hipMemcpy(resp, (const char *)c->cir.result.p + kResultBytes + bytes, bytes, hipMemcpyDeviceToHost));
     return DABGPU_OK;
 }
 

@@ -540,27 +540,9 @@ void dabgpu_destroy(dabgpu_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto &l : c->lane)
         if (l.stream) (void)hipStreamSynchronize(l.stream);
-    for (DevBuf *b : {&c->d_twiddle, &c->d_src, &c->d_dst, &c->d_phq, &c->d_mag, &c->d_taps, &c->d_firh, &c->d_eqg,
-                      &c->d_window, &c->d_coef, &c->d_rs_window, &c->d_rs_tw_in, &c->d_rs_tw_out,
-                      &c->d_rs_halo, &c->d_rs_tw_s, &c->d_rs_tw_l, &c->d_a, &c->d_b, &c->d_c, &c->d_car, &c->d_cic_chain, &c->d_car_acp, &c->d_in, &c->d_out, &c->d_count, &c->d_fmt, &c->d_clip, &c->d_phase, &c->d_seed,
-                      &c->d_acp, &c->d_tii_car, &c->d_tii_frame, &c->d_gain1, &c->d_gains, &c->d_cic,
-                      &c->d_cfr_counts, &c->d_cfr_mer, &c->d_cfr_papr, &c->d_cfr_tmp,
-                      &c->d_fe_prbs, &c->d_fe_units, &c->d_fe_owner, &c->d_fe_hist, &c->d_fe_tmp, &c->d_fe_fic, &c->d_fe_eti,
-                      &c->d_fe_seed, &c->d_demod_stats, &c->d_demod_bits, &c->d_demod_ref, &c->d_demod_soft,
-                      &c->d_spec_tw, &c->d_spec_win, &c->d_spec_rows, &c->d_spec_acc, &c->d_spec_in,
-                      &c->d_dpd_tw, &c->d_dpd_rows, &c->d_dpd_xacc, &c->d_dpd_sums, &c->d_dpd_edge, &c->d_dpd_tx, &c->d_dpd_rx,
-                      &c->d_dec_rows, &c->d_dec_tmp, &c->d_dec_slot, &c->d_dec_surv, &c->d_dec_stats, &c->d_dec_in, &c->d_dec_out,
-                      &c->d_dec_ref, &c->d_decs_rows, &c->d_decs_tmp, &c->d_decs_stats, &c->d_decs_in,
-                      &c->d_sync, &c->d_sync_power, &c->d_sync_in, &c->d_sync_out,
-                      &c->d_ch_hist, &c->d_ch_in, &c->d_ch_out,
-                      &c->d_tii_scan, &c->d_tii_rows, &c->d_tii_bins, &c->d_tii_in, &c->d_cir, &c->d_cir_rows, &c->d_cir_in})
-        b->release();
     for (auto &sl : c->slot) {
-        sl.d_eti.release();
         if (sl.h_in) (void)hipHostFree(sl.h_in);
         if (sl.h_clip) (void)hipHostFree(sl.h_clip);
-        sl.d_in.release();
-        sl.d_out.release();
         if (sl.computed) (void)hipEventDestroy(sl.computed);
         if (sl.copied) (void)hipEventDestroy(sl.copied);
     }
@@ -573,14 +555,12 @@ void dabgpu_destroy(dabgpu_ctx *c)
     for (auto &l : c->lane) {
         if (l.stream) { (void)hipStreamSynchronize(l.stream); (void)hipStreamDestroy(l.stream); }
         if (l.ev) (void)hipEventDestroy(l.ev);
-        for (DevBuf *b : {&l.d_a, &l.d_b, &l.d_fmt, &l.d_clip, &l.d_gain1, &l.d_gains, &l.d_cfr_counts, &l.d_cfr_mer, &l.d_cfr_papr, &l.d_cfr_tmp, &l.d_car})
-            b->release();
     }
     for (hipEvent_t e : {c->ho_prod[0], c->ho_prod[1], c->ho_cons[0], c->ho_cons[1], c->ho_start, c->ho_join, c->own_ev})
         if (e) (void)hipEventDestroy(e);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                             // (every DevBuf frees itself, with the context's device current)
 }
 
 int dabgpu_get_geometry(const dabgpu_ctx *c, dabgpu_geometry *g)
@@ -771,7 +751,7 @@ int dabgpu_get_num_clipped(dabgpu_ctx *c, size_t *num_clipped)
     }
     LaneScope scratch(c, c->clip_lane);
     if (!c->d_clip.p || !c->clip_valid) return DABGPU_OK;
-    HIPCHK(c, hipStreamSynchronize(c->clip_stream ? c->clip_stream : c->stream));
+    HIPCHK(c, wait_result(c, c->clip_stream));
     unsigned long long v = 0;
     HIPCHK(c, hipMemcpy(&v, c->d_clip.p, sizeof v, hipMemcpyDeviceToHost));
     *num_clipped = (size_t)v;

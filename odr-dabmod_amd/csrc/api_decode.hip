@@ -1,7 +1,7 @@
 // api_decode.hip -- the channel decoder of decode.hip behind the C-ABI (include/dabgpu.h, "the channel decoder"): coded bits in
 // the chain's input layout -> the ETI payload, per (frame, unit) figures.  The reference has no receiver: nothing here replaces
 // a plugin of its flowgraph, which is why no entry is named *_process.  The layout is the front-end's (dabgpu_frontend_configure);
-// the stream state is the last fifteen received rows, dabgpu_ctx::d_dec_rows.
+// the stream state is the last fifteen received rows of either metric width, DecodeStream::rows.
 #include "dabgpu_ctx.h"
 
 using namespace dabgpu;
@@ -37,117 +37,125 @@ std::string overlap_message(const dabgpu_fe_layout &L)
            std::to_string(cu) + " (the bits of the earlier one were never transmitted there)";
 }
 
-size_t dec_row_bytes(const dabgpu_ctx *c) { return (size_t)c->fe_fic_out + kFeCifBytes; }
-
 // every refusal of a call, before anything is queued
 int check_decode(dabgpu_ctx *c, size_t n_tf, size_t out_cap, size_t *out_bytes)
 {
     if (!c->fe_configured) return fail(c, DABGPU_E_INVALID, kDecNotConfigured);
-    if (!c->dec_refusal.empty()) return fail(c, DABGPU_E_INVALID, c->dec_refusal);
+    if (!c->decode.refusal.empty()) return fail(c, DABGPU_E_INVALID, c->decode.refusal);
     if (!n_tf) return fail(c, DABGPU_E_INVALID, "decode: n_tf is at least one transmission frame");
     if (n_tf > (size_t)c->max_frames) return fail(c, DABGPU_E_CAPACITY, "n_frames exceeds max_frames of the context");
     return check_out(c, n_tf * (size_t)c->fe_cifs * 6144, out_cap, out_bytes);
 }
 
-// the buffers of the first use: rows, survivor scratch and records for max_frames transmission frames
-int reserve_decode(dabgpu_ctx *c)
+// What differs between the two metric widths beside DecodeStream::width: the args struct, where the input goes in it, the
+// LDS figure (hard: the steps of the layout's longest unit; soft: 8 x the punctured bytes of its largest) and the launches.
+void set_input(DecArgs &a, const dabgpu_ctx *c, const void *d_bits)
 {
-    const size_t max_out = (size_t)c->max_frames * (size_t)c->fe_cifs;
-    HIPCHK(c, c->d_dec_rows.reserve(((size_t)kFeHistory + max_out) * dec_row_bytes(c)));
-    HIPCHK(c, c->d_dec_tmp.reserve((size_t)kFeHistory * dec_row_bytes(c)));
-    HIPCHK(c, c->d_dec_surv.reserve(std::max<size_t>(max_out * c->dec_slot.back() * sizeof(unsigned long long), 16)));
-    HIPCHK(c, c->d_dec_stats.reserve(max_out * (size_t)c->fe_units * sizeof(DecUnitStats)));
-    return DABGPU_OK;
-}
-
-int queue_decode(dabgpu_ctx *c, const void *d_bits, size_t n_tf, void *d_out, const void *d_ref, hipStream_t s)
-{
-    int rc = reserve_decode(c);
-    if (rc) return rc;
-    const size_t n = n_tf * (size_t)c->fe_cifs, row = dec_row_bytes(c), hist = (size_t)kFeHistory * row;
-    if (c->dec_zero_pending) {
-        // (the slot table travels with the zero history: both belong to the layout)
-        HIPCHK(c, upload(c->d_dec_slot, c->dec_slot, s));
-        HIPCHK(c, hipMemsetAsync(c->d_dec_rows.p, 0, hist, s));
-        c->dec_zero_pending = false;
-    }
-    HIPCHK(c, hipMemsetAsync(d_out, 0, n * 6144, s));
-    DecArgs a{};
     a.bits = (const uint8_t *)d_bits;
-    a.rows = (uint8_t *)c->d_dec_rows.p;
-    a.prbs = (const uint8_t *)c->d_fe_prbs.p;
-    a.units = (const FeUnit *)c->d_fe_units.p;
-    a.slot = (const uint32_t *)c->d_dec_slot.p;
-    a.surv = (unsigned long long *)c->d_dec_surv.p;
-    a.out = (uint8_t *)d_out;
-    a.ref = (const uint8_t *)d_ref;
-    a.stats = (DecUnitStats *)c->d_dec_stats.p;
-    a.n_out = (int)n; a.n_units = c->fe_units; a.cifs = c->fe_cifs; a.fic_out = c->fe_fic_out;
-    for (size_t u = 0; u + 1 < c->dec_slot.size(); ++u) a.sym_bytes = std::max(a.sym_bytes, (int)(c->dec_slot[u + 1] - c->dec_slot[u]));
-    const unsigned long long lead = c->dec_pos < (unsigned long long)kFeHistory ? (unsigned long long)kFeHistory - c->dec_pos : 0;
-    a.first_valid = (int)std::min<unsigned long long>(lead, n);
-    HIPCHK(c, launch_dec_rows(a, s));
-    HIPCHK(c, launch_dec_decode(a, s));
-    // the last fifteen rows move to the front, in stream order (through a second buffer where they overlap)
-    const uint8_t *last = a.rows + n * row;
-    if (n >= (size_t)kFeHistory) {
-        HIPCHK(c, hipMemcpyAsync(a.rows, last, hist, hipMemcpyDeviceToDevice, s));
-    } else {
-        HIPCHK(c, hipMemcpyAsync(c->d_dec_tmp.p, last, hist, hipMemcpyDeviceToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(a.rows, c->d_dec_tmp.p, hist, hipMemcpyDeviceToDevice, s));
-    }
-    c->dec_pos += n;
-    c->dec_frames = n;
-    c->dec_first_valid = (size_t)a.first_valid;
-    c->dec_stream = s;
-    return DABGPU_OK;
+    const std::vector<uint32_t> &slot = c->decode.slot;
+    for (size_t u = 0; u + 1 < slot.size(); ++u) a.sym_bytes = std::max(a.sym_bytes, (int)(slot[u + 1] - slot[u]));
 }
-
-// ---- the soft decoder: the same call on int8 metrics and on a history of its own (eight bytes where the hard one has one)
-int queue_decode_soft(dabgpu_ctx *c, const void *d_soft, size_t n_tf, void *d_out, const void *d_ref, hipStream_t s)
+void set_input(DecSoftArgs &a, const dabgpu_ctx *c, const void *d_soft)
 {
-    const size_t max_out = (size_t)c->max_frames * (size_t)c->fe_cifs;
-    const size_t n = n_tf * (size_t)c->fe_cifs, row = 8 * dec_row_bytes(c), hist = (size_t)kFeHistory * row;
-    HIPCHK(c, c->d_decs_rows.reserve(((size_t)kFeHistory + max_out) * row));
-    HIPCHK(c, c->d_decs_tmp.reserve(hist));
-    HIPCHK(c, c->d_dec_surv.reserve(std::max<size_t>(max_out * c->dec_slot.back() * sizeof(unsigned long long), 16)));
-    HIPCHK(c, c->d_decs_stats.reserve(max_out * (size_t)c->fe_units * sizeof(DecSoftUnitStats)));
-    if (c->decs_zero_pending) {
-        HIPCHK(c, upload(c->d_dec_slot, c->dec_slot, s));
-        HIPCHK(c, hipMemsetAsync(c->d_decs_rows.p, 0, hist, s));
-        c->decs_zero_pending = false;
-    }
-    HIPCHK(c, hipMemsetAsync(d_out, 0, n * 6144, s));
-    DecSoftArgs a{};
     a.soft = (const int8_t *)d_soft;
-    a.rows = (int8_t *)c->d_decs_rows.p;
-    a.prbs = (const uint8_t *)c->d_fe_prbs.p;
-    a.units = (const FeUnit *)c->d_fe_units.p;
-    a.slot = (const uint32_t *)c->d_dec_slot.p;
-    a.surv = (unsigned long long *)c->d_dec_surv.p;
-    a.out = (uint8_t *)d_out;
-    a.ref = (const uint8_t *)d_ref;
-    a.stats = (DecSoftUnitStats *)c->d_decs_stats.p;
-    a.n_out = (int)n; a.n_units = c->fe_units; a.cifs = c->fe_cifs; a.fic_out = c->fe_fic_out;
     unsigned out_bytes = (unsigned)c->fe_fic_out;
     for (uint32_t i = 0; i < c->fe_layout.nst; ++i) out_bytes = std::max(out_bytes, 8u * (unsigned)c->fe_layout.sub[i].cu);
     a.lds_bytes = (int)(8 * out_bytes);
-    const unsigned long long lead = c->decs_pos < (unsigned long long)kFeHistory ? (unsigned long long)kFeHistory - c->decs_pos : 0;
-    a.first_valid = (int)std::min<unsigned long long>(lead, n);
-    HIPCHK(c, launch_dec_soft_rows(a, s));
-    HIPCHK(c, launch_dec_soft_decode(a, s));
-    const int8_t *last = a.rows + n * row;
-    if (n >= (size_t)kFeHistory) {
-        HIPCHK(c, hipMemcpyAsync(a.rows, last, hist, hipMemcpyDeviceToDevice, s));
-    } else {
-        HIPCHK(c, hipMemcpyAsync(c->d_decs_tmp.p, last, hist, hipMemcpyDeviceToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(a.rows, c->d_decs_tmp.p, hist, hipMemcpyDeviceToDevice, s));
+}
+hipError_t launch_rows(const DecArgs &a, hipStream_t s) { return launch_dec_rows(a, s); }
+hipError_t launch_rows(const DecSoftArgs &a, hipStream_t s) { return launch_dec_soft_rows(a, s); }
+hipError_t launch_decode(const DecArgs &a, hipStream_t s) { return launch_dec_decode(a, s); }
+hipError_t launch_decode(const DecSoftArgs &a, hipStream_t s) { return launch_dec_soft_decode(a, s); }
+
+// one call on `s`, for either width (Args: DecArgs on st = decode.hard, DecSoftArgs on decode.soft).  The buffers of the
+// first use: rows, survivor scratch and records for max_frames transmission frames.
+template <typename Args>
+int queue_decode(dabgpu_ctx *c, DecodeStream &st, const void *d_in, size_t n_tf, void *d_out, const void *d_ref, hipStream_t s)
+{
+    DecodeState &d = c->decode;
+    Args a{};
+    const size_t max_out = (size_t)c->max_frames * (size_t)c->fe_cifs;
+    const size_t n = n_tf * (size_t)c->fe_cifs, row = st.width * ((size_t)c->fe_fic_out + kFeCifBytes), hist = (size_t)kFeHistory * row;
+    HIPCHK(c, st.rows.reserve(((size_t)kFeHistory + max_out) * row));
+    HIPCHK(c, st.tmp.reserve(hist));
+    HIPCHK(c, d.surv.reserve(std::max<size_t>(max_out * d.slot.back() * sizeof(unsigned long long), 16)));
+    HIPCHK(c, st.stats.reserve(max_out * (size_t)c->fe_units * sizeof(*a.stats)));
+    if (st.zero_pending) {
+        // (the slot table travels with the zero history: both belong to the layout)
+        HIPCHK(c, upload(d.slot_dev, d.slot, s));
+        HIPCHK(c, hipMemsetAsync(st.rows.p, 0, hist, s));
+        st.zero_pending = false;
     }
-    c->decs_pos += n;
-    c->decs_frames = n;
-    c->decs_first_valid = (size_t)a.first_valid;
-    c->decs_stream = s;
+    HIPCHK(c, hipMemsetAsync(d_out, 0, n * 6144, s));
+    set_input(a, c, d_in);
+    a.rows = (decltype(a.rows))st.rows.p;
+    a.prbs = (const uint8_t *)c->d_fe_prbs.p;
+    a.units = (const FeUnit *)c->d_fe_units.p;
+    a.slot = (const uint32_t *)d.slot_dev.p;
+    a.surv = (unsigned long long *)d.surv.p;
+    a.out = (uint8_t *)d_out;
+    a.ref = (const uint8_t *)d_ref;
+    a.stats = (decltype(a.stats))st.stats.p;
+    a.n_out = (int)n; a.n_units = c->fe_units; a.cifs = c->fe_cifs; a.fic_out = c->fe_fic_out;
+    const unsigned long long lead = st.pos < (unsigned long long)kFeHistory ? (unsigned long long)kFeHistory - st.pos : 0;
+    a.first_valid = (int)std::min<unsigned long long>(lead, n);
+    HIPCHK(c, launch_rows(a, s));
+    HIPCHK(c, launch_decode(a, s));
+    // the last fifteen rows move to the front, in stream order (through a second buffer where they overlap)
+    const char *last = (const char *)st.rows.p + n * row;
+    if (n >= (size_t)kFeHistory) {
+        HIPCHK(c, hipMemcpyAsync(st.rows.p, last, hist, hipMemcpyDeviceToDevice, s));
+    } else {
+        HIPCHK(c, hipMemcpyAsync(st.tmp.p, last, hist, hipMemcpyDeviceToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(st.rows.p, st.tmp.p, hist, hipMemcpyDeviceToDevice, s));
+    }
+    st.pos += n;
+    st.frames = n;
+    st.first_valid = (size_t)a.first_valid;
+    st.stream = s;
     return DABGPU_OK;
+}
+
+// the device-pointer entry of either width; `misaligned`: its refusal of an input that is not dword aligned
+template <typename Args>
+int decode_dev(dabgpu_ctx *c, DecodeStream &st, const char *misaligned, const void *d_in, size_t n_tf, void *d_eti_out, size_t out_cap,
+               const void *d_ref_eti, size_t *out_bytes, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_decode(c, n_tf, out_cap, out_bytes)) return rc;
+    if (!d_in || !d_eti_out) return fail(c, DABGPU_E_INVALID, "null argument");
+    if ((uintptr_t)d_in & 3) return fail(c, DABGPU_E_INVALID, misaligned);
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
+    return queue_decode<Args>(c, st, d_in, n_tf, d_eti_out, d_ref_eti, call.s);
+}
+
+// the host-pointer entry of either width
+template <typename Args>
+int decode_host(dabgpu_ctx *c, DecodeStream &st, const void *in, size_t n_tf, uint8_t *eti_out, size_t out_cap, const uint8_t *ref_eti,
+                size_t *out_bytes)
+{
+    CTXCHK(c);
+    int rc = check_decode(c, n_tf, out_cap, out_bytes);
+    if (rc) return rc;
+    if (!in || !eti_out) return fail(c, DABGPU_E_INVALID, "null argument");
+    if ((rc = own_stream_joins_lanes(c))) return rc;
+    const size_t need = n_tf * (size_t)c->fe_cifs * 6144;
+    HostIO io(c);
+    if ((rc = io.in(st.in, in, st.width * n_tf * tf_in_bytes(c->g)))) return rc;
+    if (ref_eti && (rc = io.in(c->decode.ref, ref_eti, need))) return rc;
+    HIPCHK(c, c->decode.out.reserve(need));
+    if ((rc = queue_decode<Args>(c, st, st.in.p, n_tf, c->decode.out.p, ref_eti ? c->decode.ref.p : nullptr, c->stream))) return rc;
+    return io.out(eti_out, c->decode.out.p, need);
+}
+
+// both streams back at their start: the next call of each zeroes its history
+void reset_streams(dabgpu_ctx *c)
+{
+    for (DecodeStream *st : {&c->decode.hard, &c->decode.soft}) {
+        st->pos = 0;
+        st->zero_pending = true;
+    }
 }
 
 }  // namespace
@@ -156,19 +164,15 @@ namespace dabgpu_api {
 
 int decode_configure(dabgpu_ctx *c)
 {
-    c->dec_refusal = overlap_message(c->fe_layout);
+    c->decode.refusal = overlap_message(c->fe_layout);
     // a unit's slot: its trellis steps rounded up to 64 survivor words (the kernel stores 64 at a time)
     std::vector<uint32_t> slot(1, 0u);
     auto add = [&](uint32_t in_bytes) { slot.push_back(slot.back() + (8 * in_bytes + 6 + 63) / 64 * 64); };
     add(c->fe_layout.fic_bytes);
     for (uint32_t i = 0; i < c->fe_layout.nst; ++i) add(c->fe_layout.sub[i].framesize);
-    c->dec_slot = slot;
-    c->dec_pos = 0;
-    c->dec_zero_pending = true;
-    c->dec_frames = 0;
-    c->decs_pos = 0;
-    c->decs_zero_pending = true;
-    c->decs_frames = 0;
+    c->decode.slot = slot;
+    reset_streams(c);
+    c->decode.hard.frames = c->decode.soft.frames = 0;
     return DABGPU_OK;
 }
 
@@ -195,57 +199,36 @@ int dabgpu_decode_reset(dabgpu_ctx *c)
     if (!c->fe_configured) return fail(c, DABGPU_E_INVALID, kDecNotConfigured);
     const int rc = dabgpu_synchronize(c);
     if (rc) return rc;
-    c->dec_pos = 0;
-    c->dec_zero_pending = true;
-    c->decs_pos = 0;
-    c->decs_zero_pending = true;
+    reset_streams(c);
     return DABGPU_OK;
 }
 
 int dabgpu_decode_dev(dabgpu_ctx *c, const void *d_bits, size_t n_tf, void *d_eti_out, size_t out_cap, const void *d_ref_eti,
                       size_t *out_bytes, void *stream)
 {
-    CTXCHK(c);
-    int rc = check_decode(c, n_tf, out_cap, out_bytes);
-    if (rc) return rc;
-    if (!d_bits || !d_eti_out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if ((uintptr_t)d_bits & 3) return fail(c, DABGPU_E_INVALID, "decode: the coded bits are read as 32-bit words (4-byte alignment)");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    return queue_decode(c, d_bits, n_tf, d_eti_out, d_ref_eti, s);
+    return decode_dev<DecArgs>(c, c->decode.hard, "decode: the coded bits are read as 32-bit words (4-byte alignment)", d_bits, n_tf,
+                               d_eti_out, out_cap, d_ref_eti, out_bytes, stream);
 }
 
 int dabgpu_decode(dabgpu_ctx *c, const uint8_t *bits, size_t n_tf, uint8_t *eti_out, size_t out_cap, const uint8_t *ref_eti,
                   size_t *out_bytes)
 {
-    CTXCHK(c);
-    int rc = check_decode(c, n_tf, out_cap, out_bytes);
-    if (rc) return rc;
-    if (!bits || !eti_out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if ((rc = own_stream_joins_lanes(c))) return rc;
-    const size_t need = n_tf * (size_t)c->fe_cifs * 6144;
-    HostIO io(c);
-    if ((rc = io.in(c->d_dec_in, bits, n_tf * tf_in_bytes(c->g)))) return rc;
-    if (ref_eti && (rc = io.in(c->d_dec_ref, ref_eti, need))) return rc;
-    HIPCHK(c, c->d_dec_out.reserve(need));
-    if ((rc = queue_decode(c, c->d_dec_in.p, n_tf, c->d_dec_out.p, ref_eti ? c->d_dec_ref.p : nullptr, c->stream))) return rc;
-    return io.out(eti_out, c->d_dec_out.p, need);
+    return decode_host<DecArgs>(c, c->decode.hard, bits, n_tf, eti_out, out_cap, ref_eti, out_bytes);
 }
 
 int dabgpu_get_decode_stats(dabgpu_ctx *c, size_t frame, int unit, dabgpu_decode_stats *out)
 {
     CTXCHK(c);
     if (!out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (frame >= c->dec_frames)
+    if (frame >= c->decode.hard.frames)
         return fail(c, DABGPU_E_INVALID, "no decoder statistics for this frame (no call yet, or frame index out of range)");
     if (unit < -1 || unit >= c->fe_units) return fail(c, DABGPU_E_INVALID, "decode: unit is -1 (the frame), 0 (the FIC) or 1 + a sub-channel");
-    HIPCHK(c, hipStreamSynchronize(c->dec_stream ? c->dec_stream : c->stream));
+    HIPCHK(c, wait_result(c, c->decode.hard.stream));
     std::vector<DecUnitStats> st((size_t)c->fe_units);
-    HIPCHK(c, hipMemcpy(st.data(), (const DecUnitStats *)c->d_dec_stats.p + frame * (size_t)c->fe_units,
+    HIPCHK(c, hipMemcpy(st.data(), (const DecUnitStats *)c->decode.hard.stats.p + frame * (size_t)c->fe_units,
                         st.size() * sizeof(DecUnitStats), hipMemcpyDeviceToHost));
     std::memset(out, 0, sizeof *out);
-    out->valid = frame >= c->dec_first_valid;
+    out->valid = frame >= c->decode.hard.first_valid;
     for (int u = unit < 0 ? 0 : unit; u < (unit < 0 ? c->fe_units : unit + 1); ++u) {
         out->corrected += st[u].corrected;
         out->coded_bits += st[u].coded_bits;
@@ -258,47 +241,29 @@ int dabgpu_get_decode_stats(dabgpu_ctx *c, size_t frame, int unit, dabgpu_decode
 int dabgpu_decode_soft_dev(dabgpu_ctx *c, const void *d_soft, size_t n_tf, void *d_eti_out, size_t out_cap, const void *d_ref_eti,
                            size_t *out_bytes, void *stream)
 {
-    CTXCHK(c);
-    int rc = check_decode(c, n_tf, out_cap, out_bytes);
-    if (rc) return rc;
-    if (!d_soft || !d_eti_out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if ((uintptr_t)d_soft & 3) return fail(c, DABGPU_E_INVALID, "decode: the soft metrics are read as 32-bit words (4-byte alignment)");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    return queue_decode_soft(c, d_soft, n_tf, d_eti_out, d_ref_eti, s);
+    return decode_dev<DecSoftArgs>(c, c->decode.soft, "decode: the soft metrics are read as 32-bit words (4-byte alignment)", d_soft, n_tf,
+                                   d_eti_out, out_cap, d_ref_eti, out_bytes, stream);
 }
 
 int dabgpu_decode_soft(dabgpu_ctx *c, const int8_t *soft, size_t n_tf, uint8_t *eti_out, size_t out_cap, const uint8_t *ref_eti,
                        size_t *out_bytes)
 {
-    CTXCHK(c);
-    int rc = check_decode(c, n_tf, out_cap, out_bytes);
-    if (rc) return rc;
-    if (!soft || !eti_out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if ((rc = own_stream_joins_lanes(c))) return rc;
-    const size_t need = n_tf * (size_t)c->fe_cifs * 6144;
-    HostIO io(c);
-    if ((rc = io.in(c->d_decs_in, soft, 8 * n_tf * tf_in_bytes(c->g)))) return rc;
-    if (ref_eti && (rc = io.in(c->d_dec_ref, ref_eti, need))) return rc;
-    HIPCHK(c, c->d_dec_out.reserve(need));
-    if ((rc = queue_decode_soft(c, c->d_decs_in.p, n_tf, c->d_dec_out.p, ref_eti ? c->d_dec_ref.p : nullptr, c->stream))) return rc;
-    return io.out(eti_out, c->d_dec_out.p, need);
+    return decode_host<DecSoftArgs>(c, c->decode.soft, soft, n_tf, eti_out, out_cap, ref_eti, out_bytes);
 }
 
 int dabgpu_get_decode_soft_stats(dabgpu_ctx *c, size_t frame, int unit, dabgpu_decode_soft_stats *out)
 {
     CTXCHK(c);
     if (!out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (frame >= c->decs_frames)
+    if (frame >= c->decode.soft.frames)
         return fail(c, DABGPU_E_INVALID, "no soft decoder statistics for this frame (no call yet, or frame index out of range)");
     if (unit < -1 || unit >= c->fe_units) return fail(c, DABGPU_E_INVALID, "decode: unit is -1 (the frame), 0 (the FIC) or 1 + a sub-channel");
-    HIPCHK(c, hipStreamSynchronize(c->decs_stream ? c->decs_stream : c->stream));
+    HIPCHK(c, wait_result(c, c->decode.soft.stream));
     std::vector<DecSoftUnitStats> st((size_t)c->fe_units);
-    HIPCHK(c, hipMemcpy(st.data(), (const DecSoftUnitStats *)c->d_decs_stats.p + frame * (size_t)c->fe_units,
+    HIPCHK(c, hipMemcpy(st.data(), (const DecSoftUnitStats *)c->decode.soft.stats.p + frame * (size_t)c->fe_units,
                         st.size() * sizeof(DecSoftUnitStats), hipMemcpyDeviceToHost));
     std::memset(out, 0, sizeof *out);
-    out->valid = frame >= c->decs_first_valid;
+    out->valid = frame >= c->decode.soft.first_valid;
     for (int u = unit < 0 ? 0 : unit; u < (unit < 0 ? c->fe_units : unit + 1); ++u) {
         out->metric += st[u].metric;
         out->contra_sum += st[u].contra_sum;

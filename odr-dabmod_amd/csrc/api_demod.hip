@@ -18,8 +18,8 @@ const char *const kEarlyRange = "demod: early must lie inside the cyclic prefix 
 int queue_demod(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *d_bits_out, const void *d_ref,
                 hipStream_t s, void *d_soft = nullptr)
 {
-    HIPCHK(c, c->d_demod_stats.reserve(std::max<size_t>(n_frames, 1) * sizeof(DemodFrameStats)));
-    HIPCHK(c, hipMemsetAsync(c->d_demod_stats.p, 0, n_frames * sizeof(DemodFrameStats), s));
+    HIPCHK(c, c->demod.stats.reserve(std::max<size_t>(n_frames, 1) * sizeof(DemodFrameStats)));
+    HIPCHK(c, hipMemsetAsync(c->demod.stats.p, 0, n_frames * sizeof(DemodFrameStats), s));
     DemodArgs a{};
     a.g = c->g;
     a.t = tables_of(c);
@@ -27,23 +27,22 @@ int queue_demod(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, in
     a.fmt = format;
     a.frame_stride = tf_samples(c->g);
     a.n_frames = (int)n_frames;
-    demod_runs(c->g, n_frames, c->demod_run_symbols, &a.runs_per_frame, &a.syms_per_run);
+    demod_runs(c->g, n_frames, c->demod.run_symbols, &a.runs_per_frame, &a.syms_per_run);
     a.early = early;
     a.bits_out = (uint8_t *)d_bits_out;
     a.ref_bits = (const uint8_t *)d_ref;
-    a.stats = (DemodFrameStats *)c->d_demod_stats.p;
+    a.stats = (DemodFrameStats *)c->demod.stats.p;
     a.soft_out = (int8_t *)d_soft;
     HIPCHK(c, launch_demod(a, s));
-    c->demod_frames = n_frames;
-    c->demod_has_ref = d_ref != nullptr;
-    c->demod_stream = s;
+    c->demod.frames = n_frames;
+    c->demod.has_ref = d_ref != nullptr;
+    c->demod.stream = s;
     return DABGPU_OK;
 }
 
 int check_demod(dabgpu_ctx *c, const void *iq, int format, size_t n_frames, int early, const void *bits_out, const void *ref)
 {
-    if (format != 0 && format != DABGPU_FMT_S16)
-        return fail(c, DABGPU_E_INVALID, "demod: input format is complexf (0) or DABGPU_FMT_S16");
+    if (int rc = check_capture_format(c, "demod", format)) return rc;
     if (early < 0 || early > c->g.sym_size - c->g.N) return fail(c, DABGPU_E_INVALID, kEarlyRange);
     if (n_frames > (size_t)c->max_frames) return fail(c, DABGPU_E_CAPACITY, "n_frames exceeds max_frames of the context");
     if (n_frames && !iq) return fail(c, DABGPU_E_INVALID, "null argument");
@@ -79,90 +78,85 @@ int run_monitor(dabgpu_ctx *c, const ChainPlan &p, const void *d_bits, const voi
 }
 }  // namespace dabgpu_api
 
-extern "C" {
-int dabgpu_demod_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *d_bits_out,
-                     const void *d_ref_bits, void *stream)
+namespace {
+// the device-pointer entry of either kernel: soft takes d_soft_out (n_frames x 8 tf_input_bytes int8), hard passes nullptr
+int demod_dev(dabgpu_ctx *c, bool soft, const void *d_iq, int format, size_t n_frames, int early, void *d_soft_out, void *d_bits_out,
+              const void *d_ref_bits, void *stream)
 {
     CTXCHK(c);
     int rc = apply_settings(c);
     if (rc) return rc;
     if ((rc = check_demod(c, d_iq, format, n_frames, early, d_bits_out, d_ref_bits))) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;       // (d_iq: a chain call's output on any lane)
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    return queue_demod(c, d_iq, format, n_frames, early, d_bits_out, d_ref_bits, s);
+    if (soft && !d_soft_out) return fail(c, DABGPU_E_INVALID, "null argument");
+    if ((uintptr_t)d_soft_out & 3u) return fail(c, DABGPU_E_INVALID, "demod: buffers must be aligned to four bytes");
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
+    return queue_demod(c, d_iq, format, n_frames, early, d_bits_out, d_ref_bits, call.s, d_soft_out);
+}
+
+// the host-pointer entry of either kernel
+int demod_host(dabgpu_ctx *c, bool soft, const void *iq, int format, size_t n_frames, int early, int8_t *soft_out, uint8_t *bits_out,
+               const uint8_t *ref_bits)
+{
+    CTXCHK(c);
+    int rc = check_demod(c, iq, format, n_frames, early, nullptr, nullptr);
+    if (rc) return rc;
+    if (soft && !soft_out) return fail(c, DABGPU_E_INVALID, "null argument");
+    if ((rc = dabgpu_synchronize(c))) return rc;                      // (d_out is the synchronous host path's)
+    const size_t iq_bytes = n_frames * tf_samples(c->g) * sample_bytes(format);
+    const size_t bit_bytes = n_frames * tf_in_bytes(c->g);
+    HostIO io(c);
+    if ((rc = io.in(c->d_out, iq, iq_bytes))) return rc;
+    if (ref_bits && (rc = io.in(c->demod.ref, ref_bits, bit_bytes))) return rc;
+    if (bits_out) HIPCHK(c, c->demod.bits.reserve(std::max<size_t>(bit_bytes, 16)));
+    if (soft) HIPCHK(c, c->demod.soft.reserve(std::max<size_t>(8 * bit_bytes, 16)));
+    if ((rc = demod_dev(c, soft, c->d_out.p, format, n_frames, early, soft ? c->demod.soft.p : nullptr,
+                        bits_out ? c->demod.bits.p : nullptr, ref_bits ? c->demod.ref.p : nullptr, c->stream)))
+        return rc;
+    if (soft && n_frames && (rc = io.out(soft_out, c->demod.soft.p, 8 * bit_bytes))) return rc;
+    return io.out(bits_out, c->demod.bits.p, bits_out ? bit_bytes : 0);
+}
+}  // namespace
+
+extern "C" {
+int dabgpu_demod_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *d_bits_out,
+                     const void *d_ref_bits, void *stream)
+{
+    return demod_dev(c, false, d_iq, format, n_frames, early, nullptr, d_bits_out, d_ref_bits, stream);
 }
 
 int dabgpu_demod(dabgpu_ctx *c, const void *iq, int format, size_t n_frames, int early, uint8_t *bits_out,
                  const uint8_t *ref_bits)
 {
-    CTXCHK(c);
-    int rc = check_demod(c, iq, format, n_frames, early, nullptr, nullptr);
-    if (rc) return rc;
-    if ((rc = dabgpu_synchronize(c))) return rc;                      // (d_out is the synchronous host path's)
-    const size_t iq_bytes = n_frames * tf_samples(c->g) * (format ? 4 : sizeof(float2));
-    const size_t bit_bytes = n_frames * tf_in_bytes(c->g);
-    HostIO io(c);
-    if ((rc = io.in(c->d_out, iq, iq_bytes))) return rc;
-    if (ref_bits && (rc = io.in(c->d_demod_ref, ref_bits, bit_bytes))) return rc;
-    if (bits_out) HIPCHK(c, c->d_demod_bits.reserve(std::max<size_t>(bit_bytes, 16)));
-    if ((rc = dabgpu_demod_dev(c, c->d_out.p, format, n_frames, early, bits_out ? c->d_demod_bits.p : nullptr,
-                               ref_bits ? c->d_demod_ref.p : nullptr, c->stream)))
-        return rc;
-    return io.out(bits_out, c->d_demod_bits.p, bits_out ? bit_bytes : 0);
+    return demod_host(c, false, iq, format, n_frames, early, nullptr, bits_out, ref_bits);
 }
 
 int dabgpu_demod_soft_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *d_soft_out,
                           void *d_bits_out, const void *d_ref_bits, void *stream)
 {
-    CTXCHK(c);
-    int rc = apply_settings(c);
-    if (rc) return rc;
-    if ((rc = check_demod(c, d_iq, format, n_frames, early, d_bits_out, d_ref_bits))) return rc;
-    if (!d_soft_out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if ((uintptr_t)d_soft_out & 3u) return fail(c, DABGPU_E_INVALID, "demod: buffers must be aligned to four bytes");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    return queue_demod(c, d_iq, format, n_frames, early, d_bits_out, d_ref_bits, s, d_soft_out);
+    return demod_dev(c, true, d_iq, format, n_frames, early, d_soft_out, d_bits_out, d_ref_bits, stream);
 }
 
 int dabgpu_demod_soft(dabgpu_ctx *c, const void *iq, int format, size_t n_frames, int early, int8_t *soft_out, uint8_t *bits_out,
                       const uint8_t *ref_bits)
 {
-    CTXCHK(c);
-    int rc = check_demod(c, iq, format, n_frames, early, nullptr, nullptr);
-    if (rc) return rc;
-    if (!soft_out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if ((rc = dabgpu_synchronize(c))) return rc;
-    const size_t iq_bytes = n_frames * tf_samples(c->g) * (format ? 4 : sizeof(float2));
-    const size_t bit_bytes = n_frames * tf_in_bytes(c->g);
-    HostIO io(c);
-    if ((rc = io.in(c->d_out, iq, iq_bytes))) return rc;
-    if (ref_bits && (rc = io.in(c->d_demod_ref, ref_bits, bit_bytes))) return rc;
-    if (bits_out) HIPCHK(c, c->d_demod_bits.reserve(std::max<size_t>(bit_bytes, 16)));
-    HIPCHK(c, c->d_demod_soft.reserve(std::max<size_t>(8 * bit_bytes, 16)));
-    if ((rc = dabgpu_demod_soft_dev(c, c->d_out.p, format, n_frames, early, c->d_demod_soft.p, bits_out ? c->d_demod_bits.p : nullptr,
-                                    ref_bits ? c->d_demod_ref.p : nullptr, c->stream)))
-        return rc;
-    if (n_frames && (rc = io.out(soft_out, c->d_demod_soft.p, 8 * bit_bytes))) return rc;
-    return io.out(bits_out, c->d_demod_bits.p, bits_out ? bit_bytes : 0);
+    return demod_host(c, true, iq, format, n_frames, early, soft_out, bits_out, ref_bits);
 }
 
 int dabgpu_get_demod_stats(dabgpu_ctx *c, size_t frame, dabgpu_demod_stats *out)
 {
     CTXCHK(c);
     if (!out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (frame >= c->demod_frames)
+    if (frame >= c->demod.frames)
         return fail(c, DABGPU_E_INVALID, "no demodulator statistics for this frame (no call yet, or frame index out of range)");
-    HIPCHK(c, hipStreamSynchronize(c->demod_stream ? c->demod_stream : c->stream));
+    HIPCHK(c, wait_result(c, c->demod.stream));
     DemodFrameStats st;
-    HIPCHK(c, hipMemcpy(&st, (const DemodFrameStats *)c->d_demod_stats.p + frame, sizeof st, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&st, (const DemodFrameStats *)c->demod.stats.p + frame, sizeof st, hipMemcpyDeviceToHost));
     std::memset(out, 0, sizeof *out);
     out->sum_signal = st.sum_signal;
     out->sum_quadrature = st.sum_quadrature;
     out->bit_errors = st.bit_errors;
-    out->n_bits = c->demod_has_ref ? 8 * (uint64_t)tf_in_bytes(c->g) : 0;
+    out->n_bits = c->demod.has_ref ? 8 * (uint64_t)tf_in_bytes(c->g) : 0;
     const unsigned mbits = ~st.min_margin_inv;
     float m;
     std::memcpy(&m, &mbits, sizeof m);
@@ -195,7 +189,7 @@ int dabgpu_debug_demod_run_symbols(dabgpu_ctx *c, int symbols)
 {
     if (!c) return DABGPU_E_INVALID;
     if (symbols < 0) return fail(c, DABGPU_E_INVALID, "demod: symbols per run: a positive number, or 0 = by the batch size");
-    c->demod_run_symbols = symbols;
+    c->demod.run_symbols = symbols;
     return DABGPU_OK;
 }
 

@@ -16,23 +16,23 @@ size_t tx_bytes(int format) { return format == 0 ? sizeof(float2) : 4; }
 
 int dpd_ready(dabgpu_ctx *c)
 {
-    if (c->dpd_ready) return DABGPU_OK;
+    if (c->dpd.ready) return DABGPU_OK;
     if (c->g.N != kXN) {                                               // (Mode I: the context's own table is this one)
         std::vector<float2> tw(kXN);
         for (int m = 0; m < kXN; ++m) {
             const double a = 2.0 * M_PI * (double)m / (double)kXN;
             tw[m] = make_float2((float)std::cos(a), (float)std::sin(a));
         }
-        HIPCHK(c, upload(c->d_dpd_tw, tw, c->stream));
+        HIPCHK(c, upload(c->dpd.tw, tw, c->stream));
     }
-    HIPCHK(c, c->d_dpd_xacc.reserve(kXAcc * sizeof(double)));
-    HIPCHK(c, c->d_dpd_sums.reserve(kSums * sizeof(unsigned long long)));
-    HIPCHK(c, c->d_dpd_edge.reserve((DPD_MAX_BINS + 1) * sizeof(float)));
-    HIPCHK(c, hipMemsetAsync(c->d_dpd_xacc.p, 0, kXAcc * sizeof(double), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_dpd_sums.p, 0, kSums * sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_dpd_edge.p, 0, (DPD_MAX_BINS + 1) * sizeof(float), c->stream));
+    HIPCHK(c, c->dpd.xacc.reserve(kXAcc * sizeof(double)));
+    HIPCHK(c, c->dpd.sums.reserve(kSums * sizeof(unsigned long long)));
+    HIPCHK(c, c->dpd.edge.reserve((DPD_MAX_BINS + 1) * sizeof(float)));
+    HIPCHK(c, hipMemsetAsync(c->dpd.xacc.p, 0, kXAcc * sizeof(double), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->dpd.sums.p, 0, kSums * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->dpd.edge.p, 0, (DPD_MAX_BINS + 1) * sizeof(float), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->dpd_ready = true;
+    c->dpd.ready = true;
     return DABGPU_OK;
 }
 
@@ -56,26 +56,26 @@ int queue_xspectrum(dabgpu_ctx *c, const void *d_tx, int format, const void *d_r
     a.rx = (const float2 *)d_rx;
     a.rx_offset = rx_offset;
     dpd_segments(n, rx_offset, &a.seg_first, &a.n_segments);
-    spectrum_runs(a.n_segments, c->dpd_run_segments, &a.n_runs, &a.segs_per_run);
+    spectrum_runs(a.n_segments, c->dpd.run_segments, &a.n_runs, &a.segs_per_run);
     if (a.n_runs > kDpdMaxRuns) {                                      // (a row is 64 KiB: never more than 256 MiB of them)
         a.segs_per_run = (int)((a.n_segments + kDpdMaxRuns - 1) / kDpdMaxRuns);
         a.n_runs = (int)((a.n_segments + a.segs_per_run - 1) / a.segs_per_run);
     }
-    a.twiddle = (const float2 *)(c->g.N == kXN ? c->d_twiddle.p : c->d_dpd_tw.p);
-    HIPCHK(c, c->d_dpd_rows.reserve(std::max<size_t>((size_t)a.n_runs, 1) * 4 * kXN * sizeof(double)));
-    a.rows = (double *)c->d_dpd_rows.p;
-    a.acc = (double *)c->d_dpd_xacc.p;
+    a.twiddle = (const float2 *)(c->g.N == kXN ? c->d_twiddle.p : c->dpd.tw.p);
+    HIPCHK(c, c->dpd.rows.reserve(std::max<size_t>((size_t)a.n_runs, 1) * 4 * kXN * sizeof(double)));
+    a.rows = (double *)c->dpd.rows.p;
+    a.acc = (double *)c->dpd.xacc.p;
     HIPCHK(c, launch_dpd_xspectrum(a, n, s));
-    c->dpd_stream = s;
+    c->dpd.stream = s;
     return DABGPU_OK;
 }
 
 int fetch_xspectrum(dabgpu_ctx *c, std::vector<double> &host)
 {
     host.assign(kXAcc, 0.0);
-    if (c->dpd_ready) {
-        HIPCHK(c, hipStreamSynchronize(c->dpd_stream ? c->dpd_stream : c->stream));
-        HIPCHK(c, hipMemcpy(host.data(), c->d_dpd_xacc.p, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (c->dpd.ready) {
+        HIPCHK(c, wait_result(c, c->dpd.stream));
+        HIPCHK(c, hipMemcpy(host.data(), c->dpd.xacc.p, host.size() * sizeof(double), hipMemcpyDeviceToHost));
     }
     return DABGPU_OK;
 }
@@ -103,14 +103,14 @@ int check_measure(dabgpu_ctx *c, const void *tx, int format, const void *rx, siz
                   int n_bins, int accumulate)
 {
     // (the sample cap first: nothing below may look at a buffer that a refused n describes)
-    const unsigned long long held = accumulate ? c->dpd_offered : 0ull;
+    const unsigned long long held = accumulate ? c->dpd.offered : 0ull;
     if ((unsigned long long)n > kDpdSampleCap || held + (unsigned long long)n > kDpdSampleCap)
         return fail(c, DABGPU_E_INVALID, "dpd: the sums hold at most 2^31 samples; dabgpu_reset_dpd, or accumulate = 0, first");
     int rc = check_pair(c, tx, format, rx, n);
     if (rc) return rc;
     if (n_bins < 1 || n_bins > DABGPU_DPD_MAX_BINS) return fail(c, DABGPU_E_INVALID, "dpd: n_bins is 1 ... 256");
     if (!(peak > 0.f) || !std::isfinite(peak)) return fail(c, DABGPU_E_INVALID, "dpd: peak must be positive and finite");
-    if (accumulate && c->dpd_bins && (c->dpd_peak != peak || c->dpd_bins != n_bins))
+    if (accumulate && c->dpd.bins && (c->dpd.peak != peak || c->dpd.bins != n_bins))
         return fail(c, DABGPU_E_INVALID, "dpd: the sums were formed with another peak or n_bins; dabgpu_reset_dpd first");
     return check_alignment(c, al);
 }
@@ -160,6 +160,18 @@ bool solve5(std::vector<double> A, std::vector<double> b, int m, double *c5, dou
     *resid = std::sqrt(r2 / (double)m);
     return true;
 }
+
+// The host-pointer form of an entry on a tx / feedback pair, after its checks: the pair staged behind whatever still reads
+// the staging buffers, the _dev entry on the context's stream (dev(d_tx, d_rx) -> rc), the result complete.
+template <typename DevEntry> int pair_from_host(dabgpu_ctx *c, const void *tx, int tx_format, const void *rx, size_t n_samples, DevEntry dev)
+{
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HostIO io(c);
+    int rc = io.in(c->dpd.tx, tx, n_samples * tx_bytes(tx_format));
+    if (!rc) rc = io.in(c->dpd.rx, rx, n_samples * sizeof(float2));
+    if (!rc) rc = dev(c->dpd.tx.p, c->dpd.rx.p);
+    return rc ? rc : io.out(nullptr, nullptr, 0);
+}
 }  // namespace
 
 extern "C" {
@@ -171,23 +183,18 @@ int dabgpu_dpd_xspectrum_dev(dabgpu_ctx *c, const void *d_tx, int tx_format, con
     if (rc) return rc;
     if ((rc = check_pair(c, d_tx, tx_format, d_rx, n_samples))) return rc;
     if (rx_offset > (1ll << 40) || rx_offset < -(1ll << 40)) return fail(c, DABGPU_E_INVALID, "dpd: |rx_offset| exceeds 2^40");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    return queue_xspectrum(c, d_tx, tx_format, d_rx, n_samples, rx_offset, s);
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
+    return queue_xspectrum(c, d_tx, tx_format, d_rx, n_samples, rx_offset, call.s);
 }
 
 int dabgpu_dpd_xspectrum(dabgpu_ctx *c, const void *tx, int tx_format, const void *rx, size_t n_samples, long long rx_offset)
 {
     CTXCHK(c);
-    int rc = check_pair(c, tx, tx_format, rx, n_samples);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));                        // (the staging buffers may still be read by the call before)
-    HostIO io(c);
-    if ((rc = io.in(c->d_dpd_tx, tx, n_samples * tx_bytes(tx_format)))) return rc;
-    if ((rc = io.in(c->d_dpd_rx, rx, n_samples * sizeof(float2)))) return rc;
-    if ((rc = dabgpu_dpd_xspectrum_dev(c, c->d_dpd_tx.p, tx_format, c->d_dpd_rx.p, n_samples, rx_offset, c->stream))) return rc;
-    return io.out(nullptr, nullptr, 0);
+    if (int rc = check_pair(c, tx, tx_format, rx, n_samples)) return rc;
+    return pair_from_host(c, tx, tx_format, rx, n_samples, [&](const void *d_tx, const void *d_rx) {
+        return dabgpu_dpd_xspectrum_dev(c, d_tx, tx_format, d_rx, n_samples, rx_offset, c->stream);
+    });
 }
 
 int dabgpu_get_dpd_xspectrum(dabgpu_ctx *c, double *s2048x2, double *p_tx2048, double *p_rx2048, uint64_t *segments)
@@ -278,17 +285,16 @@ int dabgpu_dpd_align_dev(dabgpu_ctx *c, const void *d_tx, int tx_format, const v
     if (rc) return rc;
     if ((rc = check_pair(c, d_tx, tx_format, d_rx, n_samples))) return rc;
     if (n_samples < (size_t)kXN) return fail(c, DABGPU_E_INVALID, "dpd: alignment needs 2048 samples or more");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
     std::vector<double> host, s2(2 * kXN);
     dabgpu_dpd_alignment a1{}, a2{};
-    if ((rc = queue_xspectrum(c, d_tx, tx_format, d_rx, n_samples, 0, s))) return rc;
+    if ((rc = queue_xspectrum(c, d_tx, tx_format, d_rx, n_samples, 0, call.s))) return rc;
     if ((rc = fetch_xspectrum(c, host))) return rc;
     interleave_s(host, s2.data());
     if (dabgpu_dpd_solve_alignment(s2.data(), &host[2 * kXN], &host[3 * kXN], &a1)) return fail(c, DABGPU_E_INVALID, dabgpu_last_error(nullptr));
     if ((rc = check_alignment(c, &a1))) return rc;
-    if ((rc = queue_xspectrum(c, d_tx, tx_format, d_rx, n_samples, a1.lag, s))) return rc;
+    if ((rc = queue_xspectrum(c, d_tx, tx_format, d_rx, n_samples, a1.lag, call.s))) return rc;
     if ((rc = fetch_xspectrum(c, host))) return rc;
     interleave_s(host, s2.data());
     if (dabgpu_dpd_solve_alignment(s2.data(), &host[2 * kXN], &host[3 * kXN], &a2)) return fail(c, DABGPU_E_INVALID, dabgpu_last_error(nullptr));
@@ -301,14 +307,10 @@ int dabgpu_dpd_align_dev(dabgpu_ctx *c, const void *d_tx, int tx_format, const v
 int dabgpu_dpd_align(dabgpu_ctx *c, const void *tx, int tx_format, const void *rx, size_t n_samples, dabgpu_dpd_alignment *out)
 {
     CTXCHK(c);
-    int rc = check_pair(c, tx, tx_format, rx, n_samples);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HostIO io(c);
-    if ((rc = io.in(c->d_dpd_tx, tx, n_samples * tx_bytes(tx_format)))) return rc;
-    if ((rc = io.in(c->d_dpd_rx, rx, n_samples * sizeof(float2)))) return rc;
-    if ((rc = dabgpu_dpd_align_dev(c, c->d_dpd_tx.p, tx_format, c->d_dpd_rx.p, n_samples, out, c->stream))) return rc;
-    return io.out(nullptr, nullptr, 0);
+    if (int rc = check_pair(c, tx, tx_format, rx, n_samples)) return rc;
+    return pair_from_host(c, tx, tx_format, rx, n_samples, [&](const void *d_tx, const void *d_rx) {
+        return dabgpu_dpd_align_dev(c, d_tx, tx_format, d_rx, n_samples, out, c->stream);
+    });
 }
 
 int dabgpu_dpd_delay_taps(double tau, float taps[32])
@@ -348,27 +350,26 @@ int dabgpu_dpd_measure_dev(dabgpu_ctx *c, const void *d_tx, int tx_format, const
     int rc = check_measure(c, d_tx, tx_format, d_rx, n_samples, al, peak, n_bins, accumulate);
     if (rc) return rc;
     if ((rc = apply_settings(c))) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
     if ((rc = dpd_ready(c))) return rc;
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    if (c->dpd_peak != peak || c->dpd_bins != n_bins) {
+    if (c->dpd.peak != peak || c->dpd.bins != n_bins) {
         std::vector<float> edge(DPD_MAX_BINS + 1, 0.f);
         for (int j = 0; j <= n_bins; ++j) {
             const double e = (double)j * (double)peak / (double)n_bins;
             edge[j] = (float)(e * e);
         }
-        HIPCHK(c, hipMemcpyAsync(c->d_dpd_edge.p, edge.data(), edge.size() * sizeof(float), hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipStreamSynchronize(s));                            // (edge is a temporary)
+        HIPCHK(c, hipMemcpyAsync(c->dpd.edge.p, edge.data(), edge.size() * sizeof(float), hipMemcpyHostToDevice, call.s));
+        HIPCHK(c, hipStreamSynchronize(call.s));                       // (edge is a temporary)
     }
     if (!accumulate) {
-        HIPCHK(c, hipMemsetAsync(c->d_dpd_sums.p, 0, kSums * sizeof(unsigned long long), s));
-        c->dpd_offered = 0;
+        HIPCHK(c, hipMemsetAsync(c->dpd.sums.p, 0, kSums * sizeof(unsigned long long), call.s));
+        c->dpd.offered = 0;
     }
-    c->dpd_peak = peak;
-    c->dpd_bins = n_bins;
-    c->dpd_offered += (unsigned long long)n_samples;
-    c->dpd_stream = s;
+    c->dpd.peak = peak;
+    c->dpd.bins = n_bins;
+    c->dpd.offered += (unsigned long long)n_samples;
+    c->dpd.stream = call.s;
     DpdStatsArgs a{};
     a.tx = d_tx;
     a.fmt = tx_format;
@@ -382,10 +383,10 @@ int dabgpu_dpd_measure_dev(dabgpu_ctx *c, const void *d_tx, int tx_format, const
     a.g_im = al ? (float)al->gain_im : 0.f;
     a.peak = peak;
     a.n_bins = n_bins;
-    a.edge2 = (const float *)c->d_dpd_edge.p;
-    a.tile = c->dpd_tile ? c->dpd_tile : DPD_TILE_MAX;
-    a.sums = (unsigned long long *)c->d_dpd_sums.p;
-    HIPCHK(c, launch_dpd_stats(a, s));
+    a.edge2 = (const float *)c->dpd.edge.p;
+    a.tile = c->dpd.tile ? c->dpd.tile : DPD_TILE_MAX;
+    a.sums = (unsigned long long *)c->dpd.sums.p;
+    HIPCHK(c, launch_dpd_stats(a, call.s));
     return DABGPU_OK;
 }
 
@@ -393,15 +394,10 @@ int dabgpu_dpd_measure(dabgpu_ctx *c, const void *tx, int tx_format, const void 
                        float peak, int n_bins, int accumulate)
 {
     CTXCHK(c);
-    int rc = check_measure(c, tx, tx_format, rx, n_samples, al, peak, n_bins, accumulate);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HostIO io(c);
-    if ((rc = io.in(c->d_dpd_tx, tx, n_samples * tx_bytes(tx_format)))) return rc;
-    if ((rc = io.in(c->d_dpd_rx, rx, n_samples * sizeof(float2)))) return rc;
-    if ((rc = dabgpu_dpd_measure_dev(c, c->d_dpd_tx.p, tx_format, c->d_dpd_rx.p, n_samples, al, peak, n_bins, accumulate, c->stream)))
-        return rc;
-    return io.out(nullptr, nullptr, 0);
+    if (int rc = check_measure(c, tx, tx_format, rx, n_samples, al, peak, n_bins, accumulate)) return rc;
+    return pair_from_host(c, tx, tx_format, rx, n_samples, [&](const void *d_tx, const void *d_rx) {
+        return dabgpu_dpd_measure_dev(c, d_tx, tx_format, d_rx, n_samples, al, peak, n_bins, accumulate, c->stream);
+    });
 }
 
 int dabgpu_get_dpd_stats(dabgpu_ctx *c, dabgpu_dpd_stats *out)
@@ -409,16 +405,16 @@ int dabgpu_get_dpd_stats(dabgpu_ctx *c, dabgpu_dpd_stats *out)
     CTXCHK(c);
     if (!out) return fail(c, DABGPU_E_INVALID, "null argument");
     std::vector<unsigned long long> host(kSums, 0ull);
-    if (c->dpd_ready) {
-        HIPCHK(c, hipStreamSynchronize(c->dpd_stream ? c->dpd_stream : c->stream));
-        HIPCHK(c, hipMemcpy(host.data(), c->d_dpd_sums.p, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (c->dpd.ready) {
+        HIPCHK(c, wait_result(c, c->dpd.stream));
+        HIPCHK(c, hipMemcpy(host.data(), c->dpd.sums.p, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     }
     std::memset(out, 0, sizeof *out);
-    out->n_bins = c->dpd_bins;
-    out->peak = c->dpd_peak;
+    out->n_bins = c->dpd.bins;
+    out->peak = c->dpd.peak;
     out->overflow = host[DPD_MAX_BINS * DPD_FIGURES];
     out->samples_used = host[DPD_MAX_BINS * DPD_FIGURES + 1];
-    const double peak = (double)c->dpd_peak, q = 1.0 / 16777216.0;
+    const double peak = (double)c->dpd.peak, q = 1.0 / 16777216.0;
     for (int b = 0; b < DPD_MAX_BINS; ++b) {
         const unsigned long long *r = &host[(size_t)b * DPD_FIGURES];
         for (int f = 0; f < DPD_FIGURES; ++f) out->raw[b][f] = (int64_t)r[f];
@@ -435,13 +431,13 @@ int dabgpu_get_dpd_stats(dabgpu_ctx *c, dabgpu_dpd_stats *out)
 int dabgpu_reset_dpd(dabgpu_ctx *c)
 {
     CTXCHK(c);
-    if (c->dpd_ready) {
-        HIPCHK(c, hipStreamSynchronize(c->dpd_stream ? c->dpd_stream : c->stream));
-        HIPCHK(c, hipMemset(c->d_dpd_sums.p, 0, kSums * sizeof(unsigned long long)));
+    if (c->dpd.ready) {
+        HIPCHK(c, wait_result(c, c->dpd.stream));
+        HIPCHK(c, hipMemset(c->dpd.sums.p, 0, kSums * sizeof(unsigned long long)));
     }
-    c->dpd_peak = 0.f;
-    c->dpd_bins = 0;
-    c->dpd_offered = 0;
+    c->dpd.peak = 0.f;
+    c->dpd.bins = 0;
+    c->dpd.offered = 0;
     return DABGPU_OK;
 }
 
@@ -449,7 +445,7 @@ int dabgpu_debug_dpd_run_segments(dabgpu_ctx *c, int segments)
 {
     if (!c) return DABGPU_E_INVALID;
     if (segments < 0) return fail(c, DABGPU_E_INVALID, "dpd: segments per run: a positive number, or 0 = by the input size");
-    c->dpd_run_segments = segments;
+    c->dpd.run_segments = segments;
     return DABGPU_OK;
 }
 
@@ -458,7 +454,7 @@ int dabgpu_debug_dpd_tile(dabgpu_ctx *c, int samples)
     if (!c) return DABGPU_E_INVALID;
     if (samples < 0 || samples > DPD_TILE_MAX || samples % 256)
         return fail(c, DABGPU_E_INVALID, "dpd: samples per workgroup: a multiple of 256 up to 2048, or 0 = 2048");
-    c->dpd_tile = samples;
+    c->dpd.tile = samples;
     return DABGPU_OK;
 }
 

@@ -43,27 +43,26 @@ double window_sum_w2(int window)
     return s;
 }
 
-size_t sample_bytes(int format) { return format == 0 ? sizeof(float2) : format == DABGPU_FMT_S16 ? 4 : 2; }
 
 // tables and sums on first use: written once, never rewritten, so that a call on any stream may read them
 int spectrum_ready(dabgpu_ctx *c)
 {
-    if (c->spec_ready) return DABGPU_OK;
+    if (c->spectrum.ready) return DABGPU_OK;
     if (c->g.N != SPECTRUM_NFFT) {                                     // (Mode I: the context's own table is this one)
         std::vector<float2> tw(SPECTRUM_NFFT);
         for (int m = 0; m < SPECTRUM_NFFT; ++m) {
             const double a = 2.0 * M_PI * (double)m / (double)SPECTRUM_NFFT;
             tw[m] = make_float2((float)std::cos(a), (float)std::sin(a));
         }
-        HIPCHK(c, upload(c->d_spec_tw, tw, c->stream));
+        HIPCHK(c, upload(c->spectrum.tw, tw, c->stream));
     }
     std::vector<float> win(kWindows * SPECTRUM_NFFT);
     for (int w = 0; w < kWindows; ++w) window_table(w, win.data() + (size_t)w * SPECTRUM_NFFT);
-    HIPCHK(c, upload(c->d_spec_win, win, c->stream));
-    HIPCHK(c, c->d_spec_acc.reserve((SPECTRUM_NFFT + 1) * sizeof(double)));
-    HIPCHK(c, hipMemsetAsync(c->d_spec_acc.p, 0, (SPECTRUM_NFFT + 1) * sizeof(double), c->stream));
+    HIPCHK(c, upload(c->spectrum.win, win, c->stream));
+    HIPCHK(c, c->spectrum.acc.reserve((SPECTRUM_NFFT + 1) * sizeof(double)));
+    HIPCHK(c, hipMemsetAsync(c->spectrum.acc.p, 0, (SPECTRUM_NFFT + 1) * sizeof(double), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->spec_ready = true;
+    c->spectrum.ready = true;
     return DABGPU_OK;
 }
 
@@ -75,7 +74,7 @@ int check_spectrum(dabgpu_ctx *c, const void *iq, int format, size_t n_samples, 
     if (n_samples && !iq) return fail(c, DABGPU_E_INVALID, "null argument");
     if ((uintptr_t)iq & (sample_bytes(format) - 1))
         return fail(c, DABGPU_E_INVALID, "spectrum: the buffer must be aligned to the sample size (8 / 4 / 2 / 2 bytes)");
-    if (accumulate && c->spec_window >= 0 && c->spec_window != window)
+    if (accumulate && c->spectrum.window >= 0 && c->spectrum.window != window)
         return fail(c, DABGPU_E_INVALID, "spectrum: the sums were formed with another window; dabgpu_reset_spectrum first");
     return DABGPU_OK;
 }
@@ -91,18 +90,18 @@ int queue_spectrum(dabgpu_ctx *c, const void *d_iq, int format, size_t n_samples
     a.iq = d_iq;
     a.fmt = format;
     a.n_segments = n_samples >= (size_t)SPECTRUM_NFFT ? (long long)((n_samples - SPECTRUM_NFFT) / (SPECTRUM_NFFT / 2)) + 1 : 0;
-    spectrum_runs(a.n_segments, c->spec_run_segments, &a.n_runs, &a.segs_per_run);
-    a.twiddle = (const float2 *)(c->g.N == SPECTRUM_NFFT ? c->d_twiddle.p : c->d_spec_tw.p);
-    a.window = (const float *)c->d_spec_win.p + (size_t)window * SPECTRUM_NFFT;
-    a.acc = (double *)c->d_spec_acc.p;
+    spectrum_runs(a.n_segments, c->spectrum.run_segments, &a.n_runs, &a.segs_per_run);
+    a.twiddle = (const float2 *)(c->g.N == SPECTRUM_NFFT ? c->d_twiddle.p : c->spectrum.tw.p);
+    a.window = (const float *)c->spectrum.win.p + (size_t)window * SPECTRUM_NFFT;
+    a.acc = (double *)c->spectrum.acc.p;
     a.accumulate = accumulate ? 1 : 0;
     if (a.n_segments > 0 || !accumulate) {
-        HIPCHK(c, c->d_spec_rows.reserve(std::max<size_t>((size_t)a.n_runs, 1) * SPECTRUM_NFFT * sizeof(double)));
-        a.rows = (double *)c->d_spec_rows.p;
+        HIPCHK(c, c->spectrum.rows.reserve(std::max<size_t>((size_t)a.n_runs, 1) * SPECTRUM_NFFT * sizeof(double)));
+        a.rows = (double *)c->spectrum.rows.p;
         HIPCHK(c, launch_spectrum(a, s));
-        c->spec_window = window;           // (only what was queued binds the sums to a window and a rate)
-        c->spec_rate_hz = rate_hz;
-        c->spec_stream = s;
+        c->spectrum.window = window;           // (only what was queued binds the sums to a window and a rate)
+        c->spectrum.rate_hz = rate_hz;
+        c->spectrum.stream = s;
     }
     return DABGPU_OK;
 }
@@ -114,7 +113,7 @@ int run_spectrum_monitor(dabgpu_ctx *c, const ChainPlan &p, const void *d_iq, hi
     const int window = c->cur.spectrum_window;
     const double rate = (p.mask & DABGPU_STAGE_RESAMPLE) ? 2048000.0 * (double)c->cur.rs_out / (double)c->cur.rs_in : 2048000.0;
     // the sums go on while window and rate are theirs; a change starts them over (two frequency axes do not add)
-    const bool accumulate = c->spec_window == window && c->spec_rate_hz == rate;
+    const bool accumulate = c->spectrum.window == window && c->spectrum.rate_hz == rate;
     return queue_spectrum(c, d_iq, p.fmt, p.out_bytes / sample_bytes(p.fmt), window, accumulate, rate, s);
 }
 }  // namespace dabgpu_api
@@ -133,11 +132,10 @@ int dabgpu_spectrum_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_sa
     int rc = apply_settings(c);
     if (rc) return rc;
     if ((rc = check_spectrum(c, d_iq, format, n_samples, window, accumulate))) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;       // (d_iq: a chain call's output on any lane)
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
     // (a stand-alone call does not know the rate: 0, unless it adds to sums that have one)
-    return queue_spectrum(c, d_iq, format, n_samples, window, accumulate != 0, accumulate ? c->spec_rate_hz : 0.0, s);
+    return queue_spectrum(c, d_iq, format, n_samples, window, accumulate != 0, accumulate ? c->spectrum.rate_hz : 0.0, call.s);
 }
 
 int dabgpu_spectrum(dabgpu_ctx *c, const void *iq, int format, size_t n_samples, int window, int accumulate)
@@ -147,8 +145,8 @@ int dabgpu_spectrum(dabgpu_ctx *c, const void *iq, int format, size_t n_samples,
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));                        // (the staging buffer may still be read by the call before)
     HostIO io(c);
-    if ((rc = io.in(c->d_spec_in, iq, n_samples * sample_bytes(format)))) return rc;
-    if ((rc = dabgpu_spectrum_dev(c, c->d_spec_in.p, format, n_samples, window, accumulate, c->stream))) return rc;
+    if ((rc = io.in(c->spectrum.in, iq, n_samples * sample_bytes(format)))) return rc;
+    if ((rc = dabgpu_spectrum_dev(c, c->spectrum.in.p, format, n_samples, window, accumulate, c->stream))) return rc;
     return io.out(nullptr, nullptr, 0);
 }
 
@@ -156,9 +154,9 @@ int dabgpu_get_spectrum(dabgpu_ctx *c, double *raw2048, dabgpu_spectrum_info *in
 {
     CTXCHK(c);
     std::vector<double> host(SPECTRUM_NFFT + 1, 0.0);
-    if (c->spec_ready) {
-        HIPCHK(c, hipStreamSynchronize(c->spec_stream ? c->spec_stream : c->stream));
-        HIPCHK(c, hipMemcpy(host.data(), c->d_spec_acc.p, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (c->spectrum.ready) {
+        HIPCHK(c, wait_result(c, c->spectrum.stream));
+        HIPCHK(c, hipMemcpy(host.data(), c->spectrum.acc.p, host.size() * sizeof(double), hipMemcpyDeviceToHost));
     }
     if (raw2048) std::memcpy(raw2048, host.data(), SPECTRUM_NFFT * sizeof(double));
     if (info) {
@@ -167,9 +165,9 @@ int dabgpu_get_spectrum(dabgpu_ctx *c, double *raw2048, dabgpu_spectrum_info *in
         std::memcpy(&n, &host[SPECTRUM_NFFT], sizeof n);
         info->segments = n;
         info->nfft = SPECTRUM_NFFT;
-        info->window = c->spec_window;
-        info->sum_w2 = c->spec_window >= 0 ? window_sum_w2(c->spec_window) : 0.0;
-        info->rate_hz = c->spec_rate_hz;
+        info->window = c->spectrum.window;
+        info->sum_w2 = c->spectrum.window >= 0 ? window_sum_w2(c->spectrum.window) : 0.0;
+        info->rate_hz = c->spectrum.rate_hz;
     }
     return DABGPU_OK;
 }
@@ -177,12 +175,12 @@ int dabgpu_get_spectrum(dabgpu_ctx *c, double *raw2048, dabgpu_spectrum_info *in
 int dabgpu_reset_spectrum(dabgpu_ctx *c)
 {
     CTXCHK(c);
-    if (c->spec_ready) {
-        HIPCHK(c, hipStreamSynchronize(c->spec_stream ? c->spec_stream : c->stream));
-        HIPCHK(c, hipMemset(c->d_spec_acc.p, 0, (SPECTRUM_NFFT + 1) * sizeof(double)));
+    if (c->spectrum.ready) {
+        HIPCHK(c, wait_result(c, c->spectrum.stream));
+        HIPCHK(c, hipMemset(c->spectrum.acc.p, 0, (SPECTRUM_NFFT + 1) * sizeof(double)));
     }
-    c->spec_window = -1;
-    c->spec_rate_hz = 0.0;
+    c->spectrum.window = -1;
+    c->spectrum.rate_hz = 0.0;
     return DABGPU_OK;
 }
 
@@ -202,7 +200,7 @@ int dabgpu_debug_spectrum_run_segments(dabgpu_ctx *c, int segments)
 {
     if (!c) return DABGPU_E_INVALID;
     if (segments < 0) return fail(c, DABGPU_E_INVALID, "spectrum: segments per run: a positive number, or 0 = by the input size");
-    c->spec_run_segments = segments;
+    c->spectrum.run_segments = segments;
     return DABGPU_OK;
 }
 

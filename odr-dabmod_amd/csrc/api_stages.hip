@@ -13,7 +13,7 @@ int dabgpu_get_cfr_stats(dabgpu_ctx *c, size_t frame, dabgpu_cfr_stats *out)
     if (frame >= c->cfr_last_frames)
         return fail(c, DABGPU_E_INVALID, "no CFR statistics for this frame (CFR off, or frame index out of range)");
     const size_t nsym = (size_t)c->g.nb_symbols + 1;
-    HIPCHK(c, hipStreamSynchronize(c->cfr_last_stream ? c->cfr_last_stream : c->stream));
+    HIPCHK(c, wait_result(c, c->cfr_last_stream));
     LaneScope scratch(c, c->cfr_last_lane);
     unsigned counts[2];
     double mer[2];

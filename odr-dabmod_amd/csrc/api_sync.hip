@@ -25,21 +25,17 @@ const char *shape_refusal(const Geometry &g, size_t n_samples, int max_shift)
 
 int check_sync(dabgpu_ctx *c, const void *iq, int format, size_t n_samples, int max_shift, bool device)
 {
-    if (format != 0 && format != DABGPU_FMT_S16)
-        return fail(c, DABGPU_E_INVALID, "sync: input format is complexf (0) or DABGPU_FMT_S16");
-    if (!iq) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (device && ((uintptr_t)iq & (format ? 3u : 7u)))
-        return fail(c, DABGPU_E_INVALID, "sync: buffers must be aligned to a sample (eight bytes complexf, four bytes s16)");
+    if (int rc = check_capture(c, "sync", iq, format, device)) return rc;
     if (const char *why = shape_refusal(c->g, n_samples, max_shift)) return fail(c, DABGPU_E_INVALID, why);
     return DABGPU_OK;
 }
 
-size_t sync_slots(const dabgpu_ctx *c, size_t n_samples)
+size_t frame_slots(const dabgpu_ctx *c, size_t n_samples)
 {
     return std::min<size_t>((size_t)c->max_frames, n_samples / tf_samples(c->g));
 }
 
-SyncArgs sync_args(dabgpu_ctx *c, const void *d_iq, int format, size_t n_samples, int max_shift)
+SyncArgs capture_args(dabgpu_ctx *c, const void *d_iq, int format, size_t n_samples, int max_shift)
 {
     SyncArgs a{};
     a.g = c->g;
@@ -48,11 +44,11 @@ SyncArgs sync_args(dabgpu_ctx *c, const void *d_iq, int format, size_t n_samples
     a.fmt = format;
     a.n = (long long)n_samples;
     a.max_shift = max_shift;
-    a.slots = (int)sync_slots(c, n_samples);
-    a.power = (float *)c->d_sync_power.p;
+    a.slots = (int)frame_slots(c, n_samples);
+    a.power = (float *)c->sync.power.p;
     a.nblk = (int)(std::min(n_samples, tf_samples(c->g) + (size_t)c->g.null_size) / (size_t)(c->g.N / 32));
-    a.head = (SyncHead *)c->d_sync.p;
-    a.frames = (SyncFrame *)((char *)c->d_sync.p + kHeadBytes);
+    a.head = (SyncHead *)c->sync.result.p;
+    a.frames = (SyncFrame *)((char *)c->sync.result.p + kHeadBytes);
     return a;
 }
 }  // namespace
@@ -64,46 +60,40 @@ int dabgpu_sync_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_sample
     int rc = apply_settings(c);
     if (rc) return rc;
     if ((rc = check_sync(c, d_iq, format, n_samples, max_shift, true))) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;       // (d_iq: a chain call's output on any lane)
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    const size_t slots = sync_slots(c, n_samples);
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
+    const size_t slots = frame_slots(c, n_samples);
     const size_t bytes = kHeadBytes + slots * sizeof(SyncFrame);
-    HIPCHK(c, c->d_sync.reserve(bytes));
-    HIPCHK(c, c->d_sync_power.reserve((tf_samples(c->g) + (size_t)c->g.null_size) / (size_t)(c->g.N / 32) * sizeof(float)));
-    c->sync_n = 0;                                                    // (a failed launch leaves no result behind)
-    HIPCHK(c, hipMemsetAsync(c->d_sync.p, 0, bytes, s));
-    HIPCHK(c, launch_sync(sync_args(c, d_iq, format, n_samples, max_shift), s));
-    c->sync_n = n_samples;
-    c->sync_slots = slots;
-    c->sync_stream = s;
+    HIPCHK(c, c->sync.result.reserve(bytes));
+    HIPCHK(c, c->sync.power.reserve((tf_samples(c->g) + (size_t)c->g.null_size) / (size_t)(c->g.N / 32) * sizeof(float)));
+    c->sync.n = 0;                                                    // (a failed launch leaves no result behind)
+    HIPCHK(c, hipMemsetAsync(c->sync.result.p, 0, bytes, call.s));
+    HIPCHK(c, launch_sync(capture_args(c, d_iq, format, n_samples, max_shift), call.s));
+    c->sync.n = n_samples;
+    c->sync.slots = slots;
+    c->sync.stream = call.s;
     return DABGPU_OK;
 }
 
 int dabgpu_sync(dabgpu_ctx *c, const void *iq, int format, size_t n_samples, int max_shift)
 {
     CTXCHK(c);
-    int rc = check_sync(c, iq, format, n_samples, max_shift, false);
-    if (rc) return rc;
-    if ((rc = dabgpu_synchronize(c))) return rc;
-    HostIO io(c);
-    if ((rc = io.in(c->d_sync_in, iq, n_samples * (format ? 4 : sizeof(float2))))) return rc;
-    if ((rc = dabgpu_sync_dev(c, c->d_sync_in.p, format, n_samples, max_shift, c->stream))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return DABGPU_OK;
+    if (int rc = check_sync(c, iq, format, n_samples, max_shift, false)) return rc;
+    return capture_from_host(c, c->sync.in, iq, n_samples * sample_bytes(format),
+                             [&](const void *d_iq) { return dabgpu_sync_dev(c, d_iq, format, n_samples, max_shift, c->stream); });
 }
 
 int dabgpu_get_sync_result(dabgpu_ctx *c, size_t *n_frames, dabgpu_sync_frame *out, size_t cap)
 {
     CTXCHK(c);
     if (!n_frames || (cap && !out)) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (!c->sync_n) return fail(c, DABGPU_E_INVALID, "no synchroniser result (no dabgpu_sync* call yet)");
-    HIPCHK(c, hipStreamSynchronize(c->sync_stream ? c->sync_stream : c->stream));
+    if (!c->sync.n) return fail(c, DABGPU_E_INVALID, "no synchroniser result (no dabgpu_sync* call yet)");
+    HIPCHK(c, wait_result(c, c->sync.stream));
     SyncHead h;
-    HIPCHK(c, hipMemcpy(&h, c->d_sync.p, sizeof h, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&h, c->sync.result.p, sizeof h, hipMemcpyDeviceToHost));
     *n_frames = (size_t)h.count;
     const size_t m = std::min((size_t)h.count, cap);
-    if (m) HIPCHK(c, hipMemcpy(out, (const char *)c->d_sync.p + kHeadBytes, m * sizeof(SyncFrame), hipMemcpyDeviceToHost));
+    if (m) HIPCHK(c, hipMemcpy(out, (const char *)c->sync.result.p + kHeadBytes, m * sizeof(SyncFrame), hipMemcpyDeviceToHost));
     return DABGPU_OK;
 }
 
@@ -113,13 +103,12 @@ int dabgpu_sync_extract_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t 
     int rc = check_sync(c, d_iq, format, n_samples, 0, true);
     if (rc) return rc;
     if (!d_frames_out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if ((uintptr_t)d_frames_out & 7u) return fail(c, DABGPU_E_INVALID, "sync: buffers must be aligned to a sample (eight bytes complexf, four bytes s16)");
-    if (!c->sync_n || c->sync_n != n_samples)
+    if (!sample_aligned(d_frames_out, 0)) return fail_misaligned(c, "sync");
+    if (!c->sync.n || c->sync.n != n_samples)
         return fail(c, DABGPU_E_INVALID, "sync_extract: no dabgpu_sync* call on a capture of this many samples precedes it");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    HIPCHK(c, launch_sync_extract(sync_args(c, d_iq, format, n_samples, 0), (float2 *)d_frames_out, s));
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
+    HIPCHK(c, launch_sync_extract(capture_args(c, d_iq, format, n_samples, 0), (float2 *)d_frames_out, call.s));
     return DABGPU_OK;
 }
 
@@ -129,15 +118,15 @@ int dabgpu_sync_extract(dabgpu_ctx *c, const void *iq, int format, size_t n_samp
     int rc = check_sync(c, iq, format, n_samples, 0, false);
     if (rc) return rc;
     if (!frames_out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (!c->sync_n || c->sync_n != n_samples)
+    if (!c->sync.n || c->sync.n != n_samples)
         return fail(c, DABGPU_E_INVALID, "sync_extract: no dabgpu_sync* call on a capture of this many samples precedes it");
     if ((rc = dabgpu_synchronize(c))) return rc;
-    const size_t out_bytes = c->sync_slots * tf_samples(c->g) * sizeof(float2);
+    const size_t out_bytes = c->sync.slots * tf_samples(c->g) * sizeof(float2);
     HostIO io(c);
-    if ((rc = io.in(c->d_sync_in, iq, n_samples * (format ? 4 : sizeof(float2))))) return rc;
-    HIPCHK(c, c->d_sync_out.reserve(std::max<size_t>(out_bytes, 16)));
-    if ((rc = dabgpu_sync_extract_dev(c, c->d_sync_in.p, format, n_samples, c->d_sync_out.p, c->stream))) return rc;
-    return io.out(frames_out, c->d_sync_out.p, out_bytes);
+    if ((rc = io.in(c->sync.in, iq, n_samples * sample_bytes(format)))) return rc;
+    HIPCHK(c, c->sync.out.reserve(std::max<size_t>(out_bytes, 16)));
+    if ((rc = dabgpu_sync_extract_dev(c, c->sync.in.p, format, n_samples, c->sync.out.p, c->stream))) return rc;
+    return io.out(frames_out, c->sync.out.p, out_bytes);
 }
 
 int dabgpu_sync_check(int mode, size_t n_samples, int max_shift)

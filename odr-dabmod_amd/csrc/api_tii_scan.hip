@@ -32,12 +32,7 @@ const char *settings_refusal(const Geometry &g, size_t n_frames, size_t max_fram
 int check_scan(dabgpu_ctx *c, const void *frames, int format, size_t n_frames, const dabgpu_tii_scan_config *cfg, bool device)
 {
     if (const char *why = settings_refusal(c->g, n_frames, (size_t)c->max_frames, cfg)) return fail(c, DABGPU_E_INVALID, why);
-    if (format != 0 && format != DABGPU_FMT_S16)
-        return fail(c, DABGPU_E_INVALID, "tii_scan: input format is complexf (0) or DABGPU_FMT_S16");
-    if (!frames) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (device && ((uintptr_t)frames & (format ? 3u : 7u)))
-        return fail(c, DABGPU_E_INVALID, "tii_scan: buffers must be aligned to a sample (eight bytes complexf, four bytes s16)");
-    return DABGPU_OK;
+    return check_capture(c, "tii_scan", frames, format, device);
 }
 }  // namespace
 
@@ -49,14 +44,13 @@ int dabgpu_tii_scan_dev(dabgpu_ctx *c, const void *d_frames, int format, size_t 
     int rc = check_scan(c, d_frames, format, n_frames, cfg, true);
     if (rc) return rc;
     if ((rc = apply_settings(c))) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!stream && (rc = own_stream_joins_lanes(c))) return rc;       // (d_frames: a chain call's output on any lane)
-    TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);
-    HIPCHK(c, c->d_tii_scan.reserve(kStateBytes));
-    HIPCHK(c, c->d_tii_rows.reserve(n_frames * 3 * kTiiCells * sizeof(double)));
-    HIPCHK(c, c->d_tii_bins.reserve(n_frames * (size_t)c->g.K * sizeof(float2)));
-    c->tii_scan_done = false;                                         // (a failed launch leaves no result behind)
-    HIPCHK(c, hipMemsetAsync(c->d_tii_scan.p, 0, kStateBytes, s));
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
+    HIPCHK(c, c->tii_scan.result.reserve(kStateBytes));
+    HIPCHK(c, c->tii_scan.rows.reserve(n_frames * 3 * kTiiCells * sizeof(double)));
+    HIPCHK(c, c->tii_scan.bins.reserve(n_frames * (size_t)c->g.K * sizeof(float2)));
+    c->tii_scan.done = false;                                         // (a failed launch leaves no result behind)
+    HIPCHK(c, hipMemsetAsync(c->tii_scan.result.p, 0, kStateBytes, call.s));
     TiiScanArgs a{};
     a.g = c->g;
     a.t = tables_of(c);
@@ -67,39 +61,34 @@ int dabgpu_tii_scan_dev(dabgpu_ctx *c, const void *d_frames, int format, size_t 
     a.old_variant = cfg->old_variant ? 1 : 0;
     a.min_ratio = cfg->min_ratio;
     a.min_rel = cfg->min_rel;
-    a.rows = (double *)c->d_tii_rows.p;
-    a.bins = (float2 *)c->d_tii_bins.p;
-    a.head = (TiiScanHead *)c->d_tii_scan.p;
-    a.entries = (TiiEntry *)((char *)c->d_tii_scan.p + kHeadBytes);
-    a.centre = (int *)((char *)c->d_tii_scan.p + kResultBytes);
-    HIPCHK(c, launch_tii_scan(a, s));
-    c->tii_scan_done = true;
-    c->tii_scan_stream = s;
+    a.rows = (double *)c->tii_scan.rows.p;
+    a.bins = (float2 *)c->tii_scan.bins.p;
+    a.head = (TiiScanHead *)c->tii_scan.result.p;
+    a.entries = (TiiEntry *)((char *)c->tii_scan.result.p + kHeadBytes);
+    a.centre = (int *)((char *)c->tii_scan.result.p + kResultBytes);
+    HIPCHK(c, launch_tii_scan(a, call.s));
+    c->tii_scan.done = true;
+    c->tii_scan.stream = call.s;
     return DABGPU_OK;
 }
 
 int dabgpu_tii_scan(dabgpu_ctx *c, const void *frames, int format, size_t n_frames, const dabgpu_tii_scan_config *cfg)
 {
     CTXCHK(c);
-    int rc = check_scan(c, frames, format, n_frames, cfg, false);
-    if (rc) return rc;
-    if ((rc = dabgpu_synchronize(c))) return rc;
-    HostIO io(c);
-    if ((rc = io.in(c->d_tii_in, frames, n_frames * tf_samples(c->g) * (format ? 4 : sizeof(float2))))) return rc;
-    if ((rc = dabgpu_tii_scan_dev(c, c->d_tii_in.p, format, n_frames, cfg, c->stream))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return DABGPU_OK;
+    if (int rc = check_scan(c, frames, format, n_frames, cfg, false)) return rc;
+    return capture_from_host(c, c->tii_scan.in, frames, n_frames * tf_samples(c->g) * sample_bytes(format),
+                             [&](const void *d_frames) { return dabgpu_tii_scan_dev(c, d_frames, format, n_frames, cfg, c->stream); });
 }
 
 int dabgpu_get_tii_scan(dabgpu_ctx *c, dabgpu_tii_scan_head *head, dabgpu_tii_entry *out, size_t cap)
 {
     CTXCHK(c);
     if (!head || (cap && !out)) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (!c->tii_scan_done) return fail(c, DABGPU_E_INVALID, "no TII scan result (no dabgpu_tii_scan* call yet)");
-    HIPCHK(c, hipStreamSynchronize(c->tii_scan_stream ? c->tii_scan_stream : c->stream));
-    HIPCHK(c, hipMemcpy(head, c->d_tii_scan.p, kHeadBytes, hipMemcpyDeviceToHost));
+    if (!c->tii_scan.done) return fail(c, DABGPU_E_INVALID, "no TII scan result (no dabgpu_tii_scan* call yet)");
+    HIPCHK(c, wait_result(c, c->tii_scan.stream));
+    HIPCHK(c, hipMemcpy(head, c->tii_scan.result.p, kHeadBytes, hipMemcpyDeviceToHost));
     const size_t m = std::min<size_t>(cap, kTiiCombs);                // (whole slots: zeros behind n_entries)
-    if (m) HIPCHK(c, hipMemcpy(out, (const char *)c->d_tii_scan.p + kHeadBytes, m * sizeof(TiiEntry), hipMemcpyDeviceToHost));
+    if (m) HIPCHK(c, hipMemcpy(out, (const char *)c->tii_scan.result.p + kHeadBytes, m * sizeof(TiiEntry), hipMemcpyDeviceToHost));
     return DABGPU_OK;
 }
 

@@ -25,9 +25,13 @@
 //                     phase reference symbols of whole frames; the settings check (host only)
 //   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
 //                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
+// In this order: Settings, TraceScope; the receive-side stages' state, one struct each; dabgpu_ctx with one member of each
+// beside the chain's own; what the translation units export to each other; what entry points are built from (HostIO ...
+// capture_from_host).  Device memory is DevBuf's (devbuf.h): a context's buffers free themselves when it is deleted.
 #pragma once
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
+#include "devbuf.h"
 
 #include <algorithm>
 #include <cmath>
@@ -41,27 +45,6 @@
 
 namespace dabgpu_api {
 using namespace dabgpu;
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 struct Settings {
     int gain_mode = DABGPU_GAIN_VAR;      // src/ConfigParser.h:60-91 defaults
@@ -124,6 +107,110 @@ struct TraceScope {
     }
     ~TraceScope() { trace_sink_ref() = prev; }
 };
+
+// ---- the state of the receive-side stages: one struct each, one member each in dabgpu_ctx.  `stream` is the stream the
+// most recent result is complete on (nullptr: none yet -- wait_result).  Every DevBuf frees itself with the context.
+
+// The receiver (api_demod.hip): the records of the most recent dabgpu_demod* call or monitored chain call and the staging
+// of the host-pointer entries (the capture itself is staged in the chain's d_out).  Monitored calls stay on lane 0: one set.
+struct DemodState {
+    DevBuf stats, bits, ref, soft;
+    size_t frames = 0;
+    bool has_ref = false;
+    hipStream_t stream = nullptr;
+    int run_symbols = 0;                  // dabgpu_debug_demod_run_symbols: symbols per workgroup, 0 = by the batch size
+};
+
+// The spectrum monitor (api_spectrum.hip): the 2048-entry twiddle table (the context's own in Mode I), the three window
+// tables, the rows of one launch, the sums (2048 float64 and the segment count) and the host-pointer entry's staging.
+// One accumulator: monitored calls stay on lane 0.  window: the window the sums were formed with, -1 = none yet.
+struct SpectrumState {
+    DevBuf tw, win, rows, acc, in;
+    bool ready = false;
+    int window = -1;
+    double rate_hz = 0.0;
+    hipStream_t stream = nullptr;
+    int run_segments = 0;                 // dabgpu_debug_spectrum_run_segments: segments per workgroup, 0 = by the input size
+};
+
+// The DPD measurement (api_dpd.hip): the 2048-entry twiddle table (the context's own in Mode I), the cross-spectrum's rows
+// and sums (4 x 2048 float64 and the segment count), the statistics' integer sums (256 bins x 6 figures, overflow, samples
+// used), the squared bin edges and the host-pointer entries' staging.  peak / bins: what the sums were formed with (0: none
+// yet); offered: samples offered since they started over (the cap).
+struct DpdState {
+    DevBuf tw, rows, xacc, sums, edge, tx, rx;
+    bool ready = false;
+    float peak = 0.f;
+    int bins = 0;
+    unsigned long long offered = 0;
+    hipStream_t stream = nullptr;
+    int run_segments = 0;                 // dabgpu_debug_dpd_run_segments
+    int tile = 0;                         // dabgpu_debug_dpd_tile
+};
+
+// The channel decoder (api_decode.hip, decode.hip).  One DecodeStream per metric width: the hard decoder's rows hold one byte
+// per received bit, the soft decoder's eight int8 metrics.  rows is the stream state: [15 + n][width x (fic_out + 6912)]
+// received rows, punctured FIC | CIF of one ETI frame each, rows 0 ... 14 = the last fifteen of the stream (zero after
+// configure / reset: zero_pending asks the next call to zero them).  pos: rows received since then (outputs before row 15
+// are the lead-in).  tmp: where the last fifteen rows pass through when they overlap their place at the front.  stats,
+// frames, first_valid, stream: the records of the most recent call; in: the host-pointer entry's staging.
+struct DecodeStream {
+    size_t width;                         // bytes per received bit: 1 (coded bits) or 8 (soft metrics)
+    DevBuf rows, tmp, stats, in;
+    unsigned long long pos = 0;
+    bool zero_pending = true;
+    size_t frames = 0, first_valid = 0;
+    hipStream_t stream = nullptr;
+};
+// What both streams share (both stay on lane 0): slot -- where each unit's survivor words start inside one output's share
+// of surv -- with its device copy, the survivor scratch, and the host-pointer entries' output and reference staging.
+struct DecodeState {
+    DecodeStream hard{1}, soft{8};
+    DevBuf slot_dev, surv, out, ref;
+    std::vector<uint32_t> slot;
+    std::string refusal;                  // not empty: the configured layout is not decoded (two sub-channels on one capacity unit)
+};
+
+// The synchroniser (api_sync.hip, sync.hip): head and frame records of the most recent dabgpu_sync* call (what
+// dabgpu_sync_extract* reads, straight from device memory), the block powers, what the call was given (n = 0 samples: none
+// yet) and the host-pointer entries' staging.
+struct SyncState {
+    DevBuf result, power, in, out;
+    size_t n = 0, slots = 0;
+    hipStream_t stream = nullptr;
+};
+
+// The channel emulator (api_channel.hip, channel.hip).  hist: two histories of kChMaxDelay float samples, the stream state;
+// hist_cur: the one the next call reads (a call writes the other and swaps).  zero_pending: the next call zeroes it first
+// (after dabgpu_channel_reset, and before the first call).  position: samples the stream has taken.  args: the installed
+// configuration as the kernel takes it (paths that do not rotate first, either group in the given order).
+struct ChannelState {
+    DevBuf hist, in, out;
+    dabgpu::ChannelArgs args{};
+    bool configured = false, zero_pending = true;
+    int hist_cur = 0;
+    unsigned long long position = 0;
+    hipStream_t stream = nullptr;
+    int run_samples = 0;                  // dabgpu_debug_channel_run_samples: samples per workgroup, 0 = by the call size
+};
+
+// The TII analyser (api_tii_scan.hip, tii_scan.hip).  result: head, 24 entry slots and the entries' grid centres of the most
+// recent dabgpu_tii_scan* call; rows / bins: per-frame cell sums and occupied bins (scratch); in: the host-pointer entry's
+// staging; done: a call has been queued.
+struct TiiScanState {
+    DevBuf result, rows, bins, in;
+    bool done = false;
+    hipStream_t stream = nullptr;
+};
+
+// The channel estimator (api_cir.hip, cir.hip).  result: head, 16 path slots, then the profile and the response (N doubles
+// each) of the most recent dabgpu_cir* call; rows: per-frame taps and bins (scratch, max_frames of them); in: the
+// host-pointer entry's staging; done: a call has been queued.
+struct CirState {
+    DevBuf result, rows, in;
+    bool done = false;
+    hipStream_t stream = nullptr;
+};
 }  // namespace dabgpu_api
 
 struct dabgpu_ctx {
@@ -185,84 +272,15 @@ struct dabgpu_ctx {
     int cfr_last_base = 0;
     size_t cfr_last_frames = 0;
     hipStream_t cfr_last_stream = nullptr;
-    // The receiver (api_demod.hip): the records of the most recent dabgpu_demod* call or monitored chain call, the stream
-    // they are complete on, and the staging of the host-pointer entry.  Monitored calls stay on lane 0: one set.
-    dabgpu_api::DevBuf d_demod_stats, d_demod_bits, d_demod_ref, d_demod_soft;
-    size_t demod_frames = 0;
-    bool demod_has_ref = false;
-    hipStream_t demod_stream = nullptr;
-    int demod_run_symbols = 0;            // dabgpu_debug_demod_run_symbols: symbols per workgroup, 0 = by the batch size
-    // The spectrum monitor (api_spectrum.hip): the 2048-entry twiddle table (the context's own in Mode I), the three window
-    // tables, the rows of one launch, the sums (2048 float64 and the segment count) and the host-pointer entry's staging.
-    // One accumulator: monitored calls stay on lane 0.  spec_window: the window the sums were formed with, -1 = none yet.
-    dabgpu_api::DevBuf d_spec_tw, d_spec_win, d_spec_rows, d_spec_acc, d_spec_in;
-    bool spec_ready = false;
-    int spec_window = -1;
-    double spec_rate_hz = 0.0;
-    hipStream_t spec_stream = nullptr;
-    int spec_run_segments = 0;            // dabgpu_debug_spectrum_run_segments: segments per workgroup, 0 = by the input size
-    // The DPD measurement (api_dpd.hip): the 2048-entry twiddle table (the context's own in Mode I), the cross-spectrum's rows
-    // and sums (4 x 2048 float64 and the segment count), the statistics' integer sums (256 bins x 6 figures, overflow, samples
-    // used), the squared bin edges and the host-pointer entries' staging.  dpd_peak / dpd_bins: what the sums were formed
-    // with (0: none yet); dpd_offered: samples offered since they started over (the cap).
-    dabgpu_api::DevBuf d_dpd_tw, d_dpd_rows, d_dpd_xacc, d_dpd_sums, d_dpd_edge, d_dpd_tx, d_dpd_rx;
-    bool dpd_ready = false;
-    float dpd_peak = 0.f;
-    int dpd_bins = 0;
-    unsigned long long dpd_offered = 0;
-    hipStream_t dpd_stream = nullptr;
-    int dpd_run_segments = 0;             // dabgpu_debug_dpd_run_segments
-    int dpd_tile = 0;                     // dabgpu_debug_dpd_tile
-    // The channel decoder (api_decode.hip, decode.hip).  d_dec_rows is the stream state: [15 + n][fic_out + 6912] received rows,
-    // punctured FIC | CIF of one ETI frame each, rows 0 ... 14 = the last fifteen of the stream (zero after configure / reset:
-    // dec_zero_pending asks the next call to zero them).  dec_pos: rows received since then (outputs before row 15 are the
-    // lead-in).  dec_slot: where each unit's survivor words start inside one output's share of d_dec_surv.  The records of
-    // the most recent call, the stream they are complete on and the host-pointer entry's staging follow.
-    dabgpu_api::DevBuf d_dec_rows, d_dec_tmp, d_dec_slot, d_dec_surv, d_dec_stats, d_dec_in, d_dec_out, d_dec_ref;
-    std::vector<uint32_t> dec_slot;
-    std::string dec_refusal;              // not empty: the configured layout is not decoded (two sub-channels on one capacity unit)
-    unsigned long long dec_pos = 0;
-    bool dec_zero_pending = true;
-    size_t dec_frames = 0, dec_first_valid = 0;
-    hipStream_t dec_stream = nullptr;
-    // The soft decoder (dabgpu_decode_soft*): a stream of its own beside the hard one -- fifteen rows of 8 x (fic_out + 6912)
-    // int8 metrics, its own position, records and staging; layout, refusal, slots and survivor scratch are shared (both stay
-    // on lane 0).  Zeroed with the hard history (configure, dabgpu_decode_reset).
-    dabgpu_api::DevBuf d_decs_rows, d_decs_tmp, d_decs_stats, d_decs_in;
-    unsigned long long decs_pos = 0;
-    bool decs_zero_pending = true;
-    size_t decs_frames = 0, decs_first_valid = 0;
-    hipStream_t decs_stream = nullptr;
-    // The synchroniser (api_sync.hip, sync.hip): head and frame records of the most recent dabgpu_sync* call (what
-    // dabgpu_sync_extract* reads, straight from device memory), the block powers, the stream they are complete on, what the
-    // call was given (0 samples: none yet) and the host-pointer entries' staging.
-    dabgpu_api::DevBuf d_sync, d_sync_power, d_sync_in, d_sync_out;
-    size_t sync_n = 0, sync_slots = 0;
-    hipStream_t sync_stream = nullptr;
-    // The channel emulator (api_channel.hip, channel.hip).  d_ch_hist: two histories of kChMaxDelay float samples, the stream
-    // state; ch_hist_cur: the one the next call reads (a call writes the other and swaps).  ch_zero_pending: the next call
-    // zeroes it first (after dabgpu_channel_reset, and before the first call).  ch_position: samples the stream has taken.
-    // ch_args: the installed configuration as the kernel takes it (paths that do not rotate first, either group in the
-    // given order); ch_stream: the stream the most recent call went to.
-    dabgpu_api::DevBuf d_ch_hist, d_ch_in, d_ch_out;
-    dabgpu::ChannelArgs ch_args{};
-    bool ch_configured = false, ch_zero_pending = true;
-    int ch_hist_cur = 0;
-    unsigned long long ch_position = 0;
-    hipStream_t ch_stream = nullptr;
-    int ch_run_samples = 0;               // dabgpu_debug_channel_run_samples: samples per workgroup, 0 = by the call size
-    // The TII analyser (api_tii_scan.hip, tii_scan.hip).  d_tii_scan: head, 24 entry slots and the entries' grid centres of
-    // the most recent dabgpu_tii_scan* call; d_tii_rows / d_tii_bins: per-frame cell sums and occupied bins (scratch);
-    // d_tii_in: the host-pointer entry's staging; tii_scan_done: a call has been queued; tii_scan_stream: where.
-    dabgpu_api::DevBuf d_tii_scan, d_tii_rows, d_tii_bins, d_tii_in;
-    bool tii_scan_done = false;
-    hipStream_t tii_scan_stream = nullptr;
-    // The channel estimator (api_cir.hip, cir.hip).  d_cir: head, 16 path slots, then the profile and the response (N doubles
-    // each) of the most recent dabgpu_cir* call; d_cir_rows: per-frame taps and bins (scratch, max_frames of them); d_cir_in:
-    // the host-pointer entry's staging; cir_done: a call has been queued; cir_stream: where.
-    dabgpu_api::DevBuf d_cir, d_cir_rows, d_cir_in;
-    bool cir_done = false;
-    hipStream_t cir_stream = nullptr;
+    // the receive-side stages (a new one adds its struct above and its member here)
+    dabgpu_api::DemodState demod;
+    dabgpu_api::SpectrumState spectrum;
+    dabgpu_api::DpdState dpd;
+    dabgpu_api::DecodeState decode;
+    dabgpu_api::SyncState sync;
+    dabgpu_api::ChannelState channel;
+    dabgpu_api::TiiScanState tii_scan;
+    dabgpu_api::CirState cir;
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII
     bool tables_valid = false;            // apply_settings has uploaded every table group once
     unsigned long long tii_seg_epoch = 0; // 1 while the cached segment matches the settings (apply_settings zeroes it), and its stage mask
@@ -520,5 +538,59 @@ inline int check_out(dabgpu_ctx *c, size_t need, size_t cap, size_t *out_bytes)
         hipError_t e_ = hipSetDevice((c)->device);                                             \
         if (e_ != hipSuccess) return hip_fail((c), e_, "hipSetDevice");                        \
     } while (0)
+
+// ---- what the entry points of the receive-side stages are built from
+// bytes of one complex sample: complexf, DABGPU_FMT_S16, u8 / s8
+inline size_t sample_bytes(int format) { return format == 0 ? sizeof(float2) : format == DABGPU_FMT_S16 ? 4 : 2; }
+
+// A capture argument, in this order: the format is complexf or s16, the pointer is not null, a device pointer is aligned to
+// a sample.  `stage` starts the messages.  An entry whose order or wording differs uses the pieces, or its own lines.
+inline int check_capture_format(dabgpu_ctx *c, const char *stage, int format)
+{
+    if (format == 0 || format == DABGPU_FMT_S16) return DABGPU_OK;
+    return fail(c, DABGPU_E_INVALID, std::string(stage) + ": input format is complexf (0) or DABGPU_FMT_S16");
+}
+inline bool sample_aligned(const void *p, int format) { return ((uintptr_t)p & (sample_bytes(format) - 1)) == 0; }
+inline int fail_misaligned(dabgpu_ctx *c, const char *stage)
+{
+    return fail(c, DABGPU_E_INVALID, std::string(stage) + ": buffers must be aligned to a sample (eight bytes complexf, four bytes s16)");
+}
+inline int check_capture(dabgpu_ctx *c, const char *stage, const void *p, int format, bool device)
+{
+    if (int rc = check_capture_format(c, stage, format)) return rc;
+    if (!p) return fail(c, DABGPU_E_INVALID, "null argument");
+    if (device && !sample_aligned(p, format)) return fail_misaligned(c, stage);
+    return DABGPU_OK;
+}
+
+// The prologue of a device call: the stream it goes to -- the caller's, or the context's own behind every lane (the input
+// may be a chain call's output on any lane) -- and the trace scope.  rc is not DABGPU_OK when the lanes could not be
+// joined: the entry returns it.
+struct DevCall {
+    hipStream_t s;
+    int rc;
+    TraceScope trace;
+    DevCall(dabgpu_ctx *c, void *stream)
+        : s(stream ? (hipStream_t)stream : c->stream), rc(stream ? DABGPU_OK : own_stream_joins_lanes(c)),
+          trace(rc == DABGPU_OK && c->trace_enabled ? &c->last_variant : nullptr) {}
+};
+
+// waits for a result that is complete on `result_stream` (nullptr: nothing was queued elsewhere -- the context's own)
+inline hipError_t wait_result(dabgpu_ctx *c, hipStream_t result_stream)
+{
+    return hipStreamSynchronize(result_stream ? result_stream : c->stream);
+}
+
+// The host-pointer form of a capture stage, after its checks: the context idle, the capture in `staging`, the stage's _dev
+// entry on the context's stream (dev(d_capture) -> rc), the result complete.
+template <typename DevEntry> int capture_from_host(dabgpu_ctx *c, DevBuf &staging, const void *capture, size_t bytes, DevEntry dev)
+{
+    int rc = dabgpu_synchronize(c);
+    if (rc) return rc;
+    HostIO io(c);
+    if ((rc = io.in(staging, capture, bytes))) return rc;
+    if ((rc = dev(staging.p))) return rc;
+    return io.out(nullptr, nullptr, 0);
+}
 
 }  // namespace dabgpu_api
