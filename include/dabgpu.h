@@ -380,7 +380,16 @@ DABGPU_API int dabgpu_chain_seed_dev(dabgpu_ctx *ctx, const void *d_leadin_bits,
  *   - calls that carry stream state (DABGPU_STAGE_RESAMPLE at a ratio other than 1) and batches of more than 2048 frames
  *     stay on lane 0, in call order (to overlap such calls, split the stream over contexts: "stream state" above);
  *   - a call with an explicit stream argument is what it always was: asynchronous on that stream, the context's scratch.
- *     Do not mix the two on one context without a dabgpu_synchronize in between.
+ *     Do not mix the two on one context without a dabgpu_synchronize in between;
+ *   - every receive-side `_dev` entry with stream == NULL (dabgpu_demod_dev, dabgpu_demod_soft_dev, dabgpu_sync_dev,
+ *     dabgpu_sync_extract_dev, dabgpu_channel_dev, dabgpu_tii_scan_dev, dabgpu_cir_dev, dabgpu_decode_dev,
+ *     dabgpu_decode_soft_dev, dabgpu_spectrum_dev, dabgpu_dpd_xspectrum_dev, dabgpu_dpd_align_dev, dabgpu_dpd_measure_dev)
+ *     runs on the context's own stream, behind everything queued on ANY lane before it: its input may be the output of a
+ *     chain call that is still in flight, without a dabgpu_synchronize in between.  Chain calls queued after it start behind
+ *     it, whichever lane they go to: one of them may overwrite the buffer the entry reads.  (Two chain calls are not ordered
+ *     against each other: a buffer goes to a second chain call only behind such an entry, or a synchronise.)  The result
+ *     getters (dabgpu_get_sync_result, dabgpu_get_tii_scan, ...) wait for that stream only, not for the lanes.
+ *     tests/test_receive_lanes_gpu.py holds all of this to the bytes of a one-lane context.
  * dabgpu_set_lanes: 1 ... 4 (default 3: measured best at 1 ... 64 frames per call, tools/experiments/exp_r05.py lanes; 1 = every call on the one context stream, in order).  Waits for the context. */
 DABGPU_API int dabgpu_set_lanes(dabgpu_ctx *ctx, int lanes);
 /* Diagnostic: how many lanes exist so far (lane 0 = the context's stream, the others are created on first use), and in

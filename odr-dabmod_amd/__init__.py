@@ -1087,9 +1087,15 @@ class Modulator:
             torch.cuda.current_stream(tensor.device).synchronize()
         return h
 
-    def _dev_call(self, fn, tensor, stream, *args):
+    def _dev_call(self, fn, tensor, stream, *args, queued=False):
         """The tail of a device wrapper of the receive-side stages: fn(handle, *args, stream handle), ordered as
-        _stream_handle describes."""
+        _stream_handle describes.  queued=True: the context's OWN stream (stream argument NULL) whatever torch's current
+        stream is, returning at once -- behind every chain call queued on the context before it, whichever lane that call went
+        to, and in front of the chain calls queued after it (as chain_dev_queued and post_process_dev_queued are ordered);
+        torch's stream is not touched and nothing is waited for."""
+        if queued:
+            self._chk(fn(self._h, *args, None))
+            return
         s = self._stream_handle(tensor, stream)
         self._chk(fn(self._h, *args, s))
         if not s:
@@ -1147,9 +1153,10 @@ class Modulator:
                                          out.ctypes.data if want_bits else None, ref.ctypes.data if ref is not None else None))
         return out
 
-    def demod_dev(self, d_iq, n_frames, early=0, d_bits_out=None, d_ref_bits=None, stream=None):
+    def demod_dev(self, d_iq, n_frames, early=0, d_bits_out=None, d_ref_bits=None, stream=None, queued=False):
         """Device path on torch tensors (complex64, or int16 pairs), asynchronous on the stream as chain_dev; d_bits_out
-        (uint8, n_frames x tf_input_bytes) and d_ref_bits may be None."""
+        (uint8, n_frames x tf_input_bytes) and d_ref_bits may be None.  queued=True, here and in every receive-side *_dev
+        wrapper below: on the context's own stream without waiting, behind the chain calls queued before it (_dev_call)."""
         import torch
         fmt = 0 if d_iq.dtype == torch.complex64 else (FORMATS["s16"][0] if d_iq.dtype == torch.int16 else -1)
         if fmt < 0:
@@ -1161,7 +1168,7 @@ class Modulator:
                 raise DabGpuError("demod: bit buffers are n_frames x tf_input_bytes")
         self._dev_call(self._lib.dabgpu_demod_dev, d_iq, stream, d_iq.data_ptr(), fmt, n_frames, int(early),
                        d_bits_out.data_ptr() if d_bits_out is not None else None,
-                       d_ref_bits.data_ptr() if d_ref_bits is not None else None)
+                       d_ref_bits.data_ptr() if d_ref_bits is not None else None, queued=queued)
 
     def demod_soft(self, iq, early=0, ref_bits=None, want_bits=False):
         """demod() with soft output: -> soft (n_frames x 8 tf_input_bytes int8; soft 8 p + b belongs to bit 0x80 >> b of byte
@@ -1185,7 +1192,7 @@ class Modulator:
                                               out.ctypes.data if want_bits else None, ref.ctypes.data if ref is not None else None))
         return (soft, out) if want_bits else soft
 
-    def demod_soft_dev(self, d_iq, n_frames, d_soft_out, early=0, d_bits_out=None, d_ref_bits=None, stream=None):
+    def demod_soft_dev(self, d_iq, n_frames, d_soft_out, early=0, d_bits_out=None, d_ref_bits=None, stream=None, queued=False):
         """demod_dev() with soft output: d_soft_out is int8, n_frames x 8 tf_input_bytes."""
         import torch
         fmt = 0 if d_iq.dtype == torch.complex64 else (FORMATS["s16"][0] if d_iq.dtype == torch.int16 else -1)
@@ -1200,7 +1207,7 @@ class Modulator:
                 raise DabGpuError("demod: bit buffers are n_frames x tf_input_bytes")
         self._dev_call(self._lib.dabgpu_demod_soft_dev, d_iq, stream, d_iq.data_ptr(), fmt, n_frames, int(early),
                        d_soft_out.data_ptr(), d_bits_out.data_ptr() if d_bits_out is not None else None,
-                       d_ref_bits.data_ptr() if d_ref_bits is not None else None)
+                       d_ref_bits.data_ptr() if d_ref_bits is not None else None, queued=queued)
 
     def set_monitor(self, enable, early=-1):
         """Demodulate every native-rate chain call's output against its own coded bits (off by default); early < 0: from
@@ -1271,11 +1278,11 @@ class Modulator:
         self._chk(self._lib.dabgpu_sync(self._h, iq.ctypes.data, fmt, n, int(max_shift)))
         return self.sync_result()
 
-    def sync_dev(self, d_iq, max_shift=31, stream=None):
+    def sync_dev(self, d_iq, max_shift=31, stream=None, queued=False):
         """Device path on a torch tensor (complex64, or int16 pairs), asynchronous on the stream as chain_dev; the records
         are sync_result(), the frames sync_extract_dev()."""
         fmt, n = self._capture_tensor("sync", d_iq)
-        self._dev_call(self._lib.dabgpu_sync_dev, d_iq, stream, d_iq.data_ptr(), fmt, n, int(max_shift))
+        self._dev_call(self._lib.dabgpu_sync_dev, d_iq, stream, d_iq.data_ptr(), fmt, n, int(max_shift), queued=queued)
 
     def sync_result(self):
         """The candidate frames of the most recent sync() / sync_dev() (waits for it): a list of dicts start, shift, valid, eps,
@@ -1302,13 +1309,13 @@ class Modulator:
         self._chk(self._lib.dabgpu_sync_extract(self._h, iq.ctypes.data, fmt, n, out.ctypes.data))
         return out
 
-    def sync_extract_dev(self, d_iq, d_frames_out, stream=None):
+    def sync_extract_dev(self, d_iq, d_frames_out, stream=None, queued=False):
         """Device path: d_frames_out is complex64, sync_slots(n_samples) x tf_samples."""
         import torch
         fmt, n = self._capture_tensor("sync", d_iq)
         if d_frames_out.dtype != torch.complex64 or d_frames_out.numel() != self.sync_slots(n) * self.geometry["tf_samples"]:
             raise DabGpuError("sync_extract: the output is complex64, sync_slots(n_samples) x tf_samples")
-        self._dev_call(self._lib.dabgpu_sync_extract_dev, d_iq, stream, d_iq.data_ptr(), fmt, n, d_frames_out.data_ptr())
+        self._dev_call(self._lib.dabgpu_sync_extract_dev, d_iq, stream, d_iq.data_ptr(), fmt, n, d_frames_out.data_ptr(), queued=queued)
 
     # ---- the channel emulator: paths, Doppler and seeded noise on a sample stream (include/dabgpu.h, "the channel") ----
     def set_channel(self, paths, sigma=0.0, seed=0, rate_hz=2048000.0):
@@ -1342,7 +1349,7 @@ class Modulator:
         self._chk(self._lib.dabgpu_channel(self._h, iq.ctypes.data, fmt, n, y.ctypes.data, 0 if out == "complexf" else FORMATS["s16"][0]))
         return y
 
-    def channel_dev(self, d_in, d_out, stream=None):
+    def channel_dev(self, d_in, d_out, stream=None, queued=False):
         """Device path on torch tensors (complex64, or int16 pairs; contiguous, the same number of samples), asynchronous on
         the stream as chain_dev."""
         import torch
@@ -1353,7 +1360,7 @@ class Modulator:
         fo, m = self._capture_tensor("channel", d_out)
         if n != m or not d_in.is_contiguous() or not d_out.is_contiguous():
             raise DabGpuError("channel: input and output are contiguous and hold the same number of samples")
-        self._dev_call(self._lib.dabgpu_channel_dev, d_in, stream, d_in.data_ptr(), fi, n, d_out.data_ptr(), fo)
+        self._dev_call(self._lib.dabgpu_channel_dev, d_in, stream, d_in.data_ptr(), fi, n, d_out.data_ptr(), fo, queued=queued)
 
     # ---- the TII analyser: transmitters, levels and delays of whole frames (include/dabgpu.h, "the TII analyser") ----
     def tii_scan(self, frames, early, old_variant=False, min_ratio=12.0, min_rel=1e-3):
@@ -1364,12 +1371,12 @@ class Modulator:
         self._chk(self._lib.dabgpu_tii_scan(self._h, iq.ctypes.data, fmt, n_frames, C.byref(cfg)))
         return self.tii_scan_result()
 
-    def tii_scan_dev(self, d_frames, n_frames, early, old_variant=False, min_ratio=12.0, min_rel=1e-3, stream=None):
+    def tii_scan_dev(self, d_frames, n_frames, early, old_variant=False, min_ratio=12.0, min_rel=1e-3, stream=None, queued=False):
         """Device path on a torch tensor (complex64, or int16 pairs) that holds n_frames whole frames, asynchronous on the
         stream as chain_dev; the result: tii_scan_result()."""
         fmt = self._frames_tensor("tii_scan", d_frames, n_frames)
         cfg = _tii_scan_config(early, old_variant, min_ratio, min_rel)
-        self._dev_call(self._lib.dabgpu_tii_scan_dev, d_frames, stream, d_frames.data_ptr(), fmt, int(n_frames), C.byref(cfg))
+        self._dev_call(self._lib.dabgpu_tii_scan_dev, d_frames, stream, d_frames.data_ptr(), fmt, int(n_frames), C.byref(cfg), queued=queued)
 
     def _tii_scan_raw(self):
         head, recs = _TiiScanHead(), (_TiiEntry * TII_SLOTS)()
@@ -1397,12 +1404,12 @@ class Modulator:
         self._chk(self._lib.dabgpu_cir(self._h, iq.ctypes.data, fmt, n_frames, C.byref(cfg)))
         return self.cir_result()
 
-    def cir_dev(self, d_frames, n_frames, early, window=1, min_ratio=20.0, min_rel=1e-3, stream=None):
+    def cir_dev(self, d_frames, n_frames, early, window=1, min_ratio=20.0, min_rel=1e-3, stream=None, queued=False):
         """Device path on a torch tensor (complex64, or int16 pairs) that holds n_frames whole frames, asynchronous on the
         stream as chain_dev; the result: cir_result(), cir_profile()."""
         fmt = self._frames_tensor("cir", d_frames, n_frames)
         cfg = _cir_config(early, window, min_ratio, min_rel)
-        self._dev_call(self._lib.dabgpu_cir_dev, d_frames, stream, d_frames.data_ptr(), fmt, int(n_frames), C.byref(cfg))
+        self._dev_call(self._lib.dabgpu_cir_dev, d_frames, stream, d_frames.data_ptr(), fmt, int(n_frames), C.byref(cfg), queued=queued)
 
     def _cir_raw(self):
         head, recs = _CirHead(), (_CirPath * CIR_MAX_PATHS)()
@@ -1454,12 +1461,12 @@ class Modulator:
                                           ref.ctypes.data if ref is not None else None, C.byref(ob)))
         return out[:ob.value].reshape(n, ETI_FRAME_BYTES), [self.decode_stats(i) for i in range(n)]
 
-    def decode_dev(self, d_bits, n_tf, d_eti_out, d_ref_eti=None, stream=None):
+    def decode_dev(self, d_bits, n_tf, d_eti_out, d_ref_eti=None, stream=None, queued=False):
         """Device path on torch uint8 tensors, asynchronous on the stream (as chain_dev); the figures: decode_stats."""
         ob = C.c_size_t()
         self._dev_call(self._lib.dabgpu_decode_dev, d_bits, stream, d_bits.data_ptr(), n_tf, d_eti_out.data_ptr(),
                        d_eti_out.numel() * d_eti_out.element_size(),
-                       d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob))
+                       d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob), queued=queued)
         return ob.value
 
     def decode_soft(self, soft, ref_eti=None):
@@ -1483,14 +1490,14 @@ class Modulator:
                                                ref.ctypes.data if ref is not None else None, C.byref(ob)))
         return out[:ob.value].reshape(n, ETI_FRAME_BYTES), [self.decode_soft_stats(i) for i in range(n)]
 
-    def decode_soft_dev(self, d_soft, n_tf, d_eti_out, d_ref_eti=None, stream=None):
+    def decode_soft_dev(self, d_soft, n_tf, d_eti_out, d_ref_eti=None, stream=None, queued=False):
         """Device path on torch tensors (int8 softs, uint8 images), asynchronous on the stream; the figures: decode_soft_stats."""
         if d_soft.numel() * d_soft.element_size() != 8 * n_tf * self.geometry["tf_input_bytes"]:
             raise DabGpuError("decode: input size not valid (whole transmission frames of soft metrics)")
         ob = C.c_size_t()
         self._dev_call(self._lib.dabgpu_decode_soft_dev, d_soft, stream, d_soft.data_ptr(), n_tf, d_eti_out.data_ptr(),
                        d_eti_out.numel() * d_eti_out.element_size(),
-                       d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob))
+                       d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob), queued=queued)
         return ob.value
 
     def decode_soft_stats(self, frame, unit=-1):
@@ -1525,7 +1532,7 @@ class Modulator:
         self._chk(self._lib.dabgpu_spectrum(self._h, iq.ctypes.data if n else None, fmt, n, int(window),
                                             int(bool(accumulate))))
 
-    def spectrum_dev(self, d_iq, window=2, accumulate=False, stream=None, n_samples=None):
+    def spectrum_dev(self, d_iq, window=2, accumulate=False, stream=None, n_samples=None, queued=False):
         """Device path on a torch tensor (complex64, or int16 / uint8 / int8 pairs), asynchronous on the stream as
         chain_dev; n_samples: the first so many samples of the tensor (default: all of it)."""
         import torch
@@ -1541,7 +1548,7 @@ class Modulator:
         if n > have:
             raise DabGpuError("spectrum: n_samples exceeds the tensor")
         self._dev_call(self._lib.dabgpu_spectrum_dev, d_iq, stream, d_iq.data_ptr() if n else None, fmt, n, int(window),
-                       int(bool(accumulate)))
+                       int(bool(accumulate)), queued=queued)
 
     def set_spectrum_monitor(self, enable, window=2):
         """Every chain call's output, whatever its rate and format, goes into the Welch sums (off by default); they
@@ -1617,11 +1624,11 @@ class Modulator:
                                                  n, int(rx_offset)))
         return self.dpd_xspectrum_result()
 
-    def dpd_xspectrum_dev(self, d_tx, d_rx, rx_offset=0, stream=None, n_samples=None):
+    def dpd_xspectrum_dev(self, d_tx, d_rx, rx_offset=0, stream=None, n_samples=None, queued=False):
         """Device path on torch tensors, asynchronous on the stream as chain_dev; the result: dpd_xspectrum_result()."""
         fmt, n = self._dpd_dev_pair(d_tx, d_rx, n_samples)
         self._dev_call(self._lib.dabgpu_dpd_xspectrum_dev, d_tx, stream, d_tx.data_ptr() if n else None, fmt,
-                       d_rx.data_ptr() if n else None, n, int(rx_offset))
+                       d_rx.data_ptr() if n else None, n, int(rx_offset), queued=queued)
 
     def dpd_xspectrum_result(self):
         """Waits: S (2048 complex128: sum of TX conj(RX), FFT order), p_tx, p_rx (float64) and the segments used."""
@@ -1642,12 +1649,12 @@ class Modulator:
                                              C.byref(a)))
         return _alignment_dict(a)
 
-    def dpd_align_dev(self, d_tx, d_rx, stream=None, n_samples=None):
+    def dpd_align_dev(self, d_tx, d_rx, stream=None, n_samples=None, queued=False):
         """Device path of dpd_align; waits for the stream, because the result is host data."""
         fmt, n = self._dpd_dev_pair(d_tx, d_rx, n_samples)
         a = _DpdAlignment()
         self._chk(self._lib.dabgpu_dpd_align_dev(self._h, d_tx.data_ptr() if n else None, fmt, d_rx.data_ptr() if n else None,
-                                                 n, C.byref(a), self._stream_handle(d_tx, stream)))
+                                                 n, C.byref(a), None if queued else self._stream_handle(d_tx, stream)))
         return _alignment_dict(a)
 
     def dpd_measure(self, tx, rx, alignment=None, peak=1.0, n_bins=64, accumulate=False):
@@ -1659,13 +1666,13 @@ class Modulator:
                                                None if al is None else C.byref(al), float(peak), int(n_bins),
                                                int(bool(accumulate))))
 
-    def dpd_measure_dev(self, d_tx, d_rx, alignment=None, peak=1.0, n_bins=64, accumulate=False, stream=None, n_samples=None):
+    def dpd_measure_dev(self, d_tx, d_rx, alignment=None, peak=1.0, n_bins=64, accumulate=False, stream=None, n_samples=None, queued=False):
         """Device path of dpd_measure, asynchronous on the stream as chain_dev."""
         fmt, n = self._dpd_dev_pair(d_tx, d_rx, n_samples)
         al = _alignment_struct(alignment)
         self._dev_call(self._lib.dabgpu_dpd_measure_dev, d_tx, stream, d_tx.data_ptr() if n else None, fmt,
                        d_rx.data_ptr() if n else None, n, None if al is None else C.byref(al),
-                       float(peak), int(n_bins), int(bool(accumulate)))
+                       float(peak), int(n_bins), int(bool(accumulate)), queued=queued)
 
     def dpd_stats(self):
         """Waits: n_bins, peak, overflow, samples_used, and per bin count, sum_tx, sum_rx, sum_phase, sum_rx2, sum_phase2
