@@ -665,7 +665,7 @@ DABGPU_API int dabgpu_debug_demod_run_symbols(dabgpu_ctx *ctx, int symbols);
  *   (N - K) / 2 - 1 in Mode III), an extraction without a dabgpu_sync* call on the same n_samples before it.
  * dabgpu_sync_check: host only, no context, no device: the shape refusals for a mode (1..4; 0 = IV), message via
  *   dabgpu_last_error(NULL).
- * Out of scope: sampling-clock offset, fractional-sample timing, multipath beyond the strongest path, tracking across calls,
+ * Out of scope: sampling-clock offset (since built: the clock), fractional-sample timing, multipath beyond the strongest path, tracking across calls,
  *   resampled (non-native-rate) captures, u8 / s8. */
 typedef struct dabgpu_sync_frame {
     int64_t start;
@@ -979,7 +979,7 @@ DABGPU_API int dabgpu_dpd_fit_poly(const dabgpu_dpd_stats *stats, int basis, uin
  *   pointer or one not aligned to a sample, n_samples = 0 (or above 2^40), input and output ranges that overlap, a format
  *   other than the two, more than 64 paths, a delay above 2047, a gain or sigma that is not finite, sigma < 0, rate_hz <= 0,
  *   |doppler_hz| >= rate_hz / 2, a call before any dabgpu_set_channel.
- * Out of scope: fractional-sample delays, sampling-clock offset, correlated (Jakes) fading inside the kernel (the caller
+ * Out of scope: fractional-sample delays, sampling-clock offset (since built: the clock), correlated (Jakes) fading inside the kernel (the caller
  *   composes it from paths: a sum of sinusoids per delay), u8 / s8. */
 #define DABGPU_CH_MAX_PATHS 64
 #define DABGPU_CH_MAX_DELAY 2047
@@ -1005,6 +1005,110 @@ DABGPU_API int dabgpu_channel(dabgpu_ctx *ctx, const void *in, int in_format, si
 /* Diagnostic: samples per workgroup of the channel's kernel (rounded up to a multiple of 4); 0 (the default) = chosen from the
  * call size.  Same bytes for every value; exists so that a test can walk the run geometry. */
 DABGPU_API int dabgpu_debug_channel_run_samples(dabgpu_ctx *ctx, int samples);
+
+/* ---- the clock: a sampling-clock offset on a sample stream -- put on, taken off (the resampler) and measured (the estimator) - *
+ * No capture is made on the transmitter's clock.  The resampler emulates a relative clock offset delta = ppm 1e-6 on samples
+ * that are on the device already and, with the opposite sign, corrects one; the estimator (further down) reads delta from the
+ * data symbols of whole frames.  The reference has no such stage; these entries replace nothing of its flowgraph.  The output
+ * is a function of the input stream, ppm and the absolute output index alone: a stream cut into calls of any lengths gives the
+ * bytes of one call.  delta > 0: the capture runs through the signal faster, y[m] ~ x(m (1 + delta)).
+ * Step and position: step = llrint(ppm 1e-6 2^64), the product evaluated in float64 from the left, an int64; |ppm| <= 1000.
+ *   For the absolute output index m >= 0: D(m) = m step as a signed 128-bit product; the input position
+ *   i_m = m + floor(D / 2^64); F = the upper 32 bits of the low 64 bits of D; mu = F / 2^32.  Nothing accumulates along the
+ *   stream: every output is a function of m alone.  A slip is where floor(D / 2^64) steps: i_m advances by 2, or by 0 for
+ *   delta < 0.
+ * Output: y[m] = sum_{j = 0 ... 31} h_j(mu) x[i_m + j - 15], x[.] the input stream counted from the last reset's position,
+ *   zero before the reset.
+ * Taps: a table T[p][j], p = 0 ... 512 (DABGPU_CLOCK_PHASES + 1 rows of DABGPU_CLOCK_TAPS).  Row p < 512 is
+ *   dabgpu_dpd_delay_taps(p / 512): sinc(j - 15 - tau) kaiser(beta = 10 over +-16 samples), float64 rounded to fp32 once; row 0
+ *   is the unit impulse at tap 15; row 512 is the unit impulse at tap 16 (dabgpu_clock_phase_taps returns any row).
+ *   p = F >> 23, f = (F & 0x7fffff) 2^-23 (exact in fp32), h_j = fmaf(f, T[p + 1][j] - T[p][j], T[p][j]), the difference an
+ *   fp32 subtraction.
+ * Sum, in fp32, the ONE order of every instantiation: re = im = +0; for j = 0, 1, ... 31 in this order
+ *   re = fmaf(h_j, Re x[i_m + j - 15], re), im = fmaf(h_j, Im x[i_m + j - 15], im).  With ppm = 0 the output is the input
+ *   (a negative zero comes out positive).
+ * Formats: input complexf (format 0) or DABGPU_FMT_S16 (a value becomes its float on load); output complexf or DABGPU_FMT_S16
+ *   -- dabgpu_format_process's conversion of the complexf result byte for byte (saturating, toward zero), without a clip
+ *   count.  u8 / s8 are refused.  Calls may mix the formats.
+ * State: T, the absolute number of input samples received (the reset's position included), and the last 31
+ *   (DABGPU_CLOCK_HISTORY) input samples, kept as floats in two buffers that take turns.  M(T) = the number of m >= 0 with
+ *   i_m + 16 <= T - 1: the outputs all of whose taps have arrived (= ceil((T - 16) 2^64 / (2^64 + step)), 0 for T <= 16).  A
+ *   call that brings n_in samples writes the outputs M(T) ... M(T + n_in) - 1 and returns their count in *n_out (it may be
+ *   0); the first of them has i_m + 16 >= T, so it reads no further back than T - 31.  The count is integer arithmetic on
+ *   the host, before anything is queued: no device round trip.  dabgpu_clock_count gives M, dabgpu_clock_out_max(n_in) =
+ *   n_in + n_in / 999 + 2 bounds the count of any call of n_in samples.  The output trails the input by 16 samples: after T
+ *   inputs at ppm = 0, outputs 0 ... T - 17 exist.
+ * dabgpu_clock_check, dabgpu_clock_step, dabgpu_clock_count, dabgpu_clock_out_max, dabgpu_clock_phase_taps,
+ *   dabgpu_clock_inverse_ppm: host only, no context, no device; message via dabgpu_last_error(NULL).
+ *   dabgpu_clock_inverse_ppm(ppm) = -ppm / (1 + ppm 1e-6): the setting that undoes delta, -delta / (1 + delta).
+ * dabgpu_set_clock: installs ppm and implies dabgpu_clock_reset(0).  Ordered behind the calls queued before it (the step
+ *   travels with each launch); the first one uploads the table.
+ * dabgpu_clock_reset: T = position (at most 2^62) with a zero history: the next call starts at output M(position).
+ * dabgpu_get_clock_position: T; waits for the most recent call, as dabgpu_get_channel_position does.
+ * dabgpu_clock_dev: device pointers (aligned to a sample), out_cap in samples, asynchronous on `stream` (NULL: the
+ *   context's own stream, behind every lane -- the calls stay on lane 0 in call order); at most two launches, no host round
+ *   trip.  The calls carry stream state: the caller keeps them in order.  dabgpu_clock: the host-pointer form.
+ * Refused with DABGPU_E_INVALID and a message before anything is queued (position, history and the output untouched): a ppm
+ *   that is not finite or above 1000 in magnitude, a format other than the two, a null pointer or one not aligned to a
+ *   sample, input and output ranges that overlap, n_in = 0 (or above 2^40), a position beyond 2^62, a call before any
+ *   dabgpu_set_clock.  An out_cap below the call's count: DABGPU_E_CAPACITY, the count in *n_out, nothing queued.
+ * Out of scope: a state blob or seed for the clock's history, tracking across calls, a time-varying offset, u8 / s8,
+ *   dabmod_file options (an offset moves the frames across its batch boundaries, which takes the synchroniser across
+ *   batches). */
+#define DABGPU_CLOCK_TAPS 32
+#define DABGPU_CLOCK_PHASES 512
+#define DABGPU_CLOCK_HISTORY 31
+DABGPU_API int dabgpu_clock_check(double ppm);
+DABGPU_API int dabgpu_clock_step(double ppm, int64_t *step);
+DABGPU_API int dabgpu_clock_count(double ppm, uint64_t T, uint64_t *M);
+DABGPU_API size_t dabgpu_clock_out_max(size_t n_in);
+DABGPU_API int dabgpu_clock_phase_taps(int p, float taps[32]);
+DABGPU_API double dabgpu_clock_inverse_ppm(double ppm);
+DABGPU_API int dabgpu_set_clock(dabgpu_ctx *ctx, double ppm);
+DABGPU_API int dabgpu_clock_reset(dabgpu_ctx *ctx, uint64_t position);
+DABGPU_API int dabgpu_get_clock_position(dabgpu_ctx *ctx, uint64_t *position);
+DABGPU_API int dabgpu_clock_dev(dabgpu_ctx *ctx, const void *d_in, int in_format, size_t n_in, void *d_out, int out_format,
+                                size_t out_cap, size_t *n_out, void *stream);
+DABGPU_API int dabgpu_clock(dabgpu_ctx *ctx, const void *in, int in_format, size_t n_in, void *out, int out_format,
+                            size_t out_cap, size_t *n_out);
+/* Diagnostic: outputs per workgroup of the clock's kernel (at most 2048); 0 (the default) = 1024.  Same bytes for every
+ * value; exists so that a test can walk the run geometry. */
+DABGPU_API int dabgpu_debug_clock_run_samples(dabgpu_ctx *ctx, int samples);
+
+/* The clock's estimator: the offset of whole frames from their data symbols, decision directed.  Input: whole transmission
+ * frames at the native rate as dabgpu_demod* takes them (a chain's output, or dabgpu_sync_extract's), complexf or
+ * DABGPU_FMT_S16; `early` as for dabgpu_demod*, refused the same way.  n_frames = 1 ... max_frames.
+ * Per frame, over its data blocks b and the occupied carriers k: d_{b,k} = z_s conj(z_{s-1}) is exactly dabgpu_demod's product
+ *   (s = b + 2), c its decided point, and in fp32
+ *   e = d conj(c) = (|Re d| + |Im d|) / sqrt 2 + j (Im d sgn Re d - Re d sgn Im d) / sqrt 2,  sgn x = -1 where x < 0, else +1;
+ *   |e| = sqrtf(fmaf(Re e, Re e, Im e Im e)).
+ * Sums: A_hi = sum of e over the carriers k = 1 ... K/2, A_lo = over k = -K/2 ... -1, S = sum of |e|, each over all data
+ *   blocks: float64 sums of the fp32 terms in a FIXED order -- per block the lane's carriers, a butterfly inside the wave, the
+ *   waves in wave order; then (a second kernel) the blocks in index order -- so a record repeats byte for byte and does not
+ *   depend on the run geometry (dabgpu_debug_demod_run_symbols sets it for this kernel too).
+ * Derived, in float64 on the host: ppm = 1e6 arg(A_hi conj(A_lo)) / (2 pi (sym_size / spacing) (K/2 + 1)) -- a clock offset
+ *   delta turns carrier k of d by 2 pi k delta sym_size / spacing, and with carriers of equal amplitude the two halves' mean
+ *   phases lie (K/2 + 1) carriers apart; residual_cfo = arg(A_hi + A_lo) / (2 pi sym_size / spacing), in carrier spacings;
+ *   quality = |A_hi + A_lo| / S; valid = (S > 0), and a frame that is not valid has every figure 0.
+ * The sign convention is the resampler's delta: a capture made by dabgpu_set_clock(p) reads +p, and
+ *   dabgpu_clock_inverse_ppm(estimate) is the setting that takes it off.  Working range: |2 pi (K/2) delta sym_size / spacing|
+ *   < pi/4, where the edge carriers reach the decision boundary (about +-130 ppm in Mode I); the drift of the FFT window
+ *   along the frame (delta x the frame's samples) must stay inside what `early` leaves of the cyclic prefix.  Amplitude slopes
+ *   across the band (an echo, a filter's edge) bias the estimate multiplicatively -- the sums weigh a carrier by |d| -- so
+ *   one estimate-and-correct pass leaves a residual of second order.
+ * dabgpu_sco_dev: a device pointer aligned to a sample, asynchronous on `stream` (NULL: the context's own stream, behind
+ *   every lane); two launches, no atomics, no host round trip.  dabgpu_sco: the host-pointer form.
+ * dabgpu_get_sco: waits for the most recent call, as the other getters do; frame = 0 ... n_frames - 1, or -1: the figures
+ *   from the sums over all valid frames, added in frame order.
+ * Out of scope: tracking across calls, a time-varying offset, weighting by a channel estimate, u8 / s8. */
+typedef struct dabgpu_sco_frame {
+    double a_hi_re, a_hi_im, a_lo_re, a_lo_im, s;   /* the raw sums */
+    double ppm, residual_cfo, quality;
+    int32_t valid, reserved;
+} dabgpu_sco_frame;
+DABGPU_API int dabgpu_sco_dev(dabgpu_ctx *ctx, const void *d_iq, int format, size_t n_frames, int early, void *stream);
+DABGPU_API int dabgpu_sco(dabgpu_ctx *ctx, const void *iq, int format, size_t n_frames, int early);
+DABGPU_API int dabgpu_get_sco(dabgpu_ctx *ctx, int frame, dabgpu_sco_frame *out);
 
 /* ---- the TII analyser: transmitters, levels and delays from the null symbols of whole frames -------------------------------- *
  * Reads what dabgpu_set_tii puts into a signal: which (comb, pattern) the null symbols carry, how strong every comb is and
@@ -1060,7 +1164,7 @@ DABGPU_API int dabgpu_debug_channel_run_samples(dabgpu_ctx *ctx, int samples);
  *   other than 0 / DABGPU_FMT_S16, a null or misaligned pointer.
  * dabgpu_tii_scan_check: host only, no context, no device: the refusals of mode (1..4; 0 = IV), n_frames (>= 2; max_frames is
  *   the context's) and the settings, message via dabgpu_last_error(NULL).
- * Out of scope: coherent accumulation across frames, more than one pattern per comb resolved, sampling-clock offset, u8 / s8,
+ * Out of scope: coherent accumulation across frames, more than one pattern per comb resolved, sampling-clock offset (since built: the clock), u8 / s8,
  *   resampled captures. */
 typedef struct dabgpu_tii_scan_config { int early, old_variant; float min_ratio, min_rel; } dabgpu_tii_scan_config;
 typedef struct dabgpu_tii_scan_head   { int n_used, parity, n_entries, reserved; double floor, total[2]; } dabgpu_tii_scan_head;
@@ -1124,7 +1228,7 @@ DABGPU_API int dabgpu_tii_scan_check(int mode, size_t n_frames, const dabgpu_tii
  * dabgpu_cir_check: host only, no context, no device: the refusals of mode (1..4; 0 = IV), n_frames (>= 1; max_frames is the
  *   context's) and the settings, message via dabgpu_last_error(NULL).
  * Out of scope: coherent averaging across frames, Doppler per path, a delay finer than the three-point `fine`, sampling-clock
- *   offset, u8 / s8, resampled captures, and weighting the soft metrics with resp (this measures what that would need). */
+ *   offset (since built: the clock), u8 / s8, resampled captures, and weighting the soft metrics with resp (this measures what that would need). */
 #define DABGPU_CIR_MAX_PATHS 16
 typedef struct dabgpu_cir_config { int early, window; float min_ratio, min_rel; } dabgpu_cir_config;
 typedef struct dabgpu_cir_head {

@@ -56,6 +56,9 @@ EXPORTS = [
     "dabgpu_sync_dev", "dabgpu_sync", "dabgpu_get_sync_result", "dabgpu_sync_extract_dev", "dabgpu_sync_extract", "dabgpu_sync_check",
     "dabgpu_channel_check", "dabgpu_set_channel", "dabgpu_channel_reset", "dabgpu_get_channel_position", "dabgpu_channel_dev",
     "dabgpu_channel", "dabgpu_debug_channel_run_samples",
+    "dabgpu_clock_check", "dabgpu_clock_step", "dabgpu_clock_count", "dabgpu_clock_out_max", "dabgpu_clock_phase_taps",
+    "dabgpu_clock_inverse_ppm", "dabgpu_set_clock", "dabgpu_clock_reset", "dabgpu_get_clock_position", "dabgpu_clock_dev",
+    "dabgpu_clock", "dabgpu_debug_clock_run_samples", "dabgpu_sco_dev", "dabgpu_sco", "dabgpu_get_sco",
     "dabgpu_tii_scan_dev", "dabgpu_tii_scan", "dabgpu_get_tii_scan", "dabgpu_tii_scan_check",
     "dabgpu_cir_dev", "dabgpu_cir", "dabgpu_get_cir", "dabgpu_get_cir_profile", "dabgpu_cir_check",
 ]
@@ -103,6 +106,12 @@ class _CfrStats(C.Structure):
 class _DemodStats(C.Structure):
     _fields_ = [("sum_signal", C.c_double), ("sum_quadrature", C.c_double), ("bit_errors", C.c_uint64),
                 ("n_bits", C.c_uint64), ("min_margin", C.c_double)]
+
+
+class _ScoFrame(C.Structure):
+    _fields_ = [("a_hi_re", C.c_double), ("a_hi_im", C.c_double), ("a_lo_re", C.c_double), ("a_lo_im", C.c_double),
+                ("s", C.c_double), ("ppm", C.c_double), ("residual_cfo", C.c_double), ("quality", C.c_double),
+                ("valid", C.c_int32), ("reserved", C.c_int32)]
 
 
 class _SyncFrame(C.Structure):
@@ -341,6 +350,23 @@ def load_library():
     lib.dabgpu_channel_dev.argtypes = [vp, vp, C.c_int, sz, vp, C.c_int, vp]
     lib.dabgpu_channel.argtypes = [vp, vp, C.c_int, sz, vp, C.c_int]
     lib.dabgpu_debug_channel_run_samples.argtypes = [vp, C.c_int]
+    lib.dabgpu_clock_check.argtypes = [C.c_double]
+    lib.dabgpu_clock_step.argtypes = [C.c_double, C.POINTER(C.c_int64)]
+    lib.dabgpu_clock_count.argtypes = [C.c_double, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.dabgpu_clock_out_max.argtypes = [sz]
+    lib.dabgpu_clock_out_max.restype = sz
+    lib.dabgpu_clock_phase_taps.argtypes = [C.c_int, C.POINTER(C.c_float)]
+    lib.dabgpu_clock_inverse_ppm.argtypes = [C.c_double]
+    lib.dabgpu_clock_inverse_ppm.restype = C.c_double
+    lib.dabgpu_set_clock.argtypes = [vp, C.c_double]
+    lib.dabgpu_clock_reset.argtypes = [vp, C.c_uint64]
+    lib.dabgpu_get_clock_position.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.dabgpu_clock_dev.argtypes = [vp, vp, C.c_int, sz, vp, C.c_int, sz, C.POINTER(sz), vp]
+    lib.dabgpu_clock.argtypes = [vp, vp, C.c_int, sz, vp, C.c_int, sz, C.POINTER(sz)]
+    lib.dabgpu_debug_clock_run_samples.argtypes = [vp, C.c_int]
+    lib.dabgpu_sco_dev.argtypes = [vp, vp, C.c_int, sz, C.c_int, vp]
+    lib.dabgpu_sco.argtypes = [vp, vp, C.c_int, sz, C.c_int]
+    lib.dabgpu_get_sco.argtypes = [vp, C.c_int, C.POINTER(_ScoFrame)]
     lib.dabgpu_tii_scan_dev.argtypes = [vp, vp, C.c_int, sz, C.POINTER(_TiiScanConfig), vp]
     lib.dabgpu_tii_scan.argtypes = [vp, vp, C.c_int, sz, C.POINTER(_TiiScanConfig)]
     lib.dabgpu_get_tii_scan.argtypes = [vp, C.POINTER(_TiiScanHead), C.POINTER(_TiiEntry), sz]
@@ -466,6 +492,53 @@ def channel_check(paths, sigma=0.0, seed=0, rate_hz=2048000.0):
     cfg = _channel_config(paths, sigma, seed, rate_hz)
     if lib.dabgpu_channel_check(C.byref(cfg)) != 0:
         raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def clock_check(ppm):
+    """Host only (needs the library, no device): raises DabGpuError when set_clock() would refuse this offset, with the
+    message it gives."""
+    lib = load_library()
+    if lib.dabgpu_clock_check(float(ppm)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def clock_step(ppm):
+    """Host only: the clock's step, llrint(ppm 1e-6 2^64), as a Python integer."""
+    lib = load_library()
+    step = C.c_int64()
+    if lib.dabgpu_clock_step(float(ppm), C.byref(step)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return int(step.value)
+
+
+def clock_count(ppm, T):
+    """Host only: M(T), the outputs the clock has written once T input samples have arrived."""
+    lib = load_library()
+    if not 0 <= int(T) < 2 ** 64:
+        raise DabGpuError("clock: the stream's position must not exceed 2^62")
+    m = C.c_uint64()
+    if lib.dabgpu_clock_count(float(ppm), int(T), C.byref(m)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return int(m.value)
+
+
+def clock_out_max(n_in):
+    """Host only: an upper bound of the outputs of any clock call that brings n_in samples."""
+    return int(load_library().dabgpu_clock_out_max(int(n_in)))
+
+
+def clock_phase_taps(p):
+    """Host only: row p (0 ... 512) of the clock's tap table, 32 fp32 taps."""
+    lib = load_library()
+    out = np.empty(32, np.float32)
+    if lib.dabgpu_clock_phase_taps(int(p), out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return out
+
+
+def clock_inverse_ppm(ppm):
+    """Host only: the setting that undoes an offset of ppm, -ppm / (1 + ppm 1e-6)."""
+    return float(load_library().dabgpu_clock_inverse_ppm(float(ppm)))
 
 
 def channel_sigma(power, cn_db):
@@ -1361,6 +1434,76 @@ class Modulator:
         if n != m or not d_in.is_contiguous() or not d_out.is_contiguous():
             raise DabGpuError("channel: input and output are contiguous and hold the same number of samples")
         self._dev_call(self._lib.dabgpu_channel_dev, d_in, stream, d_in.data_ptr(), fi, n, d_out.data_ptr(), fo, queued=queued)
+
+    # ---- the clock: a sampling-clock offset put on a sample stream, or taken off it (include/dabgpu.h, "the clock") ----
+    def set_clock(self, ppm):
+        """Install a clock offset in ppm (|ppm| <= 1000); implies clock_reset(0).  Takes effect at the next call."""
+        self._chk(self._lib.dabgpu_set_clock(self._h, float(ppm)))
+
+    def clock_reset(self, position=0):
+        """Zero history; the stream continues at input sample `position`, the output at clock_count(ppm, position)."""
+        if not 0 <= int(position) < 2 ** 64:
+            raise DabGpuError("clock: the stream's position must not exceed 2^62")
+        self._chk(self._lib.dabgpu_clock_reset(self._h, int(position)))
+
+    def clock_position(self):
+        """Input samples the stream has taken since the last reset, plus the reset's position (waits for the most recent call)."""
+        pos = C.c_uint64()
+        self._chk(self._lib.dabgpu_get_clock_position(self._h, C.byref(pos)))
+        return int(pos.value)
+
+    def set_clock_run_samples(self, samples=0):
+        """Diagnostic: outputs per workgroup of the clock's kernel (0: the default)."""
+        self._chk(self._lib.dabgpu_debug_clock_run_samples(self._h, int(samples)))
+
+    def clock(self, iq, out="complexf"):
+        """Host path: the next samples of the stream (complex64, or int16 interleaved re, im) through the clock -> the outputs
+        these samples complete: complex64, or int16 pairs with out="s16"."""
+        iq, fmt, n = self._capture_host("clock", iq)
+        if out not in ("complexf", "s16"):
+            raise DabGpuError("clock: formats are complexf (0) or DABGPU_FMT_S16")
+        cap = clock_out_max(n)
+        y = np.empty(cap, np.complex64) if out == "complexf" else np.empty(2 * cap, np.int16)
+        got = C.c_size_t()
+        self._chk(self._lib.dabgpu_clock(self._h, iq.ctypes.data, fmt, n, y.ctypes.data, 0 if out == "complexf" else FORMATS["s16"][0],
+                                         cap, C.byref(got)))
+        return y[:got.value if out == "complexf" else 2 * got.value].copy()
+
+    def clock_dev(self, d_in, d_out, stream=None, queued=False):
+        """Device path on torch tensors (complex64, or int16 pairs; contiguous), asynchronous on the stream as chain_dev.
+        d_out's size is the capacity.  Returns the number of output samples the call writes."""
+        import torch
+        for t in (d_in, d_out):
+            if t.dtype not in (torch.complex64, torch.int16) or (t.dtype == torch.int16 and t.numel() % 2):
+                raise DabGpuError("clock: tensors are complex64 or int16 (interleaved re, im)")
+        fi, n = self._capture_tensor("clock", d_in)
+        fo, cap = self._capture_tensor("clock", d_out)
+        if not d_in.is_contiguous() or not d_out.is_contiguous():
+            raise DabGpuError("clock: input and output are contiguous")
+        got = C.c_size_t()
+        self._dev_call(self._lib.dabgpu_clock_dev, d_in, stream, d_in.data_ptr(), fi, n, d_out.data_ptr(), fo, cap, C.byref(got),
+                       queued=queued)
+        return int(got.value)
+
+    def sco(self, frames, early=0):
+        """Host path: whole transmission frames at the native rate (complex64, or int16 interleaved re, im) -> sco_result()."""
+        iq, fmt, n_frames = self._frames_host("sco", frames)
+        self._chk(self._lib.dabgpu_sco(self._h, iq.ctypes.data, fmt, n_frames, int(early)))
+
+    def sco_dev(self, d_frames, n_frames, early=0, stream=None, queued=False):
+        """Device path on a torch tensor (complex64, or int16 pairs) holding n_frames whole frames, asynchronous on the stream
+        as chain_dev."""
+        fmt = self._frames_tensor("sco", d_frames, n_frames)
+        self._dev_call(self._lib.dabgpu_sco_dev, d_frames, stream, d_frames.data_ptr(), fmt, int(n_frames), int(early), queued=queued)
+
+    def sco_result(self, frame=-1):
+        """The clock estimate of the most recent sco* call (waits for it): dict(a_hi, a_lo, s, ppm, residual_cfo, quality,
+        valid, raw).  frame -1: from the sums over all valid frames.  raw: the record's bytes."""
+        st = _ScoFrame()
+        self._chk(self._lib.dabgpu_get_sco(self._h, int(frame), C.byref(st)))
+        return {"a_hi": complex(st.a_hi_re, st.a_hi_im), "a_lo": complex(st.a_lo_re, st.a_lo_im), "s": float(st.s),
+                "ppm": float(st.ppm), "residual_cfo": float(st.residual_cfo), "quality": float(st.quality),
+                "valid": int(st.valid), "raw": bytes(st)}
 
     # ---- the TII analyser: transmitters, levels and delays of whole frames (include/dabgpu.h, "the TII analyser") ----
     def tii_scan(self, frames, early, old_variant=False, min_ratio=12.0, min_rel=1e-3):

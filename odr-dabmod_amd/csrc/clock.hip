@@ -1,0 +1,239 @@
+// clock.hip -- the clock: a sampling-clock offset of at most 1000 ppm put on a sample stream or, with the opposite sign, taken
+// off it (the resampler), and read from the data symbols of whole frames (the estimator, further down); include/dabgpu.h, "the
+// clock".  The reference has no such stage.  Output m of the resampler is a function of its absolute index alone -- the input
+// position m + floor(m step / 2^64) and the fraction behind it come from one 64 x 64-bit product, nothing accumulates -- so a
+// stream cut into calls of any lengths, at any run geometry, gives the same bytes.
+// Its two kernels: the samples and the 31 samples of history the next call reads.  A workgroup makes `run` consecutive outputs:
+// their input span (run + run / 999 + 33 samples at most, the rate is that near 1) is staged in LDS as floats, then lane l
+// makes outputs l, l + 256, ...: consecutive lanes read consecutive LDS words whatever the slip does, which therefore costs
+// nothing -- an output's offset into the span is computed, never branched on.  The tap table stays in global memory (512 rows
+// of pairs (T[p][j], T[p + 1][j] - T[p][j]), 128 KB: L2 and the vector cache hold it), one 16-byte load per two taps; the
+// lanes of a wave read the same row or its neighbours.  No atomics, no scratch.
+#include "device_common.h"
+#include "turn_phase.h"
+
+namespace dabgpu {
+namespace {
+
+// output m: the input position i = m + floor(m step / 2^64) and F = the upper 32 bits of the low half of m step
+DEV void clock_position(unsigned long long m, long long step, long long &i, uint32_t &F)
+{
+    const unsigned long long us = (unsigned long long)step;            // step + 2^64 when step < 0: the low half is the same,
+    long long hi = (long long)__umul64hi(m, us);                       // the high half is m too large
+    if (step < 0) hi -= (long long)m;
+    i = (long long)m + hi;
+    F = (uint32_t)((m * us) >> 32);
+}
+
+template <int IF, int OF> __global__ __launch_bounds__(256) void clock_kernel(const ClockArgs a)
+{
+    __shared__ float2 span[kClkSpan];
+    const long long k0 = (long long)blockIdx.x * a.run;
+    const int cnt = (int)min((long long)a.run, a.count - k0);
+    const unsigned long long mb = a.m0 + (unsigned long long)k0;
+    long long i_first, i_last;
+    uint32_t F;
+    clock_position(mb, a.step, i_first, F);
+    clock_position(mb + (unsigned long long)(cnt - 1), a.step, i_last, F);
+    // span[t] = input sample i_first - 15 + t; r: the same index counted from the call's first sample (>= -31)
+    const int len = min((int)(i_last - i_first) + kClkTaps, kClkSpan);
+    const long long r0 = i_first - kClkCentre - (long long)a.T;
+    for (int t = threadIdx.x; t < len; t += 256) {
+        const long long r = r0 + t;
+        cf v = mk(0.f, 0.f);
+        if (r >= 0) {
+            if (r < a.n) v = ld_iq(a.in, IF, r);
+        } else if (r >= -kClkHist) {
+            v = a.hist[kClkHist + r];
+        }
+        span[t] = v;
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < cnt; k += 256) {
+        long long i;
+        clock_position(mb + (unsigned long long)k, a.step, i, F);
+        const int o = min(max((int)(i - i_first), 0), len - kClkTaps);
+        const float f = (float)(F & 0x7fffffu) * 1.1920928955078125e-07f;
+        const float4 *row = reinterpret_cast<const float4 *>(a.tab + (size_t)(F >> 23) * kClkTaps);
+        // taps 0 ... 31 in this order, one fused multiply-add per component and tap, from zero
+        float re = 0.f, im = 0.f;
+#pragma unroll
+        for (int j = 0; j < kClkTaps; j += 2) {
+            const float4 td = row[j / 2];
+            const float h0 = fmaf(f, td.y, td.x), h1 = fmaf(f, td.w, td.z);
+            const cf x0 = span[o + j], x1 = span[o + j + 1];
+            re = fmaf(h0, x0.x, re);
+            im = fmaf(h0, x0.y, im);
+            re = fmaf(h1, x1.x, re);
+            im = fmaf(h1, x1.y, im);
+        }
+        if (OF == 0) {
+            reinterpret_cast<float2 *>(a.out)[k0 + k] = mk(re, im);
+        } else {
+            // format_kernel's conversion (format_one: saturating, toward zero), without the clip count
+            unsigned unused = 0;
+            const int qr = format_one<1>(re, unused), qi = format_one<1>(im, unused);
+            reinterpret_cast<uint32_t *>(a.out)[k0 + k] = (unsigned)(qr & 0xffff) | ((unsigned)qi << 16);
+        }
+    }
+}
+
+template <int IF> __global__ __launch_bounds__(64)
+void clock_history_kernel(const void *in, long long n, const float2 *__restrict__ cur, float2 *__restrict__ next)
+{
+    const int j = (int)threadIdx.x;
+    if (j >= kClkHist) return;
+    const long long r = n - kClkHist + j;                               // (n >= 1: r < 0 reads cur[n + j], n + j < kClkHist)
+    next[j] = r >= 0 ? ld_iq(in, IF, r) : cur[kClkHist + r];
+}
+
+// ---- the estimator.  demod.hip's geometry: one workgroup of N/8 lanes per run of data symbols, eight samples per lane, the
+// forward transform, six carriers per lane (slots 0, 1, 2: bins 1 ... K/2, lane 0 taking bin 3T for its DC bin; slots 5, 6, 7:
+// bins N - K/2 ... N - 1), the product against the previous symbol's bins kept in registers.  Per block, float64 sums of the
+// fp32 terms in one order: the lane's slots in slot order, an xor butterfly inside the wave (a + b = b + a exactly: every
+// lane ends with the same sum), the waves in wave order through LDS.  A block's sums do not depend on the run it is in.
+template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void sco_kernel(ScoArgs a)
+{
+    typedef Fft<LOGN> F;
+    constexpr int N = F::N, T = F::T;
+    constexpr int NW = (T + 63) / 64, WL = T < 64 ? T : 64;
+    __shared__ cf xbuf[2 * F::LDS_ELEMS];
+    __shared__ double red[NW][kScoSums];
+
+    const int t = (int)threadIdx.x;
+    const int nblocks = a.g.nb_symbols - 1;
+    const int frame = (int)blockIdx.x / a.runs_per_frame;
+    const int run = (int)blockIdx.x - frame * a.runs_per_frame;
+    const int b0 = run * a.syms_per_run;
+    const int b1 = min(b0 + a.syms_per_run, nblocks);
+    if (frame >= a.n_frames || b0 >= b1) return;
+
+    cf tw[F::NTW > 0 ? F::NTW : 1];
+    F::template load_twiddles<false>(a.t.twiddle, t, tw);
+    constexpr int rr[6] = {0, 1, 2, 5, 6, 7};
+
+    const size_t first = (size_t)a.g.null_size + (size_t)(a.g.sym_size - N - a.early);      // window of symbol 1
+    const long long base = (long long)((size_t)frame * a.frame_stride + first);
+    auto load = [&](int s, cf *v) __attribute__((always_inline)) {      // symbol s >= 1 of the frame
+        const long long off = base + (long long)(s - 1) * (long long)a.g.sym_size + t;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) v[m] = ld_iq(a.iq, a.fmt, off + T * m);
+    };
+
+    int par = 0;
+    cf v[8], prev[6];
+    load(b0 + 1, v);
+    F::template run<-1, true, cf, false>(v, xbuf, par, tw, t);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) prev[c] = v[rr[c]];
+    if (t == 0) prev[0] = v[3];
+
+    for (int b = b0; b < b1; ++b) {
+        load(b + 2, v);
+        F::template run<-1, true, cf, false>(v, xbuf, par, tw, t);
+        double sum[kScoSums] = {0., 0., 0., 0., 0.};
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const cf z = (c == 0 && t == 0) ? v[3] : v[rr[c]], p = prev[c];
+            const float dre = fmaf(z.x, p.x, z.y * p.y), dim = fmaf(z.y, p.x, -(z.x * p.y));      // z conj(p): demod's product
+            prev[c] = z;
+            // e = d conj(c), c the decided point (sgn Re d + j sgn Im d) / sqrt 2, a negative sign where demod decides a 1
+            const float er = (fabsf(dre) + fabsf(dim)) * kSqrtHalf;
+            const float ei = ((dre < 0.f ? -dim : dim) - (dim < 0.f ? -dre : dre)) * kSqrtHalf;
+            const float mag = sqrtf(fmaf(er, er, ei * ei));
+            sum[c < 3 ? 0 : 2] += (double)er;
+            sum[c < 3 ? 1 : 3] += (double)ei;
+            sum[4] += (double)mag;
+        }
+#pragma unroll
+        for (int i = 0; i < kScoSums; ++i) {
+#pragma unroll
+            for (int off = WL / 2; off >= 1; off >>= 1) sum[i] += __shfl_xor(sum[i], off, WL);
+        }
+        if ((t & 63) == 0) {
+#pragma unroll
+            for (int i = 0; i < kScoSums; ++i) red[t >> 6][i] = sum[i];
+        }
+        lds_barrier();
+        if (t < kScoSums) {                // (the next block's writes to red come behind the barriers of its transform)
+            double s = red[0][t];
+            for (int w = 1; w < NW; ++w) s += red[w][t];
+            a.rows[((size_t)frame * (size_t)nblocks + (size_t)b) * kScoSums + t] = s;
+        }
+    }
+}
+
+// a frame's sums: its blocks in index order, one lane per (frame, sum)
+__global__ __launch_bounds__(64) void sco_frames_kernel(const double *__restrict__ rows, double *__restrict__ frames, int n, int nblocks)
+{
+    const int i = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (i >= n * kScoSums) return;
+    const int frame = i / kScoSums, k = i - frame * kScoSums;
+    double s = 0.;
+    for (int b = 0; b < nblocks; ++b) s += rows[((size_t)frame * (size_t)nblocks + (size_t)b) * kScoSums + k];
+    frames[i] = s;
+}
+
+}  // namespace
+
+hipError_t launch_sco(const ScoArgs &a, hipStream_t s)
+{
+    if (a.n_frames <= 0 || !a.iq || !a.rows || !a.frames || a.early < 0 || a.early > a.g.sym_size - a.g.N || a.runs_per_frame < 1 ||
+        a.syms_per_run < 1 || (a.fmt != 0 && a.fmt != 1) || a.g.K != 3 * a.g.N / 4 ||
+        (long long)a.runs_per_frame * a.syms_per_run < a.g.nb_symbols - 1)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)a.n_frames * (unsigned)a.runs_per_frame);
+    switch (a.g.logN) {
+    case 8: DABGPU_LAUNCH(sco_kernel<8>, grid, dim3(Fft<8>::T), 0, s, a); break;
+    case 9: DABGPU_LAUNCH(sco_kernel<9>, grid, dim3(Fft<9>::T), 0, s, a); break;
+    case 10: DABGPU_LAUNCH(sco_kernel<10>, grid, dim3(Fft<10>::T), 0, s, a); break;
+    case 11: DABGPU_LAUNCH(sco_kernel<11>, grid, dim3(Fft<11>::T), 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    DABGPU_LAUNCH(sco_frames_kernel, dim3((unsigned)((a.n_frames * kScoSums + 63) / 64)), dim3(64), 0, s, a.rows, a.frames, a.n_frames,
+                  a.g.nb_symbols - 1);
+    return hipGetLastError();
+}
+
+// outputs per workgroup: forced (1 ... kClkMaxRun), or 1024
+int clock_run(size_t count, int forced)
+{
+    (void)count;
+    if (forced > 0) return std::min(forced, kClkMaxRun);
+    return 1024;
+}
+
+hipError_t launch_clock(const ClockArgs &a, hipStream_t s)
+{
+    if (!a.in || !a.out || !a.hist || !a.tab || a.n < 1 || a.count < 1 || (a.in_fmt != 0 && a.in_fmt != 1) ||
+        (a.out_fmt != 0 && a.out_fmt != 1) || a.run < 1 || a.run > kClkMaxRun)
+        return hipErrorInvalidValue;
+    // what the kernel relies on: |step| <= 2^64 / 1000 (a run's span fits), and every output's 32 taps lie in
+    // [T - 31, T + n - 1]
+    if (a.step > 18446744073709552LL || a.step < -18446744073709552LL) return hipErrorInvalidValue;
+    const unsigned __int128 w = ((unsigned __int128)1 << 64) + (__int128)a.step;
+    const auto pos = [&](unsigned long long m) { return (long long)(((unsigned __int128)m * w) >> 64); };
+    const __int128 lo = (__int128)pos(a.m0) - kClkCentre, hi = (__int128)pos(a.m0 + (unsigned long long)(a.count - 1)) + 16;
+    if (lo < (__int128)a.T - kClkHist || hi > (__int128)a.T + a.n - 1) return hipErrorInvalidValue;
+    const long long blocks = (a.count + a.run - 1) / a.run;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), block(256);
+    if (a.in_fmt == 0 && a.out_fmt == 0) DABGPU_LAUNCH((clock_kernel<0, 0>), grid, block, 0, s, a);
+    else if (a.in_fmt == 0) DABGPU_LAUNCH((clock_kernel<0, 1>), grid, block, 0, s, a);
+    else if (a.out_fmt == 0) DABGPU_LAUNCH((clock_kernel<1, 0>), grid, block, 0, s, a);
+    else DABGPU_LAUNCH((clock_kernel<1, 1>), grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_clock_history(const void *in, int in_fmt, long long n, const float2 *cur, float2 *next, hipStream_t s)
+{
+    if (!in || !cur || !next || cur == next || n < 1 || (in_fmt != 0 && in_fmt != 1)) return hipErrorInvalidValue;
+    const dim3 grid(1), block(64);
+    if (in_fmt == 0) DABGPU_LAUNCH(clock_history_kernel<0>, grid, block, 0, s, in, n, cur, next);
+    else DABGPU_LAUNCH(clock_history_kernel<1>, grid, block, 0, s, in, n, cur, next);
+    return hipGetLastError();
+}
+
+}  // namespace dabgpu

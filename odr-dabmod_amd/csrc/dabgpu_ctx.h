@@ -19,6 +19,9 @@
 //                     receiver; the shape check (host only)
 //   api_channel.hip   the channel emulator (channel.hip): paths, Doppler and seeded noise on a sample stream, its history and
 //                     position; the settings check (host only)
+//   api_clock.hip     the clock's resampler (clock.hip): a sampling-clock offset put on a sample stream or taken off it, its
+//                     history and position; step, counts and the tap table (host only); the clock's estimator: the offset
+//                     of whole frames from their data symbols
 //   api_tii_scan.hip  the TII analyser (tii_scan.hip): transmitters, levels and delays from the null symbols of whole frames;
 //                     the settings check (host only)
 //   api_cir.hip       the channel estimator (cir.hip): impulse response, echoes and the response on the carriers from the
@@ -194,6 +197,28 @@ struct ChannelState {
     int run_samples = 0;                  // dabgpu_debug_channel_run_samples: samples per workgroup, 0 = by the call size
 };
 
+// The clock's resampler (api_clock.hip, clock.hip).  hist: two histories of kClkHist float samples, the stream state;
+// hist_cur: the one the next call reads (a call writes the other and swaps).  zero_pending: the next call zeroes it first
+// (after dabgpu_set_clock and dabgpu_clock_reset).  T: input samples the stream has taken (the reset's position included).
+// step: the installed offset as the kernel takes it.  tab: the tap table, uploaded by the first dabgpu_set_clock.
+struct ClockState {
+    DevBuf hist, tab, in, out;
+    bool configured = false, zero_pending = true;
+    int hist_cur = 0;
+    unsigned long long T = 0;
+    long long step = 0;
+    hipStream_t stream = nullptr;
+    int run_samples = 0;                  // dabgpu_debug_clock_run_samples: outputs per workgroup, 0 = the default
+};
+
+// The clock's estimator (api_clock.hip, clock.hip).  rows: every block's sums (scratch); sums: the frames' sums of the most
+// recent dabgpu_sco* call, `frames` of them (0: no call yet); in: the host-pointer entry's staging.
+struct ScoState {
+    DevBuf rows, sums, in;
+    size_t frames = 0;
+    hipStream_t stream = nullptr;
+};
+
 // The TII analyser (api_tii_scan.hip, tii_scan.hip).  result: head, 24 entry slots and the entries' grid centres of the most
 // recent dabgpu_tii_scan* call; rows / bins: per-frame cell sums and occupied bins (scratch); in: the host-pointer entry's
 // staging; done: a call has been queued.
@@ -279,6 +304,8 @@ struct dabgpu_ctx {
     dabgpu_api::DecodeState decode;
     dabgpu_api::SyncState sync;
     dabgpu_api::ChannelState channel;
+    dabgpu_api::ClockState clock;
+    dabgpu_api::ScoState sco;
     dabgpu_api::TiiScanState tii_scan;
     dabgpu_api::CirState cir;
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII

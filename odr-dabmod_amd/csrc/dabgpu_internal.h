@@ -234,6 +234,46 @@ int channel_run(size_t n, int forced);
 hipError_t launch_channel(const ChannelArgs &a, hipStream_t s);
 // the history behind a call: next[j] = sample n - kChMaxDelay + j of the call, from `in` or (calls shorter than it) from `cur`
 hipError_t launch_channel_history(const void *in, int in_fmt, long long n, const float2 *cur, float2 *next, hipStream_t s);
+// clock.hip: the clock's resampler (dabgpu_clock*): a sampling-clock offset put on a sample stream, or taken off it
+constexpr int kClkTaps = 32;              // taps of the interpolator, tap kClkCentre on the input position
+constexpr int kClkCentre = 15;
+constexpr int kClkPhases = 512;           // rows 0 ... 512 of the tap table
+constexpr int kClkHist = 31;              // the history holds this many input samples
+constexpr int kClkMaxRun = 2048;          // outputs per workgroup at most (the staged input span: kClkSpan samples of LDS)
+constexpr int kClkSpan = kClkMaxRun + kClkMaxRun / 999 + 1 + kClkTaps;
+struct ClockArgs {
+    const void *in;                       // n samples, in_fmt 0 (complexf) or 1 (s16 pairs)
+    void *out;                            // count samples, out_fmt likewise
+    const float2 *hist;                   // kClkHist samples: hist[kClkHist + r] = sample r < 0 of this call
+    const float2 *tab;                    // [kClkPhases][kClkTaps]: (T[p][j], T[p + 1][j] - T[p][j])
+    long long n;
+    unsigned long long T;                 // absolute index of input sample 0 of the call
+    unsigned long long m0;                // absolute index of the call's first output
+    long long count;                      // outputs of the call
+    long long step;                       // llrint(ppm 1e-6 2^64)
+    int in_fmt, out_fmt;
+    int run;                              // outputs per workgroup, 1 ... kClkMaxRun
+};
+int clock_run(size_t count, int forced);
+hipError_t launch_clock(const ClockArgs &a, hipStream_t s);
+// the history behind a call: next[j] = sample n - kClkHist + j of the call, from `in` or (calls shorter than it) from `cur`
+hipError_t launch_clock_history(const void *in, int in_fmt, long long n, const float2 *cur, float2 *next, hipStream_t s);
+// clock.hip, the estimator (dabgpu_sco*): per data block of whole frames the sums of e = d conj(c) over either half of the
+// carriers and of |e|, in the receiver's geometry (demod_runs); then the blocks of a frame in index order
+constexpr int kScoSums = 5;               // Re A_hi, Im A_hi, Re A_lo, Im A_lo, S
+struct ScoArgs {
+    Geometry g;
+    Tables t;                 // twiddle
+    const void *iq;           // n_frames x frame_stride samples: cf32 (fmt 0) or s16 pairs (fmt 1 = DABGPU_FMT_S16)
+    int fmt;
+    size_t frame_stride;      // samples per frame
+    int n_frames;
+    int runs_per_frame, syms_per_run;   // (demod_runs)
+    int early;                // the FFT window ends this many samples before the end of the symbol; 0 ... sym_size - N
+    double *rows;             // n_frames x (nb_symbols - 1) x kScoSums: every block's sums
+    double *frames;           // n_frames x kScoSums: the frames' sums
+};
+hipError_t launch_sco(const ScoArgs &a, hipStream_t s);
 // tii_scan.hip: the TII analyser (dabgpu_tii_scan*): which (comb, pattern) the null symbols of whole frames carry, the level
 // and the delay of every comb
 constexpr int kTiiCombs = 24;             // combs, and entry slots of a result
