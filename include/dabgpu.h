@@ -381,7 +381,8 @@ DABGPU_API int dabgpu_chain_seed_dev(dabgpu_ctx *ctx, const void *d_leadin_bits,
  *     stay on lane 0, in call order (to overlap such calls, split the stream over contexts: "stream state" above);
  *   - a call with an explicit stream argument is what it always was: asynchronous on that stream, the context's scratch.
  *     Do not mix the two on one context without a dabgpu_synchronize in between;
- *   - every receive-side `_dev` entry with stream == NULL (dabgpu_demod_dev, dabgpu_demod_soft_dev, dabgpu_sync_dev,
+ *   - every receive-side `_dev` entry with stream == NULL (dabgpu_demod_dev, dabgpu_demod_soft_dev, dabgpu_demod_csi_dev,
+ *     dabgpu_demod_carrier_state_dev, dabgpu_sync_dev,
  *     dabgpu_sync_extract_dev, dabgpu_channel_dev, dabgpu_tii_scan_dev, dabgpu_cir_dev, dabgpu_decode_dev,
  *     dabgpu_decode_soft_dev, dabgpu_spectrum_dev, dabgpu_dpd_xspectrum_dev, dabgpu_dpd_align_dev, dabgpu_dpd_measure_dev)
  *     runs on the context's own stream, behind everything queued on ANY lane before it: its input may be the output of a
@@ -609,6 +610,63 @@ DABGPU_API int dabgpu_demod_soft_dev(dabgpu_ctx *ctx, const void *d_iq, int form
                                      void *d_soft_out, void *d_bits_out, const void *d_ref_bits, void *stream);
 DABGPU_API int dabgpu_demod_soft(dabgpu_ctx *ctx, const void *iq, int format, size_t n_frames, int early, int8_t *soft_out,
                                  uint8_t *bits_out, const uint8_t *ref_bits);
+/* ---- the carrier state: soft metrics weighted by the noise on their carrier, MER per carrier ------------------------------ *
+ * d = z_s conj(z_{s-1}) carries |H[k]|^2 already; what the metrics above lack for a log-likelihood ratio is 1 / sigma_k^2, the
+ * noise-plus-interference power on carrier k -- nothing on white noise, everything behind a spur or a co-channel carrier, whose
+ * carriers have the largest |d| of the symbol and random signs.  The state is measured on the frame itself, per carrier
+ * POSITION k (0 ... K - 1 in frequency order: bins 1 ... K/2 -> k = bin - 1, bins N - K/2 ... N - 1 -> k = bin - N + K; the
+ * index in front of the frequency interleaver), over the S = nb_symbols - 1 data symbols s of the frame, with q_s the soft
+ * scale above and u = d_k q_s:
+ *   A_k = sum_s rint(2^F (|Re u| + |Im u|) / 2)      the folded amplitude
+ *   V_k = sum_s rint(2^F (|Im u| - |Re u|)^2 / 2)    the power at right angles to the decision (sum_quadrature's term)
+ * with F = DABGPU_CSI_FRAC_BITS, rint to the nearest integer (ties to even); int64 sums.  Integer sums do not depend on the
+ * order of their terms: the state, the weights and the softs are the same bytes for every run geometry
+ * (dabgpu_debug_demod_run_symbols), batch size and repetition.  The state is formed in float64 from the samples on -- the
+ * transform, d, P, q_s = 64 sqrt(2) / sqrt(P / K) and the terms -- so that a float64 evaluation of these lines gives the same
+ * integers: one count is 2^-16 of a metric step, finer than fp32 resolves at a metric's magnitude.  (Against another float64
+ * transform a term lies some 1e-8 counts off.)  The weighted metrics below use dabgpu_demod_soft's fp32 d and q_s.
+ * The weights, float64, operation by operation (every one IEEE-754 correctly rounded, so a model reproduces the bits):
+ *   T_0 = all K carriers; for i = 0 ... DABGPU_CSI_TRIM_PASSES - 1, with n_i = |T_i| and SV_i = sum of V_k over T_i (integers):
+ *                       T_(i+1) = { k of all K carriers : V_k n_i <= DABGPU_CSI_TRIM_FACTOR SV_i }      (integer comparison)
+ *   T the last set, n = |T| (never empty: the smallest V_k is always in), SA = sum of A_k over T, SV = sum of V_k over T
+ *   SA = 0 or SV = 0:   w_k = 1 for every k          (all-zero input; a clean loop whose quadrature terms all round to 0)
+ *   otherwise           floor = double(SV) / double(64 n)
+ *                       r_k = (double(A_k) * double(SV)) / (double(SA) * max(double(V_k), floor))
+ *                       w_k = float(min(DABGPU_CSI_MAX_WEIGHT, r_k))
+ *   i.e. w_k = (A_k / mean A) / (max(V_k, mean V / 64) / mean V), the means over T: the Gaussian LLR 2 A x / V with the |H|^2
+ *   that x carries taken out, 1 on a flat channel with white noise, at most DABGPU_CSI_MAX_WEIGHT, 0 on a carrier without
+ *   signal; always finite.  The means leave out the carriers whose V_k lies far above the rest, because those carriers are what
+ *   the weights exist for: with plain means a strong spur raises mean V until every clean carrier sits at the maximum weight
+ *   and its metrics at +-127 (on the models that rule gained 4 dB against a tone, this one 14 dB: profiles/csi.txt).  On white
+ *   noise V_k scatters by sqrt(2 / S) about its mean and no carrier comes near the factor: nothing is left out.
+ * The weighted metric: soft_I = clamp(rint((-Re d_k q_s) w_k), -127, 127), soft_Q likewise, fp32 in this order -- with every
+ *   w_k = 1 the bytes dabgpu_demod_soft writes.  The weights of a frame come from that frame alone: no state across frames.
+ * Per-carrier MER in dB, formed by the caller: 20 log10(A_k / sqrt(2^(F - 1) S V_k))  (= 10 log10 of 2 (A_k / S)^2 over V_k / S
+ *   in units of u^2; +inf where V_k = 0).
+ * dabgpu_demod_csi_dev / dabgpu_demod_csi: the arguments, formats, `early` rule, refusals (all before anything is queued), output
+ *   layout, bits and per-frame figures (dabgpu_get_demod_stats) of dabgpu_demod_soft_dev / dabgpu_demod_soft; the softs are the
+ *   weighted ones.  Three launches: the state (a float64 transform pass), the weights, the weighted softs (the fp32 pass of
+ *   dabgpu_demod_soft with the weights).
+ * dabgpu_demod_carrier_state_dev / dabgpu_demod_carrier_state: the state and the weights alone -- no softs, no bits, and the
+ *   figures of dabgpu_get_demod_stats stay those of the call before.
+ * dabgpu_get_carrier_state: frame `frame` of the most recent of these four calls, after waiting for it: K int64 each to A and V,
+ *   K floats to w (any of them NULL: not wanted).  DABGPU_E_INVALID before any such call and for a frame beyond it.
+ * stream == NULL: the context's own stream behind every lane, as every receive-side _dev entry. */
+#define DABGPU_CSI_FRAC_BITS 16
+#define DABGPU_CSI_MAX_WEIGHT 4
+#define DABGPU_CSI_TRIM_PASSES 3
+#define DABGPU_CSI_TRIM_FACTOR 4
+DABGPU_API int dabgpu_demod_csi_dev(dabgpu_ctx *ctx, const void *d_iq, int format, size_t n_frames, int early,
+                                    void *d_soft_out, void *d_bits_out, const void *d_ref_bits, void *stream);
+DABGPU_API int dabgpu_demod_csi(dabgpu_ctx *ctx, const void *iq, int format, size_t n_frames, int early, int8_t *soft_out,
+                                uint8_t *bits_out, const uint8_t *ref_bits);
+DABGPU_API int dabgpu_demod_carrier_state_dev(dabgpu_ctx *ctx, const void *d_iq, int format, size_t n_frames, int early,
+                                              void *stream);
+DABGPU_API int dabgpu_demod_carrier_state(dabgpu_ctx *ctx, const void *iq, int format, size_t n_frames, int early);
+DABGPU_API int dabgpu_get_carrier_state(dabgpu_ctx *ctx, size_t frame, int64_t *A, int64_t *V, float *w);
+/* Diagnostic: every weight 1 whatever the state says (the sums are still formed): dabgpu_demod_csi* then writes
+ * dabgpu_demod_soft*'s bytes. */
+DABGPU_API int dabgpu_debug_csi_unit_weights(dabgpu_ctx *ctx, int enable);
 /* host only, no context, no device: the range test of `early` for a transmission mode (1..4; 0 = IV), with the message the
  * entries above give (dabgpu_last_error(NULL), per thread) */
 DABGPU_API int dabgpu_demod_check_early(int mode, int early);

@@ -61,6 +61,8 @@ EXPORTS = [
     "dabgpu_clock", "dabgpu_debug_clock_run_samples", "dabgpu_sco_dev", "dabgpu_sco", "dabgpu_get_sco",
     "dabgpu_tii_scan_dev", "dabgpu_tii_scan", "dabgpu_get_tii_scan", "dabgpu_tii_scan_check",
     "dabgpu_cir_dev", "dabgpu_cir", "dabgpu_get_cir", "dabgpu_get_cir_profile", "dabgpu_cir_check",
+    "dabgpu_demod_csi", "dabgpu_demod_csi_dev", "dabgpu_demod_carrier_state", "dabgpu_demod_carrier_state_dev",
+    "dabgpu_get_carrier_state", "dabgpu_debug_csi_unit_weights",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -152,6 +154,7 @@ class _CirPath(C.Structure):
 
 
 CIR_MAX_PATHS = 16
+CSI_FRAC_BITS, CSI_MAX_WEIGHT = 16, 4
 CIR_RECTANGULAR, CIR_HANN = 0, 1
 CH_MAX_PATHS, CH_MAX_DELAY = 64, 2047
 
@@ -384,6 +387,12 @@ def load_library():
     lib.dabgpu_demod_soft.argtypes = [vp, vp, C.c_int, sz, C.c_int, vp, vp, vp]
     lib.dabgpu_demod_soft_dev.argtypes = [vp, vp, C.c_int, sz, C.c_int, vp, vp, vp, vp]
     lib.dabgpu_decode_soft_dev.argtypes = [vp, vp, sz, vp, sz, vp, szp, vp]
+    lib.dabgpu_demod_csi.argtypes = [vp, vp, C.c_int, sz, C.c_int, vp, vp, vp]
+    lib.dabgpu_demod_csi_dev.argtypes = [vp, vp, C.c_int, sz, C.c_int, vp, vp, vp, vp]
+    lib.dabgpu_demod_carrier_state.argtypes = [vp, vp, C.c_int, sz, C.c_int]
+    lib.dabgpu_demod_carrier_state_dev.argtypes = [vp, vp, C.c_int, sz, C.c_int, vp]
+    lib.dabgpu_get_carrier_state.argtypes = [vp, sz, vp, vp, vp]
+    lib.dabgpu_debug_csi_unit_weights.argtypes = [vp, C.c_int]
     lib.dabgpu_decode_soft.argtypes = [vp, vp, sz, vp, sz, vp, szp]
     lib.dabgpu_get_decode_soft_stats.argtypes = [vp, sz, C.c_int, C.POINTER(_DecodeSoftStats)]
     dp = C.POINTER(C.c_double)
@@ -1243,7 +1252,7 @@ class Modulator:
                        d_bits_out.data_ptr() if d_bits_out is not None else None,
                        d_ref_bits.data_ptr() if d_ref_bits is not None else None, queued=queued)
 
-    def demod_soft(self, iq, early=0, ref_bits=None, want_bits=False):
+    def demod_soft(self, iq, early=0, ref_bits=None, want_bits=False, _entry=None):
         """demod() with soft output: -> soft (n_frames x 8 tf_input_bytes int8; soft 8 p + b belongs to bit 0x80 >> b of byte
         p, > 0: more likely 1, a clean flat symbol gives +-64), or (soft, bits) with want_bits=True.  The per-frame figures
         are monitor_stats(frame), as after demod()."""
@@ -1261,11 +1270,12 @@ class Modulator:
             ref = np.ascontiguousarray(ref_bits, np.uint8).reshape(-1)
             if ref.size != n * nb:
                 raise DabGpuError("demod: reference bits do not match the frames")
-        self._chk(self._lib.dabgpu_demod_soft(self._h, iq.ctypes.data, fmt, n, int(early), soft.ctypes.data,
-                                              out.ctypes.data if want_bits else None, ref.ctypes.data if ref is not None else None))
+        self._chk((_entry or self._lib.dabgpu_demod_soft)(self._h, iq.ctypes.data, fmt, n, int(early), soft.ctypes.data,
+                                                          out.ctypes.data if want_bits else None, ref.ctypes.data if ref is not None else None))
         return (soft, out) if want_bits else soft
 
-    def demod_soft_dev(self, d_iq, n_frames, d_soft_out, early=0, d_bits_out=None, d_ref_bits=None, stream=None, queued=False):
+    def demod_soft_dev(self, d_iq, n_frames, d_soft_out, early=0, d_bits_out=None, d_ref_bits=None, stream=None, queued=False,
+                       _entry=None):
         """demod_dev() with soft output: d_soft_out is int8, n_frames x 8 tf_input_bytes."""
         import torch
         fmt = 0 if d_iq.dtype == torch.complex64 else (FORMATS["s16"][0] if d_iq.dtype == torch.int16 else -1)
@@ -1278,9 +1288,59 @@ class Modulator:
         for tns in (d_bits_out, d_ref_bits):
             if tns is not None and tns.numel() * tns.element_size() != n_frames * self.geometry["tf_input_bytes"]:
                 raise DabGpuError("demod: bit buffers are n_frames x tf_input_bytes")
-        self._dev_call(self._lib.dabgpu_demod_soft_dev, d_iq, stream, d_iq.data_ptr(), fmt, n_frames, int(early),
+        self._dev_call(_entry or self._lib.dabgpu_demod_soft_dev, d_iq, stream, d_iq.data_ptr(), fmt, n_frames, int(early),
                        d_soft_out.data_ptr(), d_bits_out.data_ptr() if d_bits_out is not None else None,
                        d_ref_bits.data_ptr() if d_ref_bits is not None else None, queued=queued)
+
+    # ---- the carrier state: weighted softs, MER per carrier (include/dabgpu.h, "the carrier state") ----
+    def demod_csi(self, iq, early=0, ref_bits=None, want_bits=False):
+        """demod_soft() with every metric weighted by the state of its carrier, measured on the frame itself (A_k / V_k,
+        normalised to 1 on white noise): the same arguments, layout, bits and per-frame figures.  carrier_state(frame) reads
+        what the weights were formed from."""
+        return self.demod_soft(iq, early, ref_bits, want_bits, _entry=self._lib.dabgpu_demod_csi)
+
+    def demod_csi_dev(self, d_iq, n_frames, d_soft_out, early=0, d_bits_out=None, d_ref_bits=None, stream=None, queued=False):
+        """demod_soft_dev() with weighted metrics; queued=True as there."""
+        self.demod_soft_dev(d_iq, n_frames, d_soft_out, early, d_bits_out, d_ref_bits, stream, queued,
+                            _entry=self._lib.dabgpu_demod_csi_dev)
+
+    def demod_carrier_state(self, iq, early=0):
+        """The carrier state and the weights alone (host path, whole frames as demod() takes them): the per-carrier MER
+        readout.  -> the number of frames; read them with carrier_state(frame)."""
+        iq = np.ascontiguousarray(iq)
+        fmt = self._iq_format(iq.dtype)
+        per = self.geometry["tf_samples"] * (2 if fmt else 1)
+        if iq.size == 0 or iq.size % per:
+            raise DabGpuError("demod: input size not valid (whole transmission frames at the native rate)")
+        self._chk(self._lib.dabgpu_demod_carrier_state(self._h, iq.ctypes.data, fmt, iq.size // per, int(early)))
+        return iq.size // per
+
+    def demod_carrier_state_dev(self, d_iq, n_frames, early=0, stream=None, queued=False):
+        """demod_carrier_state() on a torch tensor (complex64, or int16 pairs), asynchronous on the stream as demod_dev."""
+        import torch
+        fmt = 0 if d_iq.dtype == torch.complex64 else (FORMATS["s16"][0] if d_iq.dtype == torch.int16 else -1)
+        if fmt < 0:
+            raise DabGpuError("demod: input is complex64 or int16 (interleaved re, im)")
+        if d_iq.numel() != n_frames * self.geometry["tf_samples"] * (2 if fmt else 1):
+            raise DabGpuError("demod: input size not valid (whole transmission frames at the native rate)")
+        self._dev_call(self._lib.dabgpu_demod_carrier_state_dev, d_iq, stream, d_iq.data_ptr(), fmt, n_frames, int(early),
+                       queued=queued)
+
+    def carrier_state(self, frame=0):
+        """Frame `frame` of the most recent demod_csi*() / demod_carrier_state*() (waits for it): A, V (int64, the raw
+        fixed-point sums per carrier position), w (float32, the weights) and mer_db per carrier
+        (20 log10(A / sqrt(2^(CSI_FRAC_BITS - 1) S V)), S = nb_symbols - 1; inf where V = 0)."""
+        K = self.geometry["carriers"]
+        A, V, w = np.empty(K, np.int64), np.empty(K, np.int64), np.empty(K, np.float32)
+        self._chk(self._lib.dabgpu_get_carrier_state(self._h, frame, A.ctypes.data, V.ctypes.data, w.ctypes.data))
+        S = self.geometry["nb_symbols"] - 1
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mer = 20.0 * np.log10(A.astype(np.float64) / np.sqrt(2.0 ** (CSI_FRAC_BITS - 1) * S * V.astype(np.float64)))
+        return {"A": A, "V": V, "w": w, "mer_db": mer}
+
+    def set_csi_unit_weights(self, enable):
+        """Diagnostic: every weight 1 (demod_csi() then writes demod_soft()'s bytes)."""
+        self._chk(self._lib.dabgpu_debug_csi_unit_weights(self._h, int(bool(enable))))
 
     def set_monitor(self, enable, early=-1):
         """Demodulate every native-rate chain call's output against its own coded bits (off by default); early < 0: from

@@ -15,12 +15,14 @@ const char *const kEarlyRange = "demod: early must lie inside the cyclic prefix 
 
 // zero records, one launch; on `s`.  d_iq: n_frames x tf_samples samples of `format` (0 = cf32, DABGPU_FMT_S16).
 // d_soft: nullptr (the hard kernel), or n_frames x 8 tf_input_bytes int8 (the soft kernel: the same bits and sums besides).
+// weights: nullptr, or n_frames x K fp32 (with d_soft: the weighted soft kernel)
 int queue_demod(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *d_bits_out, const void *d_ref,
-                hipStream_t s, void *d_soft = nullptr)
+                hipStream_t s, void *d_soft = nullptr, const float *weights = nullptr)
 {
     HIPCHK(c, c->demod.stats.reserve(std::max<size_t>(n_frames, 1) * sizeof(DemodFrameStats)));
     HIPCHK(c, hipMemsetAsync(c->demod.stats.p, 0, n_frames * sizeof(DemodFrameStats), s));
     DemodArgs a{};
+    a.csi_w = weights;
     a.g = c->g;
     a.t = tables_of(c);
     a.iq = d_iq;
@@ -37,6 +39,30 @@ int queue_demod(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, in
     c->demod.frames = n_frames;
     c->demod.has_ref = d_ref != nullptr;
     c->demod.stream = s;
+    return DABGPU_OK;
+}
+
+// The carrier state of n_frames frames and their weights, on `s`: zero sums, the state pass, the weights kernel.
+int queue_carrier_state(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, hipStream_t s)
+{
+    const size_t K = (size_t)c->g.K;
+    HIPCHK(c, c->csi.sums.reserve(std::max<size_t>(n_frames, 1) * 2 * K * sizeof(unsigned long long)));
+    HIPCHK(c, c->csi.weights.reserve(std::max<size_t>(n_frames, 1) * K * sizeof(float)));
+    HIPCHK(c, hipMemsetAsync(c->csi.sums.p, 0, n_frames * 2 * K * sizeof(unsigned long long), s));
+    DemodArgs a{};
+    a.g = c->g;
+    a.t = tables_of(c);
+    a.iq = d_iq;
+    a.fmt = format;
+    a.frame_stride = tf_samples(c->g);
+    a.n_frames = (int)n_frames;
+    demod_runs(c->g, n_frames, c->demod.run_symbols, &a.runs_per_frame, &a.syms_per_run);
+    a.early = early;
+    a.csi_sums = (unsigned long long *)c->csi.sums.p;
+    HIPCHK(c, launch_demod(a, s));
+    HIPCHK(c, launch_csi_weights(a.csi_sums, (float *)c->csi.weights.p, c->g.K, (int)n_frames, c->csi.unit_weights, s));
+    c->csi.frames = n_frames;
+    c->csi.stream = s;
     return DABGPU_OK;
 }
 
@@ -79,8 +105,10 @@ int run_monitor(dabgpu_ctx *c, const ChainPlan &p, const void *d_bits, const voi
 }  // namespace dabgpu_api
 
 namespace {
-// the device-pointer entry of either kernel: soft takes d_soft_out (n_frames x 8 tf_input_bytes int8), hard passes nullptr
-int demod_dev(dabgpu_ctx *c, bool soft, const void *d_iq, int format, size_t n_frames, int early, void *d_soft_out, void *d_bits_out,
+enum { HARD = 0, SOFT = 1, CSI = 2 };     // the three forms of the call (CSI: SOFT behind the carrier state and its weights)
+
+// the device-pointer entry of every form: soft takes d_soft_out (n_frames x 8 tf_input_bytes int8), hard passes nullptr
+int demod_dev(dabgpu_ctx *c, int soft, const void *d_iq, int format, size_t n_frames, int early, void *d_soft_out, void *d_bits_out,
               const void *d_ref_bits, void *stream)
 {
     CTXCHK(c);
@@ -91,11 +119,15 @@ int demod_dev(dabgpu_ctx *c, bool soft, const void *d_iq, int format, size_t n_f
     if ((uintptr_t)d_soft_out & 3u) return fail(c, DABGPU_E_INVALID, "demod: buffers must be aligned to four bytes");
     DevCall call(c, stream);
     if (call.rc) return call.rc;
+    if (soft == CSI) {
+        if ((rc = queue_carrier_state(c, d_iq, format, n_frames, early, call.s))) return rc;
+        return queue_demod(c, d_iq, format, n_frames, early, d_bits_out, d_ref_bits, call.s, d_soft_out, (const float *)c->csi.weights.p);
+    }
     return queue_demod(c, d_iq, format, n_frames, early, d_bits_out, d_ref_bits, call.s, d_soft_out);
 }
 
-// the host-pointer entry of either kernel
-int demod_host(dabgpu_ctx *c, bool soft, const void *iq, int format, size_t n_frames, int early, int8_t *soft_out, uint8_t *bits_out,
+// the host-pointer entry of every form
+int demod_host(dabgpu_ctx *c, int soft, const void *iq, int format, size_t n_frames, int early, int8_t *soft_out, uint8_t *bits_out,
                const uint8_t *ref_bits)
 {
     CTXCHK(c);
@@ -122,25 +154,86 @@ extern "C" {
 int dabgpu_demod_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *d_bits_out,
                      const void *d_ref_bits, void *stream)
 {
-    return demod_dev(c, false, d_iq, format, n_frames, early, nullptr, d_bits_out, d_ref_bits, stream);
+    return demod_dev(c, HARD, d_iq, format, n_frames, early, nullptr, d_bits_out, d_ref_bits, stream);
 }
 
 int dabgpu_demod(dabgpu_ctx *c, const void *iq, int format, size_t n_frames, int early, uint8_t *bits_out,
                  const uint8_t *ref_bits)
 {
-    return demod_host(c, false, iq, format, n_frames, early, nullptr, bits_out, ref_bits);
+    return demod_host(c, HARD, iq, format, n_frames, early, nullptr, bits_out, ref_bits);
 }
 
 int dabgpu_demod_soft_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *d_soft_out,
                           void *d_bits_out, const void *d_ref_bits, void *stream)
 {
-    return demod_dev(c, true, d_iq, format, n_frames, early, d_soft_out, d_bits_out, d_ref_bits, stream);
+    return demod_dev(c, SOFT, d_iq, format, n_frames, early, d_soft_out, d_bits_out, d_ref_bits, stream);
 }
 
 int dabgpu_demod_soft(dabgpu_ctx *c, const void *iq, int format, size_t n_frames, int early, int8_t *soft_out, uint8_t *bits_out,
                       const uint8_t *ref_bits)
 {
-    return demod_host(c, true, iq, format, n_frames, early, soft_out, bits_out, ref_bits);
+    return demod_host(c, SOFT, iq, format, n_frames, early, soft_out, bits_out, ref_bits);
+}
+
+int dabgpu_demod_csi_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *d_soft_out,
+                         void *d_bits_out, const void *d_ref_bits, void *stream)
+{
+    return demod_dev(c, CSI, d_iq, format, n_frames, early, d_soft_out, d_bits_out, d_ref_bits, stream);
+}
+
+int dabgpu_demod_csi(dabgpu_ctx *c, const void *iq, int format, size_t n_frames, int early, int8_t *soft_out, uint8_t *bits_out,
+                     const uint8_t *ref_bits)
+{
+    return demod_host(c, CSI, iq, format, n_frames, early, soft_out, bits_out, ref_bits);
+}
+
+int dabgpu_demod_carrier_state_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *stream)
+{
+    CTXCHK(c);
+    int rc = apply_settings(c);
+    if (rc) return rc;
+    if ((rc = check_demod(c, d_iq, format, n_frames, early, nullptr, nullptr))) return rc;
+    DevCall call(c, stream);
+    if (call.rc) return call.rc;
+    return queue_carrier_state(c, d_iq, format, n_frames, early, call.s);
+}
+
+int dabgpu_demod_carrier_state(dabgpu_ctx *c, const void *iq, int format, size_t n_frames, int early)
+{
+    CTXCHK(c);
+    int rc = check_demod(c, iq, format, n_frames, early, nullptr, nullptr);
+    if (rc) return rc;
+    if ((rc = dabgpu_synchronize(c))) return rc;                      // (d_out is the synchronous host path's)
+    HostIO io(c);
+    if ((rc = io.in(c->d_out, iq, n_frames * tf_samples(c->g) * sample_bytes(format)))) return rc;
+    if ((rc = dabgpu_demod_carrier_state_dev(c, c->d_out.p, format, n_frames, early, c->stream))) return rc;
+    return io.out(nullptr, nullptr, 0);
+}
+
+int dabgpu_get_carrier_state(dabgpu_ctx *c, size_t frame, int64_t *A, int64_t *V, float *w)
+{
+    CTXCHK(c);
+    if (frame >= c->csi.frames)
+        return fail(c, DABGPU_E_INVALID, "no carrier state for this frame (no call yet, or frame index out of range)");
+    HIPCHK(c, wait_result(c, c->csi.stream));
+    const size_t K = (size_t)c->g.K;
+    if (A || V) {
+        std::vector<int64_t> both(2 * K);
+        HIPCHK(c, hipMemcpy(both.data(), (const int64_t *)c->csi.sums.p + frame * 2 * K, 2 * K * sizeof(int64_t), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < K; ++k) {
+            if (A) A[k] = both[2 * k];
+            if (V) V[k] = both[2 * k + 1];
+        }
+    }
+    if (w) HIPCHK(c, hipMemcpy(w, (const float *)c->csi.weights.p + frame * K, K * sizeof(float), hipMemcpyDeviceToHost));
+    return DABGPU_OK;
+}
+
+int dabgpu_debug_csi_unit_weights(dabgpu_ctx *c, int enable)
+{
+    if (!c) return DABGPU_E_INVALID;
+    c->csi.unit_weights = enable != 0;
+    return DABGPU_OK;
 }
 
 int dabgpu_get_demod_stats(dabgpu_ctx *c, size_t frame, dabgpu_demod_stats *out)

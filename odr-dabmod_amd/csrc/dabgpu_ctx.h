@@ -124,6 +124,15 @@ struct DemodState {
     int run_symbols = 0;                  // dabgpu_debug_demod_run_symbols: symbols per workgroup, 0 = by the batch size
 };
 
+// The carrier state (api_demod.hip, dabgpu_demod_csi* / dabgpu_demod_carrier_state*): the integer sums and the weights of
+// the most recent such call, sized by the largest call.
+struct CsiState {
+    DevBuf sums, weights;
+    size_t frames = 0;
+    hipStream_t stream = nullptr;
+    bool unit_weights = false;            // dabgpu_debug_csi_unit_weights
+};
+
 // The spectrum monitor (api_spectrum.hip): the 2048-entry twiddle table (the context's own in Mode I), the three window
 // tables, the rows of one launch, the sums (2048 float64 and the segment count) and the host-pointer entry's staging.
 // One accumulator: monitored calls stay on lane 0.  window: the window the sums were formed with, -1 = none yet.
@@ -299,6 +308,7 @@ struct dabgpu_ctx {
     hipStream_t cfr_last_stream = nullptr;
     // the receive-side stages (a new one adds its struct above and its member here)
     dabgpu_api::DemodState demod;
+    dabgpu_api::CsiState csi;
     dabgpu_api::SpectrumState spectrum;
     dabgpu_api::DpdState dpd;
     dabgpu_api::DecodeState decode;

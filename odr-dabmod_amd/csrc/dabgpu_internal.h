@@ -174,9 +174,15 @@ struct DemodArgs {
     const uint8_t *ref_bits;  // nullptr, or the same shape: differing bits are counted
     DemodFrameStats *stats;   // n_frames records
     int8_t *soft_out;         // nullptr (the hard kernel), or n_frames x (nb_symbols - 1) * 2 K soft metrics, dword aligned
+    // the carrier state (dabgpu_demod_csi*): csi_sums set = the state pass alone (n_frames x K x (A, V) integers, zeroed
+    // before the launch; nothing else is written); csi_w set with soft_out = the weighted soft kernel (n_frames x K fp32)
+    unsigned long long *csi_sums;
+    const float *csi_w;
 };
 void demod_runs(const Geometry &g, size_t n_frames, int forced, int *runs_per_frame, int *syms_per_run);
 hipError_t launch_demod(const DemodArgs &a, hipStream_t s);
+// the weights of n_frames frames from their carrier state (unit: every weight 1, dabgpu_debug_csi_unit_weights)
+hipError_t launch_csi_weights(const unsigned long long *sums, float *w, int K, int n_frames, bool unit, hipStream_t s);
 // sync.hip: the synchroniser (dabgpu_sync*): frame starts and carrier offset of a native-rate capture, and the frames extracted
 constexpr int kSyncMaxShift = 31;         // integer carrier offsets searched: -max_shift ... max_shift, at most this
 struct SyncHead {                         // written by the coarse kernel

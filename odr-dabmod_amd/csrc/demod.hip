@@ -5,6 +5,7 @@
 // Written from ETSI EN 300 401 (14.5 - 14.7), like tests/receiver.py; the reference has no receiver.  No synchronisation and
 // no channel estimate: the caller says where the FFT window lies (`early` samples before the end of every symbol).
 #include "device_common.h"
+#include "dabgpu.h"
 
 namespace dabgpu {
 namespace {
@@ -24,8 +25,13 @@ namespace {
 // xor butterfly inside the wave, the waves in wave order through LDS), so the bytes repeat bit for bit and do not depend on
 // the run geometry.  The softs go to an LDS image of the block by byte writes (soft n of the I half, K + n of the Q half: one
 // writer each) and leave as 3 T dwords, three per lane, contiguous across the lanes.  The hard instantiations carry none of it.
-template <int LOGN, bool SOFT> __device__ __forceinline__ void demod_body(const DemodArgs &a)
+//
+// FORM_CSI (dabgpu_demod_csi*, the second pass; the first is demod_csi_state_kernel below): FORM_SOFT with every metric times
+// the weight of its carrier POSITION (a.csi_w: K fp32 per frame, read once per run into six registers).
+enum { FORM_HARD = 0, FORM_SOFT = 1, FORM_CSI = 2 };
+template <int LOGN, int FORM> __device__ __forceinline__ void demod_body(const DemodArgs &a)
 {
+    constexpr bool SOFT = FORM == FORM_SOFT || FORM == FORM_CSI, CSI = FORM == FORM_CSI;
     typedef Fft<LOGN> F;
     constexpr int N = F::N, T = F::T, K = 3 * N / 4, WORDS = K / 16;
     static_assert(WORDS <= T, "one lane per dword of the block");
@@ -56,6 +62,7 @@ template <int LOGN, bool SOFT> __device__ __forceinline__ void demod_body(const 
     constexpr int rr[6] = {0, 1, 2, 5, 6, 7};
     int iword[6], qword[6], nsoft[SOFT ? 6 : 1];
     unsigned shift[6];
+    int kpos[CSI ? 6 : 1];
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
         const int bin = t + T * ((c == 0 && t == 0) ? 3 : rr[c]);
@@ -67,6 +74,12 @@ template <int LOGN, bool SOFT> __device__ __forceinline__ void demod_body(const 
         // (K/8 is a multiple of four bytes in every mode: the byte's place inside its word is the same in both halves)
         shift[c] = 8u * ((unsigned)ib & 3u) + (7u - ((unsigned)n & 7u));
         if constexpr (SOFT) nsoft[c] = n;
+        if constexpr (CSI) kpos[c] = k;
+    }
+    float wgt[CSI ? 6 : 1];
+    if constexpr (CSI) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) wgt[c] = a.csi_w[(size_t)frame * K + (size_t)kpos[c]];
     }
 
     const size_t first = (size_t)a.g.null_size + (size_t)(a.g.sym_size - N - a.early);      // window of symbol 1
@@ -138,8 +151,13 @@ template <int LOGN, bool SOFT> __device__ __forceinline__ void demod_body(const 
             int8_t *sb = reinterpret_cast<int8_t *>(sblk);
 #pragma unroll
             for (int c = 0; c < 6; ++c) {
-                sb[nsoft[c]] = (int8_t)(int)fminf(fmaxf(rintf(-sre[c] * q), -127.f), 127.f);
-                sb[K + nsoft[c]] = (int8_t)(int)fminf(fmaxf(rintf(-sim[c] * q), -127.f), 127.f);
+                if constexpr (CSI) {
+                    sb[nsoft[c]] = (int8_t)(int)fminf(fmaxf(rintf((-sre[c] * q) * wgt[c]), -127.f), 127.f);
+                    sb[K + nsoft[c]] = (int8_t)(int)fminf(fmaxf(rintf((-sim[c] * q) * wgt[c]), -127.f), 127.f);
+                } else {
+                    sb[nsoft[c]] = (int8_t)(int)fminf(fmaxf(rintf(-sre[c] * q), -127.f), 127.f);
+                    sb[K + nsoft[c]] = (int8_t)(int)fminf(fmaxf(rintf(-sim[c] * q), -127.f), 127.f);
+                }
             }
             lds_barrier();
             uint32_t *dst = soft_out + (size_t)b * (3 * T);
@@ -181,8 +199,180 @@ template <int LOGN, bool SOFT> __device__ __forceinline__ void demod_body(const 
     }
 }
 
-template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_kernel(DemodArgs a) { demod_body<LOGN, false>(a); }
-template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_soft_kernel(DemodArgs a) { demod_body<LOGN, true>(a); }
+template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_kernel(DemodArgs a) { demod_body<LOGN, FORM_HARD>(a); }
+template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_soft_kernel(DemodArgs a) { demod_body<LOGN, FORM_SOFT>(a); }
+template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void demod_csi_soft_kernel(DemodArgs a) { demod_body<LOGN, FORM_CSI>(a); }
+
+// The carrier state (dabgpu_demod_csi*, dabgpu_demod_carrier_state*: the first pass), in FLOAT64 from the samples on.  The sums
+// are specified as integers and are held to the float64 model count for count (include/dabgpu.h, "the carrier state"): one
+// count is 2^-16 of a metric step, an fp32 value near 64 resolves half a count, and the fp32 transform lies 1e-7 from the
+// exact one -- 0.4 counts per term.  So this pass does not share demod_body's transform: a radix-2 Stockham transform on
+// double2 in LDS (two buffers, the twiddles exp(-2 pi i m / N), m < N/2, in a third), one workgroup per run of symbols as
+// in demod_body, lane t owning the carrier positions t, t + LANES, ...: their previous-symbol values and their two integer
+// sums stay in its registers.  Per symbol: window -> LDS, log2 N stages, d = z conj(z_prev), P = sum |d|^2 through LDS,
+// q = 64 sqrt(2) / sqrt(P / K), the two terms rounded to integers.  One integer atomic per lane, carrier and figure at the
+// end of the run: integer addition is associative, the sums depend neither on the run geometry nor on the order of arrival.
+template <int LOGN> struct State64 {
+    static constexpr int N = 1 << LOGN, K = 3 * N / 4, LANES = N / 2;    // a butterfly per lane and stage: 128 ... 1024 lanes
+    static constexpr int PER = (K + LANES - 1) / LANES;          // carriers per lane
+    static constexpr int BF = (N / 2) / LANES;                   // butterflies per lane and stage
+    static constexpr size_t LDS_BYTES = (size_t)(2 * N + N / 2) * sizeof(double2) + (size_t)LANES * sizeof(double);
+};
+
+template <int LOGN> __global__ __launch_bounds__(State64<LOGN>::LANES) void demod_csi_state_kernel(DemodArgs a)
+{
+    typedef State64<LOGN> S;
+    constexpr int N = S::N, K = S::K, LANES = S::LANES, PER = S::PER, BF = S::BF;
+    // (dynamic LDS: 88 KiB in Mode I, more than a static block may hold; S::LDS_BYTES, asked for by the launch)
+    extern __shared__ double2 state64_lds[];
+    double2 (*buf)[N] = reinterpret_cast<double2 (*)[N]>(state64_lds);
+    double2 *wtab = state64_lds + 2 * N;
+    double *red = reinterpret_cast<double *>(state64_lds + 2 * N + N / 2);
+
+    const int t = (int)threadIdx.x;
+    const int nblocks = a.g.nb_symbols - 1;
+    const int frame = (int)blockIdx.x / a.runs_per_frame;
+    const int run = (int)blockIdx.x - frame * a.runs_per_frame;
+    const int b0 = run * a.syms_per_run;
+    const int b1 = min(b0 + a.syms_per_run, nblocks);
+    if (frame >= a.n_frames || b0 >= b1) return;
+
+    for (int m = t; m < N / 2; m += LANES) {
+        double sn, cs;
+        sincospi(-2.0 * (double)m / (double)N, &sn, &cs);
+        wtab[m] = make_double2(cs, sn);
+    }
+
+    const size_t first = (size_t)a.g.null_size + (size_t)(a.g.sym_size - N - a.early);      // window of symbol 1
+    const float2 *in_f = reinterpret_cast<const float2 *>(a.iq) + (size_t)frame * a.frame_stride + first;
+    const uint32_t *in_s = reinterpret_cast<const uint32_t *>(a.iq) + (size_t)frame * a.frame_stride + first;
+
+    // symbol s >= 1 of the frame -> its N bins in natural order; returns the buffer that holds them
+    auto transform = [&](int s) __attribute__((always_inline)) -> const double2 * {
+        const size_t off = (size_t)(s - 1) * (size_t)a.g.sym_size;
+        lds_barrier();                                           // (the readers of the symbol before are done; wtab is written)
+        for (int i = t; i < N; i += LANES) {
+            if (a.fmt == 0) {
+                const float2 x = in_f[off + i];
+                buf[0][i] = make_double2((double)x.x, (double)x.y);
+            } else {
+                const uint32_t w = in_s[off + i];                // s16 pair: re in the low half
+                buf[0][i] = make_double2((double)(short)(w & 0xffffu), (double)(short)(w >> 16));
+            }
+        }
+        lds_barrier_vm();
+        int cur = 0, wstep = N / 2;                              // wstep = N / (2 ns)
+#pragma unroll 1
+        for (int ns = 1; ns < N; ns <<= 1, wstep >>= 1) {
+#pragma unroll
+            for (int e = 0; e < BF; ++e) {
+                const int j = t + LANES * e, k = j & (ns - 1);
+                const double2 w = wtab[k * wstep];
+                const double2 x0 = buf[cur][j], x1 = buf[cur][j + N / 2];
+                const double pr = x1.x * w.x - x1.y * w.y, pi = x1.x * w.y + x1.y * w.x;
+                const int j0 = ((j - k) << 1) + k;               // (j / ns) 2 ns + j % ns
+                buf[cur ^ 1][j0] = make_double2(x0.x + pr, x0.y + pi);
+                buf[cur ^ 1][j0 + ns] = make_double2(x0.x - pr, x0.y - pi);
+            }
+            cur ^= 1;
+            lds_barrier();
+        }
+        return buf[cur];
+    };
+
+    int bin[PER];
+    double2 prev[PER];
+    long long sum_a[PER], sum_v[PER];
+#pragma unroll
+    for (int c = 0; c < PER; ++c) {
+        const int k = t + LANES * c;
+        bin[c] = k < K / 2 ? k + 1 : k - K + N;                  // (k >= K: a bin inside the table, never used)
+        if (k >= K) bin[c] = 0;
+        sum_a[c] = sum_v[c] = 0;
+    }
+    {
+        const double2 *z = transform(b0 + 1);
+#pragma unroll
+        for (int c = 0; c < PER; ++c) prev[c] = z[bin[c]];
+    }
+    for (int b = b0; b < b1; ++b) {
+        const double2 *z = transform(b + 2);
+        double dre[PER], dim[PER], ps = 0.0;
+#pragma unroll
+        for (int c = 0; c < PER; ++c) {
+            const double2 x = z[bin[c]], p = prev[c];
+            prev[c] = x;
+            dre[c] = x.x * p.x + x.y * p.y;                      // z conj(p)
+            dim[c] = x.y * p.x - x.x * p.y;
+            if (t + LANES * c < K) ps += dre[c] * dre[c] + dim[c] * dim[c];
+        }
+        red[t] = ps;
+        lds_barrier();
+        for (int half = LANES / 2; half >= 1; half >>= 1) {
+            if (t < half) red[t] += red[t + half];
+            lds_barrier();
+        }
+        const double P = red[0];
+        const double q = P > 0.0 ? 64.0 * sqrt(2.0) / sqrt(P / (double)K) : 0.0;
+        constexpr double kScale = (double)(1 << DABGPU_CSI_FRAC_BITS);
+#pragma unroll
+        for (int c = 0; c < PER; ++c) {
+            const double ur = fabs(dre[c] * q), ui = fabs(dim[c] * q), dq = ui - ur;
+            sum_a[c] += (long long)rint(kScale * (ur + ui) / 2.0);
+            sum_v[c] += (long long)rint(kScale * (dq * dq) / 2.0);
+        }
+        // (red is rewritten behind the barriers of the next transform)
+    }
+    unsigned long long *st = a.csi_sums + (size_t)frame * (size_t)(2 * K);
+#pragma unroll
+    for (int c = 0; c < PER; ++c) {
+        const int k = t + LANES * c;
+        if (k < K) {
+            atomicAdd(&st[2 * k], (unsigned long long)sum_a[c]);
+            atomicAdd(&st[2 * k + 1], (unsigned long long)sum_v[c]);
+        }
+    }
+}
+
+// The weights of a frame from its carrier state (include/dabgpu.h, "the carrier state": the rule, operation by operation):
+// one workgroup per frame, one lane per carrier (a lane takes carriers t, t + 256, ...).  The totals -- over all carriers,
+// then DABGPU_CSI_TRIM_PASSES times over the carriers whose V_k lies within DABGPU_CSI_TRIM_FACTOR times the mean of the set
+// before -- are integer sums (any order gives the same integer); the rest is float64 per carrier.
+constexpr int kCsiWeightLanes = 256;
+__global__ __launch_bounds__(kCsiWeightLanes) void demod_csi_weights_kernel(const unsigned long long *sums, float *w, int K, int unit)
+{
+    __shared__ long long red_n[kCsiWeightLanes], red_a[kCsiWeightLanes], red_v[kCsiWeightLanes];
+    const int t = (int)threadIdx.x;
+    const long long *st = reinterpret_cast<const long long *>(sums) + (size_t)blockIdx.x * (size_t)(2 * K);
+    float *out = w + (size_t)blockIdx.x * (size_t)K;
+    long long n = K, sa = 0, sv = 0;                 // the set before: its size and totals
+    for (int pass = 0; pass <= DABGPU_CSI_TRIM_PASSES; ++pass) {
+        long long ln = 0, la = 0, lv = 0;
+        for (int k = t; k < K; k += kCsiWeightLanes) {
+            const long long V = st[2 * k + 1];
+            if (pass == 0 || V * n <= (long long)DABGPU_CSI_TRIM_FACTOR * sv) { ++ln; la += st[2 * k]; lv += V; }
+        }
+        red_n[t] = ln; red_a[t] = la; red_v[t] = lv;
+        lds_barrier();
+        for (int half = kCsiWeightLanes / 2; half >= 1; half >>= 1) {
+            if (t < half) { red_n[t] += red_n[t + half]; red_a[t] += red_a[t + half]; red_v[t] += red_v[t + half]; }
+            lds_barrier();
+        }
+        n = red_n[0]; sa = red_a[0]; sv = red_v[0];
+        lds_barrier();                               // (everybody has read the totals before the next pass writes)
+    }
+    const bool flat = unit || sa <= 0 || sv <= 0;
+    const double SA = (double)sa, SV = (double)sv;
+    const double floor_v = SV / (double)(64ll * n);
+    for (int k = t; k < K; k += kCsiWeightLanes) {
+        double r = 1.0;
+        if (!flat) {
+            const double A = (double)st[2 * k], V = (double)st[2 * k + 1];
+            r = fmin((double)DABGPU_CSI_MAX_WEIGHT, (A * SV) / (SA * fmax(V, floor_v)));
+        }
+        out[k] = (float)r;
+    }
+}
 
 }  // namespace
 
@@ -210,6 +400,35 @@ hipError_t launch_demod(const DemodArgs &a, hipStream_t s)
         (a.fmt != 0 && a.fmt != 1) || a.g.K != 3 * a.g.N / 4)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)a.n_frames * (unsigned)a.runs_per_frame);
+    if (a.csi_sums) {                       // the first pass of the weighted call: the carrier state alone
+        // (more than 64 KiB of dynamic LDS has to be asked for)
+#define STATE64_LAUNCH(L)                                                                                                  \
+        do {                                                                                                               \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(demod_csi_state_kernel<L>),                  \
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)State64<L>::LDS_BYTES);    \
+            if (e != hipSuccess) return e;                                                                                 \
+            DABGPU_LAUNCH(demod_csi_state_kernel<L>, grid, dim3(State64<L>::LANES), State64<L>::LDS_BYTES, s, a);          \
+        } while (0)
+        switch (a.g.logN) {
+        case 8: STATE64_LAUNCH(8); break;
+        case 9: STATE64_LAUNCH(9); break;
+        case 10: STATE64_LAUNCH(10); break;
+        case 11: STATE64_LAUNCH(11); break;
+        default: return hipErrorInvalidValue;
+        }
+#undef STATE64_LAUNCH
+        return hipGetLastError();
+    }
+    if (a.soft_out && a.csi_w) {            // the second pass: weighted softs, the hard call's bits and figures
+        switch (a.g.logN) {
+        case 8: DABGPU_LAUNCH(demod_csi_soft_kernel<8>, grid, dim3(Fft<8>::T), 0, s, a); break;
+        case 9: DABGPU_LAUNCH(demod_csi_soft_kernel<9>, grid, dim3(Fft<9>::T), 0, s, a); break;
+        case 10: DABGPU_LAUNCH(demod_csi_soft_kernel<10>, grid, dim3(Fft<10>::T), 0, s, a); break;
+        case 11: DABGPU_LAUNCH(demod_csi_soft_kernel<11>, grid, dim3(Fft<11>::T), 0, s, a); break;
+        default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     if (a.soft_out) {
         switch (a.g.logN) {
         case 8: DABGPU_LAUNCH(demod_soft_kernel<8>, grid, dim3(Fft<8>::T), 0, s, a); break;
@@ -227,6 +446,13 @@ hipError_t launch_demod(const DemodArgs &a, hipStream_t s)
     case 11: DABGPU_LAUNCH(demod_kernel<11>, grid, dim3(Fft<11>::T), 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_csi_weights(const unsigned long long *sums, float *w, int K, int n_frames, bool unit, hipStream_t s)
+{
+    if (n_frames <= 0) return hipSuccess;
+    DABGPU_LAUNCH(demod_csi_weights_kernel, dim3((unsigned)n_frames), dim3(kCsiWeightLanes), 0, s, sums, w, K, unit ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -92,6 +92,14 @@
 //                        relative to the peak, in ascending delay.  A measurement, not a verdict: the exit status stays what
 //                        it is without the option.  Native-rate complexf / s16 output; not with --bits-only or
 //                        --separate-converter.
+//   --csi                with --loopback --soft: the soft metrics weighted by the state of their carrier (dabgpu_demod_csi;
+//                        include/dabgpu.h, "the carrier state") in place of dabgpu_demod_soft; everything else as --soft.
+//   --carrier-mer FILE   the per-carrier MER (dabgpu_demod_carrier_state) of the last batch that was written -- with --loopback
+//                        --channel-cn of that batch behind the channel emulator, as --cir takes it -- the window where
+//                        --monitor puts it.  FILE gets one line per carrier and frame of the batch: "frame position mer_db
+//                        weight" (position in frequency order; mer_db 400.000 where no quadrature power was measured); stderr
+//                        the median and the lowest MER of the batch.  A measurement, not a verdict.  Native-rate complexf / s16
+//                        output; not with --bits-only or --separate-converter.
 //   --state-out FILE     with --gpu-frontend: after the last frame, write where the stream stands -- the number of ETI frames
 //                        modulated since FP = 0 and both stream-state blobs (DabGpuChain::get_stream_state /
 //                        frontend_state) -- so that another run continues it
@@ -142,6 +150,8 @@ namespace {
                          "       [--tii-scan]   with --batch 2 or more: read the TII of the last batch; exit 2 when it is not the one --tii configures\n"
                          "       [--cir FILE]   impulse response of the channel the last batch went through (with --loopback --channel-cn: the\n"
                          "                        emulator's), per tap into FILE (lines of: delay_samples level_db), paths on stderr\n"
+                         "       [--csi]   with --loopback --soft: weight the metrics by the measured state of their carrier\n"
+                         "       [--carrier-mer FILE]   MER per carrier of the last batch (lines of: frame position mer_db weight)\n"
                          "       [--state-out FILE] [--state-in FILE]   with --gpu-frontend: leave / take up the stream's state\n");
     std::exit(2);
 }
@@ -202,7 +212,8 @@ int main(int argc, char **argv)
     size_t batch = 1;
     bool reference_latency = false;
     long contexts = 1;
-    bool gpu_frontend = false, loopback = false, soft = false;
+    bool gpu_frontend = false, loopback = false, soft = false, csi = false;
+    std::string carrier_mer_path;
     bool channel = false;
     double channel_cn = 0.0;
     unsigned long long channel_seed = 0;
@@ -259,6 +270,8 @@ int main(int argc, char **argv)
             else if (a == "--monitor") gs.monitor = true;
             else if (a == "--loopback") loopback = true;
             else if (a == "--soft") soft = true;
+            else if (a == "--csi") csi = true;
+            else if (a == "--carrier-mer") carrier_mer_path = val();
             else if (a == "--channel-cn") { channel_cn = std::stod(val()); channel = true; }
             else if (a == "--channel-seed") channel_seed = std::stoull(val());
             else if (a == "--channel-echo") {
@@ -311,6 +324,11 @@ int main(int argc, char **argv)
             return 2;
         }
 
+        if (csi && !soft) {
+            std::fprintf(stderr, "dabmod_file: --csi does not go without --loopback --soft: it weights the metrics of that loop\n");
+            return 2;
+        }
+
         if ((channel || channel_seed || !channel_echoes.empty()) && !(loopback && channel)) {
             std::fprintf(stderr, "dabmod_file: --channel-seed and --channel-echo go with --channel-cn, and that with --loopback: the "
                                  "channel sits between the IQ and that loop's demodulator\n");
@@ -344,6 +362,16 @@ int main(int argc, char **argv)
                          : bits_only  ? "--bits-only: nothing is modulated"
                          : separate_converter ? "--separate-converter: the chain's own output is what is measured"
                                       : "u8 / s8 output: the estimator takes complexf or s16");
+            return 2;
+        }
+
+        const bool carrier_mer = !carrier_mer_path.empty();
+        if (carrier_mer && (gs.outputRate != 2048000 || (format != "complexf" && format != "s16") || bits_only || separate_converter)) {
+            std::fprintf(stderr, "dabmod_file: --carrier-mer does not go with %s\n",
+                         gs.outputRate != 2048000 ? "--rate: the receiver takes the native rate"
+                         : bits_only  ? "--bits-only: nothing is modulated"
+                         : separate_converter ? "--separate-converter: the chain's own output is what is measured"
+                                      : "u8 / s8 output: the receiver takes complexf or s16");
             return 2;
         }
 
@@ -493,7 +521,7 @@ int main(int argc, char **argv)
         std::vector<uint8_t> cir_last;
         DabGpuChain *cir_chain = nullptr;
         auto cir_keep = [&](DabGpuChain *ch, const void *p, size_t bytes) {
-            if (!cir || bytes < ch->output_bytes_per_frame()) return;
+            if ((!cir && !carrier_mer) || bytes < ch->output_bytes_per_frame()) return;
             cir_last.assign(static_cast<const uint8_t *>(p), static_cast<const uint8_t *>(p) + bytes);
             cir_chain = ch;
         };
@@ -554,7 +582,8 @@ int main(int argc, char **argv)
             loop_ref.assign(n * 6144, 0);
             if (soft) {
                 loop_soft.resize(8 * loop_bits.size());
-                chk(dabgpu_demod_soft(c, p, format == "s16" ? DABGPU_FMT_S16 : 0, n_frames, loop_early, loop_soft.data(), nullptr, nullptr));
+                chk((csi ? dabgpu_demod_csi : dabgpu_demod_soft)(c, p, format == "s16" ? DABGPU_FMT_S16 : 0, n_frames, loop_early,
+                                                                 loop_soft.data(), nullptr, nullptr));
             } else {
                 chk(dabgpu_demod(c, p, format == "s16" ? DABGPU_FMT_S16 : 0, n_frames, loop_early, loop_bits.data(), nullptr));
             }
@@ -958,6 +987,48 @@ int main(int argc, char **argv)
                 std::fprintf(stderr, "dabmod_file: cannot write %s\n", cir_path.c_str());
                 return 1;
             }
+        }
+        if (carrier_mer) {
+            if (!cir_chain) {
+                std::fprintf(stderr, "dabmod_file: --carrier-mer: no frame was written, there is nothing to measure\n");
+                return 1;
+            }
+            dabgpu_ctx *c = cir_chain->context();
+            dabgpu_geometry g{};
+            int early = static_cast<int>(gs.ofdmWindowOverlap);           // where --monitor puts the window
+            for (RemoteControllable *rc : cir_chain->remote_controllables())
+                if (rc->get_rc_name() == "firfilter") early += std::stoi(rc->get_parameter("ntaps")) - 1;
+            const size_t n_frames = cir_last.size() / cir_chain->output_bytes_per_frame();
+            if (dabgpu_get_geometry(c, &g) != 0 ||
+                dabgpu_demod_carrier_state(c, cir_last.data(), format == "s16" ? DABGPU_FMT_S16 : 0, n_frames, early) != 0)
+                throw std::runtime_error(std::string("--carrier-mer: ") + dabgpu_last_error(c));
+            std::FILE *mf = std::fopen(carrier_mer_path.c_str(), "w");
+            if (!mf) {
+                std::fprintf(stderr, "dabmod_file: cannot write %s\n", carrier_mer_path.c_str());
+                return 1;
+            }
+            const size_t K = static_cast<size_t>(g.carriers);
+            std::vector<int64_t> A(K), V(K);
+            std::vector<float> w(K);
+            std::vector<double> all;
+            const double scale = std::ldexp(1.0, DABGPU_CSI_FRAC_BITS - 1) * static_cast<double>(g.nb_symbols - 1);
+            for (size_t f = 0; f < n_frames; ++f) {
+                if (dabgpu_get_carrier_state(c, f, A.data(), V.data(), w.data()) != 0)
+                    throw std::runtime_error(std::string("--carrier-mer: ") + dabgpu_last_error(c));
+                for (size_t k = 0; k < K; ++k) {
+                    const double mer = V[k] > 0 && A[k] > 0 ? 20.0 * std::log10(static_cast<double>(A[k]) / std::sqrt(scale * static_cast<double>(V[k])))
+                                       : A[k] > 0 ? 400.0 : -400.0;
+                    all.push_back(mer);
+                    std::fprintf(mf, "%zu %zu %.3f %.6f\n", f, k, mer, static_cast<double>(w[k]));
+                }
+            }
+            if (std::fclose(mf) != 0) {
+                std::fprintf(stderr, "dabmod_file: cannot write %s\n", carrier_mer_path.c_str());
+                return 1;
+            }
+            std::sort(all.begin(), all.end());
+            std::fprintf(stderr, "dabmod_file: carrier-mer: %zu frames%s, window %d samples early, %zu carriers: median %.2f dB, lowest %.2f dB\n",
+                         n_frames, loopback && channel ? " behind the channel" : "", early, K, all[all.size() / 2], all.front());
         }
         if (gs.monitor && mon.bit_errors) return 2;
         if (loopback && (loop.fic_errors || loop.msc_errors)) return 2;
