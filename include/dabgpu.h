@@ -1168,6 +1168,89 @@ DABGPU_API int dabgpu_sco_dev(dabgpu_ctx *ctx, const void *d_iq, int format, siz
 DABGPU_API int dabgpu_sco(dabgpu_ctx *ctx, const void *iq, int format, size_t n_frames, int early);
 DABGPU_API int dabgpu_get_sco(dabgpu_ctx *ctx, int frame, dabgpu_sco_frame *out);
 
+/* ---- the tuner: any capture rate and offset down to native-rate IQ -- mix, channel-filter, decimate ------------------------- *
+ * Everything on the receive side takes IQ at 2.048 MS/s.  The tuner is the stage in front of it: a position-exact polyphase
+ * rate converter L / M with a mixer in front, for the transmitter's own resampled output (dabgpu_set_resampler's chains) and for
+ * the captures receivers make (2.4, 2.5, 2.56, 3.2, 10 MS/s ..., a wide capture with several blocks in it: one tuner each).
+ * The reference has no such stage; these entries replace nothing of its flowgraph.  Every output is a function of the input
+ * stream, the setting and its absolute index alone: a stream cut into calls of any lengths gives the bytes of one call.
+ * Settings: dabgpu_tuner_config { in_rate_hz, selectivity, offset_hz }.
+ * Ratio: g = gcd(2 048 000, in_rate_hz), L = 2 048 000 / g, M = in_rate_hz / g.  Accepted: in_rate_hz >= 2 048 000,
+ *   L <= 512 (DABGPU_TUNER_MAX_L), M <= 8 L.  That covers 2.048 (1/1), 2.304 (8/9), 2.4 (64/75), 2.5 (512/625), 2.56 (4/5),
+ *   3.072 (2/3), 3.2 (16/25), 4.096 (1/2), 6.144 (1/3), 8.192 (1/4), 10.0 (128/625) and 16.384 (1/8) MS/s.
+ * Tap count: D = ceil(M / L) (1 at ratio 1); taps per output P = 32 D for selectivity 0 ("wide") and 96 D for 1 ("channel");
+ *   at most 768 (DABGPU_TUNER_MAX_TAPS).
+ * Mixer: r[n] = x[n] exp(2 pi j frac(n step / 2^64)), n the absolute input index, step = rint(-offset_hz / in_rate_hz 2^64)
+ *   as an int64 (the quotient and the product in float64, from the left), the product n step modulo 2^64.  The phase is
+ *   taken from the upper 32 bits of that product: the nearest quarter turn comes off in integers, the rest is rounded to fp32
+ *   once.  Nothing accumulates.  |offset_hz| < in_rate_hz / 4.  A signal at +offset_hz in the capture comes out at 0.  With
+ *   step = 0 the sample's bits pass: no multiply.  Otherwise, with w the phase's (cos, sin) in fp32:
+ *   Re r = fmaf(Re x, Re w, -(Im x Im w)), Im r = fmaf(Re x, Im w, Im x Re w), the inner products rounded.
+ * Position: for the absolute output index m >= 0: q = m M, i_m = q div L, p = q mod L, in integers; positions up to 2^50
+ *   input samples.
+ * Output: y[m] = sum_{j = 0 ... P - 1} T[p][j] r[i_m + j - (P/2 - 1)], r[.] the mixed input stream counted from the last
+ *   reset's position, zero before the reset.
+ * Taps: T[p][j] = fp32(h_j / sum_j h_j + 0), h and the sum (in the order j = 0 ... P - 1) in float64, with
+ *   t = j - (P/2 - 1) - p / L, c = min(1, B / in_rate_hz), B = 2 048 000 for wide (-6 dB at 1024 kHz) and 1 712 000 for channel
+ *   (-6 dB at 856 kHz, halfway between the block's edge at 768 kHz and the neighbour's at 944 kHz), and
+ *   h = c sinc(c t) I0(10 sqrt(1 - (t / (P/2))^2)) / I0(10) for |t| <= P/2, else 0.
+ *   sinc(x) = 1 at x = 0, else (-1)^n sin(pi (x - n)) / (pi x) with n = x rounded to the nearest integer (ties to even), so that
+ *   it is exactly 0 at every other integer; I0(x) = sum_k ((x/2)^k / k!)^2, the terms formed by term *= (x / 2k)(x / 2k),
+ *   added from k = 0 until one is below 1e-18 of the sum.  At 2.048 MS/s wide every row is the unit impulse at tap 15.
+ * Sum, in fp32, the ONE order of every instantiation: re = im = +0; for j = 0, 1, ... P - 1 in this order
+ *   re = fmaf(T[p][j], Re r, re), im = fmaf(T[p][j], Im r, im).
+ * Formats: input complexf (format 0), DABGPU_FMT_S16, DABGPU_FMT_U8 (byte - 128) or DABGPU_FMT_S8, as dabgpu_spectrum* loads
+ *   them (a value becomes its float on load); output complexf or DABGPU_FMT_S16 -- dabgpu_format_process's conversion of the
+ *   complexf result byte for byte (saturating, toward zero), without a clip count.  Calls may mix the formats.
+ * State: T, the absolute number of input samples received (the reset's position included), and the last P - 1 input samples,
+ *   kept as floats (not mixed) in two buffers that take turns.  M(T) = the number of m >= 0 with i_m + P/2 <= T - 1: the
+ *   outputs all of whose taps have arrived (= ceil((T - P/2) L / M), 0 for T <= P/2).  A call that brings n_in samples writes
+ *   the outputs M(T) ... M(T + n_in) - 1 and returns their count in *n_out (it may be 0).  The count is integer arithmetic on
+ *   the host, before anything is queued: no device round trip.  dabgpu_tuner_count gives M, dabgpu_tuner_out_max(cfg, n_in) =
+ *   ceil(n_in L / M) + 1 bounds the count of any call of n_in samples (0 for a setting that is refused).  The output trails
+ *   the input by P/2 input samples: at 2.048 MS/s wide and offset 0 it is the input's bytes, trailing by 16 (a negative zero
+ *   comes out positive).
+ * dabgpu_tuner_check, dabgpu_tuner_geometry, dabgpu_tuner_taps (row p = 0 ... L - 1, P floats), dabgpu_tuner_count,
+ *   dabgpu_tuner_out_max: host only, no context, no device; message via dabgpu_last_error(NULL).
+ * dabgpu_set_tuner: installs a setting and implies dabgpu_tuner_reset(0); uploads the tap table when rate or selectivity
+ *   change, after the tuner's queued calls have finished.
+ * dabgpu_tuner_reset: T = position (at most 2^50) with a zero history: the next call starts at output M(position).
+ * dabgpu_get_tuner_position: T; waits for the most recent call, as dabgpu_get_clock_position does.
+ * dabgpu_tuner_dev: device pointers (aligned to a sample of their format), out_cap in samples, asynchronous on `stream` (NULL:
+ *   the context's own stream, behind every lane -- the calls stay on lane 0 in call order); at most two launches, no host
+ *   round trip.  The calls carry stream state: the caller keeps them in order.  dabgpu_tuner: the host-pointer form.
+ * Refused with DABGPU_E_INVALID and a message before anything is queued (position, history and the output untouched): a rate
+ *   below 2 048 000 or with L above 512 or M above 8 L, a selectivity other than 0 and 1, an offset that is not finite or not
+ *   below in_rate_hz / 4 in magnitude, an input format other than the four or an output format other than the two, a null
+ *   pointer or one not aligned to a sample, input and output ranges that overlap, n_in = 0 (or above 2^40), a position beyond
+ *   2^50, a call before any dabgpu_set_tuner.  An out_cap below the call's count: DABGPU_E_CAPACITY, the count in *n_out,
+ *   nothing queued.
+ * Out of scope: input rates below 2.048 MS/s, a time-varying offset, a state blob or seed for the history, dabmod_file
+ *   options (the resampler's delay moves the frames across its batch boundaries), and the monitor on resampled chains
+ *   (dabgpu_set_monitor still refuses them). */
+#define DABGPU_TUNER_MAX_L 512
+#define DABGPU_TUNER_MAX_TAPS 768
+typedef struct dabgpu_tuner_config {
+    uint32_t in_rate_hz;
+    int selectivity;          /* 0: wide (32 D taps), 1: channel (96 D taps) */
+    double offset_hz;
+} dabgpu_tuner_config;
+DABGPU_API int dabgpu_tuner_check(const dabgpu_tuner_config *cfg);
+DABGPU_API int dabgpu_tuner_geometry(const dabgpu_tuner_config *cfg, int *L, int *M, int *P);
+DABGPU_API int dabgpu_tuner_taps(const dabgpu_tuner_config *cfg, int p, float *taps);
+DABGPU_API int dabgpu_tuner_count(const dabgpu_tuner_config *cfg, uint64_t T, uint64_t *M_out);
+DABGPU_API size_t dabgpu_tuner_out_max(const dabgpu_tuner_config *cfg, size_t n_in);
+DABGPU_API int dabgpu_set_tuner(dabgpu_ctx *ctx, const dabgpu_tuner_config *cfg);
+DABGPU_API int dabgpu_tuner_reset(dabgpu_ctx *ctx, uint64_t position);
+DABGPU_API int dabgpu_get_tuner_position(dabgpu_ctx *ctx, uint64_t *position);
+DABGPU_API int dabgpu_tuner_dev(dabgpu_ctx *ctx, const void *d_in, int in_format, size_t n_in, void *d_out, int out_format,
+                                size_t out_cap, size_t *n_out, void *stream);
+DABGPU_API int dabgpu_tuner(dabgpu_ctx *ctx, const void *in, int in_format, size_t n_in, void *out, int out_format,
+                            size_t out_cap, size_t *n_out);
+/* Diagnostic: outputs per workgroup of the tuner's kernels (at most what the staged span holds, 2048 at most); 0 (the
+ * default) = chosen from the setting.  Same bytes for every value; exists so that a test can walk the run geometry. */
+DABGPU_API int dabgpu_debug_tuner_run_samples(dabgpu_ctx *ctx, int samples);
+
 /* ---- the TII analyser: transmitters, levels and delays from the null symbols of whole frames -------------------------------- *
  * Reads what dabgpu_set_tii puts into a signal: which (comb, pattern) the null symbols carry, how strong every comb is and
  * when it arrives -- of one transmitter, or of the several of a single-frequency network in one monitoring capture.  The

@@ -59,6 +59,9 @@ EXPORTS = [
     "dabgpu_clock_check", "dabgpu_clock_step", "dabgpu_clock_count", "dabgpu_clock_out_max", "dabgpu_clock_phase_taps",
     "dabgpu_clock_inverse_ppm", "dabgpu_set_clock", "dabgpu_clock_reset", "dabgpu_get_clock_position", "dabgpu_clock_dev",
     "dabgpu_clock", "dabgpu_debug_clock_run_samples", "dabgpu_sco_dev", "dabgpu_sco", "dabgpu_get_sco",
+    "dabgpu_tuner_check", "dabgpu_tuner_geometry", "dabgpu_tuner_taps", "dabgpu_tuner_count", "dabgpu_tuner_out_max",
+    "dabgpu_set_tuner", "dabgpu_tuner_reset", "dabgpu_get_tuner_position", "dabgpu_tuner_dev", "dabgpu_tuner",
+    "dabgpu_debug_tuner_run_samples",
     "dabgpu_tii_scan_dev", "dabgpu_tii_scan", "dabgpu_get_tii_scan", "dabgpu_tii_scan_check",
     "dabgpu_cir_dev", "dabgpu_cir", "dabgpu_get_cir", "dabgpu_get_cir_profile", "dabgpu_cir_check",
     "dabgpu_demod_csi", "dabgpu_demod_csi_dev", "dabgpu_demod_carrier_state", "dabgpu_demod_carrier_state_dev",
@@ -166,6 +169,10 @@ class _ChannelPath(C.Structure):
 class _ChannelConfig(C.Structure):
     _fields_ = [("n_paths", C.c_uint32), ("sigma", C.c_float), ("seed", C.c_uint64), ("rate_hz", C.c_double),
                 ("paths", _ChannelPath * CH_MAX_PATHS)]
+
+
+class _TunerConfig(C.Structure):
+    _fields_ = [("in_rate_hz", C.c_uint32), ("selectivity", C.c_int), ("offset_hz", C.c_double)]
 
 
 class _DecodeSoftStats(C.Structure):
@@ -367,6 +374,19 @@ def load_library():
     lib.dabgpu_clock_dev.argtypes = [vp, vp, C.c_int, sz, vp, C.c_int, sz, C.POINTER(sz), vp]
     lib.dabgpu_clock.argtypes = [vp, vp, C.c_int, sz, vp, C.c_int, sz, C.POINTER(sz)]
     lib.dabgpu_debug_clock_run_samples.argtypes = [vp, C.c_int]
+    tcp = C.POINTER(_TunerConfig)
+    lib.dabgpu_tuner_check.argtypes = [tcp]
+    lib.dabgpu_tuner_geometry.argtypes = [tcp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.dabgpu_tuner_taps.argtypes = [tcp, C.c_int, C.POINTER(C.c_float)]
+    lib.dabgpu_tuner_count.argtypes = [tcp, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.dabgpu_tuner_out_max.argtypes = [tcp, sz]
+    lib.dabgpu_tuner_out_max.restype = sz
+    lib.dabgpu_set_tuner.argtypes = [vp, tcp]
+    lib.dabgpu_tuner_reset.argtypes = [vp, C.c_uint64]
+    lib.dabgpu_get_tuner_position.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.dabgpu_tuner_dev.argtypes = [vp, vp, C.c_int, sz, vp, C.c_int, sz, C.POINTER(sz), vp]
+    lib.dabgpu_tuner.argtypes = [vp, vp, C.c_int, sz, vp, C.c_int, sz, C.POINTER(sz)]
+    lib.dabgpu_debug_tuner_run_samples.argtypes = [vp, C.c_int]
     lib.dabgpu_sco_dev.argtypes = [vp, vp, C.c_int, sz, C.c_int, vp]
     lib.dabgpu_sco.argtypes = [vp, vp, C.c_int, sz, C.c_int]
     lib.dabgpu_get_sco.argtypes = [vp, C.c_int, C.POINTER(_ScoFrame)]
@@ -548,6 +568,64 @@ def clock_phase_taps(p):
 def clock_inverse_ppm(ppm):
     """Host only: the setting that undoes an offset of ppm, -ppm / (1 + ppm 1e-6)."""
     return float(load_library().dabgpu_clock_inverse_ppm(float(ppm)))
+
+
+def _tuner_config(in_rate, selectivity, offset_hz):
+    """The C structure of a tuner setting; what cannot be written into it is refused here, with the library's words."""
+    if not 0 <= int(in_rate) < 2 ** 32:
+        raise DabGpuError("tuner: in_rate_hz must not be below 2048000" if int(in_rate) < 0
+                          else "tuner: in_rate_hz must not exceed 8 x 2048000 (M <= 8 L)")
+    if not -2 ** 31 <= int(selectivity) < 2 ** 31:
+        raise DabGpuError("tuner: selectivity is 0 (wide) or 1 (channel)")
+    return _TunerConfig(int(in_rate), int(selectivity), float(offset_hz))
+
+
+def tuner_check(in_rate, selectivity=0, offset_hz=0.0):
+    """Host only (needs the library, no device): raises DabGpuError when set_tuner() would refuse this setting, with the
+    message it gives."""
+    lib = load_library()
+    cfg = _tuner_config(in_rate, selectivity, offset_hz)
+    if lib.dabgpu_tuner_check(C.byref(cfg)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def tuner_geometry(in_rate, selectivity=0, offset_hz=0.0):
+    """Host only: (L, M, P) of a tuner setting: the ratio 2048000 / in_rate = L / M in lowest terms and the taps per output."""
+    lib = load_library()
+    cfg = _tuner_config(in_rate, selectivity, offset_hz)
+    L, M, P = C.c_int(), C.c_int(), C.c_int()
+    if lib.dabgpu_tuner_geometry(C.byref(cfg), C.byref(L), C.byref(M), C.byref(P)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return int(L.value), int(M.value), int(P.value)
+
+
+def tuner_taps(in_rate, selectivity, p):
+    """Host only: row p (0 ... L - 1) of the tuner's tap table, P fp32 taps."""
+    lib = load_library()
+    cfg = _tuner_config(in_rate, selectivity, 0.0)
+    out = np.empty(tuner_geometry(in_rate, selectivity)[2], np.float32)
+    if lib.dabgpu_tuner_taps(C.byref(cfg), int(p), out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return out
+
+
+def tuner_count(in_rate, selectivity, T):
+    """Host only: M(T), the outputs the tuner has written once T input samples have arrived."""
+    lib = load_library()
+    if not 0 <= int(T) < 2 ** 64:
+        raise DabGpuError("tuner: the stream's position must not exceed 2^50")
+    cfg = _tuner_config(in_rate, selectivity, 0.0)
+    m = C.c_uint64()
+    if lib.dabgpu_tuner_count(C.byref(cfg), int(T), C.byref(m)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return int(m.value)
+
+
+def tuner_out_max(in_rate, selectivity, n_in):
+    """Host only: an upper bound of the outputs of any tuner call that brings n_in samples."""
+    tuner_check(in_rate, selectivity)
+    cfg = _tuner_config(in_rate, selectivity, 0.0)
+    return int(load_library().dabgpu_tuner_out_max(C.byref(cfg), int(n_in)))
 
 
 def channel_sigma(power, cn_db):
@@ -1542,6 +1620,75 @@ class Modulator:
             raise DabGpuError("clock: input and output are contiguous")
         got = C.c_size_t()
         self._dev_call(self._lib.dabgpu_clock_dev, d_in, stream, d_in.data_ptr(), fi, n, d_out.data_ptr(), fo, cap, C.byref(got),
+                       queued=queued)
+        return int(got.value)
+
+    # ---- the tuner: any capture rate and offset down to native-rate IQ (include/dabgpu.h, "the tuner") ----
+    _TUNER_HOST = {np.dtype(np.complex64): 0, np.dtype(np.int16): 1, np.dtype(np.uint8): 2, np.dtype(np.int8): 3}
+
+    def set_tuner(self, in_rate, selectivity=0, offset_hz=0.0):
+        """Install a tuner setting: the capture's rate in Hz, selectivity 0 (wide) or 1 (channel), and the offset of the wanted
+        block's centre in the capture; implies tuner_reset(0).  Takes effect at the next call."""
+        cfg = _tuner_config(in_rate, selectivity, offset_hz)
+        self._chk(self._lib.dabgpu_set_tuner(self._h, C.byref(cfg)))
+        self._tuner_cfg = cfg
+
+    def tuner_reset(self, position=0):
+        """Zero history; the stream continues at input sample `position`, the output at tuner_count(..., position)."""
+        if not 0 <= int(position) < 2 ** 64:
+            raise DabGpuError("tuner: the stream's position must not exceed 2^50")
+        self._chk(self._lib.dabgpu_tuner_reset(self._h, int(position)))
+
+    def tuner_position(self):
+        """Input samples the stream has taken since the last reset, plus the reset's position (waits for the most recent call)."""
+        pos = C.c_uint64()
+        self._chk(self._lib.dabgpu_get_tuner_position(self._h, C.byref(pos)))
+        return int(pos.value)
+
+    def set_tuner_run_samples(self, samples=0):
+        """Diagnostic: outputs per workgroup of the tuner's kernels (0: chosen from the setting; clamped to what fits)."""
+        self._chk(self._lib.dabgpu_debug_tuner_run_samples(self._h, int(samples)))
+
+    def _tuner_out_max(self, n_in):
+        cfg = getattr(self, "_tuner_cfg", None)
+        if cfg is None:
+            raise DabGpuError("tuner: no setting (no dabgpu_set_tuner call yet)")
+        return int(self._lib.dabgpu_tuner_out_max(C.byref(cfg), int(n_in)))
+
+    def tuner(self, x, out="complexf"):
+        """Host path: the next samples of the capture (complex64, or int16 / uint8 / int8 interleaved re, im) through the tuner
+        -> the native-rate outputs these samples complete: complex64, or int16 pairs with out="s16"."""
+        x = np.ascontiguousarray(x).reshape(-1)
+        fmt = self._TUNER_HOST.get(x.dtype)
+        if fmt is None or (fmt and x.size % 2):
+            raise DabGpuError("tuner: input is complex64, or int16 / uint8 / int8 (interleaved re, im)")
+        if out not in ("complexf", "s16"):
+            raise DabGpuError("tuner: output format is complexf (0) or DABGPU_FMT_S16")
+        n = x.size if fmt == 0 else x.size // 2
+        cap = self._tuner_out_max(n)
+        y = np.empty(cap, np.complex64) if out == "complexf" else np.empty(2 * cap, np.int16)
+        got = C.c_size_t()
+        self._chk(self._lib.dabgpu_tuner(self._h, x.ctypes.data, fmt, n, y.ctypes.data, 0 if out == "complexf" else FORMATS["s16"][0],
+                                         cap, C.byref(got)))
+        return y[:got.value if out == "complexf" else 2 * got.value].copy()
+
+    def tuner_dev(self, d_in, d_out, stream=None, queued=False):
+        """Device path on torch tensors (input complex64, or int16 / uint8 / int8 pairs; output complex64 or int16 pairs;
+        contiguous), asynchronous on the stream as chain_dev.  d_out's size is the capacity.  Returns the number of output
+        samples the call writes."""
+        import torch
+        fi = {torch.complex64: 0, torch.int16: 1, torch.uint8: 2, torch.int8: 3}.get(d_in.dtype)
+        fo = {torch.complex64: 0, torch.int16: 1}.get(d_out.dtype)
+        if fi is None or (fi and d_in.numel() % 2):
+            raise DabGpuError("tuner: input is complex64, or int16 / uint8 / int8 (interleaved re, im)")
+        if fo is None or (fo and d_out.numel() % 2):
+            raise DabGpuError("tuner: output is complex64 or int16 (interleaved re, im)")
+        if not d_in.is_contiguous() or not d_out.is_contiguous():
+            raise DabGpuError("tuner: input and output are contiguous")
+        n = d_in.numel() if fi == 0 else d_in.numel() // 2
+        cap = d_out.numel() if fo == 0 else d_out.numel() // 2
+        got = C.c_size_t()
+        self._dev_call(self._lib.dabgpu_tuner_dev, d_in, stream, d_in.data_ptr(), fi, n, d_out.data_ptr(), fo, cap, C.byref(got),
                        queued=queued)
         return int(got.value)
 

@@ -22,6 +22,8 @@
 //   api_clock.hip     the clock's resampler (clock.hip): a sampling-clock offset put on a sample stream or taken off it, its
 //                     history and position; step, counts and the tap table (host only); the clock's estimator: the offset
 //                     of whole frames from their data symbols
+//   api_tuner.hip     the tuner (tuner.hip): mixer, channel filter and decimator from any accepted capture rate and offset to
+//                     the native rate, its history and position; ratio, tap rows and counts (host only)
 //   api_tii_scan.hip  the TII analyser (tii_scan.hip): transmitters, levels and delays from the null symbols of whole frames;
 //                     the settings check (host only)
 //   api_cir.hip       the channel estimator (cir.hip): impulse response, echoes and the response on the carriers from the
@@ -228,6 +230,24 @@ struct ScoState {
     hipStream_t stream = nullptr;
 };
 
+// The tuner (api_tuner.hip, tuner.hip).  hist: two histories of kTunMaxHist float samples (the first P - 1 in use), the stream
+// state; hist_cur: the one the next call reads (a call writes the other and swaps).  zero_pending: the next call zeroes it
+// first (after dabgpu_set_tuner and dabgpu_tuner_reset).  T: input samples the stream has taken (the reset's position
+// included).  cfg, L, M, P, step: the installed setting and what follows from it.  tab: the tap table [L][P] of (tab_rate,
+// tab_selectivity), uploaded by the dabgpu_set_tuner that changes either.
+struct TunerState {
+    DevBuf hist, tab, in, out;
+    bool configured = false, zero_pending = true;
+    int hist_cur = 0;
+    unsigned long long T = 0, step = 0;
+    dabgpu_tuner_config cfg{};
+    int L = 1, M = 1, P = 32;
+    uint32_t tab_rate = 0;
+    int tab_selectivity = -1;
+    hipStream_t stream = nullptr;
+    int run_samples = 0;                  // dabgpu_debug_tuner_run_samples: outputs per workgroup, 0 = chosen
+};
+
 // The TII analyser (api_tii_scan.hip, tii_scan.hip).  result: head, 24 entry slots and the entries' grid centres of the most
 // recent dabgpu_tii_scan* call; rows / bins: per-frame cell sums and occupied bins (scratch); in: the host-pointer entry's
 // staging; done: a call has been queued.
@@ -316,6 +336,7 @@ struct dabgpu_ctx {
     dabgpu_api::ChannelState channel;
     dabgpu_api::ClockState clock;
     dabgpu_api::ScoState sco;
+    dabgpu_api::TunerState tuner;
     dabgpu_api::TiiScanState tii_scan;
     dabgpu_api::CirState cir;
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII

@@ -280,6 +280,31 @@ struct ScoArgs {
     double *frames;           // n_frames x kScoSums: the frames' sums
 };
 hipError_t launch_sco(const ScoArgs &a, hipStream_t s);
+// tuner.hip: the tuner (dabgpu_tuner*): mixer, channel filter and rational decimator L / M from any capture rate to the native one
+constexpr int kTunMaxL = 512;             // rows of the tap table at most
+constexpr int kTunMaxTaps = 768;          // taps per output at most: 96 x ceil(M / L), M <= 8 L
+constexpr int kTunMaxHist = kTunMaxTaps - 1;
+constexpr int kTunSpan = 5120;            // samples of LDS a workgroup stages its input span in (40 KB)
+constexpr int kTunMaxRun = 2048;          // outputs per workgroup at most (fewer where the span does not hold them: tuner_run_max)
+struct TunerArgs {
+    const void *in;                       // n samples, in_fmt 0 (complexf), 1 (s16 pairs), 2 (u8 pairs, byte - 128), 3 (s8 pairs)
+    void *out;                            // count samples, out_fmt 0 or 1
+    const float2 *hist;                   // P - 1 samples as floats, not mixed: hist[P - 1 + r] = sample r < 0 of this call
+    const float *tab;                     // [L][P]
+    long long n;
+    unsigned long long T;                 // absolute index of input sample 0 of the call
+    unsigned long long m0;                // absolute index of the call's first output
+    long long count;                      // outputs of the call
+    unsigned long long step;              // the mixer's turns per input sample x 2^64 (two's complement); 0: no mixer
+    int L, M, P;
+    int in_fmt, out_fmt;
+    int run;                              // outputs per workgroup, 1 ... tuner_run_max
+};
+int tuner_run_max(int L, int M, int P);
+int tuner_run(int L, int M, int P, int forced);
+hipError_t launch_tuner(const TunerArgs &a, hipStream_t s);
+// the history behind a call: next[j] = sample n - H + j of the call (H = P - 1), from `in` or (calls shorter than H) from `cur`
+hipError_t launch_tuner_history(const void *in, int in_fmt, long long n, int H, const float2 *cur, float2 *next, hipStream_t s);
 // tii_scan.hip: the TII analyser (dabgpu_tii_scan*): which (comb, pattern) the null symbols of whole frames carry, the level
 // and the delay of every comb
 constexpr int kTiiCombs = 24;             // combs, and entry slots of a result
