@@ -571,7 +571,9 @@ template <int LOGN> struct Fft {
     // imaginary parts apart, and gathers eight (last stage: four) adjacent dwords of a row.  On the LDS path a wave's exchange is
     // then 16 ds_write_addtid_b32 (2 cycles each: no address register, one data dword) + 4 ds_read_b128 (4 each) = 48 cycles where
     // 8 ds_write_b64 (6 each) + 8 ds_read_b64 (2 each) are 64; all of it conflict-free (tools/fft_planes_check.cpp).
-    // The lane of the caller works on first-stage index fftp::in_index(lane) and leaves with x[lane + T m] like run().
+    // The lane of the caller works on first-stage index fftp::in_index(lane) and leaves with PAIRS of consecutive samples:
+    // x[2 lane + b + 512 k3] in v[b + 2 k3] (run() leaves x[lane + T m] in v[m]) -- lane t runs the two final butterflies of outputs
+    // 2 t and 2 t + 1 (mod 512), which is a read address and a twiddle index, no arithmetic; the frame kernel stores 16 bytes per lane.
 
     // twiddles of stages 3 and 4 (stage 2 reads the LDS table): the layout of load_twiddles<true>, the lane's indices from the maps
     static DEV void load_twiddles_planes(const cf *__restrict__ wtab, int t, cf *tw)
@@ -584,7 +586,7 @@ template <int LOGN> struct Fft {
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
-            for (int r = 1; r < RF; ++r) tw[n++] = wtab[(r * (t + T * b)) & (N - 1)];
+            for (int r = 1; r < RF; ++r) tw[n++] = wtab[(r * fftp::tw4_index(t, b)) & (N - 1)];
     }
 
     // one exchange's sixteen stores: v[slot] of this lane to row `slot`, column = the lane's index in the workgroup.  m0base: LDS
@@ -658,7 +660,7 @@ template <int LOGN> struct Fft {
         xbarrier();
         {
             // inputs c = 0 .. 3 of butterfly beta sit in v[beta + 2 c]
-            const float *r0 = re + fftp::read3(t), *r1 = r0 + fftp::kRead3Second;
+            const float *r0 = re + fftp::read3(t, 0), *r1 = re + fftp::read3(t, 1);
             const float4 a0 = *reinterpret_cast<const float4 *>(r0), b0 = *reinterpret_cast<const float4 *>(r0 + fftp::kPlane);
             const float4 a1 = *reinterpret_cast<const float4 *>(r1), b1 = *reinterpret_cast<const float4 *>(r1 + fftp::kPlane);
             v[0] = mk(a0.x, b0.x); v[2] = mk(a0.y, b0.y); v[4] = mk(a0.z, b0.z); v[6] = mk(a0.w, b0.w);

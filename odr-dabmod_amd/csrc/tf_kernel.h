@@ -188,6 +188,19 @@ void tf_kernel(const TfArgs a)
     static_assert(kEqElems == 3 * kEqW + kEqDLen + (kEqTaps + 8) / 2 + 16 && 2 * kEqWinMax <= 32 && 2 * kEqWinMax + 44 <= 64,
                   "LDS share of the EQ variants (tf_lds_bytes)");
     cf *eq_zp = bnd, *eq_w = bnd + 2 * kEqW, *eq_d = eq_w + kEqW;
+    // PLANES: the transform leaves pairs of consecutive samples (fft_planes.h).  Window index 0 is sample N - cp - kEqQL = 1441 of
+    // the symbol, an odd one: the two PARKED windows (eq_zp) sit ONE slot up (kEqSh), index i = q + kEqQL + 1, so that a lane's pair
+    // is one aligned 16-byte access, written and read; their index 0 is then q = -kEqQL - 1, written and never used (see where the
+    // windows are written).  204 of the kEqW = 240 slots are in use.  The difference w (eq_w) stays where it is, index q + kEqQL: the
+    // inverse filter reads thirteen entries of it from an EVEN index as six 16-byte reads and one of 8; moved up by one with the
+    // others, the compiler pairs them from the odd index as 8-byte-aligned ds_read2_b64 (8 LDS cycles where ds_read_b128 takes 4:
+    // measured +72 conflict cycles per symbol and -1.2 % in frames/s), and every spelling of the aligned reads tried cost registers
+    // the kernel does not have (128, spills).  A pair of w is written as two 8-byte halves instead, which costs what one 16-byte
+    // LDS write does (MI355X: 2 x 6 against 13 cycles).
+    constexpr int kEqSh = PLANES ? 1 : 0;
+    static_assert(!PLANES || (kEqQL == fftp::kWinQL && kEqQH == fftp::kWinQH && kEqQL + kEqSh == fftp::kWinQ0 && fftp::kWinLen <= kEqW &&
+                              G::sym_size - N == fftp::kCp && NT - 1 == fftp::kC && G::sym_size == fftp::kSeg),
+                  "PLANES: the store and window arithmetic of fft_planes.h is this kernel's geometry");
     float *g_l = reinterpret_cast<float *>(eq_d + kEqDLen);
     // BWIN (round 6; modes II - IV, packed dual transform, 45 taps): the boundary filter reads a register window of fifteen samples
     // per lane; the last tap group's window runs up to three slots past the buffers (under zero taps): four slots of zeros there
@@ -351,8 +364,11 @@ void tf_kernel(const TfArgs a)
     // board's 1400 W power limit, where the stores are a third of a frame's energy (tools/microbench/energy_cost.hip) and the
     // cheaper path wins -- cfg 3 +2.5 ... 3.8 %, 16 frames per launch +10 %, 256 +4 %, cfg 4 +0.5 %, the default chain, CFR and
     // windowing unchanged (tools/experiments/exp_store_policy.sh, exp_store_policy2.sh; same-box A/B).  (16-byte stores, which the same
-    // microbenchmark prices a third cheaper per byte, were tried too: neighbouring lanes swap half of their samples by DPP and
-    // store pairs -- parity green, -2 % with either policy: the 40 instructions of the swap and two 512-byte halves per store.)  The chains from carriers (cfg 2, the
+    // microbenchmark prices a third cheaper per byte: built from natural-order registers -- neighbouring lanes swap half of their
+    // samples by DPP and store pairs -- they lost 2 % with either policy, to the 40 instructions of the swap and to stores that
+    // were still two 512-byte halves.  The PLANES kernels get them for nothing: their last FFT stage leaves every lane with pairs
+    // of consecutive samples, and a symbol's body and prefix go out as five 1 KB stores per wave, put16 below; policy and A/B:
+    // profiles/store16_ab.txt.)  The chains from carriers (cfg 2, the
     // IFFT + FIR stage) ARE bandwidth-bound, at the nominal clock with power to spare, and lose 0 ... 1.5 %: they keep plain stores.
     // (tool builds only, tools/experiments/exp_store_policy.sh: -DDABGPU_STORE_AUX=n forces the policy bits of every variant's stores --
     // 0 plain, 1 sc0, 2 nt, 16 sc1 and their sums -- so that the A/B behind the figures above can be re-run from the tree)
@@ -365,6 +381,12 @@ void tf_kernel(const TfArgs a)
     // frames' slots by v_permlane32_swap so that a store instruction writes 512 contiguous bytes of ONE frame: -1.5 %, not kept.)
     constexpr int kStoreAux = (FROM_BITS && LOGN != 8) ? 2 : 0;
 #endif
+    // the 16-byte stores of the PLANES kernels (tool builds: -DDABGPU_STORE_AUX16=n forces the policy of these stores alone)
+#ifdef DABGPU_STORE_AUX16
+    constexpr int kStoreAux16 = DABGPU_STORE_AUX16;
+#else
+    constexpr int kStoreAux16 = kStoreAux;
+#endif
     auto put = [&](int soff, int voff, cf y) __attribute__((always_inline)) {
         if constexpr (OFMT == 1) {
             __builtin_amdgcn_raw_buffer_store_b32(s16_pack(y, nclip), orsrc, voff * 4, soff * 4, kStoreAux);
@@ -374,6 +396,14 @@ void tf_kernel(const TfArgs a)
             const v2u_ d = {__builtin_bit_cast(unsigned, y.x), __builtin_bit_cast(unsigned, y.y)};
             __builtin_amdgcn_raw_buffer_store_b64(d, orsrc, (voff + hvoff) * 8, soff * 8, kStoreAux);
         }
+    };
+    // PLANES: two consecutive complexf samples in one 16-byte store; soff: the wave-uniform sample index (even), pvoff: the lane's
+    // PAIR index.  16 bytes from the frame's base, which is sample-aligned -- a buffer store wants dword alignment and no more.
+    typedef unsigned v4u_ __attribute__((ext_vector_type(4)));
+    [[maybe_unused]] auto put16 = [&](int soff, int pvoff, cf y0, cf y1) __attribute__((always_inline)) {
+        const v4u_ d = {__builtin_bit_cast(unsigned, y0.x), __builtin_bit_cast(unsigned, y0.y),
+                        __builtin_bit_cast(unsigned, y1.x), __builtin_bit_cast(unsigned, y1.y)};
+        __builtin_amdgcn_raw_buffer_store_b128(d, orsrc, pvoff * 16, soff * 8, kStoreAux16);
     };
 
     // advance the differential state over one data block (K/4 bytes: I bits, then Q bits) staged in LDS.
@@ -1015,7 +1045,7 @@ void tf_kernel(const TfArgs a)
 #pragma unroll
             for (int k = 0; k < 11; ++k) y = axpy(y, tq[4 * k], dq[4 * k]);
             quad_sum2_dpp(y.x, y.y);
-            y = cadd(y, zp[kEqQL - C + i]);
+            y = cadd(y, zp[kEqQL - C + i + kEqSh]);
             if (TII_IN && tii_on && prev_pos == 0) {          // (the null symbol's boundary outputs: plus the TII segment's)
                 const cf ts = a.tii_seg[len0 - C + i];
                 y = mk(fmaf(g1s, ts.x, y.x), fmaf(g1s, ts.y, y.y));
@@ -1097,7 +1127,7 @@ void tf_kernel(const TfArgs a)
         }
         // the 44 samples of z_prev this boundary's step 2 will add -- kept, the window they come from is rewritten by then
         // (the lanes behind the 176: otherwise idle here)
-        if (t >= kEqLanes && t < kEqLanes + 44) eq_d[88 + 44 * cur + (t - kEqLanes)] = zp[kEqQL - C + (t - kEqLanes)];
+        if (t >= kEqLanes && t < kEqLanes + 44) eq_d[88 + 44 * cur + (t - kEqLanes)] = zp[kEqQL - C + (t - kEqLanes) + kEqSh];
         if (pb_pos >= 0 && t < kEqLanes) eq_store_pending(ypend);
         pb_pos = prev_pos + prev_seg - C;                      // this boundary becomes the pending one (the caller flips `cur`)
     };
@@ -1408,7 +1438,32 @@ void tf_kernel(const TfArgs a)
             // for the next symbol.  Index of q everywhere: q + kEqQL.
             cf *zp_prev = eq_zp + cur * kEqW, *zp_new = eq_zp + (cur ^ 1) * kEqW;
             [[maybe_unused]] constexpr int n0 = (N - cp) - kEqQL;              // first sample of the window in z_cur (1441)
-            if constexpr (LOGN == 11) {
+            if constexpr (PLANES) {
+                // Pairs (fft_planes.h: out_sample, win_*): w from pair slot 2, lanes >= 208 (samples 1440 ... 1535) and pair slot 3,
+                // lanes < 54 (1536 ... 1643); parked for the next symbol: the tail from pair slot 3, lanes >= 204 (1944 ... 2047), the
+                // head from pair slot 0, lanes < 50 (0 ... 99).  Parked index = q + kEqQL + kEqSh, every access 16 bytes, aligned;
+                // w at the parked index - kEqSh, two 8-byte halves, and its entry for sample 1440 (q = -104) does not exist (below).
+                // The extra slot of the parked windows, index 0 (q = -104: samples 1944 and 1440): the tails are read at
+                // kEqQL - C + i + kEqSh, i in [0, 43] -- indices 60 ... 103 --, the end of the frame at i + kEqSh >= 1, and the
+                // z_prev pair read below at index 0 feeds nothing but the w entry that is not written.  Nothing uses it.
+                auto wpair = [&](int k3, cf y0, cf y1) __attribute__((always_inline)) {
+                    const int iw = fftp::win_index_w(fftp::out_sample(t, 0, k3));
+                    const float4 zz = *reinterpret_cast<const float4 *>(zp_prev + iw);
+                    // (both halves unconditionally, so that they leave as ONE ds_write2_b64 -- 8 lanes x 16 bytes per LDS cycle, no
+                    // conflict; two ds_write_b64 at a 16-byte stride are 2-way conflicts, measured.  Lane 208's first half, the
+                    // entry that does not exist, lands in front of w: slot kEqW - 1 of the second parked window, which nothing reads
+                    // -- the windows use 204 slots, and the end-of-frame copy moves it to w's entry 238, past the 203 in use.)
+                    static_assert(kEqSh == 1 && fftp::kWinLen < kEqW - 1, "the slot in front of w is a spare one");
+                    eq_w[iw - kEqSh] = csub(y0, mk(zz.x, zz.y));
+                    eq_w[iw + 1 - kEqSh] = csub(y1, mk(zz.z, zz.w));
+                };
+                if (fftp::win_w_lane(2, t)) wpair(2, v[4], v[5]);
+                if (fftp::win_w_lane(3, t)) wpair(3, v[6], v[7]);
+                if (fftp::win_tail_lane(3, t))
+                    *reinterpret_cast<float4 *>(zp_new + fftp::win_index_tail(fftp::out_sample(t, 0, 3))) = make_float4(v[6].x, v[6].y, v[7].x, v[7].y);
+                if (fftp::win_head_lane(0, t))
+                    *reinterpret_cast<float4 *>(zp_new + fftp::win_index_head(fftp::out_sample(t, 0, 0))) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
+            } else if constexpr (LOGN == 11) {
                 static_assert(LOGN != 11 || (n0 >= 5 * T && n0 + kEqQL + kEqQH < 7 * T && kEqQL < T && kEqQH < T), "EQ windows: slots 5, 6, 7, 0");
                 if (t >= n0 - 5 * T) { const int iw = t - (n0 - 5 * T); eq_w[iw] = csub(v[5], zp_prev[iw]); }
                 if (t <= n0 + kEqQL + kEqQH - 6 * T) { const int iw = t + (6 * T - n0); eq_w[iw] = csub(v[6], zp_prev[iw]); }
@@ -1541,7 +1596,19 @@ void tf_kernel(const TfArgs a)
         }
         if (FROM_BITS) bb ^= 1;
         if (lookahead && !EQ) break;
-        if (lane_on && !(EQ && lookahead)) {
+        if constexpr (PLANES) {
+            // pair slot k3 = registers 2 k3, 2 k3 + 1 = samples 2 t + 512 k3 and the next: per wave four 1 KB stores for the body
+            // (the last C samples belong to the boundary: pair slot 3 stops at lane 234) and one for the cyclic prefix (pair slot 3
+            // from lane 4 on) -- tools/fft_planes_check.cpp: with the 44 boundary outputs, every position of the segment exactly once
+            if (!lookahead) {
+#pragma unroll
+                for (int k3 = 0; k3 < fftp::kPairSlots; ++k3) {
+                    const cf y0 = scaled(v[2 * k3]), y1 = scaled(v[2 * k3 + 1]);
+                    if (k3 < 3 || fftp::body_lane(3, t)) put16(pos + cpl + 2 * T * k3, t, y0, y1);
+                    if (k3 == 3 && fftp::prefix_lane(3, t)) put16(pos, fftp::prefix_at(3, t) / 2, y0, y1);
+                }
+            }
+        } else if (lane_on && !(EQ && lookahead)) {
             const int m_cp = (N - cpl) / T;   // first register slot that is also copied into the prefix
             const bool keep_tail = !WIN || s == nsym - 1;    // WIN: the last W samples belong to the next seam
 #pragma unroll
@@ -1586,7 +1653,8 @@ void tf_kernel(const TfArgs a)
         // end of the frame: nothing follows (a zero symbol: w = -z_prev), missing terms are dropped
         const cf *zp = eq_zp + cur * kEqW;
         lds_barrier();
-        for (int i = t; i < kEqW; i += (int)blockDim.x) eq_w[i] = mk(-zp[i].x, -zp[i].y);
+        // (PLANES: the parked windows sit kEqSh slots above w; what lies past them is past every entry the boundary reads)
+        for (int i = t; i < kEqW - kEqSh; i += (int)blockDim.x) eq_w[i] = mk(-zp[i + kEqSh].x, -zp[i + kEqSh].y);
         lds_barrier();
         if constexpr (LOGN == 11) eq_boundary(zp, true); else eq_boundary_small(zp);
     } else if (WIN && FIR && s_end == nsym && have_prev) {

@@ -2,12 +2,14 @@
 # TIMING EXPERIMENT (wrong results): what would the cfg 3 kernel gain if its final FFT stage left every lane with PAIRS of
 # consecutive samples, so that a symbol went out in 16-byte stores, 1 KB contiguous per wave (four for the body, one or two for the
 # cyclic prefix) instead of ten 512-byte ones?  The scratch build stores the registers it has as if they were such pairs.
+# (Applies to the tree BEFORE the pair stores went in -- the kernel of today stores exactly this way, with the right samples, and the
+# patch below no longer finds its place.  profiles/store16_ab.txt has the bound measured on the last commit without them.)
 set -e
 ROOT="$(cd "$(dirname "$0")/../.." && pwd)"
 "$ROOT/tools/variants.sh" base ""
 d="$ROOT/tools/_variants/src_st16"
 rm -rf "$d"; mkdir -p "$d/odr-dabmod_amd" "$d/include"
-cp -r "$ROOT/odr-dabmod_amd/csrc" "$d/odr-dabmod_amd/csrc"; cp "$ROOT/include/"*.h "$d/include/"
+cp -r "$ROOT/odr-dabmod_amd/csrc" "$d/odr-dabmod_amd/csrc"; cp -r "$ROOT/odr-dabmod_amd/host" "$d/odr-dabmod_amd/host"; cp "$ROOT/include/"*.h "$d/include/"
 rm -f "$d/odr-dabmod_amd/csrc/"*.o "$d/odr-dabmod_amd/csrc/libdabgpu.so"
 python3 - "$d/odr-dabmod_amd/csrc/tf_kernel.h" <<'PY'
 import sys

@@ -9,7 +9,12 @@
 //   3. every gather is 16-byte aligned, inside its row, and bank-conflict-free under the lane groups and the bank rule of
 //      ds_read_b128 (four groups of sixteen lanes, bank = dword address mod 64); the partner read of the gain statistic
 //      likewise under the rule of ds_read_b32 (two groups of 32 lanes, bank = dword address mod 32);
-//   4. a float64 transform that moves its data ONLY through those maps equals a direct DFT.
+//   4. a float64 transform that moves its data ONLY through those maps equals a direct DFT, its outputs placed where the last
+//      stage's lanes leave them: x[2 t + b + 512 k3] in register b + 2 k3 of lane t;
+//   5. the 16-byte output stores of the frame kernel (body, cyclic prefix) and the 44 boundary outputs together write every one of
+//      a symbol segment's 2552 positions exactly once, every 16-byte store at an even sample offset from the frame's base, and the
+//      16-byte accesses to the equalised boundary's parked windows are aligned pairs; with the difference window, which is kept one
+//      entry lower, they cover exactly the samples the boundary reads.
 // Exit status 0 and one summary line when all of it holds; the first failure is reported and ends the run with status 1.
 #include <cmath>
 #include <complex>
@@ -97,6 +102,7 @@ static void dft(const cd *in, cd *out, int n)          // backward: exp(+2 pi i 
 
 int main()
 {
+    double rel_out = 0.;
     static_assert(kN == 8 * kT && kPitch >= kT && kPitch % 4 == 0 && kBytes == 2 * 8 * kPitch * 4 && kElems * 8 == kBytes, "geometry");
 
     // ---- 1. bijections ----------------------------------------------------------------------------------------------------
@@ -141,6 +147,22 @@ int main()
         }
         CHECK(s1.size() == (size_t)kT && s2.size() == (size_t)kT, "lane1 / lane2 are no bijections");
     }
+    {
+        // last stage: butterfly b of lane t is the butterfly (k0, k1, k2) of outputs k0 + 8 k1 + 64 k2 + 512 k3 = 2 t + b + 512 k3
+        std::set<int> s, o;
+        for (int t = 0; t < kT; ++t)
+            for (int b = 0; b < 2; ++b) {
+                const int k0 = last_k0(t, b), k1 = last_k1(t), k2 = last_k2(t);
+                CHECK(k0 >= 0 && k0 < 8 && k1 >= 0 && k1 < 8 && k2 >= 0 && k2 < 8, "last stage: indices of lane %d", t);
+                CHECK(k0 + 8 * k1 + 64 * k2 == 2 * t + b && tw4_index(t, b) == 2 * t + b, "last stage: lane %d, butterfly %d", t, b);
+                s.insert(k0 + 8 * k1 + 64 * k2);
+                for (int k3 = 0; k3 < 4; ++k3) {
+                    CHECK(out_sample(t, b, k3) == k0 + 8 * k1 + 64 * k2 + 512 * k3, "out_sample at lane %d", t);
+                    o.insert(out_sample(t, b, k3));
+                }
+            }
+        CHECK(s.size() == 512 && o.size() == (size_t)kN && *o.begin() == 0 && *o.rbegin() == kN - 1, "the last stage's lanes are no bijection");
+    }
 
     // ---- 2. writes: 64 consecutive dwords per wave and slot, rows apart, inside the plane ----------------------------------
     for (int slot = 0; slot < 8; ++slot)
@@ -157,8 +179,10 @@ int main()
         for (int l = 0; l < kT; ++l) {
             a1[l] = read1(l);
             a2[l] = read2(l);
-            a3[l] = read3(l);
-            a3b[l] = read3(l) + kRead3Second;
+            a3[l] = read3(l, 0);
+            a3b[l] = read3(l, 1);
+            const int row = write_at(last_k2(l), 0);
+            CHECK(a3b[l] == row + ((a3[l] - row) ^ kRead3Flip), "gather 3: butterfly 1 of lane %d is not butterfly 0's column ^ %d", l, kRead3Flip);
             ap[l] = in_partner(l);
         }
         check_gather("gather 1", a1, 8);
@@ -202,9 +226,9 @@ int main()
         for (int t = 0; t < kT; ++t)                           // last stage: two radix-4 butterflies
             for (int beta = 0; beta < 2; ++beta) {
                 for (int c = 0; c < 4; ++c)
-                    v[c] = plane[read3(t) + beta * kRead3Second + c] * std::polar(1.0, 2.0 * M_PI * ((c * (t + kT * beta)) % kN) / (double)kN);
+                    v[c] = plane[read3(t, beta) + c] * std::polar(1.0, 2.0 * M_PI * ((c * tw4_index(t, beta)) % kN) / (double)kN);
                 dft(v, y, 4);
-                for (int k3 = 0; k3 < 4; ++k3) got[t + kT * (beta + 2 * k3)] = y[k3];
+                for (int k3 = 0; k3 < 4; ++k3) got[out_sample(t, beta, k3)] = y[k3];
             }
         double err = 0., ref = 0.;
         for (int k = 0; k < kN; ++k) {
@@ -214,7 +238,77 @@ int main()
         const double rel = std::sqrt(err / ref);
         // (float64: the four stages and the direct sum both round at a few 1e-16 per operation)
         CHECK(rel < 1e-13, "transform through the maps differs from the DFT: rel. error %.3g", rel);
-        if (!failures) std::printf("fft_planes_check: maps, writes, gathers ok; transform rel. error %.3g\n", rel);
+        rel_out = rel;
     }
+
+    // ---- 5. the output stores of a symbol and the windows of the equalised boundary ----------------------------------------------
+    {
+        // Mode I frame: a null segment of 2656 samples, then segments of kSeg = 2552; every length that enters a store offset is even
+        static_assert(kSeg == 2552 && 2656 % 2 == 0 && kSeg % 2 == 0 && kCp % 2 == 0 && (kN - kC) % 2 == 0, "even lengths");
+        std::vector<int> written(kSeg, 0);
+        int stores16 = 0;
+        for (int k3 = 0; k3 < kPairSlots; ++k3)
+            for (int t = 0; t < kT; ++t) {
+                CHECK(out_sample(t, 1, k3) == out_sample(t, 0, k3) + 1 && out_sample(t, 0, k3) % 2 == 0, "pair slot %d, lane %d holds no pair", k3, t);
+                if (body_lane(k3, t)) {
+                    const int at = body_at(k3, t);
+                    CHECK(at % 2 == 0 && at >= kCp && at + 1 < kSeg - kC, "body store of slot %d, lane %d at %d", k3, t, at);
+                    CHECK(at == kCp + out_sample(t, 0, k3), "body store of slot %d, lane %d holds other samples", k3, t);
+                    if (at >= 0 && at + 1 < kSeg) { ++written[at]; ++written[at + 1]; }
+                    ++stores16;
+                }
+                if (prefix_lane(k3, t)) {
+                    const int at = prefix_at(k3, t);
+                    CHECK(k3 == 3 && t >= 4 && at == 2 * (t - 4), "prefix store of slot %d, lane %d", k3, t);
+                    CHECK(at % 2 == 0 && at >= 0 && at + 1 < kCp, "prefix store of slot %d, lane %d at %d", k3, t, at);
+                    if (at >= 0 && at + 1 < kSeg) { ++written[at]; ++written[at + 1]; }
+                    ++stores16;
+                }
+                // (a lane's four 16-byte body stores lie 1 KB apart per wave: lane t at byte 16 t of its pair slot)
+                CHECK(body_at(k3, t) - body_at(k3, 0) == 2 * t, "body stores of slot %d are not lane-contiguous", k3);
+            }
+        for (int i = 0; i < kC; ++i) ++written[kSeg - kC + i];                 // the boundary outputs (8-byte stores)
+        for (int n = 0; n < kSeg; ++n) CHECK(written[n] == 1, "segment position %d is written %d times", n, written[n]);
+        CHECK(stores16 * 2 + kC == kSeg, "%d 16-byte stores", stores16);
+        // every segment starts at an even sample of the frame, so an even offset inside it is a 16-byte multiple from the frame's base
+        for (int s = 1; s <= 76; ++s) CHECK((2656 + (s - 1) * kSeg) % 2 == 0, "segment %d starts at an odd sample", s);
+
+        // windows: w and the two parked ones, each entry written exactly once, by aligned pairs
+        std::vector<int> w(kWinLen, 0), parked(kWinLen, 0), zread(kWinLen, 0);
+        for (int k3 = 0; k3 < kPairSlots; ++k3)
+            for (int t = 0; t < kT; ++t) {
+                const int n = out_sample(t, 0, k3);
+                if (win_w_lane(k3, t)) {
+                    const int i = win_index_w(n);
+                    CHECK(i % 2 == 0 && i >= 0 && i + 1 < kWinLen, "w pair of slot %d, lane %d at %d", k3, t, i);
+                    CHECK(n == kN - kCp + (i - kWinQ0), "w index %d is sample %d", i, n);
+                    // (the z_prev pair is read at i, aligned; w is kept kWinWShift lower, as two halves, the one for q = -104 dropped)
+                    if (i >= 0 && i + 1 < kWinLen) { ++zread[i]; ++zread[i + 1]; }
+                    for (int h = 0; h < 2; ++h)
+                        if (i + h - kWinWShift >= 0 && i + h - kWinWShift < kWinLen) ++w[i + h - kWinWShift];
+                    CHECK((k3 == 2 && t >= 208) || (k3 == 3 && t < 54), "w written by slot %d, lane %d", k3, t);
+                }
+                if (win_tail_lane(k3, t)) {
+                    const int i = win_index_tail(n);
+                    CHECK(i % 2 == 0 && i >= 0 && i + 1 < kWinQ0 && n == kN + (i - kWinQ0), "tail window pair of slot %d, lane %d at %d", k3, t, i);
+                    if (i >= 0 && i + 1 < kWinLen) { ++parked[i]; ++parked[i + 1]; }
+                    CHECK(k3 == 3 && t >= 204, "tail window written by slot %d, lane %d", k3, t);
+                }
+                if (win_head_lane(k3, t)) {
+                    const int i = win_index_head(n);
+                    CHECK(i % 2 == 0 && i >= kWinQ0 && i + 1 < kWinLen && n == i - kWinQ0, "head window pair of slot %d, lane %d at %d", k3, t, i);
+                    if (i >= 0 && i + 1 < kWinLen) { ++parked[i]; ++parked[i + 1]; }
+                    CHECK(k3 == 0 && t < 50, "head window written by slot %d, lane %d", k3, t);
+                }
+            }
+        for (int i = 0; i < kWinLen; ++i) {
+            CHECK(parked[i] == 1 && zread[i] == 1, "parked window entry %d: written %d times, read %d times", i, parked[i], zread[i]);
+            // w: entries 0 .. kWinLen - 2 = q in [-kWinQL, kWinQH], what the inverse filter reads (index q + kWinQL)
+            CHECK(w[i] == (i < kWinLen - kWinWShift ? 1 : 0), "w entry %d is written %d times", i, w[i]);
+        }
+        // parked: q in [-kWinQL, kWinQH] = indices 1 .. kWinLen - 1: entry 0 (q = -kWinQL - 1) is there for the alignment alone
+        CHECK(kWinQ0 - kWinQL == 1 && kWinQ0 + kWinQH == kWinLen - 1 && kWinWShift == kWinQ0 - kWinQL, "window range");
+    }
+    if (!failures) std::printf("fft_planes_check: maps, writes, gathers ok; transform rel. error %.3g\n", rel_out);
     return failures ? 1 : 0;
 }

@@ -9,7 +9,7 @@ while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
   d="$ROOT/tools/_variants/src_$name"
   rm -rf "$d"; mkdir -p "$d/odr-dabmod_amd" "$d/include"
-  cp -r "$ROOT/odr-dabmod_amd/csrc" "$d/odr-dabmod_amd/csrc"; cp "$ROOT/include/"*.h "$d/include/"
+  cp -r "$ROOT/odr-dabmod_amd/csrc" "$d/odr-dabmod_amd/csrc"; cp -r "$ROOT/odr-dabmod_amd/host" "$d/odr-dabmod_amd/host"; cp "$ROOT/include/"*.h "$d/include/"
   rm -f "$d/odr-dabmod_amd/csrc/"*.o "$d/odr-dabmod_amd/csrc/libdabgpu.so"
   make -s -C "$d/odr-dabmod_amd/csrc" -j8 NOSLP="-fno-slp-vectorize $flags" > "$ROOT/tools/_variants/$name.log" 2>&1
   cp "$d/odr-dabmod_amd/csrc/libdabgpu.so" "$ROOT/tools/_variants/libdabgpu_$name.so"
