@@ -1385,6 +1385,133 @@ DABGPU_API int dabgpu_get_cir(dabgpu_ctx *ctx, dabgpu_cir_head *head, dabgpu_cir
 DABGPU_API int dabgpu_get_cir_profile(dabgpu_ctx *ctx, double *pdp, double *resp);
 DABGPU_API int dabgpu_cir_check(int mode, size_t n_frames, const dabgpu_cir_config *cfg);
 
+/* ---- the FIC reader: FIB CRCs, FIG 0/0, 0/1, 0/2, 1/0, 1/1, and a decoder that configures itself from them ------------------ *
+ * dabgpu_decode* reads the tables dabgpu_frontend_configure uploads from a raw ETI frame's FC / STC words.  A capture that did
+ * not come from this modulator has no ETI frame: its layout is written down in the Fast Information Channel only.  These
+ * entries read it on the device and build the ETI header the decoder is configured with.  What the reference has of this is
+ * on the CPU (FICDecoder, src/FigParser.cpp:94-321,650-713); nothing here replaces a plugin of its flowgraph.
+ * Input: n_images images of 6144 bytes on the device, four-byte aligned: what dabgpu_decode* writes (the FIC at the configured
+ *   layout's fic_offset, zeros in the headers), or raw ETI(NI) frames.  fic_offset says where the FIC lies in every image;
+ *   DABGPU_FIC_OFFSET_CONFIGURED: at the configured layout's fic_offset.  The FIC is the 96 bytes (128 in Mode III) of the
+ *   context's mode: 3 or 4 FIBs of 32 bytes per image.  FIB index = image x FIBs per image + i: stream order.
+ * Per FIB, one dabgpu_fic_record (288 bytes):
+ *   CRC      CRC-16, x^16 + x^12 + x^5 + 1, register 0xFFFF at the start, result complemented, over bytes 0 ... 29, compared big
+ *            endian with bytes 30 ... 31 (EN 300 401 5.2.1; "123456789" gives 0xD64E).  flags: DABGPU_FIC_CRC_OK.  A FIB of 32
+ *            zero bytes fails it (30 zero bytes give 0xD5BA) and is flagged DABGPU_FIC_ZERO: what the decoder's fifteen
+ *            lead-in outputs hold, counted as fibs_zero, not as fibs_bad.  A FIB that fails carries nothing but its flags.
+ *   Walk     only when the CRC holds, over bytes 0 ... 29, to the end marker 0xFF: type (3 bits) | length (5 bits), then
+ *            `length` bytes.  A FIG whose length runs past byte 29 ends the walk: figs_truncated, DABGPU_FIC_TRUNCATED, the FIG
+ *            is not counted.  An entry cut off by the end of its FIG is dropped with what follows it in that FIG.  No byte
+ *            outside the FIB's 32 is ever read.  (FICDecoder trusts the lengths and reads on: the deliberate deviation.)
+ *            figs_type[t]: FIGs of type t;  fig0_ext[e]: FIGs 0/e (length >= 1), whatever their flags.
+ *   FIG 0    header C/N | OE | P/D | extension (5 bits).  Extensions 0, 1, 2 are read only with C/N = OE = P/D = 0, as the
+ *            reference does (fig0_skipped counts those that were not); every other extension is counted only.
+ *   FIG 0/0  (>= 4 field bytes) EId, change flags (2 bits), alarm flag, CIF count (5 + 8 bits).  eid_first / eid: the first and
+ *            the last EId of the FIB, eid_seen how many, eid_changes how often one differed from the one before.
+ *   FIG 0/1  per entry SubChId (6 bits), start address (10 bits), then the short form (0, table switch, 6-bit table index: 3
+ *            bytes) or the long form (1, option (3 bits), protection level (2 bits), size (10 bits): 4 bytes).  sub[]: raw = the
+ *            entry's 3 or 4 bytes, first byte highest, zero behind a short entry;  form;  sw_option = table switch or option;
+ *            index_level = table index or the level field (0 ... 3);  size (0 in the short form).  At most 9 per FIB.
+ *   FIG 0/2  (P/D = 0) SId (16 bits), info = local flag | CAId (3 bits) | number of components (4 bits), then per component two
+ *            bytes: TMId (2 bits); ASCTy / DSCTy (6 bits; `type`, 0 for TMId 3); SubChId (6 bits) or, for TMId 3, SCId (12 bits)
+ *            (`id`); P/S (`primary`); CA flag.  4 services and 8 components are kept per FIB, a service with all of its
+ *            components or not at all: services_dropped, components_dropped.
+ *   FIG 1    header charset (4 bits) | OE | extension (3 bits).  1/0 (kind 1, id = EId) and 1/1 (kind 2, id = SId) with OE = 0
+ *            and exactly 2 + 16 + 2 field bytes: 16 label bytes and the 16-bit character flag.  The first label of a FIB is
+ *            kept, later ones are counted (labels_dropped).
+ * Over the call, dabgpu_fic_result: the sums of the above (fibs = fibs_ok + fibs_bad + fibs_zero), and per SubChId 0 ... 63 and
+ *   for the EId what one pass over the FIBs in stream order, entries in walk order, gives: seen = sightings, changes = how often
+ *   the raw word differed from the sighting before, first_fib / last_fib, raw = the last word.  Formed without atomics in a fixed
+ *   order, from per-run summaries whose combination is associative: the same bytes for the same input, whatever the grid.
+ *   sub[0 ... n_subch - 1]: the SubChIds seen, ascending; the rest is zero.  Derived on the host from the last raw word:
+ *   short form: table_switch = 0 is supported: index_option = the table index, row i of the standard's 64-row table (EN 300 401
+ *     table 6: ascending bit rate, level 5 down to 1) built from the UEP profiles of host/protection_tables.inc -> bitrate,
+ *     level 1 ... 5, size_cu;  tpl = level - 1.
+ *   long form: index_option = option, level = the level field + 1.  Option 0 (EEP-A): bitrate = size / {12, 8, 6, 4}[level - 1]
+ *     x 8;  option 1 (EEP-B): bitrate = size / {27, 21, 18, 15}[level - 1] x 32;  supported when the option is 0 or 1 and the
+ *     size a non-zero multiple of its factor;  tpl = 0x20 | option << 2 | (level - 1);  size_cu = size.
+ *   stl = 3 x bitrate / 8 (64-bit words per 24 ms).  supported = 0: bitrate, level (short form), tpl, stl are 0.
+ * dabgpu_fic_scan_dev: asynchronous on `stream` (NULL: the context's own, behind every lane); three launches, no host round
+ *   trip.  dabgpu_fic_scan: the host-pointer form.  A result is per call; the getters wait for the most recent one.
+ *   Refused with DABGPU_E_INVALID and a message before anything is queued (the previous result stays): n_images = 0 or above
+ *   2^22; a null or misaligned pointer; an offset that is not a multiple of 4 or with fic_offset + fic_bytes > 6144;
+ *   DABGPU_FIC_OFFSET_CONFIGURED on a context whose front-end is not configured; a get before any call.
+ * dabgpu_get_fic_records: min(cap, n) records to `out`, *n = FIBs of the call.  dabgpu_get_fic_services: merged on the host
+ *   from the records (a few hundred bytes per call's worth of 16-bit identifiers): services in order of first appearance (in
+ *   a FIG 0/2, or as the id of a FIG 1/1; within one FIB the FIG 0/2 entries come first), sightings = FIG 0/2 entries, the
+ *   components in order of first appearance ((TMId, id) names one; the latest type / primary / ca), at most
+ *   DABGPU_FIC_MAX_COMPONENTS, the latest label.  min(cap, n) services to `out`, *n = services found; `ensemble` (may be NULL):
+ *   the latest FIG 1/0, kind 0 when none was seen.
+ * Host only -- no context, no device, message via dabgpu_last_error(NULL):
+ *   dabgpu_fic_bootstrap_frame: the ETI header of an ensemble with FICF = 1 and NST = 0 in `mode` (1 ... 4).
+ *     dabgpu_frontend_configure on it leaves a decoder that decodes the FIC alone: the FIC's puncturing depends on the mode only.
+ *   dabgpu_fic_make_header: from a result, the ETI frame dabgpu_frontend_configure wants: SYNC, FC (FCT 0, FICF 1, NST, FP 0, MID,
+ *     FL), one STC word per sub-channel in ascending SubChId (SCId = SubChId, SAD, TPL, STL), EOH zero, zero payload, EOF 00 00 FF
+ *     FF, TIST FF FF FF FF, 0x55 behind it.  Refused: n_subch = 0 (no FIG 0/1 seen is not an empty ensemble); n_subch above 64; a
+ *     sub-channel with changes > 0 (a reconfiguration inside the capture); a sub-channel with supported = 0.  Then whatever
+ *     dabgpu_frontend_describe and dabgpu_decode_check_layout refuse (overlap, beyond CU 864), with their message.
+ * dabgpu_decode_configure_from_fic: dabgpu_fic_make_header on the most recent result in the context's mode, then
+ *   dabgpu_frontend_configure -- which zeroes the histories of front-end and decoder.
+ * The blind loop: coded bits of a capture -> a context configured with dabgpu_fic_bootstrap_frame -> dabgpu_decode_dev ->
+ *   dabgpu_fic_scan_dev on its output (past the fifteen lead-in images, or with them: they count as fibs_zero) ->
+ *   dabgpu_decode_configure_from_fic -> dabgpu_decode_dev on the same coded bits again.  The FIC leaves the decoder fifteen ETI
+ *   frames late, like every unit: A CAPTURE MUST HOLD MORE THAN 15 ETI FRAMES BEFORE ANYTHING CAN BE READ.  A FIC path
+ *   without the delay line is out of scope; so are the other FIG 0 extensions, FIG 1/4 ... and FIG 2, and CRC-less recovery. */
+#define DABGPU_FIC_OFFSET_CONFIGURED (~(size_t)0)
+#define DABGPU_FIC_CRC_OK 1u
+#define DABGPU_FIC_ZERO 2u
+#define DABGPU_FIC_TRUNCATED 4u
+#define DABGPU_FIC_REC_SUBCH 9
+#define DABGPU_FIC_REC_SERVICES 4
+#define DABGPU_FIC_REC_COMPONENTS 8
+#define DABGPU_FIC_MAX_COMPONENTS 12
+typedef struct dabgpu_fic_sub_entry {
+    uint32_t raw;
+    uint16_t sad, size;
+    uint8_t subchid, form, sw_option, index_level;
+} dabgpu_fic_sub_entry;                                                                              /* 12 bytes */
+typedef struct dabgpu_fic_service_entry { uint16_t sid; uint8_t info, first_comp; } dabgpu_fic_service_entry;
+typedef struct dabgpu_fic_component { uint16_t id; uint8_t tmid, type, primary, ca, service, reserved; } dabgpu_fic_component;
+typedef struct dabgpu_fic_label { uint8_t kind, charset; uint16_t id, flag; uint8_t text[16]; uint16_t reserved; } dabgpu_fic_label;
+typedef struct dabgpu_fic_record {
+    uint32_t flags;
+    uint16_t eid_first, eid;
+    uint8_t eid_seen, eid_changes, change, alarm;
+    uint8_t cif_hi, cif_lo, n_sub, n_svc;
+    uint8_t n_comp, services_dropped, components_dropped, labels_dropped;
+    uint8_t figs_truncated, fig0_skipped, reserved[2];
+    uint8_t figs_type[8];
+    uint8_t fig0_ext[32];
+    dabgpu_fic_sub_entry sub[DABGPU_FIC_REC_SUBCH];
+    dabgpu_fic_service_entry svc[DABGPU_FIC_REC_SERVICES];
+    dabgpu_fic_component comp[DABGPU_FIC_REC_COMPONENTS]; /* `service`: index into svc[] */
+    dabgpu_fic_label label;
+    uint8_t pad[12];
+} dabgpu_fic_record;                                                                                 /* 288 bytes */
+typedef struct dabgpu_fic_subch {
+    uint32_t subchid, sad, size_cu, form, index_option, level, bitrate, tpl, stl, supported, seen, changes, first_fib, last_fib, raw;
+    uint32_t table_switch;
+} dabgpu_fic_subch;                                                                                  /* 64 bytes */
+typedef struct dabgpu_fic_result {
+    uint32_t fibs, fibs_ok, fibs_bad, fibs_zero, figs_truncated, fig0_skipped, services_dropped, components_dropped, labels_dropped;
+    uint32_t eid, eid_seen, eid_changes, eid_first_fib, eid_last_fib, n_subch, reserved;
+    uint32_t figs_type[8], fig0_ext[32];
+    dabgpu_fic_subch sub[64];
+} dabgpu_fic_result;                                                                                 /* 4320 bytes */
+typedef struct dabgpu_fic_service {
+    uint32_t sid, n_components, sightings, components_dropped;
+    dabgpu_fic_component comp[DABGPU_FIC_MAX_COMPONENTS]; /* `service` is 0 here */
+    dabgpu_fic_label label;                               /* kind 0: no FIG 1/1 seen */
+} dabgpu_fic_service;                                                                                /* 136 bytes */
+DABGPU_API int dabgpu_fic_scan_dev(dabgpu_ctx *ctx, const void *d_images, size_t n_images, size_t fic_offset, void *stream);
+DABGPU_API int dabgpu_fic_scan(dabgpu_ctx *ctx, const uint8_t *images, size_t n_images, size_t fic_offset);
+DABGPU_API int dabgpu_get_fic_result(dabgpu_ctx *ctx, dabgpu_fic_result *out);
+DABGPU_API int dabgpu_get_fic_records(dabgpu_ctx *ctx, dabgpu_fic_record *out, size_t cap, size_t *n);
+DABGPU_API int dabgpu_get_fic_services(dabgpu_ctx *ctx, dabgpu_fic_service *out, size_t cap, size_t *n, dabgpu_fic_label *ensemble);
+DABGPU_API int dabgpu_fic_bootstrap_frame(int mode, uint8_t frame[6144]);
+DABGPU_API int dabgpu_fic_make_header(const dabgpu_fic_result *result, int mode, uint8_t frame[6144]);
+DABGPU_API int dabgpu_decode_configure_from_fic(dabgpu_ctx *ctx);
+
 /* wait for everything queued on the context's own stream(s): every lane */
 DABGPU_API int dabgpu_synchronize(dabgpu_ctx *ctx);
 

@@ -66,6 +66,8 @@ EXPORTS = [
     "dabgpu_cir_dev", "dabgpu_cir", "dabgpu_get_cir", "dabgpu_get_cir_profile", "dabgpu_cir_check",
     "dabgpu_demod_csi", "dabgpu_demod_csi_dev", "dabgpu_demod_carrier_state", "dabgpu_demod_carrier_state_dev",
     "dabgpu_get_carrier_state", "dabgpu_debug_csi_unit_weights",
+    "dabgpu_fic_scan_dev", "dabgpu_fic_scan", "dabgpu_get_fic_result", "dabgpu_get_fic_records", "dabgpu_get_fic_services",
+    "dabgpu_fic_bootstrap_frame", "dabgpu_fic_make_header", "dabgpu_decode_configure_from_fic",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -245,6 +247,60 @@ class _FeLayout(C.Structure):
                 ("sub", _FeSubch * 127)]
 
 
+class _FicSubEntry(C.Structure):
+    _fields_ = [("raw", C.c_uint32), ("sad", C.c_uint16), ("size", C.c_uint16), ("subchid", C.c_uint8), ("form", C.c_uint8),
+                ("sw_option", C.c_uint8), ("index_level", C.c_uint8)]
+
+
+class _FicServiceEntry(C.Structure):
+    _fields_ = [("sid", C.c_uint16), ("info", C.c_uint8), ("first_comp", C.c_uint8)]
+
+
+class _FicComponent(C.Structure):
+    _fields_ = [("id", C.c_uint16), ("tmid", C.c_uint8), ("type", C.c_uint8), ("primary", C.c_uint8), ("ca", C.c_uint8),
+                ("service", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+class _FicLabel(C.Structure):
+    _fields_ = [("kind", C.c_uint8), ("charset", C.c_uint8), ("id", C.c_uint16), ("flag", C.c_uint16), ("text", C.c_uint8 * 16),
+                ("reserved", C.c_uint16)]
+
+
+class _FicRecord(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("eid_first", C.c_uint16), ("eid", C.c_uint16), ("eid_seen", C.c_uint8),
+                ("eid_changes", C.c_uint8), ("change", C.c_uint8), ("alarm", C.c_uint8), ("cif_hi", C.c_uint8),
+                ("cif_lo", C.c_uint8), ("n_sub", C.c_uint8), ("n_svc", C.c_uint8), ("n_comp", C.c_uint8),
+                ("services_dropped", C.c_uint8), ("components_dropped", C.c_uint8), ("labels_dropped", C.c_uint8),
+                ("figs_truncated", C.c_uint8), ("fig0_skipped", C.c_uint8), ("reserved", C.c_uint8 * 2),
+                ("figs_type", C.c_uint8 * 8), ("fig0_ext", C.c_uint8 * 32), ("sub", _FicSubEntry * 9),
+                ("svc", _FicServiceEntry * 4), ("comp", _FicComponent * 8), ("label", _FicLabel), ("pad", C.c_uint8 * 12)]
+
+
+_FIC_SUBCH_FIELDS = ("subchid", "sad", "size_cu", "form", "index_option", "level", "bitrate", "tpl", "stl", "supported", "seen",
+                     "changes", "first_fib", "last_fib", "raw", "table_switch")
+_FIC_RESULT_FIELDS = ("fibs", "fibs_ok", "fibs_bad", "fibs_zero", "figs_truncated", "fig0_skipped", "services_dropped",
+                      "components_dropped", "labels_dropped", "eid", "eid_seen", "eid_changes", "eid_first_fib", "eid_last_fib",
+                      "n_subch", "reserved")
+
+
+class _FicSubch(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in _FIC_SUBCH_FIELDS]
+
+
+class _FicResult(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in _FIC_RESULT_FIELDS] + [("figs_type", C.c_uint32 * 8), ("fig0_ext", C.c_uint32 * 32),
+                                                                 ("sub", _FicSubch * 64)]
+
+
+class _FicService(C.Structure):
+    _fields_ = [("sid", C.c_uint32), ("n_components", C.c_uint32), ("sightings", C.c_uint32), ("components_dropped", C.c_uint32),
+                ("comp", _FicComponent * 12), ("label", _FicLabel)]
+
+
+assert C.sizeof(_FicRecord) == 288 and C.sizeof(_FicResult) == 4320 and C.sizeof(_FicService) == 136
+FIC_RECORD_BYTES, FIC_OFFSET_CONFIGURED = 288, C.c_size_t(-1).value
+FIC_CRC_OK, FIC_ZERO, FIC_TRUNCATED = 1, 2, 4
+
 ETI_FRAME_BYTES = 6144
 CIFS_PER_FRAME = {1: 4, 2: 1, 3: 1, 4: 2}      # ETI frames per transmission frame
 FE_HISTORY_FRAMES = 15                         # ETI frames the time interleaver looks back (DABGPU_FE_HISTORY_FRAMES)
@@ -399,6 +455,14 @@ def load_library():
     lib.dabgpu_get_cir.argtypes = [vp, C.POINTER(_CirHead), C.POINTER(_CirPath), sz]
     lib.dabgpu_get_cir_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.dabgpu_cir_check.argtypes = [C.c_int, sz, C.POINTER(_CirConfig)]
+    lib.dabgpu_fic_scan_dev.argtypes = [vp, vp, sz, sz, vp]
+    lib.dabgpu_fic_scan.argtypes = [vp, vp, sz, sz]
+    lib.dabgpu_get_fic_result.argtypes = [vp, C.POINTER(_FicResult)]
+    lib.dabgpu_get_fic_records.argtypes = [vp, vp, sz, szp]
+    lib.dabgpu_get_fic_services.argtypes = [vp, vp, sz, szp, C.POINTER(_FicLabel)]
+    lib.dabgpu_fic_bootstrap_frame.argtypes = [C.c_int, vp]
+    lib.dabgpu_fic_make_header.argtypes = [C.POINTER(_FicResult), C.c_int, vp]
+    lib.dabgpu_decode_configure_from_fic.argtypes = [vp]
     lib.dabgpu_decode_check_layout.argtypes = [C.POINTER(_FeLayout)]
     lib.dabgpu_decode_reset.argtypes = [vp]
     lib.dabgpu_decode_dev.argtypes = [vp, vp, sz, vp, sz, vp, szp, vp]
@@ -664,6 +728,57 @@ def decode_check_layout(frame):
     lay = _FeLayout()
     if lib.dabgpu_frontend_describe(frame.ctypes.data, C.byref(lay)) != 0 or lib.dabgpu_decode_check_layout(C.byref(lay)) != 0:
         raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def fic_bootstrap_frame(mode):
+    """Host only (needs the library, no device): the 6144-byte ETI frame of an ensemble with FICF = 1 and NST = 0 in `mode`.
+    frontend_configure() on it leaves a decoder that decodes the FIC alone -- where a blind receiver starts."""
+    lib = load_library()
+    frame = np.empty(ETI_FRAME_BYTES, np.uint8)
+    if lib.dabgpu_fic_bootstrap_frame(int(mode), frame.ctypes.data) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return frame
+
+
+def _fic_label_dict(l):
+    return None if not l.kind else dict(kind=int(l.kind), charset=int(l.charset), id=int(l.id), flag=int(l.flag),
+                                        text=bytes(bytearray(l.text)))
+
+
+def _fic_result_dict(r):
+    d = {k: int(getattr(r, k)) for k in _FIC_RESULT_FIELDS if k != "reserved"}
+    d["figs_type"], d["fig0_ext"] = list(r.figs_type), list(r.fig0_ext)
+    d["sub"] = [{k: int(getattr(r.sub[i], k)) for k in _FIC_SUBCH_FIELDS} for i in range(min(r.n_subch, 64))]
+    return d
+
+
+def _fic_result_struct(result):
+    """a result dictionary of fic_result() (or a _FicResult) as the C structure"""
+    if isinstance(result, _FicResult):
+        return result
+    r = _FicResult()
+    for k in _FIC_RESULT_FIELDS:
+        setattr(r, k, int(result.get(k, 0)))
+    for name in ("figs_type", "fig0_ext"):
+        for i, v in enumerate(result.get(name, ())):
+            getattr(r, name)[i] = int(v)
+    for i, sub in enumerate(result.get("sub", ())[:64]):
+        for k in _FIC_SUBCH_FIELDS:
+            setattr(r.sub[i], k, int(sub.get(k, 0)))
+    return r
+
+
+def fic_make_header(result, mode):
+    """Host only (needs the library, no device): the ETI frame frontend_configure() wants, from a result of fic_result() -- FC and
+    one STC word per sub-channel in ascending SubChId.  Raises DabGpuError when the result does not say how the ensemble is laid
+    out (no FIG 0/1, a redefinition inside the capture, a form that is not supported) or says a layout the front-end or the
+    decoder refuses."""
+    lib = load_library()
+    r = _fic_result_struct(result)
+    frame = np.empty(ETI_FRAME_BYTES, np.uint8)
+    if lib.dabgpu_fic_make_header(C.byref(r), int(mode), frame.ctypes.data) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+    return frame
 
 
 def decode_reference(eti, e, n):
@@ -1787,6 +1902,67 @@ class Modulator:
         dp = C.POINTER(C.c_double)
         self._chk(self._lib.dabgpu_get_cir_profile(self._h, pdp.ctypes.data_as(dp), resp.ctypes.data_as(dp)))
         return pdp, resp
+
+    # ---- the FIC reader: FIB CRCs, the sub-channel table, a decoder that sets itself up (include/dabgpu.h, "the FIC reader") ----
+    def fic_scan(self, images, fic_offset=None):
+        """Host path: (n, 6144) uint8 images -- decode()'s output or raw ETI frames -> fic_result().  fic_offset: where the FIC
+        lies in every image; None: at the configured layout's offset."""
+        images, n = self._eti(images)
+        off = FIC_OFFSET_CONFIGURED if fic_offset is None else int(fic_offset)
+        self._chk(self._lib.dabgpu_fic_scan(self._h, images.ctypes.data, n, off))
+        return self.fic_result()
+
+    def fic_scan_dev(self, d_images, n_images, fic_offset=None, stream=None, queued=False):
+        """Device path on a torch uint8 tensor that holds n_images images, asynchronous on the stream as chain_dev; the result:
+        fic_result(), fic_records(), fic_services()."""
+        if d_images.numel() * d_images.element_size() < int(n_images) * ETI_FRAME_BYTES:
+            raise DabGpuError("fic_scan: the tensor is shorter than n_images images of 6144 bytes")
+        off = FIC_OFFSET_CONFIGURED if fic_offset is None else int(fic_offset)
+        self._dev_call(self._lib.dabgpu_fic_scan_dev, d_images, stream, d_images.data_ptr(), int(n_images), off, queued=queued)
+
+    def _fic_result_raw(self):
+        r = _FicResult()
+        self._chk(self._lib.dabgpu_get_fic_result(self._h, C.byref(r)))
+        return r
+
+    def fic_result(self):
+        """The most recent fic_scan() / fic_scan_dev() (waits for it): a dict of the fields of dabgpu_fic_result; "sub": one
+        dict per SubChId seen, ascending."""
+        return _fic_result_dict(self._fic_result_raw())
+
+    def fic_result_bytes(self):
+        """The same result as the 4320 bytes of dabgpu_fic_result."""
+        return bytes(self._fic_result_raw())
+
+    def fic_records(self):
+        """The per-FIB records of the same call as a (FIBs, 288) uint8 array: rows of dabgpu_fic_record, in stream order."""
+        n = C.c_size_t()
+        self._chk(self._lib.dabgpu_get_fic_records(self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, FIC_RECORD_BYTES), np.uint8)
+        self._chk(self._lib.dabgpu_get_fic_records(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def fic_services(self):
+        """(ensemble label or None, services) of the same call, merged on the host from the records: per service sid,
+        sightings, components_dropped, label (dict or None) and components [dict(id, tmid, type, primary, ca)], in order of
+        first appearance."""
+        n, ens = C.c_size_t(), _FicLabel()
+        self._chk(self._lib.dabgpu_get_fic_services(self._h, None, 0, C.byref(n), C.byref(ens)))
+        recs = (_FicService * max(n.value, 1))()
+        self._chk(self._lib.dabgpu_get_fic_services(self._h, recs, n.value, C.byref(n), C.byref(ens)))
+        out = []
+        for i in range(n.value):
+            s = recs[i]
+            out.append(dict(sid=int(s.sid), sightings=int(s.sightings), components_dropped=int(s.components_dropped),
+                            label=_fic_label_dict(s.label),
+                            components=[{k: int(getattr(s.comp[j], k)) for k in ("id", "tmid", "type", "primary", "ca")}
+                                        for j in range(s.n_components)]))
+        return _fic_label_dict(ens), out
+
+    def configure_from_fic(self):
+        """fic_make_header() on the most recent fic_scan result, then frontend_configure(): the decoder set up from what the
+        signal says about itself.  Zeroes the histories, as frontend_configure does.  Waits."""
+        self._chk(self._lib.dabgpu_decode_configure_from_fic(self._h))
 
     # ---- the channel decoder: coded bits -> the ETI payload (include/dabgpu.h, "the channel decoder") ----
     def decode(self, bits, ref_eti=None):

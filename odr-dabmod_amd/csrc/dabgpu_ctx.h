@@ -28,6 +28,9 @@
 //                     the settings check (host only)
 //   api_cir.hip       the channel estimator (cir.hip): impulse response, echoes and the response on the carriers from the
 //                     phase reference symbols of whole frames; the settings check (host only)
+//   api_fic.hip       the FIC reader (fic.hip): FIB CRCs and FIG 0/0, 0/1, 0/2, 1/0, 1/1 of decoded images or ETI frames, the
+//                     sub-channel table of a call; the short-form table, the derived fields, the ETI header made from a
+//                     result and the bootstrap frame (host only); the decoder configured from a result
 //   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
 //                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
 // In this order: Settings, TraceScope; the receive-side stages' state, one struct each; dabgpu_ctx with one member of each
@@ -265,6 +268,16 @@ struct CirState {
     bool done = false;
     hipStream_t stream = nullptr;
 };
+
+// The FIC reader (api_fic.hip, fic.hip).  rec: one record per FIB of the most recent dabgpu_fic_scan* call, `fibs` of them;
+// partial: one summary per 256 FIBs (scratch); result: the call's summary; in: the host-pointer entry's staging; done: a call
+// has been queued.
+struct FicState {
+    DevBuf rec, partial, result, in;
+    size_t fibs = 0;
+    bool done = false;
+    hipStream_t stream = nullptr;
+};
 }  // namespace dabgpu_api
 
 struct dabgpu_ctx {
@@ -339,6 +352,7 @@ struct dabgpu_ctx {
     dabgpu_api::TunerState tuner;
     dabgpu_api::TiiScanState tii_scan;
     dabgpu_api::CirState cir;
+    dabgpu_api::FicState fic;
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII
     bool tables_valid = false;            // apply_settings has uploaded every table group once
     unsigned long long tii_seg_epoch = 0; // 1 while the cached segment matches the settings (apply_settings zeroes it), and its stage mask

@@ -47,6 +47,15 @@
 //                        never returns the last fifteen of the file.  After the run: frames compared, FIC and MSC payload
 //                        bit errors, corrected channel bits and coded bits on stderr; exit status 2 on any payload bit error.
 //                        Native-rate complexf / s16 output; not with --state-in (the decoder's history is not in the file).
+//   --blind              with --loopback: the receiving side knows nothing of the file's layout.  It decodes on a context of its
+//                        own, configured with dabgpu_fic_bootstrap_frame (NST = 0: the FIC alone).  It reads the FIC of the
+//                        first batch (dabgpu_fic_scan on the decoder's output), configures itself from it
+//                        (dabgpu_decode_configure_from_fic) and decodes that batch again from its start; every later batch is
+//                        decoded as --loopback does.  Prints the FIBs good / bad / zero, the EId and the sub-channel table it
+//                        found.  The first batch must hold more than fifteen ETI frames (--batch), and the file's FIC must be
+//                        a real one that numbers the sub-channels as the STC words do.  Exit status 4 when no configuration
+//                        could be read, or when it is not the file's; 2 on a payload bit error, as --loopback.  Hard decisions
+//                        only (not with --soft).
 //   --soft               with --loopback: soft decisions -- dabgpu_demod_soft (one int8 metric per coded bit) and
 //                        dabgpu_decode_soft in place of the hard pair, the same bookkeeping and exit status.  The summary line
 //                        adds the path metric over the sum of the metrics' magnitudes, and the erasures.  On the modulator's
@@ -125,6 +134,11 @@
 #include <vector>
 
 namespace {
+// --blind: the receiving side found no configuration in the FIC, or not the file's (exit status 4)
+struct BlindFailure : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+
 [[noreturn]] void usage()
 {
     std::fprintf(stderr, "usage: dabmod_file <in.eti> <out> [--mode N] [--format complexf|s16|u8|s8] [--gainmode var|fix|max]\n"
@@ -140,6 +154,7 @@ namespace {
                          "                        --separate-converter)\n"
                          "       [--loopback]   with --gpu-frontend: demodulate and channel-decode every batch on the device against the ETI\n"
                          "                        frames read; totals on stderr, exit 2 on a payload bit error\n"
+                         "       [--blind]   with --loopback: the decoder configures itself from the FIC of the first batch (exit status 4: it could not)\n"
                          "       [--soft]   with --loopback: soft decisions (int8 metrics, soft Viterbi) in place of hard ones\n"
                          "       [--channel-cn DB [--channel-seed N] [--channel-echo DELAY,DB,PHASE]...]   with --loopback: noise and echoes\n"
                          "           between the IQ and the demodulator (the channel emulator)\n"
@@ -212,7 +227,7 @@ int main(int argc, char **argv)
     size_t batch = 1;
     bool reference_latency = false;
     long contexts = 1;
-    bool gpu_frontend = false, loopback = false, soft = false, csi = false;
+    bool gpu_frontend = false, loopback = false, soft = false, csi = false, blind = false;
     std::string carrier_mer_path;
     bool channel = false;
     double channel_cn = 0.0;
@@ -269,6 +284,7 @@ int main(int argc, char **argv)
             else if (a == "--gpu-frontend") gpu_frontend = true;
             else if (a == "--monitor") gs.monitor = true;
             else if (a == "--loopback") loopback = true;
+            else if (a == "--blind") blind = true;
             else if (a == "--soft") soft = true;
             else if (a == "--csi") csi = true;
             else if (a == "--carrier-mer") carrier_mer_path = val();
@@ -316,6 +332,13 @@ int main(int argc, char **argv)
                          : gs.outputRate != 2048000 ? "--rate: the receiver takes the native rate"
                          : !state_in.empty() ? "--state-in: the decoder's history is not part of the state file"
                                              : "u8 / s8 output: the receiver takes complexf or s16");
+            return 2;
+        }
+
+        if (blind && (!loopback || soft)) {
+            std::fprintf(stderr, "dabmod_file: --blind does not go %s\n",
+                         !loopback ? "without --loopback: it is that loop's receiving side that configures itself"
+                                   : "with --soft: the FIC is read from the hard decoder's output");
             return 2;
         }
 
@@ -517,6 +540,12 @@ int main(int argc, char **argv)
         double channel_sigma = -1.0;              //   < 0: not installed yet (the first batch sets the level)
         int loop_early = -1;
         size_t loop_cifs = 1;
+        // --blind: the receiving side's own context, and whether it has read its configuration yet
+        struct RxContext {
+            dabgpu_ctx *c = nullptr;
+            ~RxContext() { if (c) dabgpu_destroy(c); }
+        } rx;
+        bool blind_configured = false;
         // --cir: the last batch, as written or (--loopback --channel-cn) as the channel emulator left it, and its chain
         std::vector<uint8_t> cir_last;
         DabGpuChain *cir_chain = nullptr;
@@ -587,12 +616,56 @@ int main(int argc, char **argv)
             } else {
                 chk(dabgpu_demod(c, p, format == "s16" ? DABGPU_FMT_S16 : 0, n_frames, loop_early, loop_bits.data(), nullptr));
             }
+            dabgpu_ctx *dc = c;                       // the context that decodes
+            if (blind) {
+                if (!rx.c) {
+                    dabgpu_geometry g{};
+                    chk(dabgpu_get_geometry(c, &g));
+                    const dabgpu_config rc{g.mode, 0, static_cast<int>(batch), 0};
+                    uint8_t boot[6144];
+                    if (dabgpu_create(&rc, &rx.c) || dabgpu_fic_bootstrap_frame(g.mode ? g.mode : 4, boot))
+                        throw std::runtime_error(std::string("--blind: ") + dabgpu_last_error(nullptr));
+                    if (dabgpu_frontend_configure(rx.c, boot)) throw std::runtime_error(std::string("--blind: ") + dabgpu_last_error(rx.c));
+                }
+                dc = rx.c;
+            }
+            auto chk_dc = [&](int rc) { if (rc) throw std::runtime_error(std::string("--loopback: ") + dabgpu_last_error(dc)); };
+            if (blind && !blind_configured) {
+                // the FIC alone, fifteen frames late; what it says; the decoder set up from it.  The batch is decoded again below.
+                size_t ob0 = 0;
+                chk_dc(dabgpu_decode(dc, loop_bits.data(), n_frames, loop_out.data(), loop_out.size(), nullptr, &ob0));
+                chk_dc(dabgpu_fic_scan(dc, loop_out.data(), n, DABGPU_FIC_OFFSET_CONFIGURED));
+                std::vector<dabgpu_fic_result> res(1);
+                chk_dc(dabgpu_get_fic_result(dc, res.data()));
+                const dabgpu_fic_result &r = res[0];
+                std::fprintf(stderr, "dabmod_file: blind: %u FIBs: %u good, %u bad, %u zero; EId 0x%04X; %u sub-channels\n", r.fibs, r.fibs_ok,
+                             r.fibs_bad, r.fibs_zero, r.eid, r.n_subch);
+                for (uint32_t i = 0; i < r.n_subch && i < 64; ++i) {
+                    const dabgpu_fic_subch &sc = r.sub[i];
+                    std::fprintf(stderr, "dabmod_file: blind: SubChId %2u: start %3u CU, size %3u CU, %s, %3u kbit/s (TPL 0x%02X, STL %u)%s\n",
+                                 sc.subchid, sc.sad, sc.size_cu,
+                                 !sc.supported ? "not supported"
+                                 : !sc.form    ? ("UEP " + std::to_string(sc.level)).c_str()
+                                               : ("EEP " + std::to_string(sc.level) + (sc.index_option ? "-B" : "-A")).c_str(),
+                                 sc.bitrate, sc.tpl, sc.stl, sc.changes ? ", redefined inside the batch" : "");
+                }
+                if (dabgpu_decode_configure_from_fic(dc)) throw BlindFailure(dabgpu_last_error(dc));
+                std::vector<uint8_t> made(6144);
+                if (dabgpu_fic_make_header(&r, static_cast<int>(gs.dabMode), made.data())) throw BlindFailure(dabgpu_last_error(nullptr));
+                const std::vector<uint8_t> &sent = loop_eti.front();
+                const size_t nst = sent[5] & 0x7fu;
+                bool same = made[5] == sent[5] && ((made[6] ^ sent[6]) & 0x18) == 0;
+                for (size_t k = 0; same && k < nst; ++k)                // (SAD, TPL, STL; the SCId is the SubChId here)
+                    same = ((made[8 + 4 * k] ^ sent[8 + 4 * k]) & 3) == 0 && !std::memcmp(&made[9 + 4 * k], &sent[9 + 4 * k], 3);
+                if (!same) throw BlindFailure("the FIC describes another layout than the file's STC words");
+                blind_configured = true;
+            }
             // output i is frame loop_pos + i - 15 of the stream
             for (size_t i = 0; i < n; ++i)
                 if (loop_pos + i >= 15) std::memcpy(&loop_ref[i * 6144], loop_eti.at(loop_pos + i - 15 - loop_first).data(), 6144);
             size_t ob = 0;
             if (soft) chk(dabgpu_decode_soft(c, loop_soft.data(), n_frames, loop_out.data(), loop_out.size(), loop_ref.data(), &ob));
-            else chk(dabgpu_decode(c, loop_bits.data(), n_frames, loop_out.data(), loop_out.size(), loop_ref.data(), &ob));
+            else chk_dc(dabgpu_decode(dc, loop_bits.data(), n_frames, loop_out.data(), loop_out.size(), loop_ref.data(), &ob));
             for (size_t i = 0; i < n; ++i) {
                 dabgpu_decode_stats all{}, fic{};
                 if (soft) {
@@ -608,8 +681,8 @@ int main(int argc, char **argv)
                         loop.erasures += sa.erasures;
                     }
                 } else {
-                    chk(dabgpu_get_decode_stats(c, i, -1, &all));
-                    chk(dabgpu_get_decode_stats(c, i, 0, &fic));
+                    chk_dc(dabgpu_get_decode_stats(dc, i, -1, &all));
+                    chk_dc(dabgpu_get_decode_stats(dc, i, 0, &fic));
                 }
                 if (!all.valid) continue;
                 ++loop.frames;
@@ -1035,6 +1108,9 @@ int main(int argc, char **argv)
         if (tii_mismatch) return 2;
         if (mask_violations) return 3;
         return 0;
+    } catch (const BlindFailure &e) {
+        std::fprintf(stderr, "dabmod_file: blind: no configuration could be read: %s\n", e.what());
+        return 4;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "dabmod_file: %s\n", e.what());
         return 1;
