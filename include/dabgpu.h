@@ -170,7 +170,9 @@ DABGPU_API int dabgpu_poly_process(dabgpu_ctx *ctx, const void *in, size_t in_by
  * parameters cfr, clip, errorclip of OfdmGeneratorCF32 (src/OfdmGenerator.h:50-56, .cpp:376-404).
  * When enabled every symbol is clipped, transformed forward, its error against the input
  * constellation clipped, and transformed back (cfr_one_iteration, src/OfdmGenerator.cpp:310-373),
- * in dabgpu_ofdm_process and in the chain entry points alike. */
+ * in dabgpu_ofdm_process and in the chain entry points alike.  Any float is taken, as by the reference's remote control: the
+ * thresholds act through their squares (a negative one is its magnitude), 0 clips every non-zero sample (bin) to 0, one whose
+ * square overflows clips nothing; the output stays finite where |x|^2 is subnormal (tests/test_cfr_gpu.py). */
 DABGPU_API int dabgpu_set_cfr(dabgpu_ctx *ctx, int enable, float clip, float error_clip);
 /* Per-frame raw statistics of the most recent call that ran with CFR on (frame = index inside that
  * call); the reference's running averages (clip_stats, papr: src/OfdmGenerator.cpp:285-306,419-451,
@@ -423,8 +425,9 @@ DABGPU_API int dabgpu_chain_submit(dabgpu_ctx *ctx, const uint8_t *bits, size_t 
                                    unsigned stage_mask);
 DABGPU_API int dabgpu_chain_collect(dabgpu_ctx *ctx, const void **iq, size_t *out_bytes);
 
-/* Which kernels did the most recent chain call (dabgpu_chain_process / _process_dev / _submit, dabgpu_symbols_process_dev)
- * launch?  A "; "-separated list of kernel names in launch order, the frame kernel with the VALUES of its template arguments
+/* Which kernels did the most recent chain call (dabgpu_chain_process / _process_dev / _submit, dabgpu_symbols_process_dev,
+ * and dabgpu_ofdm_process: the frame kernel from carriers without its epilogue) launch?  A "; "-separated list of kernel
+ * names in launch order, the frame kernel with the VALUES of its template arguments
  * ("tf_kernel<logn=11 bits=1 gain=1 guard=1 fir=1 nt=45 cfr=0 gvar=0 zonly=0 ofmt=0 win=0 eq=1>").  The fused chain picks
  * one of ~120 instantiations from the settings (mode, gain mode, filter length, windowing, CFR, TII, output format): this
  * makes the choice observable, so that a test can walk the whole matrix (tests/test_dispatch_matrix.py) and a user can see

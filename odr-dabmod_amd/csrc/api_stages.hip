@@ -198,7 +198,10 @@ int dabgpu_ofdm_process(dabgpu_ctx *c, const void *in, size_t in_bytes, void *ou
     HIPCHK(c, c->d_b.reserve(need));
     if ((rc = apply_settings(c))) return rc;
     size_t ob = 0;
-    rc = run_chain(c, plan_chain(c, false, 1, DABGPU_STAGE_NOGUARD, false), c->d_c.p, c->d_b.p, need, &ob, c->stream, false);
+    {
+        TraceScope trace(c->trace_enabled ? &c->last_variant : nullptr);     // (the frame kernel's bits=0, no-epilogue form)
+        rc = run_chain(c, plan_chain(c, false, 1, DABGPU_STAGE_NOGUARD, false), c->d_c.p, c->d_b.p, need, &ob, c->stream, false);
+    }
     if (rc) return rc;
     return io.out(out, c->d_b.p, need);
 }

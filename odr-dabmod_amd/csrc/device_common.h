@@ -79,6 +79,9 @@ DEV cf mk(float x, float y) { return make_float2(x, y); }
 DEV float fast_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 DEV float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 DEV float fast_rsq(float x) { return __builtin_amdgcn_rsqf(x); }
+// (the three flush a subnormal argument to zero: where one can occur -- crest-factor reduction at a threshold of 0 -- the caller
+// holds the argument at the smallest normal number)
+constexpr float kFltMin = 1.17549435e-38f;
 DEV cf cadd(cf a, cf b) { return mk(a.x + b.x, a.y + b.y); }
 DEV cf csub(cf a, cf b) { return mk(a.x - b.x, a.y - b.y); }
 DEV cf cmul(cf a, cf b) { return mk(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x)); }

@@ -622,9 +622,11 @@ void tf_kernel(const TfArgs a)
             if (KEEP_BEFORE) before[m] = v[m];
             // :320-330, x * sqrt(clip^2 / |x|^2) as x * clip * rsq(|x|^2): one v_rsq_f32 and a select, no branch, no
             // correctly rounded division and square root (twenty-odd instructions each; the factor is good to 1 ulp and
-            // the transforms that follow round more than that)
+            // the transforms that follow round more than that).  v_rsq_f32 flushes a subnormal argument: with a threshold of 0 (or
+            // one whose square underflows) a subnormal |x|^2 is `over`, and 0 * rsq -> 0 * inf would be NaN -- the argument is
+            // held at the smallest normal number, where the factor is still below 1
             const bool over = mag2 > clip2;
-            v[m] = cscale(v[m], over ? fabsf(a.cfr_clip) * fast_rsq(mag2) : 1.0f);
+            v[m] = cscale(v[m], over ? fabsf(a.cfr_clip) * fast_rsq(fmaxf(mag2, kFltMin)) : 1.0f);
             nclip += over ? 1u : 0u;
         }
         if (stats) {
@@ -659,7 +661,7 @@ void tf_kernel(const TfArgs a)
             cf e = csub(refv[m], c);
             const float mag2 = e.x * e.x + e.y * e.y;
             const bool over = mag2 > eclip2;                      // :357-360
-            const float f = over ? fabsf(a.cfr_errclip) * fast_rsq(mag2) : 1.0f;
+            const float f = over ? fabsf(a.cfr_errclip) * fast_rsq(fmaxf(mag2, kFltMin)) : 1.0f;   // (as above)
             neclip += over ? 1u : 0u;
             v[m] = mk(fmaf(e.x, f, c.x), fmaf(e.y, f, c.y));
         }
