@@ -10,7 +10,7 @@ using namespace dabgpu_api;
 static_assert(DABGPU_CH_MAX_PATHS == kChMaxPaths && DABGPU_CH_MAX_DELAY == kChMaxDelay, "the header's limits are the kernel's");
 
 namespace {
-constexpr size_t kHistBytes = (size_t)kChMaxDelay * sizeof(float2);
+constexpr StreamRules kRules{"channel", "n_samples", "samples", nullptr, 0, nullptr};       // (any reset position)
 
 // the refusals that depend on the settings alone (dabgpu_channel_check: no context, no device); nullptr = fine
 const char *settings_refusal(const dabgpu_channel_config *cfg)
@@ -40,14 +40,8 @@ int check_call(dabgpu_ctx *c, const void *in, int in_format, size_t n_samples, c
     if (!c->channel.configured) return fail(c, DABGPU_E_INVALID, "channel: no configuration (no dabgpu_set_channel call yet)");
     if ((in_format != 0 && in_format != DABGPU_FMT_S16) || (out_format != 0 && out_format != DABGPU_FMT_S16))
         return fail(c, DABGPU_E_INVALID, "channel: formats are complexf (0) or DABGPU_FMT_S16");
-    if (!in || !out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (!sample_aligned(in, in_format) || !sample_aligned(out, out_format)) return fail_misaligned(c, "channel");
-    if (n_samples == 0) return fail(c, DABGPU_E_INVALID, "channel: n_samples must not be 0");
-    if (n_samples > ((size_t)1 << 40)) return fail(c, DABGPU_E_INVALID, "channel: n_samples must not exceed 2^40");
-    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + n_samples * sample_bytes(in_format);
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + n_samples * sample_bytes(out_format);
-    if (i0 < o1 && o0 < i1) return fail(c, DABGPU_E_INVALID, "channel: input and output must not overlap");
-    return DABGPU_OK;
+    size_t made;                          // (as many outputs as inputs: the capacity is never short)
+    return check_stream_call(c, c->channel, kRules, in, in_format, n_samples, out, out_format, n_samples, n_samples, &made);
 }
 }  // namespace
 
@@ -88,26 +82,19 @@ int dabgpu_set_channel(dabgpu_ctx *c, const dabgpu_channel_config *cfg)
 int dabgpu_channel_reset(dabgpu_ctx *c, uint64_t position)
 {
     CTXCHK(c);
-    c->channel.zero_pending = true;       // (the next call zeroes the history on its own stream, in front of its kernels)
-    c->channel.position = position;
-    return DABGPU_OK;
+    return stream_reset(c, c->channel, kRules, position);
 }
 
 int dabgpu_get_channel_position(dabgpu_ctx *c, uint64_t *position)
 {
     CTXCHK(c);
-    if (!position) return fail(c, DABGPU_E_INVALID, "null argument");
-    HIPCHK(c, wait_result(c, c->channel.stream));
-    *position = c->channel.position;
-    return DABGPU_OK;
+    return stream_position(c, c->channel, position);
 }
 
 int dabgpu_debug_channel_run_samples(dabgpu_ctx *c, int samples)
 {
     CTXCHK(c);
-    if (samples < 0) return fail(c, DABGPU_E_INVALID, "channel: samples per workgroup must not be negative (0 = chosen)");
-    c->channel.run_samples = samples;
-    return DABGPU_OK;
+    return stream_run_samples(c, c->channel, kRules, samples);
 }
 
 int dabgpu_channel_dev(dabgpu_ctx *c, const void *d_in, int in_format, size_t n_samples, void *d_out, int out_format, void *stream)
@@ -117,28 +104,19 @@ int dabgpu_channel_dev(dabgpu_ctx *c, const void *d_in, int in_format, size_t n_
     if (rc) return rc;
     DevCall call(c, stream);
     if (call.rc) return call.rc;
-    HIPCHK(c, c->channel.hist.reserve(2 * kHistBytes));
-    float2 *cur = (float2 *)((char *)c->channel.hist.p + (size_t)c->channel.hist_cur * kHistBytes);
-    float2 *next = (float2 *)((char *)c->channel.hist.p + (size_t)(c->channel.hist_cur ^ 1) * kHistBytes);
-    if (c->channel.zero_pending) {
-        HIPCHK(c, hipMemsetAsync(cur, 0, kHistBytes, call.s));
-        c->channel.zero_pending = false;
-    }
+    StreamHistory h;
+    if ((rc = h.begin(c, c->channel, kChMaxDelay, call.s))) return rc;
     ChannelArgs a = c->channel.args;
     a.in = d_in;
     a.out = d_out;
-    a.hist = cur;
+    a.hist = h.cur;
     a.n = (long long)n_samples;
     a.position = c->channel.position;
     a.in_fmt = in_format ? 1 : 0;
     a.out_fmt = out_format ? 1 : 0;
     a.run = channel_run(n_samples, c->channel.run_samples);
     HIPCHK(c, launch_channel(a, call.s));
-    HIPCHK(c, launch_channel_history(d_in, a.in_fmt, a.n, cur, next, call.s));
-    c->channel.hist_cur ^= 1;
-    c->channel.position += n_samples;
-    c->channel.stream = call.s;
-    return DABGPU_OK;
+    return h.end(c, c->channel, d_in, in_format, n_samples, kChMaxDelay, call.s);
 }
 
 int dabgpu_channel(dabgpu_ctx *c, const void *in, int in_format, size_t n_samples, void *out, int out_format)
@@ -146,13 +124,10 @@ int dabgpu_channel(dabgpu_ctx *c, const void *in, int in_format, size_t n_sample
     CTXCHK(c);
     int rc = check_call(c, in, in_format, n_samples, out, out_format);
     if (rc) return rc;
-    if ((rc = dabgpu_synchronize(c))) return rc;
-    const size_t out_bytes = n_samples * sample_bytes(out_format);
-    HostIO io(c);
-    if ((rc = io.in(c->channel.in, in, n_samples * sample_bytes(in_format)))) return rc;
-    HIPCHK(c, c->channel.out.reserve(std::max<size_t>(out_bytes, 16)));
-    if ((rc = dabgpu_channel_dev(c, c->channel.in.p, in_format, n_samples, c->channel.out.p, out_format, c->stream))) return rc;
-    return io.out(out, c->channel.out.p, out_bytes);
+    return stream_from_host(c, c->channel, in, n_samples * sample_bytes(in_format), out, n_samples * sample_bytes(out_format),
+                            [&](const void *d_in, void *d_out) {
+                                return dabgpu_channel_dev(c, d_in, in_format, n_samples, d_out, out_format, c->stream);
+                            });
 }
 
 }  // extern "C"

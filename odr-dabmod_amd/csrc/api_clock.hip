@@ -12,9 +12,7 @@ static_assert(DABGPU_CLOCK_TAPS == kClkTaps && DABGPU_CLOCK_PHASES == kClkPhases
               "the header's figures are the kernel's");
 
 namespace {
-constexpr size_t kHistBytes = (size_t)kClkHist * sizeof(float2);
-constexpr unsigned long long kMaxPosition = 1ULL << 62;
-constexpr size_t kMaxCall = (size_t)1 << 40;
+constexpr StreamRules kRules{"clock", "n_in", "outputs", nullptr, 1ULL << 62, "clock: the stream's position must not exceed 2^62"};
 
 const char *ppm_refusal(double ppm)
 {
@@ -51,20 +49,9 @@ int check_call(dabgpu_ctx *c, const void *in, int in_format, size_t n_in, const 
     if (!c->clock.configured) return fail(c, DABGPU_E_INVALID, "clock: no setting (no dabgpu_set_clock call yet)");
     if ((in_format != 0 && in_format != DABGPU_FMT_S16) || (out_format != 0 && out_format != DABGPU_FMT_S16))
         return fail(c, DABGPU_E_INVALID, "clock: formats are complexf (0) or DABGPU_FMT_S16");
-    if (!in || !out || !n_out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (!sample_aligned(in, in_format) || !sample_aligned(out, out_format)) return fail_misaligned(c, "clock");
-    if (n_in == 0) return fail(c, DABGPU_E_INVALID, "clock: n_in must not be 0");
-    if (n_in > kMaxCall) return fail(c, DABGPU_E_INVALID, "clock: n_in must not exceed 2^40");
-    if (c->clock.T + n_in > kMaxPosition) return fail(c, DABGPU_E_INVALID, "clock: the stream's position must not exceed 2^62");
-    *count = count_of(c->clock.step, c->clock.T + n_in) - count_of(c->clock.step, c->clock.T);
-    if (*count > out_cap) {
-        *n_out = (size_t)*count;
-        return fail(c, DABGPU_E_CAPACITY, "clock: output buffer too small");
-    }
-    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + n_in * sample_bytes(in_format);
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)*count * sample_bytes(out_format);
-    if (i0 < o1 && o0 < i1) return fail(c, DABGPU_E_INVALID, "clock: input and output must not overlap");
-    return DABGPU_OK;
+    // (unsigned arithmetic on any n_in: a count the checks below refuse is never used)
+    *count = count_of(c->clock.step, c->clock.position + n_in) - count_of(c->clock.step, c->clock.position);
+    return check_stream_call(c, c->clock, kRules, in, in_format, n_in, out, out_format, *count, out_cap, n_out);
 }
 const char *const kScoEarlyRange = "sco: early must lie inside the cyclic prefix (0 ... sym_size - spacing)";
 
@@ -118,7 +105,7 @@ int dabgpu_clock_count(double ppm, uint64_t T, uint64_t *M)
 {
     if (!M) return fail(nullptr, DABGPU_E_INVALID, "null argument");
     if (const char *why = ppm_refusal(ppm)) return fail(nullptr, DABGPU_E_INVALID, why);
-    if (T > kMaxPosition) return fail(nullptr, DABGPU_E_INVALID, "clock: the stream's position must not exceed 2^62");
+    if (T > kRules.max_position) return fail(nullptr, DABGPU_E_INVALID, kRules.bad_position);
     *M = count_of(step_of(ppm), T);
     return DABGPU_OK;
 }
@@ -153,34 +140,26 @@ int dabgpu_set_clock(dabgpu_ctx *c, double ppm)
     c->clock.step = step_of(ppm);
     c->clock.configured = true;
     c->clock.zero_pending = true;
-    c->clock.T = 0;
+    c->clock.position = 0;
     return DABGPU_OK;
 }
 
 int dabgpu_clock_reset(dabgpu_ctx *c, uint64_t position)
 {
     CTXCHK(c);
-    if (position > kMaxPosition) return fail(c, DABGPU_E_INVALID, "clock: the stream's position must not exceed 2^62");
-    c->clock.zero_pending = true;         // (the next call zeroes the history on its own stream, in front of its kernels)
-    c->clock.T = position;
-    return DABGPU_OK;
+    return stream_reset(c, c->clock, kRules, position);
 }
 
 int dabgpu_get_clock_position(dabgpu_ctx *c, uint64_t *position)
 {
     CTXCHK(c);
-    if (!position) return fail(c, DABGPU_E_INVALID, "null argument");
-    HIPCHK(c, wait_result(c, c->clock.stream));
-    *position = c->clock.T;
-    return DABGPU_OK;
+    return stream_position(c, c->clock, position);
 }
 
 int dabgpu_debug_clock_run_samples(dabgpu_ctx *c, int samples)
 {
     CTXCHK(c);
-    if (samples < 0) return fail(c, DABGPU_E_INVALID, "clock: outputs per workgroup must not be negative (0 = chosen)");
-    c->clock.run_samples = samples;
-    return DABGPU_OK;
+    return stream_run_samples(c, c->clock, kRules, samples);
 }
 
 int dabgpu_clock_dev(dabgpu_ctx *c, const void *d_in, int in_format, size_t n_in, void *d_out, int out_format, size_t out_cap,
@@ -192,22 +171,17 @@ int dabgpu_clock_dev(dabgpu_ctx *c, const void *d_in, int in_format, size_t n_in
     if (rc) return rc;
     DevCall call(c, stream);
     if (call.rc) return call.rc;
-    HIPCHK(c, c->clock.hist.reserve(2 * kHistBytes));
-    float2 *cur = (float2 *)((char *)c->clock.hist.p + (size_t)c->clock.hist_cur * kHistBytes);
-    float2 *next = (float2 *)((char *)c->clock.hist.p + (size_t)(c->clock.hist_cur ^ 1) * kHistBytes);
-    if (c->clock.zero_pending) {
-        HIPCHK(c, hipMemsetAsync(cur, 0, kHistBytes, call.s));
-        c->clock.zero_pending = false;
-    }
+    StreamHistory h;
+    if ((rc = h.begin(c, c->clock, kClkHist, call.s))) return rc;
     if (count) {
         ClockArgs a{};
         a.in = d_in;
         a.out = d_out;
-        a.hist = cur;
+        a.hist = h.cur;
         a.tab = (const float2 *)c->clock.tab.p;
         a.n = (long long)n_in;
-        a.T = c->clock.T;
-        a.m0 = count_of(c->clock.step, c->clock.T);
+        a.T = c->clock.position;
+        a.m0 = count_of(c->clock.step, c->clock.position);
         a.count = (long long)count;
         a.step = c->clock.step;
         a.in_fmt = in_format ? 1 : 0;
@@ -215,10 +189,7 @@ int dabgpu_clock_dev(dabgpu_ctx *c, const void *d_in, int in_format, size_t n_in
         a.run = clock_run((size_t)count, c->clock.run_samples);
         HIPCHK(c, launch_clock(a, call.s));
     }
-    HIPCHK(c, launch_clock_history(d_in, in_format ? 1 : 0, (long long)n_in, cur, next, call.s));
-    c->clock.hist_cur ^= 1;
-    c->clock.T += n_in;
-    c->clock.stream = call.s;
+    if ((rc = h.end(c, c->clock, d_in, in_format, n_in, kClkHist, call.s))) return rc;
     *n_out = (size_t)count;
     return DABGPU_OK;
 }
@@ -229,13 +200,10 @@ int dabgpu_clock(dabgpu_ctx *c, const void *in, int in_format, size_t n_in, void
     unsigned long long count = 0;
     int rc = check_call(c, in, in_format, n_in, out, out_format, out_cap, n_out, &count);
     if (rc) return rc;
-    if ((rc = dabgpu_synchronize(c))) return rc;
-    const size_t out_bytes = (size_t)count * sample_bytes(out_format);
-    HostIO io(c);
-    if ((rc = io.in(c->clock.in, in, n_in * sample_bytes(in_format)))) return rc;
-    HIPCHK(c, c->clock.out.reserve(std::max<size_t>(out_bytes, 16)));
-    if ((rc = dabgpu_clock_dev(c, c->clock.in.p, in_format, n_in, c->clock.out.p, out_format, (size_t)count, n_out, c->stream))) return rc;
-    return io.out(out, c->clock.out.p, out_bytes);
+    return stream_from_host(c, c->clock, in, n_in * sample_bytes(in_format), out, (size_t)count * sample_bytes(out_format),
+                            [&](const void *d_in, void *d_out) {
+                                return dabgpu_clock_dev(c, d_in, in_format, n_in, d_out, out_format, (size_t)count, n_out, c->stream);
+                            });
 }
 
 int dabgpu_sco_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, void *stream)

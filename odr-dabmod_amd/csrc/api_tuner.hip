@@ -14,10 +14,9 @@ static_assert(DABGPU_TUNER_MAX_L == kTunMaxL && DABGPU_TUNER_MAX_TAPS == kTunMax
 
 namespace {
 constexpr uint32_t kNative = 2048000;
-constexpr size_t kHistBytes = (size_t)kTunMaxHist * sizeof(float2);
-constexpr unsigned long long kMaxPosition = 1ULL << 50;
-constexpr size_t kMaxCall = (size_t)1 << 40;
-const char *const kBadPosition = "tuner: the stream's position must not exceed 2^50";
+constexpr StreamRules kRules{"tuner", "n_in", "outputs",
+                             "tuner: buffers must be aligned to a sample (eight bytes complexf, four bytes s16, two bytes u8 / s8)",
+                             1ULL << 50, "tuner: the stream's position must not exceed 2^50"};
 
 struct Ratio {
     int L, M, P;
@@ -100,22 +99,10 @@ int check_call(dabgpu_ctx *c, const void *in, int in_format, size_t n_in, const 
         return fail(c, DABGPU_E_INVALID, "tuner: input format is complexf (0), DABGPU_FMT_S16, DABGPU_FMT_U8 or DABGPU_FMT_S8");
     if (out_format != 0 && out_format != DABGPU_FMT_S16)
         return fail(c, DABGPU_E_INVALID, "tuner: output format is complexf (0) or DABGPU_FMT_S16");
-    if (!in || !out || !n_out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (!sample_aligned(in, in_format) || !sample_aligned(out, out_format))
-        return fail(c, DABGPU_E_INVALID, "tuner: buffers must be aligned to a sample (eight bytes complexf, four bytes s16, two bytes u8 / s8)");
-    if (n_in == 0) return fail(c, DABGPU_E_INVALID, "tuner: n_in must not be 0");
-    if (n_in > kMaxCall) return fail(c, DABGPU_E_INVALID, "tuner: n_in must not exceed 2^40");
-    if (t.T + n_in > kMaxPosition) return fail(c, DABGPU_E_INVALID, kBadPosition);
+    // (unsigned arithmetic on any n_in: a count the checks below refuse is never used)
     const Ratio r{t.L, t.M, t.P, 0.0, 0};
-    *count = count_of(r, t.T + n_in) - count_of(r, t.T);
-    if (*count > out_cap) {
-        *n_out = (size_t)*count;
-        return fail(c, DABGPU_E_CAPACITY, "tuner: output buffer too small");
-    }
-    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + n_in * sample_bytes(in_format);
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)*count * sample_bytes(out_format);
-    if (i0 < o1 && o0 < i1) return fail(c, DABGPU_E_INVALID, "tuner: input and output must not overlap");
-    return DABGPU_OK;
+    *count = count_of(r, t.position + n_in) - count_of(r, t.position);
+    return check_stream_call(c, t, kRules, in, in_format, n_in, out, out_format, *count, out_cap, n_out);
 }
 }  // namespace
 
@@ -153,7 +140,7 @@ int dabgpu_tuner_count(const dabgpu_tuner_config *cfg, uint64_t T, uint64_t *M_o
     Ratio r;
     if (!M_out) return fail(nullptr, DABGPU_E_INVALID, "null argument");
     if (const char *why = resolve(cfg, &r)) return fail(nullptr, DABGPU_E_INVALID, why);
-    if (T > kMaxPosition) return fail(nullptr, DABGPU_E_INVALID, kBadPosition);
+    if (T > kRules.max_position) return fail(nullptr, DABGPU_E_INVALID, kRules.bad_position);
     *M_out = count_of(r, T);
     return DABGPU_OK;
 }
@@ -190,34 +177,26 @@ int dabgpu_set_tuner(dabgpu_ctx *c, const dabgpu_tuner_config *cfg)
     t.step = (unsigned long long)r.step;
     t.configured = true;
     t.zero_pending = true;
-    t.T = 0;
+    t.position = 0;
     return DABGPU_OK;
 }
 
 int dabgpu_tuner_reset(dabgpu_ctx *c, uint64_t position)
 {
     CTXCHK(c);
-    if (position > kMaxPosition) return fail(c, DABGPU_E_INVALID, kBadPosition);
-    c->tuner.zero_pending = true;         // (the next call zeroes the history on its own stream, in front of its kernels)
-    c->tuner.T = position;
-    return DABGPU_OK;
+    return stream_reset(c, c->tuner, kRules, position);
 }
 
 int dabgpu_get_tuner_position(dabgpu_ctx *c, uint64_t *position)
 {
     CTXCHK(c);
-    if (!position) return fail(c, DABGPU_E_INVALID, "null argument");
-    HIPCHK(c, wait_result(c, c->tuner.stream));
-    *position = c->tuner.T;
-    return DABGPU_OK;
+    return stream_position(c, c->tuner, position);
 }
 
 int dabgpu_debug_tuner_run_samples(dabgpu_ctx *c, int samples)
 {
     CTXCHK(c);
-    if (samples < 0) return fail(c, DABGPU_E_INVALID, "tuner: outputs per workgroup must not be negative (0 = chosen)");
-    c->tuner.run_samples = samples;
-    return DABGPU_OK;
+    return stream_run_samples(c, c->tuner, kRules, samples);
 }
 
 int dabgpu_tuner_dev(dabgpu_ctx *c, const void *d_in, int in_format, size_t n_in, void *d_out, int out_format, size_t out_cap,
@@ -230,23 +209,18 @@ int dabgpu_tuner_dev(dabgpu_ctx *c, const void *d_in, int in_format, size_t n_in
     DevCall call(c, stream);
     if (call.rc) return call.rc;
     TunerState &t = c->tuner;
-    HIPCHK(c, t.hist.reserve(2 * kHistBytes));
-    float2 *cur = (float2 *)((char *)t.hist.p + (size_t)t.hist_cur * kHistBytes);
-    float2 *next = (float2 *)((char *)t.hist.p + (size_t)(t.hist_cur ^ 1) * kHistBytes);
-    if (t.zero_pending) {
-        HIPCHK(c, hipMemsetAsync(cur, 0, kHistBytes, call.s));
-        t.zero_pending = false;
-    }
+    StreamHistory h;
+    if ((rc = h.begin(c, t, kTunMaxHist, call.s))) return rc;
     if (count) {
         const Ratio r{t.L, t.M, t.P, 0.0, 0};
         TunerArgs a{};
         a.in = d_in;
         a.out = d_out;
-        a.hist = cur;
+        a.hist = h.cur;
         a.tab = (const float *)t.tab.p;
         a.n = (long long)n_in;
-        a.T = t.T;
-        a.m0 = count_of(r, t.T);
+        a.T = t.position;
+        a.m0 = count_of(r, t.position);
         a.count = (long long)count;
         a.step = t.step;
         a.L = t.L;
@@ -257,10 +231,7 @@ int dabgpu_tuner_dev(dabgpu_ctx *c, const void *d_in, int in_format, size_t n_in
         a.run = tuner_run(t.L, t.M, t.P, t.run_samples);
         HIPCHK(c, launch_tuner(a, call.s));
     }
-    HIPCHK(c, launch_tuner_history(d_in, in_format, (long long)n_in, t.P - 1, cur, next, call.s));
-    t.hist_cur ^= 1;
-    t.T += n_in;
-    t.stream = call.s;
+    if ((rc = h.end(c, t, d_in, in_format, n_in, t.P - 1, call.s))) return rc;
     *n_out = (size_t)count;
     return DABGPU_OK;
 }
@@ -271,13 +242,10 @@ int dabgpu_tuner(dabgpu_ctx *c, const void *in, int in_format, size_t n_in, void
     unsigned long long count = 0;
     int rc = check_call(c, in, in_format, n_in, out, out_format, out_cap, n_out, &count);
     if (rc) return rc;
-    if ((rc = dabgpu_synchronize(c))) return rc;
-    const size_t out_bytes = (size_t)count * sample_bytes(out_format);
-    HostIO io(c);
-    if ((rc = io.in(c->tuner.in, in, n_in * sample_bytes(in_format)))) return rc;
-    HIPCHK(c, c->tuner.out.reserve(std::max<size_t>(out_bytes, 16)));
-    if ((rc = dabgpu_tuner_dev(c, c->tuner.in.p, in_format, n_in, c->tuner.out.p, out_format, (size_t)count, n_out, c->stream))) return rc;
-    return io.out(out, c->tuner.out.p, out_bytes);
+    return stream_from_host(c, c->tuner, in, n_in * sample_bytes(in_format), out, (size_t)count * sample_bytes(out_format),
+                            [&](const void *d_in, void *d_out) {
+                                return dabgpu_tuner_dev(c, d_in, in_format, n_in, d_out, out_format, (size_t)count, n_out, c->stream);
+                            });
 }
 
 }  // extern "C"

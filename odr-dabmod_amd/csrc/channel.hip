@@ -3,8 +3,8 @@
 // has no such stage.  Every output sample is a function of its absolute index a = position + i alone -- the phase is the
 // integer phase of sync.hip's extraction (nothing accumulates), the noise is Philox4x32-10 on the counter a >> 1 -- so a stream
 // cut into calls of any lengths, at any run geometry, gives the same bytes.  No atomics, no LDS.
-// Two kernels: the samples (a lane makes kChLane consecutive ones; the shifted reads x[a - d] go straight to memory, contiguous
-// per path and eight-byte aligned only) and the 2047 samples of history the next call reads.  The path table travels in the
+// A lane makes kChLane consecutive samples; the shifted reads x[a - d] go straight to memory, contiguous per path and eight-byte
+// aligned only.  The 2047 samples of history the next call reads are stream_history.hip's.  The path table travels in the
 // kernel arguments: uniform loads, and a new configuration is ordered behind the calls queued before it with nothing to copy.
 #include "device_common.h"
 #include "turn_phase.h"
@@ -43,7 +43,7 @@ DEV cf gauss_pair(uint32_t wa, uint32_t wb)
 // sample j of the call, j >= -kChMaxDelay: the input, or the history in front of it
 template <int IF> DEV cf ld_x(const ChannelArgs &a, long long j)
 {
-    if (j >= 0) return ld_iq(a.in, IF, j);
+    if (j >= 0) return load_sample<IF>(a.in, j);
     return a.hist[kChMaxDelay + j];
 }
 
@@ -113,15 +113,11 @@ template <int IF, int OF> __global__ __launch_bounds__(256) void channel_kernel(
                     if (on[k]) out[k] = y[k];
             }
         } else {
-            // format_kernel's conversion (format_one: saturating, toward zero), without the clip count
             uint32_t *out = reinterpret_cast<uint32_t *>(a.out) + i0;
             unsigned unused = 0;
             uint32_t v[kChLane];
 #pragma unroll
-            for (int k = 0; k < kChLane; ++k) {
-                const int re = format_one<1>(y[k].x, unused), im = format_one<1>(y[k].y, unused);
-                v[k] = (unsigned)(re & 0xffff) | ((unsigned)im << 16);
-            }
+            for (int k = 0; k < kChLane; ++k) v[k] = s16_pair<unsigned &>(y[k].x, y[k].y, unused);
             if (on[kChLane - 1] && ((uintptr_t)out & 15u) == 0) {
                 reinterpret_cast<uint4 *>(out)[0] = make_uint4(v[0], v[1], v[2], v[3]);
             } else {
@@ -131,15 +127,6 @@ template <int IF, int OF> __global__ __launch_bounds__(256) void channel_kernel(
             }
         }
     }
-}
-
-template <int IF> __global__ __launch_bounds__(256)
-void channel_history_kernel(const void *in, long long n, const float2 *__restrict__ cur, float2 *__restrict__ next)
-{
-    const int j = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (j >= kChMaxDelay) return;
-    const long long r = n - kChMaxDelay + j;                            // (n >= 1: r < 0 reads cur[n + j], n + j < kChMaxDelay)
-    next[j] = r >= 0 ? ld_iq(in, IF, r) : cur[kChMaxDelay + r];
 }
 
 constexpr int kChMaxRun = 8 * kChTile;
@@ -169,15 +156,6 @@ hipError_t launch_channel(const ChannelArgs &a, hipStream_t s)
     else if (a.in_fmt == 0) DABGPU_LAUNCH((channel_kernel<0, 1>), grid, block, 0, s, a);
     else if (a.out_fmt == 0) DABGPU_LAUNCH((channel_kernel<1, 0>), grid, block, 0, s, a);
     else DABGPU_LAUNCH((channel_kernel<1, 1>), grid, block, 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_channel_history(const void *in, int in_fmt, long long n, const float2 *cur, float2 *next, hipStream_t s)
-{
-    if (!in || !cur || !next || cur == next || n < 1 || (in_fmt != 0 && in_fmt != 1)) return hipErrorInvalidValue;
-    const dim3 grid((kChMaxDelay + 255) / 256), block(256);
-    if (in_fmt == 0) DABGPU_LAUNCH(channel_history_kernel<0>, grid, block, 0, s, in, n, cur, next);
-    else DABGPU_LAUNCH(channel_history_kernel<1>, grid, block, 0, s, in, n, cur, next);
     return hipGetLastError();
 }
 

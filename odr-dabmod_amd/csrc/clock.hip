@@ -3,8 +3,8 @@
 // clock".  The reference has no such stage.  Output m of the resampler is a function of its absolute index alone -- the input
 // position m + floor(m step / 2^64) and the fraction behind it come from one 64 x 64-bit product, nothing accumulates -- so a
 // stream cut into calls of any lengths, at any run geometry, gives the same bytes.
-// Its two kernels: the samples and the 31 samples of history the next call reads.  A workgroup makes `run` consecutive outputs:
-// their input span (run + run / 999 + 33 samples at most, the rate is that near 1) is staged in LDS as floats, then lane l
+// The 31 samples of history the next call reads are stream_history.hip's.  A workgroup makes `run` consecutive outputs: their
+// input span (run + run / 999 + 33 samples at most, the rate is that near 1) is staged in LDS as floats, then lane l
 // makes outputs l, l + 256, ...: consecutive lanes read consecutive LDS words whatever the slip does, which therefore costs
 // nothing -- an output's offset into the span is computed, never branched on.  The tap table stays in global memory (512 rows
 // of pairs (T[p][j], T[p + 1][j] - T[p][j]), 128 KB: L2 and the vector cache hold it), one 16-byte load per two taps; the
@@ -42,7 +42,7 @@ template <int IF, int OF> __global__ __launch_bounds__(256) void clock_kernel(co
         const long long r = r0 + t;
         cf v = mk(0.f, 0.f);
         if (r >= 0) {
-            if (r < a.n) v = ld_iq(a.in, IF, r);
+            if (r < a.n) v = load_sample<IF>(a.in, r);
         } else if (r >= -kClkHist) {
             v = a.hist[kClkHist + r];
         }
@@ -67,24 +67,8 @@ template <int IF, int OF> __global__ __launch_bounds__(256) void clock_kernel(co
             re = fmaf(h1, x1.x, re);
             im = fmaf(h1, x1.y, im);
         }
-        if (OF == 0) {
-            reinterpret_cast<float2 *>(a.out)[k0 + k] = mk(re, im);
-        } else {
-            // format_kernel's conversion (format_one: saturating, toward zero), without the clip count
-            unsigned unused = 0;
-            const int qr = format_one<1>(re, unused), qi = format_one<1>(im, unused);
-            reinterpret_cast<uint32_t *>(a.out)[k0 + k] = (unsigned)(qr & 0xffff) | ((unsigned)qi << 16);
-        }
+        store_sample<OF>(a.out, k0 + k, re, im);
     }
-}
-
-template <int IF> __global__ __launch_bounds__(64)
-void clock_history_kernel(const void *in, long long n, const float2 *__restrict__ cur, float2 *__restrict__ next)
-{
-    const int j = (int)threadIdx.x;
-    if (j >= kClkHist) return;
-    const long long r = n - kClkHist + j;                               // (n >= 1: r < 0 reads cur[n + j], n + j < kClkHist)
-    next[j] = r >= 0 ? ld_iq(in, IF, r) : cur[kClkHist + r];
 }
 
 // ---- the estimator.  demod.hip's geometry: one workgroup of N/8 lanes per run of data symbols, eight samples per lane, the
@@ -224,15 +208,6 @@ hipError_t launch_clock(const ClockArgs &a, hipStream_t s)
     else if (a.in_fmt == 0) DABGPU_LAUNCH((clock_kernel<0, 1>), grid, block, 0, s, a);
     else if (a.out_fmt == 0) DABGPU_LAUNCH((clock_kernel<1, 0>), grid, block, 0, s, a);
     else DABGPU_LAUNCH((clock_kernel<1, 1>), grid, block, 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_clock_history(const void *in, int in_fmt, long long n, const float2 *cur, float2 *next, hipStream_t s)
-{
-    if (!in || !cur || !next || cur == next || n < 1 || (in_fmt != 0 && in_fmt != 1)) return hipErrorInvalidValue;
-    const dim3 grid(1), block(64);
-    if (in_fmt == 0) DABGPU_LAUNCH(clock_history_kernel<0>, grid, block, 0, s, in, n, cur, next);
-    else DABGPU_LAUNCH(clock_history_kernel<1>, grid, block, 0, s, in, n, cur, next);
     return hipGetLastError();
 }
 

@@ -33,9 +33,10 @@
 //                     result and the bootstrap frame (host only); the decoder configured from a result
 //   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
 //                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
-// In this order: Settings, TraceScope; the receive-side stages' state, one struct each; dabgpu_ctx with one member of each
-// beside the chain's own; what the translation units export to each other; what entry points are built from (HostIO ...
-// capture_from_host).  Device memory is DevBuf's (devbuf.h): a context's buffers free themselves when it is deleted.
+// In this order: Settings, TraceScope; the receive-side stages' state, one struct each (the streamed stages' on StreamStage);
+// dabgpu_ctx with one member of each beside the chain's own; what the translation units export to each other; what entry
+// points are built from (HostIO ... capture_from_host for the capture stages, StreamRules ... stream_run_samples for the
+// streamed ones).  Device memory is DevBuf's (devbuf.h): a context's buffers free themselves when it is deleted.
 #pragma once
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
@@ -197,32 +198,32 @@ struct SyncState {
     hipStream_t stream = nullptr;
 };
 
-// The channel emulator (api_channel.hip, channel.hip).  hist: two histories of kChMaxDelay float samples, the stream state;
-// hist_cur: the one the next call reads (a call writes the other and swaps).  zero_pending: the next call zeroes it first
-// (after dabgpu_channel_reset, and before the first call).  position: samples the stream has taken.  args: the installed
-// configuration as the kernel takes it (paths that do not rotate first, either group in the given order).
-struct ChannelState {
+// What the streamed stages share (channel emulator, clock's resampler, tuner): a call takes the next n samples of a stream and
+// reads a few samples of history in front of them.  hist: two histories of float samples, the stream state (kChMaxDelay,
+// kClkHist, kTunMaxHist samples each); hist_cur: the one the next call reads (a call writes the other and swaps).
+// zero_pending: the next call zeroes it first (before the first call, after the stage's setter -- the channel's keeps the
+// stream -- and after its reset).  position: input samples the stream has taken (the reset's position included).  in, out:
+// the host-pointer entry's staging.  run_samples: dabgpu_debug_*_run_samples, samples or outputs per workgroup, 0 = chosen.
+struct StreamStage {
     DevBuf hist, in, out;
-    dabgpu::ChannelArgs args{};
     bool configured = false, zero_pending = true;
     int hist_cur = 0;
     unsigned long long position = 0;
     hipStream_t stream = nullptr;
-    int run_samples = 0;                  // dabgpu_debug_channel_run_samples: samples per workgroup, 0 = by the call size
+    int run_samples = 0;
 };
 
-// The clock's resampler (api_clock.hip, clock.hip).  hist: two histories of kClkHist float samples, the stream state;
-// hist_cur: the one the next call reads (a call writes the other and swaps).  zero_pending: the next call zeroes it first
-// (after dabgpu_set_clock and dabgpu_clock_reset).  T: input samples the stream has taken (the reset's position included).
-// step: the installed offset as the kernel takes it.  tab: the tap table, uploaded by the first dabgpu_set_clock.
-struct ClockState {
-    DevBuf hist, tab, in, out;
-    bool configured = false, zero_pending = true;
-    int hist_cur = 0;
-    unsigned long long T = 0;
+// The channel emulator (api_channel.hip, channel.hip).  args: the installed configuration as the kernel takes it (paths that
+// do not rotate first, either group in the given order).
+struct ChannelState : StreamStage {
+    dabgpu::ChannelArgs args{};
+};
+
+// The clock's resampler (api_clock.hip, clock.hip).  step: the installed offset as the kernel takes it.  tab: the tap table,
+// uploaded by the first dabgpu_set_clock.
+struct ClockState : StreamStage {
+    DevBuf tab;
     long long step = 0;
-    hipStream_t stream = nullptr;
-    int run_samples = 0;                  // dabgpu_debug_clock_run_samples: outputs per workgroup, 0 = the default
 };
 
 // The clock's estimator (api_clock.hip, clock.hip).  rows: every block's sums (scratch); sums: the frames' sums of the most
@@ -233,22 +234,16 @@ struct ScoState {
     hipStream_t stream = nullptr;
 };
 
-// The tuner (api_tuner.hip, tuner.hip).  hist: two histories of kTunMaxHist float samples (the first P - 1 in use), the stream
-// state; hist_cur: the one the next call reads (a call writes the other and swaps).  zero_pending: the next call zeroes it
-// first (after dabgpu_set_tuner and dabgpu_tuner_reset).  T: input samples the stream has taken (the reset's position
-// included).  cfg, L, M, P, step: the installed setting and what follows from it.  tab: the tap table [L][P] of (tab_rate,
-// tab_selectivity), uploaded by the dabgpu_set_tuner that changes either.
-struct TunerState {
-    DevBuf hist, tab, in, out;
-    bool configured = false, zero_pending = true;
-    int hist_cur = 0;
-    unsigned long long T = 0, step = 0;
+// The tuner (api_tuner.hip, tuner.hip).  Of a history's kTunMaxHist samples the first P - 1 are in use.  cfg, L, M, P, step: the
+// installed setting and what follows from it.  tab: the tap table [L][P] of (tab_rate, tab_selectivity), uploaded by the
+// dabgpu_set_tuner that changes either.
+struct TunerState : StreamStage {
+    DevBuf tab;
+    unsigned long long step = 0;
     dabgpu_tuner_config cfg{};
     int L = 1, M = 1, P = 32;
     uint32_t tab_rate = 0;
     int tab_selectivity = -1;
-    hipStream_t stream = nullptr;
-    int run_samples = 0;                  // dabgpu_debug_tuner_run_samples: outputs per workgroup, 0 = chosen
 };
 
 // The TII analyser (api_tii_scan.hip, tii_scan.hip).  result: head, 24 entry slots and the entries' grid centres of the most
@@ -663,6 +658,105 @@ template <typename DevEntry> int capture_from_host(dabgpu_ctx *c, DevBuf &stagin
     if ((rc = io.in(staging, capture, bytes))) return rc;
     if ((rc = dev(staging.p))) return rc;
     return io.out(nullptr, nullptr, 0);
+}
+
+// ---- what the entry points of the streamed stages (StreamStage) are built from.  What differs between them in a refusal:
+struct StreamRules {
+    const char *stage;                    // starts the messages
+    const char *n_name;                   // the call's sample count in the header: n_samples, n_in
+    const char *unit;                     // what dabgpu_debug_*_run_samples counts per workgroup: samples, outputs
+    const char *misaligned;               // the stage's own alignment refusal; nullptr: fail_misaligned's
+    unsigned long long max_position;      // the stream's position at most; 0: any
+    const char *bad_position;             // ... and its refusal
+};
+
+// A call's buffers, after the stage's own lines (configured, formats), in this order: not null, aligned to a sample, n not 0
+// and at most 2^40, the position bound, the capacity (*n_out = count first: what the caller has to offer), no overlap.
+// count: the outputs the call makes (the channel's: n, with out_cap = n and an n_out of its own).
+inline int check_stream_call(dabgpu_ctx *c, const StreamStage &st, const StreamRules &r, const void *in, int in_format, size_t n,
+                             const void *out, int out_format, unsigned long long count, size_t out_cap, size_t *n_out)
+{
+    const std::string stage = std::string(r.stage) + ": ";
+    if (!in || !out || !n_out) return fail(c, DABGPU_E_INVALID, "null argument");
+    if (!sample_aligned(in, in_format) || !sample_aligned(out, out_format))
+        return r.misaligned ? fail(c, DABGPU_E_INVALID, r.misaligned) : fail_misaligned(c, r.stage);
+    if (n == 0) return fail(c, DABGPU_E_INVALID, stage + r.n_name + " must not be 0");
+    if (n > ((size_t)1 << 40)) return fail(c, DABGPU_E_INVALID, stage + r.n_name + " must not exceed 2^40");
+    if (r.max_position && st.position + n > r.max_position) return fail(c, DABGPU_E_INVALID, r.bad_position);
+    if (count > out_cap) {
+        *n_out = (size_t)count;
+        return fail(c, DABGPU_E_CAPACITY, stage + "output buffer too small");
+    }
+    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + n * sample_bytes(in_format);
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)count * sample_bytes(out_format);
+    if (i0 < o1 && o0 < i1) return fail(c, DABGPU_E_INVALID, stage + "input and output must not overlap");
+    return DABGPU_OK;
+}
+
+// The history hand-over of a streamed _dev call on stream s.  begin, in front of the stage's kernels: the two histories of
+// `capacity` samples, cur (what this call reads, zeroed first where that is pending) and next.  end, behind them: the call's
+// last H <= capacity inputs into next, which the next call reads; the position moves on; the result is complete on s.
+struct StreamHistory {
+    float2 *cur = nullptr, *next = nullptr;
+    int capacity = 0;
+    int begin(dabgpu_ctx *c, StreamStage &st, int capacity_, hipStream_t s)
+    {
+        capacity = capacity_;
+        const size_t bytes = (size_t)capacity * sizeof(float2);
+        HIPCHK(c, st.hist.reserve(2 * bytes));
+        cur = (float2 *)((char *)st.hist.p + (size_t)st.hist_cur * bytes);
+        next = (float2 *)((char *)st.hist.p + (size_t)(st.hist_cur ^ 1) * bytes);
+        if (st.zero_pending) {
+            HIPCHK(c, hipMemsetAsync(cur, 0, bytes, s));
+            st.zero_pending = false;
+        }
+        return DABGPU_OK;
+    }
+    int end(dabgpu_ctx *c, StreamStage &st, const void *d_in, int in_format, size_t n, int H, hipStream_t s)
+    {
+        HIPCHK(c, H <= capacity ? launch_stream_history(d_in, in_format, (long long)n, H, cur, next, s) : hipErrorInvalidValue);
+        st.hist_cur ^= 1;
+        st.position += n;
+        st.stream = s;
+        return DABGPU_OK;
+    }
+};
+
+// The host-pointer form of a streamed stage, after its checks: the context idle, the input in st.in, room for the output in
+// st.out, the stage's _dev entry on the context's stream (dev(d_in, d_out) -> rc), the output copied out and complete.
+template <typename DevEntry>
+int stream_from_host(dabgpu_ctx *c, StreamStage &st, const void *in, size_t in_bytes, void *out, size_t out_bytes, DevEntry dev)
+{
+    int rc = dabgpu_synchronize(c);
+    if (rc) return rc;
+    HostIO io(c);
+    if ((rc = io.in(st.in, in, in_bytes))) return rc;
+    HIPCHK(c, st.out.reserve(std::max<size_t>(out_bytes, 16)));
+    if ((rc = dev(st.in.p, st.out.p))) return rc;
+    return io.out(out, st.out.p, out_bytes);
+}
+
+// the bodies of dabgpu_*_reset, dabgpu_get_*_position and dabgpu_debug_*_run_samples, behind the entry's CTXCHK
+inline int stream_reset(dabgpu_ctx *c, StreamStage &st, const StreamRules &r, uint64_t position)
+{
+    if (r.max_position && position > r.max_position) return fail(c, DABGPU_E_INVALID, r.bad_position);
+    st.zero_pending = true;               // (the next call zeroes the history on its own stream, in front of its kernels)
+    st.position = position;
+    return DABGPU_OK;
+}
+inline int stream_position(dabgpu_ctx *c, const StreamStage &st, uint64_t *position)
+{
+    if (!position) return fail(c, DABGPU_E_INVALID, "null argument");
+    HIPCHK(c, wait_result(c, st.stream));
+    *position = st.position;
+    return DABGPU_OK;
+}
+inline int stream_run_samples(dabgpu_ctx *c, StreamStage &st, const StreamRules &r, int samples)
+{
+    if (samples < 0)
+        return fail(c, DABGPU_E_INVALID, std::string(r.stage) + ": " + r.unit + " per workgroup must not be negative (0 = chosen)");
+    st.run_samples = samples;
+    return DABGPU_OK;
 }
 
 }  // namespace dabgpu_api

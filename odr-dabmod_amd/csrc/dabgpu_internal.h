@@ -238,8 +238,6 @@ struct ChannelArgs {                      // by value in the kernel arguments: a
 };
 int channel_run(size_t n, int forced);
 hipError_t launch_channel(const ChannelArgs &a, hipStream_t s);
-// the history behind a call: next[j] = sample n - kChMaxDelay + j of the call, from `in` or (calls shorter than it) from `cur`
-hipError_t launch_channel_history(const void *in, int in_fmt, long long n, const float2 *cur, float2 *next, hipStream_t s);
 // clock.hip: the clock's resampler (dabgpu_clock*): a sampling-clock offset put on a sample stream, or taken off it
 constexpr int kClkTaps = 32;              // taps of the interpolator, tap kClkCentre on the input position
 constexpr int kClkCentre = 15;
@@ -262,8 +260,6 @@ struct ClockArgs {
 };
 int clock_run(size_t count, int forced);
 hipError_t launch_clock(const ClockArgs &a, hipStream_t s);
-// the history behind a call: next[j] = sample n - kClkHist + j of the call, from `in` or (calls shorter than it) from `cur`
-hipError_t launch_clock_history(const void *in, int in_fmt, long long n, const float2 *cur, float2 *next, hipStream_t s);
 // clock.hip, the estimator (dabgpu_sco*): per data block of whole frames the sums of e = d conj(c) over either half of the
 // carriers and of |e|, in the receiver's geometry (demod_runs); then the blocks of a frame in index order
 constexpr int kScoSums = 5;               // Re A_hi, Im A_hi, Re A_lo, Im A_lo, S
@@ -303,8 +299,11 @@ struct TunerArgs {
 int tuner_run_max(int L, int M, int P);
 int tuner_run(int L, int M, int P, int forced);
 hipError_t launch_tuner(const TunerArgs &a, hipStream_t s);
-// the history behind a call: next[j] = sample n - H + j of the call (H = P - 1), from `in` or (calls shorter than H) from `cur`
-hipError_t launch_tuner_history(const void *in, int in_fmt, long long n, int H, const float2 *cur, float2 *next, hipStream_t s);
+// stream_history.hip: the history behind a call of the three stages above (H = kChMaxDelay, kClkHist, the tuner's P - 1):
+// next[j] = sample n - H + j of the call, in_fmt 0 ... 3 as TunerArgs, from `in` or (calls shorter than H) from `cur`
+constexpr int kStreamMaxHist = kChMaxDelay;
+static_assert(kClkHist <= kStreamMaxHist && kTunMaxHist <= kStreamMaxHist, "the largest history in use");
+hipError_t launch_stream_history(const void *in, int in_fmt, long long n, int H, const float2 *cur, float2 *next, hipStream_t s);
 // tii_scan.hip: the TII analyser (dabgpu_tii_scan*): which (comb, pattern) the null symbols of whole frames carry, the level
 // and the delay of every comb
 constexpr int kTiiCombs = 24;             // combs, and entry slots of a result

@@ -11,19 +11,13 @@
 // integer atomics, LDS first, one global 64-bit add per bin and figure and workgroup): the same bits for every repetition and
 // every tile size.  tx is complexf or s16 pairs (the chain writes both), rx is complexf.
 #include "device_common.h"
+#include "turn_phase.h"     // load_sample
 
 namespace dabgpu {
 namespace {
 
 typedef Fft<11> SF;
 static_assert(SF::N == SPECTRUM_NFFT && SF::T == 256, "2048 points on 256 lanes");
-
-template <int FMT> DEV cf dpd_load_tx(const void *base, size_t i)
-{
-    if (FMT == 0) return reinterpret_cast<const float2 *>(base)[i];
-    const uint32_t w = reinterpret_cast<const uint32_t *>(base)[i];                        // re in the low half
-    return mk((float)(short)(w & 0xffffu), (float)(short)(w >> 16));
-}
 
 // One workgroup = one run of consecutive segments, as in spectrum_kernel; run segment s is segment a.seg_first + s of the
 // buffers.  Lane t holds samples t + 256 m of the current segment of either buffer; the second half of a segment is the first
@@ -48,7 +42,7 @@ template <int FMT> __global__ __launch_bounds__(SF::T) void dpd_xspectrum_kernel
     cf xt[8], xr[8];
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        xt[4 + m] = dpd_load_tx<FMT>(a.tx, tbase + T * m);
+        xt[4 + m] = load_sample<FMT>(a.tx, tbase + T * m);
         xr[4 + m] = a.rx[rbase + T * m];
     }
 
@@ -62,7 +56,7 @@ template <int FMT> __global__ __launch_bounds__(SF::T) void dpd_xspectrum_kernel
         for (int m = 0; m < 4; ++m) {
             xt[m] = xt[4 + m];
             xr[m] = xr[4 + m];
-            xt[4 + m] = dpd_load_tx<FMT>(a.tx, tbase + half + T * m);
+            xt[4 + m] = load_sample<FMT>(a.tx, tbase + half + T * m);
             xr[4 + m] = a.rx[rbase + half + T * m];
         }
         cf u[8], v[8];
@@ -135,7 +129,7 @@ template <int FMT> __global__ __launch_bounds__(256) void dpd_stats_kernel(DpdSt
     for (int j = t; j < a.tile; j += 256) {
         const long long i = base + j;
         if (i < a.i_first || i >= a.i_end) continue;
-        const cf x = dpd_load_tx<FMT>(a.tx, (size_t)i);
+        const cf x = load_sample<FMT>(a.tx, (size_t)i);
         float sr = 0.f, si = 0.f;
 #pragma unroll
         for (int q = 0; q < DPD_TAPS; ++q) {

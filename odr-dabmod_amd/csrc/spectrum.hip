@@ -5,25 +5,13 @@
 // one row of 2048 partial sums per workgroup, spectrum_reduce_kernel adds the rows in workgroup order.  No floating-point
 // atomics: the result is a function of input, window and run geometry alone.
 #include "device_common.h"
+#include "turn_phase.h"     // load_sample
 
 namespace dabgpu {
 namespace {
 
 typedef Fft<11> SF;
 static_assert(SF::N == SPECTRUM_NFFT && SF::T == 256, "2048 points on 256 lanes");
-
-// one sample of format FMT (0 = complexf, 1 = s16 pair, 2 = u8 pair: byte - 128, 3 = s8 pair) as fp32
-template <int FMT> DEV cf spectrum_load(const void *base, size_t i)
-{
-    if (FMT == 0) return reinterpret_cast<const float2 *>(base)[i];
-    if (FMT == 1) {
-        const uint32_t w = reinterpret_cast<const uint32_t *>(base)[i];                    // re in the low half
-        return mk((float)(short)(w & 0xffffu), (float)(short)(w >> 16));
-    }
-    const unsigned w = reinterpret_cast<const uint16_t *>(base)[i];                         // re in the low byte
-    if (FMT == 2) return mk((float)((int)(w & 0xffu) - 128), (float)((int)(w >> 8) - 128));
-    return mk((float)(signed char)(w & 0xffu), (float)(signed char)(w >> 8));
-}
 
 // One workgroup = one RUN of consecutive segments (a.segs_per_run of them; the last run may be shorter).  Segment i is
 // samples 1024 i ... 1024 i + 2047; lane t holds the raw samples x[t + 256 m] of the current segment in raw[m].  The next
@@ -50,8 +38,8 @@ template <int FMT> __global__ __launch_bounds__(SF::T) void spectrum_kernel(Spec
     const size_t first = (size_t)s0 * HOP + (size_t)t;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        raw[4 + m] = spectrum_load<FMT>(a.iq, first + T * m);                                // the first half of segment s0
-        nxt[m] = spectrum_load<FMT>(a.iq, first + HOP + T * m);                              // ... and its second half
+        raw[4 + m] = load_sample<FMT>(a.iq, first + T * m);                                // the first half of segment s0
+        nxt[m] = load_sample<FMT>(a.iq, first + HOP + T * m);                              // ... and its second half
     }
 
     double acc[8];
@@ -70,7 +58,7 @@ template <int FMT> __global__ __launch_bounds__(SF::T) void spectrum_kernel(Spec
         if (s + 1 < s1) {
             const size_t half = (size_t)(s + 2) * HOP + (size_t)t;
 #pragma unroll
-            for (int m = 0; m < 4; ++m) nxt[m] = spectrum_load<FMT>(a.iq, half + T * m);
+            for (int m = 0; m < 4; ++m) nxt[m] = load_sample<FMT>(a.iq, half + T * m);
         }
 #pragma unroll
         for (int m = 0; m < 8; ++m) v[m] = mk(raw[m].x * w[m], raw[m].y * w[m]);

@@ -15,25 +15,12 @@
 //     in global memory, one 16-byte load per four taps and output; the span is staged in input order and output k reads it
 //     from floor((p0 + k M) / L) on: 32 consecutive lanes cover 32 M / L consecutive samples, a conflict of degree ceil(M / L)
 //     at most (2 at 64/75).  Two outputs per lane.
-// A third kernel writes the P - 1 samples of history the next call reads.  No atomics, no scratch.
+// The P - 1 samples of history the next call reads are stream_history.hip's.  No atomics, no scratch.
 #include "device_common.h"
 #include "turn_phase.h"
 
 namespace dabgpu {
 namespace {
-
-// one sample of format FMT (0 = complexf, 1 = s16 pair, 2 = u8 pair: byte - 128, 3 = s8 pair) as fp32: spectrum.hip's load
-template <int FMT> DEV cf tuner_load(const void *base, long long i)
-{
-    if (FMT == 0) return reinterpret_cast<const float2 *>(base)[i];
-    if (FMT == 1) {
-        const uint32_t w = reinterpret_cast<const uint32_t *>(base)[i];                    // re in the low half
-        return mk((float)(short)(w & 0xffffu), (float)(short)(w >> 16));
-    }
-    const unsigned w = reinterpret_cast<const uint16_t *>(base)[i];                         // re in the low byte
-    if (FMT == 2) return mk((float)((int)(w & 0xffu) - 128), (float)((int)(w >> 8) - 128));
-    return mk((float)(signed char)(w & 0xffu), (float)(signed char)(w >> 8));
-}
 
 // input sample r of the call (r < 0: the history, zero in front of it; r >= n is asked for by no output), mixed by the phase
 // of its absolute index T + r.  step = 0: the sample's bits.
@@ -42,7 +29,7 @@ template <int IF> DEV cf tuner_sample(const TunerArgs &a, long long r)
     const int H = a.P - 1;
     cf v = mk(0.f, 0.f);
     if (r >= 0) {
-        if (r < a.n) v = tuner_load<IF>(a.in, r);
+        if (r < a.n) v = load_sample<IF>(a.in, r);
     } else if (r >= -(long long)H) {
         v = a.hist[H + r];
     }
@@ -51,18 +38,6 @@ template <int IF> DEV cf tuner_sample(const TunerArgs &a, long long r)
         v = mk(fmaf(v.x, w.x, -__fmul_rn(v.y, w.y)), fmaf(v.x, w.y, __fmul_rn(v.y, w.x)));
     }
     return v;
-}
-
-template <int OF> DEV void tuner_store(void *out, long long at, float re, float im)
-{
-    if (OF == 0) {
-        reinterpret_cast<float2 *>(out)[at] = mk(re, im);
-    } else {
-        // format_kernel's conversion (format_one: saturating, toward zero), without the clip count
-        unsigned unused = 0;
-        const int qr = format_one<1>(re, unused), qi = format_one<1>(im, unused);
-        reinterpret_cast<uint32_t *>(out)[at] = (unsigned)(qr & 0xffff) | ((unsigned)qi << 16);
-    }
 }
 
 constexpr int kDecOut = 4, kRatOut = 2;   // outputs a lane makes at a time
@@ -121,7 +96,7 @@ template <int IF, int OF> __global__ __launch_bounds__(256) void tuner_dec_kerne
 #pragma unroll
         for (int u = 0; u < kDecOut; ++u) {
             const int ku = kb + (int)threadIdx.x + 256 * u;
-            if (ku < cnt) tuner_store<OF>(a.out, k0 + ku, re[u], im[u]);
+            if (ku < cnt) store_sample<OF>(a.out, k0 + ku, re[u], im[u]);
         }
     }
 }
@@ -171,18 +146,9 @@ template <int IF, int OF> __global__ __launch_bounds__(256) void tuner_rat_kerne
 #pragma unroll
         for (int u = 0; u < kRatOut; ++u) {
             const int ku = kb + (int)threadIdx.x + 256 * u;
-            if (ku < cnt) tuner_store<OF>(a.out, k0 + ku, re[u], im[u]);
+            if (ku < cnt) store_sample<OF>(a.out, k0 + ku, re[u], im[u]);
         }
     }
-}
-
-template <int IF> __global__ __launch_bounds__(256)
-void tuner_history_kernel(const void *in, long long n, int H, const float2 *__restrict__ cur, float2 *__restrict__ next)
-{
-    const int j = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (j >= H) return;
-    const long long r = n - H + j;                                      // (n >= 1: r < 0 reads cur[n + j], n + j < H)
-    next[j] = r >= 0 ? tuner_load<IF>(in, r) : cur[H + r];
 }
 
 template <int IF, int OF> void launch_one(const TunerArgs &a, dim3 grid, hipStream_t s)
@@ -238,19 +204,6 @@ hipError_t launch_tuner(const TunerArgs &a, hipStream_t s)
     case 1: launch_in<1>(a, grid, s); break;
     case 2: launch_in<2>(a, grid, s); break;
     default: launch_in<3>(a, grid, s); break;
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_tuner_history(const void *in, int in_fmt, long long n, int H, const float2 *cur, float2 *next, hipStream_t s)
-{
-    if (!in || !cur || !next || cur == next || n < 1 || in_fmt < 0 || in_fmt > 3 || H < 1 || H > kTunMaxHist) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((H + 255) / 256)), block(256);
-    switch (in_fmt) {
-    case 0: DABGPU_LAUNCH(tuner_history_kernel<0>, grid, block, 0, s, in, n, H, cur, next); break;
-    case 1: DABGPU_LAUNCH(tuner_history_kernel<1>, grid, block, 0, s, in, n, H, cur, next); break;
-    case 2: DABGPU_LAUNCH(tuner_history_kernel<2>, grid, block, 0, s, in, n, H, cur, next); break;
-    default: DABGPU_LAUNCH(tuner_history_kernel<3>, grid, block, 0, s, in, n, H, cur, next); break;
     }
     return hipGetLastError();
 }

@@ -155,6 +155,13 @@ def test_any_chunking_and_run_geometry_gives_the_bytes_and_counts_of_one_call(md
             assert np.array_equal(got.view(np.uint32), whole0.view(np.uint32)) and sum(counts) == counts0[0], run
             got, _ = _run(md, pkg, q, KC.splits(step)["sevens"], position=position, alternate=True)
             assert np.array_equal(got.view(np.uint32), whole_q.view(np.uint32)), (run, "alternating formats")
+        # the history is handed over by one kernel for every input format: each of them cut into sevens (every call shorter
+        # than the history) and at [1, n - 1], at one run geometry
+        md.set_clock_run_samples(0)
+        for fmt, stream, want in (("complexf", x, whole), ("s16", q, whole_q)):
+            for name in ("sevens", "one_rest"):
+                got, _ = _run(md, pkg, stream, KC.splits(step)[name], position=position)
+                assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (fmt, name)
     finally:
         md.set_clock_run_samples(0)
 

@@ -125,6 +125,17 @@ def test_any_chunking_and_run_geometry_gives_the_bytes_and_counts_of_one_call(md
                     expect.append(pkg.tuner_count(rate, sel, at + m) - pkg.tuner_count(rate, sel, at))
                     at += m
                 assert counts == expect, (run, split)
+        # the history is handed over by one kernel for every input format: each of them cut into sevens (every call shorter
+        # than the history) and at [1, n - 1], at one run geometry
+        md.set_tuner_run_samples(0)
+        streams = {"complexf": x, "s16": TC.signal(TC.N_STREAM, 3, s16=True), "u8": TC.signal_u8(TC.N_STREAM, 4),
+                   "s8": TC.signal_u8(TC.N_STREAM, 5, signed=True)}
+        for fmt, stream in streams.items():
+            want, _ = _run(md, pkg, (rate, sel), stream, position=position)
+            assert len(np.unique(want.view(np.uint32))) > total // 2, fmt
+            for split in ("sevens", "one_rest"):
+                got, _ = _run(md, pkg, (rate, sel), stream, TC.splits(P)[split], position=position)
+                assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (fmt, split)
     finally:
         md.set_tuner_run_samples(0)
 
