@@ -1515,6 +1515,83 @@ DABGPU_API int dabgpu_fic_bootstrap_frame(int mode, uint8_t frame[6144]);
 DABGPU_API int dabgpu_fic_make_header(const dabgpu_fic_result *result, int mode, uint8_t frame[6144]);
 DABGPU_API int dabgpu_decode_configure_from_fic(dabgpu_ctx *ctx);
 
+/* ---- the superframe reader: DAB+ Fire code, RS(120,110) and AU CRCs of one sub-channel ------------------------------------- *
+ * What a receiver judges a DAB+ sub-channel by (ETSI TS 102 563 5.2-5.4, 6): whether the superframes are found, how many bytes the
+ * outer code had to correct and how many words it could not, and whether the access units pass their CRC.  These figures need no
+ * reference ETI: they are the ground truth a capture carries itself.  The reference sends superframes and reads none; the outer
+ * code is checked against its lib/fec (decode_rs_char), set up as init_rs_char(8, 0x11d, 0, 1, 10, 135).
+ * Input: n_images images of 6144 bytes on the device, four-byte aligned: what dabgpu_decode* writes, or raw ETI(NI) frames; one
+ *   sub-channel as (offset, framesize), the fields dabgpu_frontend_describe gives.  framesize = 24 s, s = bitrate / 8 in 1 ... 24.
+ * Candidate f (0 ... n_images - 5): the 120 s bytes of the sub-channel in images f ... f + 4.  EVERY alignment is decoded, n_images - 4
+ *   candidates per call: nothing depends on an earlier candidate and the device never waits for a host decision.  The fivefold
+ *   work is deliberate (profiles/superframe.txt has its cost).
+ * Per candidate, one dabgpu_sf_record (64 bytes):
+ *   RS       codeword i (i < s) is bytes i, i + s, ..., i + 119 s: 110 data bytes, 10 parity bytes.  GF(2^8) with x^8 + x^4 + x^3 +
+ *            x^2 + 1, g(x) = prod_{i = 0 ... 9} (x + alpha^i), shortened from (255,245).  Syndromes, Berlekamp-Massey, a Chien search
+ *            over the 120 real positions, Forney.  cw_errors[i]: bytes corrected in word i; DABGPU_SF_WORD_FAILED for a word that
+ *            is uncorrectable -- the locator has fewer roots among the 120 real positions than its degree, which covers a degree
+ *            above 5 and a root in the 135 padding positions -- and whose bytes stay as received; 0 behind s.  (lib/fec applies
+ *            the in-range part of a locator with a root in the padding and reports success: the deliberate deviation.)
+ *            rs_corrected: bytes over the candidate; rs_failed: words; rs_max: the most corrections in one word;
+ *            DABGPU_SF_RS_FAILED: rs_failed > 0.  No erasure decoding.
+ *   Fire     on the corrected bytes: CRC-16 with x^16 + x^14 + x^13 + x^12 + x^11 + x^5 + x^3 + x^2 + x + 1 (0x782F), register 0 at the
+ *            start, not complemented, over bytes 2 ... 10 (fire_crc), compared big endian with bytes 0 ... 1: DABGPU_SF_FIRE_OK.
+ *            Eleven zero bytes pass it -- and are what the decoder's fifteen lead-in images hold: DABGPU_SF_ZERO, never accepted.
+ *   Header   byte 2 (`header`): rfa | dac_rate | sbr_flag | aac_channel_mode | ps_flag | mpeg_surround_config (3 bits).
+ *            (dac_rate, sbr_flag) -> (num_aus, au_start[0]): (0,1) -> (2, 5); (1,1) -> (3, 6); (0,0) -> (4, 8); (1,0) -> (6, 11).
+ *            au_start[1 ... num_aus - 1]: 12-bit big-endian fields packed from byte 3; au_start[num_aus] = 110 s; 0 behind it.
+ *            DABGPU_SF_HEADER_VALID: every AU is at least 3 bytes long (so the starts ascend and the last lies below 110 s).
+ *            The fields are written whatever the Fire code says.
+ *   AU CRC   the FIB's CRC (0x1021, register 0xFFFF, complemented) over an AU without its last two bytes, compared big endian with
+ *            them; au_ok: bit k = AU k passes.  Computed only for an ACCEPTED candidate: FIRE_OK, not ZERO, HEADER_VALID.
+ * Output bytes: candidate f at f x 110 s of d_out: its data bytes after correction, in superframe order (uncorrectable words
+ *   contribute their received bytes).  *out_bytes = (n_images - 4) x 110 s.
+ * Over the call, dabgpu_sf_result: formed on the host by the getter from the records.  Walk f from 0; an accepted candidate
+ *   counts and f += 5, any other f += 1.  Stateless: no lock, no hysteresis.  candidates; superframes; first: the first
+ *   accepted candidate, -1 if none; phase_changes: accepted candidates whose f mod 5 differs from the one before; over the
+ *   accepted candidates aus, aus_ok, aus_bad, rs_corrected, rs_failed, rs_max; `accepted` receives min(cap, superframes) of
+ *   their indices (may be NULL with cap 0).
+ * THERE IS NO STREAM STATE.  A superframe that straddles two calls is the caller's business: hand the last four images of one
+ *   call in again in front of the next (the decoder keeps its history of fifteen rows itself; this stage keeps nothing).
+ * dabgpu_superframe_dev: asynchronous on `stream` (NULL: the context's own, behind every lane); one launch, one workgroup per
+ *   candidate, no atomics: the same records and bytes for the same images, whatever the split into calls.  dabgpu_superframe:
+ *   the host-pointer form.  A result is per call; the getters wait for the most recent one.
+ *   Refused before anything is queued (the previous result stays), DABGPU_E_INVALID and a message: n_images below 5 or above 2^22;
+ *   a null or misaligned pointer; a framesize that is not 24 s with s in 1 ... 24; an offset that is not a multiple of 4 or with
+ *   offset + framesize > 6144; a get before any call.  DABGPU_E_CAPACITY: out_cap too small (*out_bytes receives the size).
+ * dabgpu_get_superframe_records: min(cap, n) records to `out`, *n = candidates of the call.
+ * dabgpu_superframe_check: the shape refusals alone -- host only, no context, message via dabgpu_last_error(NULL).
+ * Out of scope: erasure decoding from the soft metrics; AAC, PAD; DAB (MP2) frames; packet mode. */
+#define DABGPU_SF_FIRE_OK 1u
+#define DABGPU_SF_ZERO 2u
+#define DABGPU_SF_HEADER_VALID 4u
+#define DABGPU_SF_RS_FAILED 8u
+#define DABGPU_SF_WORD_FAILED 0xFFu
+#define DABGPU_SF_MAX_WORDS 24
+typedef struct dabgpu_sf_record {
+    uint32_t flags;
+    uint16_t rs_corrected, rs_failed;
+    uint8_t rs_max, num_aus, au_ok, header;
+    uint8_t rfa, dac_rate, sbr_flag, aac_channel_mode, ps_flag, mpeg_surround_config, reserved0[2];
+    uint16_t au_start[7];
+    uint16_t fire_crc;
+    uint8_t cw_errors[DABGPU_SF_MAX_WORDS];
+    uint32_t reserved1;
+} dabgpu_sf_record;                                                                                  /* 64 bytes */
+typedef struct dabgpu_sf_result {
+    uint32_t candidates, superframes;
+    int32_t first;
+    uint32_t phase_changes, aus, aus_ok, aus_bad, rs_failed, rs_max, reserved;
+    uint64_t rs_corrected;
+} dabgpu_sf_result;                                                                                  /* 48 bytes */
+DABGPU_API int dabgpu_superframe_dev(dabgpu_ctx *ctx, const void *d_images, size_t n_images, size_t offset, size_t framesize,
+                                     void *d_out, size_t out_cap, size_t *out_bytes, void *stream);
+DABGPU_API int dabgpu_superframe(dabgpu_ctx *ctx, const uint8_t *images, size_t n_images, size_t offset, size_t framesize,
+                                 uint8_t *out, size_t out_cap, size_t *out_bytes);
+DABGPU_API int dabgpu_get_superframe_result(dabgpu_ctx *ctx, dabgpu_sf_result *out, uint32_t *accepted, size_t cap);
+DABGPU_API int dabgpu_get_superframe_records(dabgpu_ctx *ctx, dabgpu_sf_record *out, size_t cap, size_t *n);
+DABGPU_API int dabgpu_superframe_check(size_t n_images, size_t offset, size_t framesize);
+
 /* wait for everything queued on the context's own stream(s): every lane */
 DABGPU_API int dabgpu_synchronize(dabgpu_ctx *ctx);
 

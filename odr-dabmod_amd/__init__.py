@@ -68,6 +68,8 @@ EXPORTS = [
     "dabgpu_get_carrier_state", "dabgpu_debug_csi_unit_weights",
     "dabgpu_fic_scan_dev", "dabgpu_fic_scan", "dabgpu_get_fic_result", "dabgpu_get_fic_records", "dabgpu_get_fic_services",
     "dabgpu_fic_bootstrap_frame", "dabgpu_fic_make_header", "dabgpu_decode_configure_from_fic",
+    "dabgpu_superframe_dev", "dabgpu_superframe", "dabgpu_get_superframe_result", "dabgpu_get_superframe_records",
+    "dabgpu_superframe_check",
 ]
 
 FORMATS = {"s16": (1, np.int16), "u8": (2, np.uint8), "s8": (3, np.int8)}
@@ -301,6 +303,27 @@ assert C.sizeof(_FicRecord) == 288 and C.sizeof(_FicResult) == 4320 and C.sizeof
 FIC_RECORD_BYTES, FIC_OFFSET_CONFIGURED = 288, C.c_size_t(-1).value
 FIC_CRC_OK, FIC_ZERO, FIC_TRUNCATED = 1, 2, 4
 
+
+class _SfRecord(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("rs_corrected", C.c_uint16), ("rs_failed", C.c_uint16), ("rs_max", C.c_uint8),
+                ("num_aus", C.c_uint8), ("au_ok", C.c_uint8), ("header", C.c_uint8), ("rfa", C.c_uint8), ("dac_rate", C.c_uint8),
+                ("sbr_flag", C.c_uint8), ("aac_channel_mode", C.c_uint8), ("ps_flag", C.c_uint8), ("mpeg_surround_config", C.c_uint8),
+                ("reserved0", C.c_uint8 * 2), ("au_start", C.c_uint16 * 7), ("fire_crc", C.c_uint16), ("cw_errors", C.c_uint8 * 24),
+                ("reserved1", C.c_uint32)]
+
+
+_SF_RESULT_FIELDS = ("candidates", "superframes", "first", "phase_changes", "aus", "aus_ok", "aus_bad", "rs_failed", "rs_max",
+                     "reserved", "rs_corrected")
+
+
+class _SfResult(C.Structure):
+    _fields_ = [(k, C.c_int32 if k == "first" else C.c_uint64 if k == "rs_corrected" else C.c_uint32) for k in _SF_RESULT_FIELDS]
+
+
+assert C.sizeof(_SfRecord) == 64 and C.sizeof(_SfResult) == 48
+SF_RECORD_BYTES, SF_WORD_FAILED = 64, 0xFF
+SF_FIRE_OK, SF_ZERO, SF_HEADER_VALID, SF_RS_FAILED = 1, 2, 4, 8
+
 ETI_FRAME_BYTES = 6144
 CIFS_PER_FRAME = {1: 4, 2: 1, 3: 1, 4: 2}      # ETI frames per transmission frame
 FE_HISTORY_FRAMES = 15                         # ETI frames the time interleaver looks back (DABGPU_FE_HISTORY_FRAMES)
@@ -463,6 +486,11 @@ def load_library():
     lib.dabgpu_fic_bootstrap_frame.argtypes = [C.c_int, vp]
     lib.dabgpu_fic_make_header.argtypes = [C.POINTER(_FicResult), C.c_int, vp]
     lib.dabgpu_decode_configure_from_fic.argtypes = [vp]
+    lib.dabgpu_superframe_dev.argtypes = [vp, vp, sz, sz, sz, vp, sz, szp, vp]
+    lib.dabgpu_superframe.argtypes = [vp, vp, sz, sz, sz, vp, sz, szp]
+    lib.dabgpu_get_superframe_result.argtypes = [vp, C.POINTER(_SfResult), vp, sz]
+    lib.dabgpu_get_superframe_records.argtypes = [vp, vp, sz, szp]
+    lib.dabgpu_superframe_check.argtypes = [sz, sz, sz]
     lib.dabgpu_decode_check_layout.argtypes = [C.POINTER(_FeLayout)]
     lib.dabgpu_decode_reset.argtypes = [vp]
     lib.dabgpu_decode_dev.argtypes = [vp, vp, sz, vp, sz, vp, szp, vp]
@@ -779,6 +807,37 @@ def fic_make_header(result, mode):
     if lib.dabgpu_fic_make_header(C.byref(r), int(mode), frame.ctypes.data) != 0:
         raise DabGpuError(lib.dabgpu_last_error(None).decode())
     return frame
+
+
+def superframe_check(n_images, offset, framesize):
+    """Host only (needs the library, no device): raises DabGpuError with the refusal superframe() would give this shape."""
+    lib = load_library()
+    if lib.dabgpu_superframe_check(int(n_images), int(offset), int(framesize)) != 0:
+        raise DabGpuError(lib.dabgpu_last_error(None).decode())
+
+
+def superframe_record_dict(row):
+    """one row of superframe_records() as a dict of the fields of dabgpu_sf_record"""
+    r = _SfRecord.from_buffer_copy(bytes(row))
+    d = {k: int(getattr(r, k)) for k, t in _SfRecord._fields_ if not k.startswith("reserved") and k not in ("au_start", "cw_errors")}
+    d["au_start"] = [int(v) for v in r.au_start]
+    d["cw_errors"] = [int(v) for v in r.cw_errors]
+    return d
+
+
+def superframe_aus(out, result, records):
+    """The access units of a call's accepted superframes, sliced on the host: (aus, crc_ok) -- aus: the AUs without their CRC as
+    bytes, in stream order; crc_ok: one bool each.  out, result, records: what superframe() / superframe_result() /
+    superframe_records() gave for the call."""
+    out = np.frombuffer(out, np.uint8) if isinstance(out, (bytes, bytearray)) else np.ascontiguousarray(out, np.uint8)
+    out = out.reshape(result["candidates"], -1)
+    aus, ok = [], []
+    for f in result["accepted"]:
+        r = superframe_record_dict(records[f])
+        for k in range(r["num_aus"]):
+            aus.append(out[f, r["au_start"][k]:r["au_start"][k + 1] - 2].tobytes())
+            ok.append(bool(r["au_ok"] >> k & 1))
+    return aus, ok
 
 
 def decode_reference(eti, e, n):
@@ -1244,6 +1303,7 @@ class Modulator:
         if frame.size != ETI_FRAME_BYTES:
             raise DabGpuError("frontend: ETI frames are 6144 bytes")
         self._chk(self._lib.dabgpu_frontend_configure(self._h, frame.ctypes.data))
+        self._fe_frame = frame.copy()                    # (dabplus_subchannels: the configured layout)
 
     def frontend_reset(self):
         """Zero history (the start of a stream), layout kept.  Waits."""
@@ -1963,6 +2023,72 @@ class Modulator:
         """fic_make_header() on the most recent fic_scan result, then frontend_configure(): the decoder set up from what the
         signal says about itself.  Zeroes the histories, as frontend_configure does.  Waits."""
         self._chk(self._lib.dabgpu_decode_configure_from_fic(self._h))
+        self._fe_frame = None                            # (dabplus_subchannels: the layout is the one the FIC result gives)
+
+    # ---- the superframe reader: DAB+ Fire code, RS(120,110), AU CRCs (include/dabgpu.h, "the superframe reader") ----
+    def superframe(self, images, offset, framesize):
+        """Host path: (n, 6144) uint8 images -- decode()'s output or raw ETI frames -- and one sub-channel as the (offset,
+        framesize) of frontend_describe() -> (out, result): out (n - 4, 110 s) uint8, the corrected data bytes of every
+        candidate; result: superframe_result()."""
+        images, n = self._eti(images)
+        s = int(framesize) // 24
+        out = np.zeros(max(n - 4, 1) * 110 * max(s, 1), np.uint8)
+        ob = C.c_size_t()
+        self._chk(self._lib.dabgpu_superframe(self._h, images.ctypes.data, n, int(offset), int(framesize), out.ctypes.data,
+                                              out.nbytes, C.byref(ob)))
+        return out[:ob.value].reshape(n - 4, 110 * s), self.superframe_result()
+
+    def superframe_dev(self, d_images, n_images, offset, framesize, d_out, stream=None, queued=False):
+        """Device path on torch uint8 tensors (n_images images; room for (n_images - 4) x 110 s bytes), asynchronous on the
+        stream as chain_dev; returns the bytes written.  The figures: superframe_result(), superframe_records()."""
+        if d_images.numel() * d_images.element_size() < int(n_images) * ETI_FRAME_BYTES:
+            raise DabGpuError("superframe: the tensor is shorter than n_images images of 6144 bytes")
+        ob = C.c_size_t()
+        self._dev_call(self._lib.dabgpu_superframe_dev, d_images, stream, d_images.data_ptr(), int(n_images), int(offset),
+                       int(framesize), d_out.data_ptr(), d_out.numel() * d_out.element_size(), C.byref(ob), queued=queued)
+        return ob.value
+
+    def superframe_result(self):
+        """The most recent superframe() / superframe_dev() (waits for it): a dict of the fields of dabgpu_sf_result and
+        "accepted": the indices of the accepted candidates."""
+        r = _SfResult()
+        self._chk(self._lib.dabgpu_get_superframe_result(self._h, C.byref(r), None, 0))
+        idx = np.zeros(max(r.superframes, 1), np.uint32)
+        self._chk(self._lib.dabgpu_get_superframe_result(self._h, C.byref(r), idx.ctypes.data, r.superframes))
+        d = {k: int(getattr(r, k)) for k in _SF_RESULT_FIELDS if k != "reserved"}
+        d["accepted"] = [int(i) for i in idx[:r.superframes]]
+        return d
+
+    def superframe_records(self):
+        """The per-candidate records of the same call as a (candidates, 64) uint8 array: rows of dabgpu_sf_record."""
+        n = C.c_size_t()
+        self._chk(self._lib.dabgpu_get_superframe_records(self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, SF_RECORD_BYTES), np.uint8)
+        self._chk(self._lib.dabgpu_get_superframe_records(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def dabplus_subchannels(self):
+        """The DAB+ audio sub-channels of the most recent fic_scan: per component with TMId 0 and ASCTy 63 a dict of sid,
+        subchid, bitrate and, from the configured layout (the sub-channel with the same start address), offset and
+        framesize -- what superframe() takes.  A sub-channel the configured layout does not hold is left out."""
+        res, (_, services) = self.fic_result(), self.fic_services()
+        frame = getattr(self, "_fe_frame", None)
+        if frame is None:                                # configured by configure_from_fic, or not at all
+            frame = fic_make_header(res, self.geometry["mode"])
+        lay = self.frontend_describe(frame)
+        out = []
+        for svc in services:
+            for comp in svc["components"]:
+                if comp["tmid"] != 0 or comp["type"] != 63:
+                    continue
+                for sub in res["sub"]:
+                    if sub["subchid"] != comp["id"]:
+                        continue
+                    for i, t in enumerate(lay["subchannels"]):
+                        if t["sad"] == sub["sad"]:
+                            out.append(dict(sid=svc["sid"], subchid=sub["subchid"], bitrate=sub["bitrate"], index=i,
+                                            offset=t["offset"], framesize=t["framesize"]))
+        return out
 
     # ---- the channel decoder: coded bits -> the ETI payload (include/dabgpu.h, "the channel decoder") ----
     def decode(self, bits, ref_eti=None):

@@ -31,6 +31,9 @@
 //   api_fic.hip       the FIC reader (fic.hip): FIB CRCs and FIG 0/0, 0/1, 0/2, 1/0, 1/1 of decoded images or ETI frames, the
 //                     sub-channel table of a call; the short-form table, the derived fields, the ETI header made from a
 //                     result and the bootstrap frame (host only); the decoder configured from a result
+//   api_superframe.hip the superframe reader (superframe.hip): Fire code, RS(120,110) and AU CRCs of one DAB+ sub-channel of
+//                     decoded images or ETI frames, a record per alignment of five images; the greedy walk over a call's
+//                     records and the shape check (host only)
 //   api_frontend.hip  the front-end on the device: layout of an ETI frame (host), configure / reset, ETI -> coded bits -> IQ,
 //                     its own stream state (the time interleaver's history): read, installed, computed from lead-in frames
 // In this order: Settings, TraceScope; the receive-side stages' state, one struct each (the streamed stages' on StreamStage);
@@ -273,6 +276,16 @@ struct FicState {
     bool done = false;
     hipStream_t stream = nullptr;
 };
+
+// The superframe reader (api_superframe.hip, superframe.hip).  rec: one record per candidate of the most recent
+// dabgpu_superframe* call, `candidates` of them; in, out: the host-pointer entry's staging; done: a call has been queued.
+// No stream state: a candidate is five images of the call.
+struct SuperframeState {
+    DevBuf rec, in, out;
+    size_t candidates = 0;
+    bool done = false;
+    hipStream_t stream = nullptr;
+};
 }  // namespace dabgpu_api
 
 struct dabgpu_ctx {
@@ -348,6 +361,7 @@ struct dabgpu_ctx {
     dabgpu_api::TiiScanState tii_scan;
     dabgpu_api::CirState cir;
     dabgpu_api::FicState fic;
+    dabgpu_api::SuperframeState superframe;
     bool tii_insert = true;               // TII::m_insert (src/TII.h:112): this frame of the stream carries TII
     bool tables_valid = false;            // apply_settings has uploaded every table group once
     unsigned long long tii_seg_epoch = 0; // 1 while the cached segment matches the settings (apply_settings zeroes it), and its stage mask

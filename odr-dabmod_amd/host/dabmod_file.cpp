@@ -103,6 +103,13 @@
 //                        --separate-converter.
 //   --csi                with --loopback --soft: the soft metrics weighted by the state of their carrier (dabgpu_demod_csi;
 //                        include/dabgpu.h, "the carrier state") in place of dabgpu_demod_soft; everything else as --soft.
+//   --superframe N       with --loopback: the superframe reader (dabgpu_superframe; include/dabgpu.h, "the superframe reader") on
+//                        sub-channel N (in STC order) of every batch's decoded images behind the fifteen of the lead-in, the
+//                        last four images carried into the next batch so that every alignment of five is looked at once.  After
+//                        the run: candidates, superframes found by the greedy walk over all of them, AUs ok / bad, RS bytes
+//                        corrected and words failed on stderr.  WITH THE OPTION THE RUN'S VERDICT IS THE AUs': exit status 2
+//                        when an accepted superframe has an AU whose CRC fails, and payload bit errors no longer count -- a
+//                        noisy loop passes where the outer code copes.  No superframe at all is no error (exit status 0).
 //   --carrier-mer FILE   the per-carrier MER (dabgpu_demod_carrier_state) of the last batch that was written -- with --loopback
 //                        --channel-cn of that batch behind the channel emulator, as --cir takes it -- the window where
 //                        --monitor puts it.  FILE gets one line per carrier and frame of the batch: "frame position mer_db
@@ -165,6 +172,7 @@ struct BlindFailure : std::runtime_error {
                          "       [--tii-scan]   with --batch 2 or more: read the TII of the last batch; exit 2 when it is not the one --tii configures\n"
                          "       [--cir FILE]   impulse response of the channel the last batch went through (with --loopback --channel-cn: the\n"
                          "                        emulator's), per tap into FILE (lines of: delay_samples level_db), paths on stderr\n"
+                         "       [--superframe N]   with --loopback: DAB+ superframes of sub-channel N; the exit status is the AU CRCs' (2: a bad AU)\n"
                          "       [--csi]   with --loopback --soft: weight the metrics by the measured state of their carrier\n"
                          "       [--carrier-mer FILE]   MER per carrier of the last batch (lines of: frame position mer_db weight)\n"
                          "       [--state-out FILE] [--state-in FILE]   with --gpu-frontend: leave / take up the stream's state\n");
@@ -229,6 +237,7 @@ int main(int argc, char **argv)
     long contexts = 1;
     bool gpu_frontend = false, loopback = false, soft = false, csi = false, blind = false;
     std::string carrier_mer_path;
+    long superframe = -1;
     bool channel = false;
     double channel_cn = 0.0;
     unsigned long long channel_seed = 0;
@@ -288,6 +297,12 @@ int main(int argc, char **argv)
             else if (a == "--soft") soft = true;
             else if (a == "--csi") csi = true;
             else if (a == "--carrier-mer") carrier_mer_path = val();
+            else if (a == "--superframe") {
+                const std::string v = val();
+                size_t used = 0;
+                superframe = std::stol(v, &used);
+                if (used != v.size() || superframe < 0) usage();
+            }
             else if (a == "--channel-cn") { channel_cn = std::stod(val()); channel = true; }
             else if (a == "--channel-seed") channel_seed = std::stoull(val());
             else if (a == "--channel-echo") {
@@ -344,6 +359,11 @@ int main(int argc, char **argv)
 
         if (soft && !loopback) {
             std::fprintf(stderr, "dabmod_file: --soft does not go without --loopback: it chooses the decisions of that loop\n");
+            return 2;
+        }
+
+        if (superframe >= 0 && !loopback) {
+            std::fprintf(stderr, "dabmod_file: --superframe does not go without --loopback: it reads that loop's decoded images\n");
             return 2;
         }
 
@@ -546,6 +566,13 @@ int main(int argc, char **argv)
             ~RxContext() { if (c) dabgpu_destroy(c); }
         } rx;
         bool blind_configured = false;
+        // --superframe: the sub-channel's place (read from the first frame's layout), the images carried over (four at the most),
+        // and every candidate's record in stream order
+        struct {
+            size_t offset = 0, framesize = 0;
+            std::vector<uint8_t> images, out;
+            std::vector<dabgpu_sf_record> records;
+        } sf;
         // --cir: the last batch, as written or (--loopback --channel-cn) as the channel emulator left it, and its chain
         std::vector<uint8_t> cir_last;
         DabGpuChain *cir_chain = nullptr;
@@ -691,6 +718,31 @@ int main(int argc, char **argv)
                 loop.n_bits += all.n_bits;
                 loop.corrected += all.corrected;
                 loop.coded_bits += all.coded_bits;
+            }
+            if (superframe >= 0) {
+                if (!sf.framesize) {
+                    std::vector<dabgpu_fe_layout> lay(1);
+                    if (dabgpu_frontend_describe(loop_eti.front().data(), lay.data()))
+                        throw std::runtime_error(std::string("--superframe: ") + dabgpu_last_error(nullptr));
+                    if (static_cast<size_t>(superframe) >= lay[0].nst)
+                        throw std::runtime_error("--superframe: the file has " + std::to_string(lay[0].nst) + " sub-channels");
+                    sf.offset = lay[0].sub[superframe].offset;
+                    sf.framesize = lay[0].sub[superframe].framesize;
+                    if (dabgpu_superframe_check(5, sf.offset, sf.framesize))
+                        throw std::runtime_error(std::string("--superframe: ") + dabgpu_last_error(nullptr));
+                }
+                for (size_t i = 0; i < n; ++i)
+                    if (loop_pos + i >= 15) sf.images.insert(sf.images.end(), &loop_out[i * 6144], &loop_out[(i + 1) * 6144]);
+                const size_t have = sf.images.size() / 6144;
+                if (have >= 5) {
+                    size_t ob = 0, got = 0;
+                    sf.out.resize((have - 4) * 110 * (sf.framesize / 24));
+                    chk_dc(dabgpu_superframe(dc, sf.images.data(), have, sf.offset, sf.framesize, sf.out.data(), sf.out.size(), &ob));
+                    const size_t at = sf.records.size();
+                    sf.records.resize(at + have - 4);
+                    chk_dc(dabgpu_get_superframe_records(dc, &sf.records[at], have - 4, &got));
+                    sf.images.erase(sf.images.begin(), sf.images.end() - 4 * 6144);
+                }
             }
             loop_pos += n;
             while (loop_first + 15 < loop_pos) {
@@ -895,6 +947,32 @@ int main(int argc, char **argv)
             if (soft)
                 std::fprintf(stderr, "dabmod_file: loopback: soft decisions, metric %llu / soft_sum %llu, %llu erasures\n", loop.metric,
                              loop.soft_sum, loop.erasures);
+        }
+        unsigned long long sf_bad_aus = 0;
+        if (superframe >= 0) {
+            // the greedy walk of dabgpu_get_superframe_result, over the candidates of every batch
+            unsigned long long found = 0, aus_ok = 0, corrected = 0, failed = 0;
+            unsigned most = 0;
+            long first = -1;
+            for (size_t f = 0; f < sf.records.size();) {
+                const dabgpu_sf_record &r = sf.records[f];
+                if ((r.flags & (DABGPU_SF_FIRE_OK | DABGPU_SF_ZERO | DABGPU_SF_HEADER_VALID)) != (DABGPU_SF_FIRE_OK | DABGPU_SF_HEADER_VALID)) {
+                    f += 1;
+                    continue;
+                }
+                if (first < 0) first = static_cast<long>(f);
+                const unsigned ok = static_cast<unsigned>(__builtin_popcount(r.au_ok));
+                ++found;
+                aus_ok += ok;
+                sf_bad_aus += r.num_aus - ok;
+                corrected += r.rs_corrected;
+                failed += r.rs_failed;
+                most = std::max<unsigned>(most, r.rs_max);
+                f += 5;
+            }
+            std::fprintf(stderr, "dabmod_file: superframe: sub-channel %ld, %zu candidates, %llu superframes (first at %ld), AUs %llu ok / %llu bad, "
+                                 "%llu RS bytes corrected (at most %u in a word), %llu words failed\n",
+                         superframe, sf.records.size(), found, first, aus_ok, sf_bad_aus, corrected, most, failed);
         }
         int mask_violations = 0;
         if (gs.spectrum) {
@@ -1104,7 +1182,9 @@ int main(int argc, char **argv)
                          n_frames, loopback && channel ? " behind the channel" : "", early, K, all[all.size() / 2], all.front());
         }
         if (gs.monitor && mon.bit_errors) return 2;
-        if (loopback && (loop.fic_errors || loop.msc_errors)) return 2;
+        if (superframe >= 0) {
+            if (sf_bad_aus) return 2;
+        } else if (loopback && (loop.fic_errors || loop.msc_errors)) return 2;
         if (tii_mismatch) return 2;
         if (mask_violations) return 3;
         return 0;
