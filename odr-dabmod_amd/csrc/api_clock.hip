@@ -218,14 +218,7 @@ int dabgpu_sco_dev(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames,
     HIPCHK(c, c->sco.rows.reserve(n_frames * nblocks * kScoSums * sizeof(double)));
     HIPCHK(c, c->sco.sums.reserve((size_t)c->max_frames * kScoSums * sizeof(double)));
     ScoArgs a{};
-    a.g = c->g;
-    a.t = tables_of(c);
-    a.iq = d_iq;
-    a.fmt = format ? 1 : 0;
-    a.frame_stride = tf_samples(c->g);
-    a.n_frames = (int)n_frames;
-    demod_runs(c->g, n_frames, c->demod.run_symbols, &a.runs_per_frame, &a.syms_per_run);
-    a.early = early;
+    fill_rx_symbols(c, d_iq, format, n_frames, early, a);
     a.rows = (double *)c->sco.rows.p;
     a.frames = (double *)c->sco.sums.p;
     HIPCHK(c, launch_sco(a, call.s));

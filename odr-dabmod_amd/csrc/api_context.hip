@@ -59,6 +59,12 @@ void trace_launch(const char *what)
     if (!g_trace_sink->empty()) *g_trace_sink += "; ";
     *g_trace_sink += w;
 }
+void trace_launch(const char *what, std::initializer_list<int> targs)
+{
+    std::string w = std::string(what) + "<";
+    for (int v : targs) w += std::to_string(v) + ", ";
+    trace_launch(w.replace(w.size() - 2, 2, ">").c_str());
+}
 }  // namespace dabgpu
 
 
@@ -96,7 +102,7 @@ bool mode_geometry(int mode, Geometry *g)
 size_t tf_in_bytes(const Geometry &g) { return (size_t)(g.nb_symbols - 1) * (size_t)(g.K / 4); }
 size_t tf_samples(const Geometry &g)
 {
-    return (size_t)g.null_size + (size_t)g.nb_symbols * (size_t)g.sym_size;
+    return (size_t)frame_samples(g);
 }
 
 // Least squares min |A x - b| by Householder QR in float64.  A: m x n, column-major, m >= n; A and b are overwritten (R in

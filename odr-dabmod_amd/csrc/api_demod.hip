@@ -10,6 +10,18 @@ namespace dabgpu_api {
 const char *const kMonitorNoSubmit =
     "monitor: dabgpu_chain_submit* is not monitored (statistics per streaming slot are not kept); turn the monitor off";
 
+void fill_rx_symbols(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, RxSymbolArgs &a)
+{
+    a.g = c->g;
+    a.t = tables_of(c);
+    a.iq = d_iq;
+    a.fmt = format;                      // (0 or DABGPU_FMT_S16: the entries refuse the rest, the launchers check again)
+    a.frame_stride = tf_samples(c->g);
+    a.n_frames = (int)n_frames;
+    demod_runs(c->g, n_frames, c->demod.run_symbols, &a.runs_per_frame, &a.syms_per_run);
+    a.early = early;
+}
+
 namespace {
 const char *const kEarlyRange = "demod: early must lie inside the cyclic prefix (0 ... sym_size - spacing)";
 
@@ -22,15 +34,8 @@ int queue_demod(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, in
     HIPCHK(c, c->demod.stats.reserve(std::max<size_t>(n_frames, 1) * sizeof(DemodFrameStats)));
     HIPCHK(c, hipMemsetAsync(c->demod.stats.p, 0, n_frames * sizeof(DemodFrameStats), s));
     DemodArgs a{};
+    fill_rx_symbols(c, d_iq, format, n_frames, early, a);
     a.csi_w = weights;
-    a.g = c->g;
-    a.t = tables_of(c);
-    a.iq = d_iq;
-    a.fmt = format;
-    a.frame_stride = tf_samples(c->g);
-    a.n_frames = (int)n_frames;
-    demod_runs(c->g, n_frames, c->demod.run_symbols, &a.runs_per_frame, &a.syms_per_run);
-    a.early = early;
     a.bits_out = (uint8_t *)d_bits_out;
     a.ref_bits = (const uint8_t *)d_ref;
     a.stats = (DemodFrameStats *)c->demod.stats.p;
@@ -50,14 +55,7 @@ int queue_carrier_state(dabgpu_ctx *c, const void *d_iq, int format, size_t n_fr
     HIPCHK(c, c->csi.weights.reserve(std::max<size_t>(n_frames, 1) * K * sizeof(float)));
     HIPCHK(c, hipMemsetAsync(c->csi.sums.p, 0, n_frames * 2 * K * sizeof(unsigned long long), s));
     DemodArgs a{};
-    a.g = c->g;
-    a.t = tables_of(c);
-    a.iq = d_iq;
-    a.fmt = format;
-    a.frame_stride = tf_samples(c->g);
-    a.n_frames = (int)n_frames;
-    demod_runs(c->g, n_frames, c->demod.run_symbols, &a.runs_per_frame, &a.syms_per_run);
-    a.early = early;
+    fill_rx_symbols(c, d_iq, format, n_frames, early, a);
     a.csi_sums = (unsigned long long *)c->csi.sums.p;
     HIPCHK(c, launch_demod(a, s));
     HIPCHK(c, launch_csi_weights(a.csi_sums, (float *)c->csi.weights.p, c->g.K, (int)n_frames, c->csi.unit_weights, s));

@@ -11,7 +11,7 @@
 // floating-point atomics.
 #include "device_common.h"
 #include "turn_phase.h"      // ld_iq
-#include "fixed_order.h"     // group_sum, group_arg, better, carrier_pos
+#include "fixed_order.h"     // group_sum, group_arg, better, carrier_pos, bin_carrier, carrier_occupied, twiddle64
 
 #include <climits>
 
@@ -30,9 +30,6 @@ DEV cd mul_quarter_d(cd z, unsigned q)                                  // z i^q
     default: return mkd(z.y, -z.x);
     }
 }
-// carrier of bin b, and whether it is occupied (k = -K/2 ... -1, 1 ... K/2)
-DEV int bin_carrier(int b, int N) { return b <= N / 2 ? b : b - N; }
-DEV bool carrier_occupied(int k, int K) { return k != 0 && k >= -K / 2 && k <= K / 2; }
 
 // ---- 1. per frame: R = DFT_N of the phase reference symbol's window, H = R conj(P), h = the weighted inverse transform --------
 // N / 2 lanes, one butterfly per lane and stage; a stage reads and writes the two elements of its own pair, a barrier between
@@ -47,7 +44,7 @@ template <int LOGN, int FMT> __global__ __launch_bounds__((1 << LOGN) / 2) void 
     const int t = (int)threadIdx.x;
     const int f = (int)blockIdx.x;
     if (f >= a.n_frames) return;
-    const long long tf = (long long)a.g.null_size + (long long)a.g.nb_symbols * a.g.sym_size;
+    const long long tf = frame_samples(a.g);
     const long long w0 = (long long)f * tf + (long long)(a.g.null_size + a.g.sym_size - N - a.early);   // 0 <= early <= CP
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -55,11 +52,7 @@ template <int LOGN, int FMT> __global__ __launch_bounds__((1 << LOGN) / 2) void 
         const cf x = ld_iq(a.iq, FMT, w0 + i);
         X[i] = mkd((double)x.x, (double)x.y);
     }
-    {
-        double sn, cs;
-        sincospi(-2.0 * (double)t / (double)N, &sn, &cs);               // (the argument is exact)
-        W[t] = mkd(cs, sn);
-    }
+    W[t] = twiddle64(t, N);
     lds_barrier();
     // forward, decimation in frequency: spans N / 2 ... 1
 #pragma unroll
@@ -312,23 +305,14 @@ hipError_t launch_cir(const CirArgs &a, hipStream_t s)
         !a.t.phase_q)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)a.n_frames);
-#define DABGPU_CIR_FRAME(L)                                                                          \
-    case L:                                                                                          \
-        if (a.fmt == 0)                                                                              \
-            DABGPU_LAUNCH((cir_frame_kernel<L, 0>), grid, dim3((1 << L) / 2), 0, s, a);              \
-        else                                                                                         \
-            DABGPU_LAUNCH((cir_frame_kernel<L, 1>), grid, dim3((1 << L) / 2), 0, s, a);              \
-        break
-    switch (a.g.logN) {
-        DABGPU_CIR_FRAME(8);
-        DABGPU_CIR_FRAME(9);
-        DABGPU_CIR_FRAME(10);
-        DABGPU_CIR_FRAME(11);
-    default: return hipErrorInvalidValue;
-    }
-#undef DABGPU_CIR_FRAME
-    DABGPU_LAUNCH(cir_decide_kernel, dim3(1), dim3(kDecideThreads), 0, s, a);
-    return hipGetLastError();
+    return by_fft_size(a.g.logN, [&](auto L) {
+        if (a.fmt == 0)
+            DABGPU_LAUNCH_T(cir_frame_kernel, (L, 0), grid, dim3((1 << L) / 2), 0, s, a);
+        else
+            DABGPU_LAUNCH_T(cir_frame_kernel, (L, 1), grid, dim3((1 << L) / 2), 0, s, a);
+        DABGPU_LAUNCH(cir_decide_kernel, dim3(1), dim3(kDecideThreads), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace dabgpu

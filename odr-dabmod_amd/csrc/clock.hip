@@ -11,6 +11,8 @@
 // lanes of a wave read the same row or its neighbours.  No atomics, no scratch.
 #include "device_common.h"
 #include "turn_phase.h"
+#include "fixed_order.h"     // wave_sum_w
+#include "rx_symbols.h"      // the estimator's walk
 
 namespace dabgpu {
 namespace {
@@ -71,14 +73,14 @@ template <int IF, int OF> __global__ __launch_bounds__(256) void clock_kernel(co
     }
 }
 
-// ---- the estimator.  demod.hip's geometry: one workgroup of N/8 lanes per run of data symbols, eight samples per lane, the
-// forward transform, six carriers per lane (slots 0, 1, 2: bins 1 ... K/2, lane 0 taking bin 3T for its DC bin; slots 5, 6, 7:
-// bins N - K/2 ... N - 1), the product against the previous symbol's bins kept in registers.  Per block, float64 sums of the
-// fp32 terms in one order: the lane's slots in slot order, an xor butterfly inside the wave (a + b = b + a exactly: every
-// lane ends with the same sum), the waves in wave order through LDS.  A block's sums do not depend on the run it is in.
+// ---- the estimator.  demod.hip's walk (rx_symbols.h): one workgroup per run of data symbols, a lane's six carriers against
+// the previous symbol.  Per block, float64 sums of the fp32 terms in one order: the lane's carriers in their order, an xor
+// butterfly inside the wave (a + b = b + a exactly: every lane ends with the same sum), the waves in wave order through LDS.
+// A block's sums do not depend on the run it is in.
 template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void sco_kernel(ScoArgs a)
 {
     typedef Fft<LOGN> F;
+    typedef SixCarriers<LOGN> C;
     constexpr int N = F::N, T = F::T;
     constexpr int NW = (T + 63) / 64, WL = T < 64 ? T : 64;
     __shared__ cf xbuf[2 * F::LDS_ELEMS];
@@ -86,31 +88,21 @@ template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void sco_kernel(S
 
     const int t = (int)threadIdx.x;
     const int nblocks = a.g.nb_symbols - 1;
-    const int frame = (int)blockIdx.x / a.runs_per_frame;
-    const int run = (int)blockIdx.x - frame * a.runs_per_frame;
-    const int b0 = run * a.syms_per_run;
-    const int b1 = min(b0 + a.syms_per_run, nblocks);
-    if (frame >= a.n_frames || b0 >= b1) return;
+    const RxRun r = rx_run(a);
+    if (r.idle) return;
+    const int frame = r.frame, b0 = r.b0, b1 = r.b1;
 
     cf tw[F::NTW > 0 ? F::NTW : 1];
     F::template load_twiddles<false>(a.t.twiddle, t, tw);
-    constexpr int rr[6] = {0, 1, 2, 5, 6, 7};
 
-    const size_t first = (size_t)a.g.null_size + (size_t)(a.g.sym_size - N - a.early);      // window of symbol 1
-    const long long base = (long long)((size_t)frame * a.frame_stride + first);
-    auto load = [&](int s, cf *v) __attribute__((always_inline)) {      // symbol s >= 1 of the frame
-        const long long off = base + (long long)(s - 1) * (long long)a.g.sym_size + t;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) v[m] = ld_iq(a.iq, a.fmt, off + T * m);
-    };
-
+    const RxWindows<N> w(a, frame);
+    auto load = [&](int s, cf *v) __attribute__((always_inline)) { C::load(a, w, s, t, v); };      // (a lambda: see SixCarriers::load)
     int par = 0;
-    cf v[8], prev[6];
+    cf v[8];
+    C six;
     load(b0 + 1, v);
     F::template run<-1, true, cf, false>(v, xbuf, par, tw, t);
-#pragma unroll
-    for (int c = 0; c < 6; ++c) prev[c] = v[rr[c]];
-    if (t == 0) prev[0] = v[3];
+    six.start(v, t);
 
     for (int b = b0; b < b1; ++b) {
         load(b + 2, v);
@@ -118,22 +110,18 @@ template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void sco_kernel(S
         double sum[kScoSums] = {0., 0., 0., 0., 0.};
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
-            const cf z = (c == 0 && t == 0) ? v[3] : v[rr[c]], p = prev[c];
-            const float dre = fmaf(z.x, p.x, z.y * p.y), dim = fmaf(z.y, p.x, -(z.x * p.y));      // z conj(p): demod's product
-            prev[c] = z;
+            const cf d = six.against_previous(v, c, t);                 // demod's product
+            const float dre = d.x, dim = d.y;
             // e = d conj(c), c the decided point (sgn Re d + j sgn Im d) / sqrt 2, a negative sign where demod decides a 1
             const float er = (fabsf(dre) + fabsf(dim)) * kSqrtHalf;
             const float ei = ((dre < 0.f ? -dim : dim) - (dim < 0.f ? -dre : dre)) * kSqrtHalf;
             const float mag = sqrtf(fmaf(er, er, ei * ei));
-            sum[c < 3 ? 0 : 2] += (double)er;
-            sum[c < 3 ? 1 : 3] += (double)ei;
+            sum[C::upper(c) ? 0 : 2] += (double)er;
+            sum[C::upper(c) ? 1 : 3] += (double)ei;
             sum[4] += (double)mag;
         }
 #pragma unroll
-        for (int i = 0; i < kScoSums; ++i) {
-#pragma unroll
-            for (int off = WL / 2; off >= 1; off >>= 1) sum[i] += __shfl_xor(sum[i], off, WL);
-        }
+        for (int i = 0; i < kScoSums; ++i) sum[i] = wave_sum_w<WL>(sum[i]);
         if ((t & 63) == 0) {
 #pragma unroll
             for (int i = 0; i < kScoSums; ++i) red[t >> 6][i] = sum[i];
@@ -167,14 +155,10 @@ hipError_t launch_sco(const ScoArgs &a, hipStream_t s)
         (long long)a.runs_per_frame * a.syms_per_run < a.g.nb_symbols - 1)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)a.n_frames * (unsigned)a.runs_per_frame);
-    switch (a.g.logN) {
-    case 8: DABGPU_LAUNCH(sco_kernel<8>, grid, dim3(Fft<8>::T), 0, s, a); break;
-    case 9: DABGPU_LAUNCH(sco_kernel<9>, grid, dim3(Fft<9>::T), 0, s, a); break;
-    case 10: DABGPU_LAUNCH(sco_kernel<10>, grid, dim3(Fft<10>::T), 0, s, a); break;
-    case 11: DABGPU_LAUNCH(sco_kernel<11>, grid, dim3(Fft<11>::T), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
-    hipError_t e = hipGetLastError();
+    hipError_t e = by_fft_size(a.g.logN, [&](auto L) {
+        DABGPU_LAUNCH_T(sco_kernel, (L), grid, dim3(Fft<L>::T), 0, s, a);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return e;
     DABGPU_LAUNCH(sco_frames_kernel, dim3((unsigned)((a.n_frames * kScoSums + 63) / 64)), dim3(64), 0, s, a.rows, a.frames, a.n_frames,
                   a.g.nb_symbols - 1);

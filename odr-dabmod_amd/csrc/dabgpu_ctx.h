@@ -576,6 +576,8 @@ int run_chain(dabgpu_ctx *c, const ChainPlan &p, const void *d_in, void *d_out_v
 const char *monitor_refusal(const dabgpu_ctx *c, const ChainPlan &p);
 extern const char *const kMonitorNoSubmit;
 int run_monitor(dabgpu_ctx *c, const ChainPlan &p, const void *d_bits, const void *d_iq, hipStream_t s);
+// the arguments every walk over the data symbols of whole frames shares (DemodArgs, ScoArgs), at the context's run geometry
+void fill_rx_symbols(dabgpu_ctx *c, const void *d_iq, int format, size_t n_frames, int early, RxSymbolArgs &a);
 
 // ---- api_decode.hip
 // dabgpu_frontend_configure's last step: the decoder's view of the new layout (survivor slots, the overlap refusal) and a zero

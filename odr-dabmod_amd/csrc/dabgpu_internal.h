@@ -5,6 +5,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <initializer_list>
+#include <type_traits>
+
 #include "resampler_runs.h"
 
 namespace dabgpu {
@@ -24,6 +27,8 @@ struct Geometry {
     int null_size;
     int sym_size;
 };
+// samples of one transmission frame (the host's tf_samples is this as a size_t; stage_kernels.hip still writes the sum out)
+__host__ __device__ inline long long frame_samples(const Geometry &g) { return (long long)g.null_size + (long long)g.nb_symbols * g.sym_size; }
 
 // Device-resident constant tables, built once per context.
 struct Tables {
@@ -48,6 +53,26 @@ void trace_launch(const char *what);
         if (::dabgpu::trace_on()) ::dabgpu::trace_launch(#kernel);      \
         hipLaunchKernelGGL(kernel, __VA_ARGS__);                        \
     } while (0)
+// The same for a kernel template whose arguments the launch holds as constants without spelling them out (by_fft_size):
+// DABGPU_LAUNCH_T(kernel, (L, 0), ...) launches kernel<L, 0> and names it with the arguments' values, "kernel<11, 0>".
+void trace_launch(const char *what, std::initializer_list<int> targs);
+#define DABGPU_TARGS(...) __VA_ARGS__
+#define DABGPU_LAUNCH_T(kernel, targs, ...)                                                     \
+    do {                                                                                        \
+        if (::dabgpu::trace_on()) ::dabgpu::trace_launch(#kernel, {DABGPU_TARGS targs});        \
+        hipLaunchKernelGGL((kernel<DABGPU_TARGS targs>), __VA_ARGS__);                          \
+    } while (0)
+// The launch by FFT size: logN = 8 ... 11 as a compile-time constant L to f, whose result it returns; any other size is refused.
+template <typename F> hipError_t by_fft_size(int logN, F &&f)
+{
+    switch (logN) {
+    case 8: return f(std::integral_constant<int, 8>());
+    case 9: return f(std::integral_constant<int, 9>());
+    case 10: return f(std::integral_constant<int, 10>());
+    case 11: return f(std::integral_constant<int, 11>());
+    default: return hipErrorInvalidValue;
+    }
+}
 
 // stream_probe.hip: streams on hardware queues of their own (the lanes of a context; the async host path's copy stream)
 bool streams_overlap(hipStream_t a, hipStream_t b);
@@ -161,7 +186,8 @@ struct DemodFrameStats {                  // zeroed before the launch; every run
     unsigned min_margin_inv;              // ~(bit pattern of the smallest margin so far); 0: no decision yet
     unsigned reserved;
 };
-struct DemodArgs {
+// what the kernels that walk the data symbols of whole frames take (rx_symbols.h); the host fills it in fill_rx_symbols
+struct RxSymbolArgs {
     Geometry g;
     Tables t;                 // twiddle, src_carrier
     const void *iq;           // n_frames x frame_stride samples: cf32 (fmt 0) or s16 pairs (fmt 1 = DABGPU_FMT_S16)
@@ -170,6 +196,8 @@ struct DemodArgs {
     int n_frames;
     int runs_per_frame, syms_per_run;   // (demod_runs)
     int early;                // the FFT window ends this many samples before the end of the symbol; 0 ... sym_size - N
+};
+struct DemodArgs : RxSymbolArgs {
     uint8_t *bits_out;        // nullptr, or n_frames x (nb_symbols - 1) * K / 4 bytes, dword aligned
     const uint8_t *ref_bits;  // nullptr, or the same shape: differing bits are counted
     DemodFrameStats *stats;   // n_frames records
@@ -263,15 +291,7 @@ hipError_t launch_clock(const ClockArgs &a, hipStream_t s);
 // clock.hip, the estimator (dabgpu_sco*): per data block of whole frames the sums of e = d conj(c) over either half of the
 // carriers and of |e|, in the receiver's geometry (demod_runs); then the blocks of a frame in index order
 constexpr int kScoSums = 5;               // Re A_hi, Im A_hi, Re A_lo, Im A_lo, S
-struct ScoArgs {
-    Geometry g;
-    Tables t;                 // twiddle
-    const void *iq;           // n_frames x frame_stride samples: cf32 (fmt 0) or s16 pairs (fmt 1 = DABGPU_FMT_S16)
-    int fmt;
-    size_t frame_stride;      // samples per frame
-    int n_frames;
-    int runs_per_frame, syms_per_run;   // (demod_runs)
-    int early;                // the FFT window ends this many samples before the end of the symbol; 0 ... sym_size - N
+struct ScoArgs : RxSymbolArgs {
     double *rows;             // n_frames x (nb_symbols - 1) x kScoSums: every block's sums
     double *frames;           // n_frames x kScoSums: the frames' sums
 };

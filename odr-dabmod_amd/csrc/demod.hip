@@ -1,24 +1,19 @@
 // demod.hip -- the receiver beside the modulator: native-rate IQ of whole transmission frames -> the coded bits a chain call
-// takes as input, plus per-frame quality figures.  The frame kernel's geometry backwards: one workgroup of N/8 lanes, eight
-// samples per lane, the forward transform CFR already runs (Fft<LOGN>::run<-1>), differential demodulation against the
-// previous symbol's bins kept in registers, hard decisions, and the frequency interleaver undone through Tables::src_carrier.
-// Written from ETSI EN 300 401 (14.5 - 14.7), like tests/receiver.py; the reference has no receiver.  No synchronisation and
-// no channel estimate: the caller says where the FFT window lies (`early` samples before the end of every symbol).
+// takes as input, plus per-frame quality figures.  The frame kernel's geometry backwards, walked as rx_symbols.h says (runs of
+// symbols, the windows, a lane's six carriers against the previous symbol); here: hard decisions, the softs, the figures, and
+// the frequency interleaver undone through Tables::src_carrier.  Written from ETSI EN 300 401 (14.5 - 14.7), like
+// tests/receiver.py; the reference has no receiver.  No synchronisation and no channel estimate.
 #include "device_common.h"
+#include "fixed_order.h"     // wave_sum_w, twiddle64
+#include "rx_symbols.h"
 #include "dabgpu.h"
 
 namespace dabgpu {
 namespace {
 
-// One workgroup = one RUN of consecutive data symbols of one frame (a.syms_per_run of them; the last run of a frame may be
-// shorter).  Data block b (0 ...  nb_symbols - 2) is symbol b + 2 of the frame -- symbol 0 is the null symbol, symbol 1 the
-// phase reference -- and is decided against symbol b + 1, so a run first transforms the symbol in front of its first.
-//
-// After the transform lane t holds bins t + T m.  Occupied: bins 1 ... K/2 = 3T (m = 0 without lane 0's DC bin, m = 1, 2, and
-// bin 3T itself: lane 0, m = 3) and bins N - K/2 = 5T ... N - 1 (m = 5, 6, 7): six carriers per lane, the frame kernel's set.
-// Carrier position k (bins 1 ... K/2 -> k = bin - 1, bins N - K/2 ... -> k = bin - N + K) is bit n = src_carrier[k] of the
-// block: I half then Q half, K/8 bytes each, MSB first.  The lanes OR their bits into one LDS image of the
-// block; the first K/16 lanes store it as dwords and count the bits that differ from the reference block.
+// One workgroup = one run of data symbols (RxRun).  Carrier position k is bit n = src_carrier[k] of the block: I half then Q
+// half, K/8 bytes each, MSB first.  The lanes OR their bits into one LDS image of the block; the first K/16
+// lanes store it as dwords and count the bits that differ from the reference block.
 //
 // SOFT (dabgpu_demod_soft*): besides all of the above, one int8 metric per coded bit -- clamp(rint(-Re d q)), clamp(rint(-Im d
 // q)) with q = 64 sqrt(2) / sqrt(P / K), P = the symbol's sum of |d|^2.  P is added in a FIXED order (the lane's six terms, an
@@ -33,6 +28,7 @@ template <int LOGN, int FORM> __device__ __forceinline__ void demod_body(const D
 {
     constexpr bool SOFT = FORM == FORM_SOFT || FORM == FORM_CSI, CSI = FORM == FORM_CSI;
     typedef Fft<LOGN> F;
+    typedef SixCarriers<LOGN> C;
     constexpr int N = F::N, T = F::T, K = 3 * N / 4, WORDS = K / 16;
     static_assert(WORDS <= T, "one lane per dword of the block");
     static_assert(2 * K == 12 * T, "three soft dwords per lane");
@@ -47,26 +43,21 @@ template <int LOGN, int FORM> __device__ __forceinline__ void demod_body(const D
 
     const int t = (int)threadIdx.x;
     const int nblocks = a.g.nb_symbols - 1;
-    const int frame = (int)blockIdx.x / a.runs_per_frame;
-    const int run = (int)blockIdx.x - frame * a.runs_per_frame;
-    const int b0 = run * a.syms_per_run;
-    const int b1 = min(b0 + a.syms_per_run, nblocks);
-    if (frame >= a.n_frames || b0 >= b1) return;
+    const RxRun r = rx_run(a);
+    if (r.idle) return;
+    const int frame = r.frame, b0 = r.b0, b1 = r.b1;
 
     cf tw[F::NTW > 0 ? F::NTW : 1];
     F::template load_twiddles<false>(a.t.twiddle, t, tw);
     if (t < WORDS) blk[t] = 0u;            // (ordered in front of the first OR by the barriers of the first transform)
 
-    // the lane's six carriers: slot, and where the carrier's two bits go in the LDS image (word, bit inside the word)
-    // (slot 0 of lane 0 is the DC bin: its first carrier is bin 3T, slot 3; selected by value, never by a register index)
-    constexpr int rr[6] = {0, 1, 2, 5, 6, 7};
+    // the lane's six carriers: where the carrier's two bits go in the LDS image (word, bit inside the word)
     int iword[6], qword[6], nsoft[SOFT ? 6 : 1];
     unsigned shift[6];
     int kpos[CSI ? 6 : 1];
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
-        const int bin = t + T * ((c == 0 && t == 0) ? 3 : rr[c]);
-        const int k = (bin <= K / 2) ? bin - 1 : bin - N + K;
+        const int k = C::position(c, t);
         const int n = a.t.src_carrier[k];
         const int ib = n >> 3, qb = ib + K / 8;
         iword[c] = ib >> 2;
@@ -82,29 +73,14 @@ template <int LOGN, int FORM> __device__ __forceinline__ void demod_body(const D
         for (int c = 0; c < 6; ++c) wgt[c] = a.csi_w[(size_t)frame * K + (size_t)kpos[c]];
     }
 
-    const size_t first = (size_t)a.g.null_size + (size_t)(a.g.sym_size - N - a.early);      // window of symbol 1
-    const float2 *in_f = reinterpret_cast<const float2 *>(a.iq) + (size_t)frame * a.frame_stride + first;
-    const uint32_t *in_s = reinterpret_cast<const uint32_t *>(a.iq) + (size_t)frame * a.frame_stride + first;
-    auto load = [&](int s, cf *v) __attribute__((always_inline)) {      // symbol s >= 1 of the frame
-        const size_t off = (size_t)(s - 1) * (size_t)a.g.sym_size + (size_t)t;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            if (a.fmt == 0) {
-                v[m] = in_f[off + T * m];
-            } else {
-                const uint32_t w = in_s[off + T * m];                   // s16 pair: re in the low half
-                v[m] = mk((float)(short)(w & 0xffffu), (float)(short)(w >> 16));
-            }
-        }
-    };
-
+    const RxWindows<N> w(a, frame);
+    auto load = [&](int s, cf *v) __attribute__((always_inline)) { C::load(a, w, s, t, v); };      // (a lambda: see SixCarriers::load)
     int par = 0;
-    cf v[8], prev[6];
+    cf v[8];
+    C six;
     load(b0 + 1, v);
     F::template run<-1, true, cf, false>(v, xbuf, par, tw, t);
-#pragma unroll
-    for (int c = 0; c < 6; ++c) prev[c] = v[rr[c]];
-    if (t == 0) prev[0] = v[3];
+    six.start(v, t);
 
     const size_t block_words = (size_t)frame * (size_t)nblocks * WORDS;
     uint32_t *soft_out = SOFT ? reinterpret_cast<uint32_t *>(a.soft_out) + (size_t)frame * (size_t)nblocks * (3 * T) : nullptr;
@@ -118,9 +94,8 @@ template <int LOGN, int FORM> __device__ __forceinline__ void demod_body(const D
         float sre[SOFT ? 6 : 1], sim[SOFT ? 6 : 1];
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
-            const cf z = (c == 0 && t == 0) ? v[3] : v[rr[c]], p = prev[c];
-            const float dre = fmaf(z.x, p.x, z.y * p.y), dim = fmaf(z.y, p.x, -(z.x * p.y));      // z conj(p)
-            prev[c] = z;
+            const cf d = six.against_previous(v, c, t);
+            const float dre = d.x, dim = d.y;
             if constexpr (SOFT) { sre[c] = dre; sim[c] = dim; }
             const unsigned I = dre < 0.f ? 1u : 0u, Q = dim < 0.f ? 1u : 0u;
             if (I) atomicOr(&blk[iword[c]], 1u << shift[c]);
@@ -137,9 +112,7 @@ template <int LOGN, int FORM> __device__ __forceinline__ void demod_body(const D
         acc_q += (double)pq;
         if constexpr (SOFT) {
             // the symbol's power: the butterfly leaves the same sum in every lane of the wave (a + b = b + a exactly)
-            float pw = ps;
-#pragma unroll
-            for (int off = WL / 2; off >= 1; off >>= 1) pw += __shfl_xor(pw, off, WL);
+            const float pw = wave_sum_w<WL>(ps);
             if ((t & 63) == 0) red_p[t >> 6] = pw;
         }
         lds_barrier();
@@ -230,35 +203,20 @@ template <int LOGN> __global__ __launch_bounds__(State64<LOGN>::LANES) void demo
     double *red = reinterpret_cast<double *>(state64_lds + 2 * N + N / 2);
 
     const int t = (int)threadIdx.x;
-    const int nblocks = a.g.nb_symbols - 1;
-    const int frame = (int)blockIdx.x / a.runs_per_frame;
-    const int run = (int)blockIdx.x - frame * a.runs_per_frame;
-    const int b0 = run * a.syms_per_run;
-    const int b1 = min(b0 + a.syms_per_run, nblocks);
-    if (frame >= a.n_frames || b0 >= b1) return;
+    const RxRun r = rx_run(a);
+    if (r.idle) return;
+    const int frame = r.frame, b0 = r.b0, b1 = r.b1;
 
-    for (int m = t; m < N / 2; m += LANES) {
-        double sn, cs;
-        sincospi(-2.0 * (double)m / (double)N, &sn, &cs);
-        wtab[m] = make_double2(cs, sn);
-    }
-
-    const size_t first = (size_t)a.g.null_size + (size_t)(a.g.sym_size - N - a.early);      // window of symbol 1
-    const float2 *in_f = reinterpret_cast<const float2 *>(a.iq) + (size_t)frame * a.frame_stride + first;
-    const uint32_t *in_s = reinterpret_cast<const uint32_t *>(a.iq) + (size_t)frame * a.frame_stride + first;
+    for (int m = t; m < N / 2; m += LANES) wtab[m] = twiddle64(m, N);
+    const RxWindows<N> w(a, frame);
 
     // symbol s >= 1 of the frame -> its N bins in natural order; returns the buffer that holds them
     auto transform = [&](int s) __attribute__((always_inline)) -> const double2 * {
-        const size_t off = (size_t)(s - 1) * (size_t)a.g.sym_size;
+        const long long off = w.of(s);
         lds_barrier();                                           // (the readers of the symbol before are done; wtab is written)
         for (int i = t; i < N; i += LANES) {
-            if (a.fmt == 0) {
-                const float2 x = in_f[off + i];
-                buf[0][i] = make_double2((double)x.x, (double)x.y);
-            } else {
-                const uint32_t w = in_s[off + i];                // s16 pair: re in the low half
-                buf[0][i] = make_double2((double)(short)(w & 0xffffu), (double)(short)(w >> 16));
-            }
+            const cf x = ld_iq(a.iq, a.fmt, off + i);
+            buf[0][i] = make_double2((double)x.x, (double)x.y);
         }
         lds_barrier_vm();
         int cur = 0, wstep = N / 2;                              // wstep = N / (2 ns)
@@ -286,7 +244,7 @@ template <int LOGN> __global__ __launch_bounds__(State64<LOGN>::LANES) void demo
 #pragma unroll
     for (int c = 0; c < PER; ++c) {
         const int k = t + LANES * c;
-        bin[c] = k < K / 2 ? k + 1 : k - K + N;                  // (k >= K: a bin inside the table, never used)
+        bin[c] = position_bin<N>(k);                             // (k >= K: a bin inside the table, never used)
         if (k >= K) bin[c] = 0;
         sum_a[c] = sum_v[c] = 0;
     }
@@ -400,53 +358,23 @@ hipError_t launch_demod(const DemodArgs &a, hipStream_t s)
         (a.fmt != 0 && a.fmt != 1) || a.g.K != 3 * a.g.N / 4)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)a.n_frames * (unsigned)a.runs_per_frame);
-    if (a.csi_sums) {                       // the first pass of the weighted call: the carrier state alone
-        // (more than 64 KiB of dynamic LDS has to be asked for)
-#define STATE64_LAUNCH(L)                                                                                                  \
-        do {                                                                                                               \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(demod_csi_state_kernel<L>),                  \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)State64<L>::LDS_BYTES);    \
-            if (e != hipSuccess) return e;                                                                                 \
-            DABGPU_LAUNCH(demod_csi_state_kernel<L>, grid, dim3(State64<L>::LANES), State64<L>::LDS_BYTES, s, a);          \
-        } while (0)
-        switch (a.g.logN) {
-        case 8: STATE64_LAUNCH(8); break;
-        case 9: STATE64_LAUNCH(9); break;
-        case 10: STATE64_LAUNCH(10); break;
-        case 11: STATE64_LAUNCH(11); break;
-        default: return hipErrorInvalidValue;
-        }
-#undef STATE64_LAUNCH
-        return hipGetLastError();
-    }
-    if (a.soft_out && a.csi_w) {            // the second pass: weighted softs, the hard call's bits and figures
-        switch (a.g.logN) {
-        case 8: DABGPU_LAUNCH(demod_csi_soft_kernel<8>, grid, dim3(Fft<8>::T), 0, s, a); break;
-        case 9: DABGPU_LAUNCH(demod_csi_soft_kernel<9>, grid, dim3(Fft<9>::T), 0, s, a); break;
-        case 10: DABGPU_LAUNCH(demod_csi_soft_kernel<10>, grid, dim3(Fft<10>::T), 0, s, a); break;
-        case 11: DABGPU_LAUNCH(demod_csi_soft_kernel<11>, grid, dim3(Fft<11>::T), 0, s, a); break;
-        default: return hipErrorInvalidValue;
+    return by_fft_size(a.g.logN, [&](auto L) {
+        const dim3 block(Fft<L>::T);
+        if (a.csi_sums) {                   // the first pass of the weighted call: the carrier state alone
+            typedef State64<L> S;           // (more than 64 KiB of dynamic LDS has to be asked for)
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(demod_csi_state_kernel<L>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::LDS_BYTES);
+            if (e != hipSuccess) return e;
+            DABGPU_LAUNCH_T(demod_csi_state_kernel, (L), grid, dim3(S::LANES), S::LDS_BYTES, s, a);
+        } else if (a.soft_out && a.csi_w) { // the second pass: weighted softs, the hard call's bits and figures
+            DABGPU_LAUNCH_T(demod_csi_soft_kernel, (L), grid, block, 0, s, a);
+        } else if (a.soft_out) {
+            DABGPU_LAUNCH_T(demod_soft_kernel, (L), grid, block, 0, s, a);
+        } else {
+            DABGPU_LAUNCH_T(demod_kernel, (L), grid, block, 0, s, a);
         }
         return hipGetLastError();
-    }
-    if (a.soft_out) {
-        switch (a.g.logN) {
-        case 8: DABGPU_LAUNCH(demod_soft_kernel<8>, grid, dim3(Fft<8>::T), 0, s, a); break;
-        case 9: DABGPU_LAUNCH(demod_soft_kernel<9>, grid, dim3(Fft<9>::T), 0, s, a); break;
-        case 10: DABGPU_LAUNCH(demod_soft_kernel<10>, grid, dim3(Fft<10>::T), 0, s, a); break;
-        case 11: DABGPU_LAUNCH(demod_soft_kernel<11>, grid, dim3(Fft<11>::T), 0, s, a); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (a.g.logN) {
-    case 8: DABGPU_LAUNCH(demod_kernel<8>, grid, dim3(Fft<8>::T), 0, s, a); break;
-    case 9: DABGPU_LAUNCH(demod_kernel<9>, grid, dim3(Fft<9>::T), 0, s, a); break;
-    case 10: DABGPU_LAUNCH(demod_kernel<10>, grid, dim3(Fft<10>::T), 0, s, a); break;
-    case 11: DABGPU_LAUNCH(demod_kernel<11>, grid, dim3(Fft<11>::T), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    });
 }
 
 hipError_t launch_csi_weights(const unsigned long long *sums, float *w, int K, int n_frames, bool unit, hipStream_t s)

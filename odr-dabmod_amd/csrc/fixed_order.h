@@ -1,6 +1,7 @@
-// fixed_order.h -- what the kernels that must repeat bit for bit share (sync.hip, tii_scan.hip): workgroup sums and searches in
-// a FIXED order -- the lane's own terms, an xor butterfly inside the wave, the waves in wave order through LDS; ties go to the
-// first index -- and the phase reference symbol's quarter turns.  Anonymous namespace, as device_common.h.
+// fixed_order.h -- what the kernels that must repeat bit for bit share (sync.hip, tii_scan.hip, cir.hip; through rx_symbols.h
+// demod.hip and the estimator of clock.hip): workgroup sums and searches in a FIXED order -- the lane's own terms, an xor
+// butterfly inside the wave, the waves in wave order through LDS; ties go to the first index -- the phase reference symbol's
+// quarter turns, which bins carry a carrier, and the float64 twiddle.  Anonymous namespace, as device_common.h.
 #pragma once
 #include "device_common.h"
 
@@ -59,6 +60,16 @@ template <bool MAX, int NW, int WL, typename V> DEV void group_arg(V &v, int &i,
 
 // position of carrier k (k = 1 ... K/2, -K/2 ... -1) in Tables::phase_q: the frame kernel's order, positive carriers first
 template <int K> DEV int carrier_pos(int k) { return k > 0 ? k - 1 : k + K; }
+// carrier of bin b of an N-point transform, and whether it is occupied (k = -K/2 ... -1, 1 ... K/2)
+DEV int bin_carrier(int b, int N) { return b <= N / 2 ? b : b - N; }
+DEV bool carrier_occupied(int k, int K) { return k != 0 && k >= -K / 2 && k <= K / 2; }
+// e^{-j 2 pi m / N} in float64 (sincospi of an exact argument): the twiddle of the float64 transforms
+DEV double2 twiddle64(int m, int N)
+{
+    double sn, cs;
+    sincospi(-2.0 * (double)m / (double)N, &sn, &cs);
+    return make_double2(cs, sn);
+}
 
 }  // namespace
 }  // namespace dabgpu

@@ -9,7 +9,7 @@
 // and ties go to the first index.  No floating-point atomics.
 #include "device_common.h"
 #include "turn_phase.h"      // ld_iq, turn_phase, turn_step
-#include "fixed_order.h"     // group_sum, group_arg, mul_quarter, carrier_pos
+#include "fixed_order.h"     // group_sum, group_arg, mul_quarter, carrier_pos, bin_carrier, carrier_occupied
 
 namespace dabgpu {
 namespace {
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(kCoarseThreads) void sync_coarse_kernel(SyncArgs a)
     __shared__ int red_i[NW];
     const int t = (int)threadIdx.x;
     const int B = a.g.N / 32, NB = a.g.null_size / B;
-    const long long tf = (long long)a.g.null_size + (long long)a.g.nb_symbols * a.g.sym_size;
+    const long long tf = frame_samples(a.g);
     const int nwin = min((int)(tf / B), a.nblk - NB + 1);
 
     double total = 0.;
@@ -88,7 +88,7 @@ template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void sync_frame_k
     const SyncHead head = *a.head;
     if (slot >= head.count) return;                                     // (its record stays zero: the API zeroes them all)
     const int L = a.g.nb_symbols, null = a.g.null_size, sym = a.g.sym_size, CP = sym - N;
-    const long long tf = (long long)null + (long long)L * sym;
+    const long long tf = frame_samples(a.g);
     const long long ck = head.coarse0 + (long long)slot * tf;           // ck + tf <= n: every read below lies inside the frame
 
     cf tw[F::NTW > 0 ? F::NTW : 1];
@@ -172,8 +172,8 @@ template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void sync_frame_k
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
         const int b = t + T * m;
-        const int k = b <= N / 2 ? b : b - N;
-        const bool occ = k != 0 && k >= -K / 2 && k <= K / 2;
+        const int k = bin_carrier(b, N);
+        const bool occ = carrier_occupied(k, K);
         const cf r = bins[(b + mstar) & (N - 1)];
         const unsigned q = a.t.phase_q[carrier_pos<K>(occ ? k : 1)];
         v[m] = occ ? mul_quarter(r, 0u - q) : mk(0.f, 0.f);
@@ -207,7 +207,7 @@ template <int LOGN> __global__ __launch_bounds__(Fft<LOGN>::T) void sync_frame_k
 // ---- 7. extraction: out[k][i] = x[start_k + i] e^{j phi_i}, phi from the 64-bit integer step; zeros for what is not valid ----
 template <int FMT> __global__ __launch_bounds__(256) void sync_extract_kernel(SyncArgs a, float2 *out)
 {
-    const long long tf = (long long)a.g.null_size + (long long)a.g.nb_symbols * a.g.sym_size;
+    const long long tf = frame_samples(a.g);
     const long long i = (long long)blockIdx.x * 256 + (long long)threadIdx.x;
     const int slot = (int)blockIdx.y;
     if (i >= tf) return;
@@ -224,7 +224,7 @@ template <int FMT> __global__ __launch_bounds__(256) void sync_extract_kernel(Sy
 
 bool sync_args_ok(const SyncArgs &a)
 {
-    const long long tf = (long long)a.g.null_size + (long long)a.g.nb_symbols * a.g.sym_size;
+    const long long tf = frame_samples(a.g);
     const int B = a.g.N / 32;
     return (a.fmt == 0 || a.fmt == 1) && a.g.K == 3 * a.g.N / 4 && a.g.logN >= 8 && a.g.logN <= 11 && a.iq && a.head &&
            a.frames && a.slots >= 1 && a.n >= 2 * tf + a.g.null_size && a.max_shift >= 0 && a.max_shift <= kSyncMaxShift &&
@@ -238,28 +238,18 @@ hipError_t launch_sync(const SyncArgs &a, hipStream_t s)
     if (!sync_args_ok(a) || !a.power) return hipErrorInvalidValue;
     const int B = a.g.N / 32;
     const dim3 pgrid((unsigned)(((long long)a.nblk * B + 255) / 256));
-    switch (a.g.logN) {
-    case 8: DABGPU_LAUNCH(sync_power_kernel<8>, pgrid, dim3(256), 0, s, a); break;
-    case 9: DABGPU_LAUNCH(sync_power_kernel<16>, pgrid, dim3(256), 0, s, a); break;
-    case 10: DABGPU_LAUNCH(sync_power_kernel<32>, pgrid, dim3(256), 0, s, a); break;
-    default: DABGPU_LAUNCH(sync_power_kernel<64>, pgrid, dim3(256), 0, s, a); break;
-    }
-    DABGPU_LAUNCH(sync_coarse_kernel, dim3(1), dim3(kCoarseThreads), 0, s, a);
-    const dim3 grid((unsigned)a.slots);
-    switch (a.g.logN) {
-    case 8: DABGPU_LAUNCH(sync_frame_kernel<8>, grid, dim3(Fft<8>::T), 0, s, a); break;
-    case 9: DABGPU_LAUNCH(sync_frame_kernel<9>, grid, dim3(Fft<9>::T), 0, s, a); break;
-    case 10: DABGPU_LAUNCH(sync_frame_kernel<10>, grid, dim3(Fft<10>::T), 0, s, a); break;
-    default: DABGPU_LAUNCH(sync_frame_kernel<11>, grid, dim3(Fft<11>::T), 0, s, a); break;
-    }
-    return hipGetLastError();
+    return by_fft_size(a.g.logN, [&](auto L) {
+        DABGPU_LAUNCH_T(sync_power_kernel, ((1 << L) / 32), pgrid, dim3(256), 0, s, a);
+        DABGPU_LAUNCH(sync_coarse_kernel, dim3(1), dim3(kCoarseThreads), 0, s, a);
+        DABGPU_LAUNCH_T(sync_frame_kernel, (L), dim3((unsigned)a.slots), dim3(Fft<L>::T), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_sync_extract(const SyncArgs &a, float2 *out, hipStream_t s)
 {
     if (!sync_args_ok(a) || !out) return hipErrorInvalidValue;
-    const long long tf = (long long)a.g.null_size + (long long)a.g.nb_symbols * a.g.sym_size;
-    const dim3 grid((unsigned)((tf + 255) / 256), (unsigned)a.slots);
+    const dim3 grid((unsigned)((frame_samples(a.g) + 255) / 256), (unsigned)a.slots);
     if (a.fmt == 0)
         DABGPU_LAUNCH(sync_extract_kernel<0>, grid, dim3(256), 0, s, a, out);
     else

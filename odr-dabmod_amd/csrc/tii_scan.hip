@@ -9,7 +9,7 @@
 // (fixed_order.h); no floating-point atomics.
 #include "device_common.h"
 #include "turn_phase.h"      // ld_iq, turn_phase
-#include "fixed_order.h"     // group_sum, group_arg, mul_quarter, carrier_pos
+#include "fixed_order.h"     // group_sum, group_arg, mul_quarter, carrier_pos, twiddle64
 
 namespace dabgpu {
 namespace {
@@ -44,15 +44,13 @@ template <int LOGN> __global__ __launch_bounds__((1 << LOGN) / 8) void tii_frame
     const int t = (int)threadIdx.x;
     const int f = (int)blockIdx.x;
     if (f >= a.n_frames) return;
-    const long long tf = (long long)a.g.null_size + (long long)a.g.nb_symbols * a.g.sym_size;
+    const long long tf = frame_samples(a.g);
     const long long w0 = (long long)f * tf + (long long)(a.g.null_size - a.early - N);       // 0 <= early <= null - N
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
         const int i = t + T * m;
         xs[i] = ld_iq(a.iq, a.fmt, w0 + i);
-        double sn, cs;
-        sincospi(-2.0 * (double)i / (double)N, &sn, &cs);               // (the argument is exact)
-        W[i] = make_double2(cs, sn);
+        W[i] = twiddle64(i, N);
     }
     lds_barrier();
     if (t >= kTiiCells) return;                                         // (Mode I's last wave; no barrier follows)
@@ -274,16 +272,14 @@ hipError_t launch_tii_scan(const TiiScanArgs &a, hipStream_t s)
         a.early < 0 || a.early > a.g.null_size - a.g.N || !a.iq || !a.rows || !a.bins || !a.head || !a.entries || !a.centre)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)a.n_frames);
-    if (a.g.logN == 11)
-        DABGPU_LAUNCH(tii_frame_kernel<11>, grid, dim3(2048 / 8), 0, s, a);
-    else
-        DABGPU_LAUNCH(tii_frame_kernel<9>, grid, dim3(512 / 8), 0, s, a);
-    DABGPU_LAUNCH(tii_decide_kernel, dim3(1), dim3(kDecideThreads), 0, s, a);
-    if (a.g.logN == 11)
-        DABGPU_LAUNCH(tii_delay_kernel<11>, dim3(kTiiCombs), dim3(kDelayThreads), 0, s, a);
-    else
-        DABGPU_LAUNCH(tii_delay_kernel<9>, dim3(kTiiCombs), dim3(kDelayThreads), 0, s, a);
-    return hipGetLastError();
+    return by_fft_size(a.g.logN, [&](auto L) {
+        if constexpr (L == 9 || L == 11) {                              // (the sizes the check above lets through)
+            DABGPU_LAUNCH_T(tii_frame_kernel, (L), grid, dim3((1 << L) / 8), 0, s, a);
+            DABGPU_LAUNCH(tii_decide_kernel, dim3(1), dim3(kDecideThreads), 0, s, a);
+            DABGPU_LAUNCH_T(tii_delay_kernel, (L), dim3(kTiiCombs), dim3(kDelayThreads), 0, s, a);
+        }
+        return hipGetLastError();
+    });
 }
 
 }  // namespace dabgpu

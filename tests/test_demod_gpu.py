@@ -111,7 +111,9 @@ def test_early_outside_the_cyclic_prefix_and_other_formats_are_refused(pkg):
 @pytest.mark.parametrize("mode", [1, 3])
 def test_run_geometry_gives_the_same_bits_and_the_same_sums(pkg, mode):
     """Symbols per workgroup forced to 1, 2, 7 (divides neither 75 nor 152) and the whole frame: the clean output decodes to
-    the input bits, the noisy one to the same bits every time, and its sums stay within the bars of the quality test."""
+    the input bits, the noisy one to the same bits every time, and its sums stay within the bars of the quality test.  The
+    same with the noisy frames as s16 (scaled into the format's range and truncated, as test_clock_gpu.py does): the same
+    bytes at every geometry and on repetition."""
     import torch
     md = pkg.Modulator(mode=mode, max_frames=3)
     try:
@@ -119,23 +121,30 @@ def test_run_geometry_gives_the_same_bits_and_the_same_sums(pkg, mode):
         nblocks = md.geometry["nb_symbols"] - 1
         bits = DC.case_bits(mode, 3, per)
         d_y = _chain(pkg, md, bits, 0)
-        d_n = torch.from_numpy(_noisy(d_y.cpu().numpy(), mode, 40 + mode)).cuda()
-        first = None
-        for spr in (1, 2, 7, nblocks):
-            assert nblocks % 7
-            md.set_demod_run_symbols(spr)
-            got, _ = _demod(md, d_y, 3, 0, ref=bits)
-            assert np.array_equal(got, bits), spr
-            nb, st = _demod(md, d_n, 3, 0, ref=bits)
-            if first is None:
-                first = (nb, st)
-                continue
-            assert np.array_equal(nb, first[0]), spr
-            for f in range(3):
-                assert st[f]["bit_errors"] == first[1][f]["bit_errors"]
-                assert st[f]["min_margin"] == first[1][f]["min_margin"]
-                assert abs(st[f]["sum_signal"] / first[1][f]["sum_signal"] - 1.0) <= BAR_SIGNAL
-                assert abs(st[f]["sum_quadrature"] / first[1][f]["sum_quadrature"] - 1.0) <= BAR_QUADRATURE
+        noisy = _noisy(d_y.cpu().numpy(), mode, 40 + mode)
+        scale = 20000.0 / float(np.abs(noisy.view(np.float32)).max())
+        q = np.trunc(noisy.view(np.float32).reshape(3, -1) * scale).astype(np.int16)
+        for fmt, d_n in (("complexf", torch.from_numpy(noisy).cuda()), ("s16", torch.from_numpy(q).cuda())):
+            first = None
+            for spr in (1, 2, 7, nblocks):
+                assert nblocks % 7
+                md.set_demod_run_symbols(spr)
+                if fmt == "complexf":
+                    got, _ = _demod(md, d_y, 3, 0, ref=bits)
+                    assert np.array_equal(got, bits), spr
+                nb, st = _demod(md, d_n, 3, 0, ref=bits)
+                if first is None:
+                    first = (nb, st)
+                if fmt == "s16":
+                    again, st2 = _demod(md, d_n, 3, 0, ref=bits)
+                    assert np.array_equal(again, nb), spr
+                    assert [s["bit_errors"] for s in st2] == [s["bit_errors"] for s in st], spr
+                assert np.array_equal(nb, first[0]), (fmt, spr)
+                for f in range(3):
+                    assert st[f]["bit_errors"] == first[1][f]["bit_errors"]
+                    assert st[f]["min_margin"] == first[1][f]["min_margin"]
+                    assert abs(st[f]["sum_signal"] / first[1][f]["sum_signal"] - 1.0) <= BAR_SIGNAL
+                    assert abs(st[f]["sum_quadrature"] / first[1][f]["sum_quadrature"] - 1.0) <= BAR_QUADRATURE
     finally:
         md.close()
 

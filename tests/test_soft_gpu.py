@@ -126,14 +126,19 @@ def test_run_geometry_and_repetition_give_the_same_soft_bytes(pkg, mode):
         nblocks = md.geometry["nb_symbols"] - 1
         bits = DC.case_bits(mode, 2, per)
         noisy = S.add_noise(md.chain(bits, 0).reshape(2, -1), mode, 8.0, 60 + mode).astype(np.complex64)
-        first = md.demod_soft(noisy)
-        assert len(np.unique(first)) > 200
-        assert np.array_equal(md.demod_soft(noisy), first)
-        for spr in (1, 2, 7, nblocks):
-            md.set_demod_run_symbols(spr)
-            soft, got = md.demod_soft(noisy, want_bits=True)
-            assert np.array_equal(soft, first), spr
-            assert np.array_equal(got, md.demod(noisy)), spr
+        # the same frames as s16: scaled into the format's range and truncated, as test_clock_gpu.py does
+        scale = 20000.0 / float(np.abs(noisy.view(np.float32)).max())
+        q = np.trunc(noisy.view(np.float32).reshape(2, -1) * scale).astype(np.int16)
+        for frames in (noisy, q):
+            md.set_demod_run_symbols(0)
+            first = md.demod_soft(frames)
+            assert len(np.unique(first)) > 200
+            assert np.array_equal(md.demod_soft(frames), first)
+            for spr in (1, 2, 7, nblocks):
+                md.set_demod_run_symbols(spr)
+                soft, got = md.demod_soft(frames, want_bits=True)
+                assert np.array_equal(soft, first), (frames.dtype, spr)
+                assert np.array_equal(got, md.demod(frames)), (frames.dtype, spr)
     finally:
         md.close()
 
