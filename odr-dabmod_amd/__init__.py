@@ -2091,66 +2091,56 @@ class Modulator:
         return out
 
     # ---- the channel decoder: coded bits -> the ETI payload (include/dabgpu.h, "the channel decoder") ----
+    def _decode_host(self, call, stats, data, dtype, per, what, ref_eti):
+        """decode() / decode_soft(): `per` input items per transmission frame, `what` names them in the refusal."""
+        data = np.ascontiguousarray(data, dtype).reshape(-1)
+        if data.size % per:
+            raise DabGpuError("decode: input size not valid (whole transmission frames of %s)" % what)
+        n_tf = data.size // per
+        n = n_tf * CIFS_PER_FRAME[self.geometry["mode"]]
+        ref = None
+        if ref_eti is not None:
+            ref = np.ascontiguousarray(ref_eti, np.uint8).reshape(-1)
+            if ref.size != n * ETI_FRAME_BYTES:
+                raise DabGpuError("decode: the reference is one 6144-byte ETI frame per output")
+        out = np.empty(max(n, 1) * ETI_FRAME_BYTES, np.uint8)
+        ob = C.c_size_t()
+        self._chk(call(self._h, data.ctypes.data, n_tf, out.ctypes.data, out.nbytes,
+                       ref.ctypes.data if ref is not None else None, C.byref(ob)))
+        return out[:ob.value].reshape(n, ETI_FRAME_BYTES), [stats(i) for i in range(n)]
+
+    def _decode_dev(self, call, d_in, n_tf, d_eti_out, d_ref_eti, stream, queued):
+        """decode_dev() / decode_soft_dev()."""
+        ob = C.c_size_t()
+        self._dev_call(call, d_in, stream, d_in.data_ptr(), n_tf, d_eti_out.data_ptr(),
+                       d_eti_out.numel() * d_eti_out.element_size(),
+                       d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob), queued=queued)
+        return ob.value
+
     def decode(self, bits, ref_eti=None):
         """Host path: whole transmission frames of coded bits (the chain's input layout) -> (eti_images, stats).  eti_images:
         (n, 6144) uint8, the decoded FIC and sub-channel payload at their places, zeros elsewhere; output i of the call
         that brings rows e ... is ETI frame e + i - 15 of the stream (decode_reference).  ref_eti: (n, 6144), counted
         against.  stats: decode_stats(i) per output."""
-        bits = np.ascontiguousarray(bits, np.uint8).reshape(-1)
-        per = self.geometry["tf_input_bytes"]
-        if bits.size % per:
-            raise DabGpuError("decode: input size not valid (whole transmission frames of coded bits)")
-        n_tf = bits.size // per
-        n = n_tf * CIFS_PER_FRAME[self.geometry["mode"]]
-        ref = None
-        if ref_eti is not None:
-            ref = np.ascontiguousarray(ref_eti, np.uint8).reshape(-1)
-            if ref.size != n * ETI_FRAME_BYTES:
-                raise DabGpuError("decode: the reference is one 6144-byte ETI frame per output")
-        out = np.empty(max(n, 1) * ETI_FRAME_BYTES, np.uint8)
-        ob = C.c_size_t()
-        self._chk(self._lib.dabgpu_decode(self._h, bits.ctypes.data, n_tf, out.ctypes.data, out.nbytes,
-                                          ref.ctypes.data if ref is not None else None, C.byref(ob)))
-        return out[:ob.value].reshape(n, ETI_FRAME_BYTES), [self.decode_stats(i) for i in range(n)]
+        return self._decode_host(self._lib.dabgpu_decode, self.decode_stats, bits, np.uint8, self.geometry["tf_input_bytes"],
+                                 "coded bits", ref_eti)
 
     def decode_dev(self, d_bits, n_tf, d_eti_out, d_ref_eti=None, stream=None, queued=False):
         """Device path on torch uint8 tensors, asynchronous on the stream (as chain_dev); the figures: decode_stats."""
-        ob = C.c_size_t()
-        self._dev_call(self._lib.dabgpu_decode_dev, d_bits, stream, d_bits.data_ptr(), n_tf, d_eti_out.data_ptr(),
-                       d_eti_out.numel() * d_eti_out.element_size(),
-                       d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob), queued=queued)
-        return ob.value
+        return self._decode_dev(self._lib.dabgpu_decode_dev, d_bits, n_tf, d_eti_out, d_ref_eti, stream, queued)
 
     def decode_soft(self, soft, ref_eti=None):
         """decode() on soft metrics: whole transmission frames of int8 softs in demod_soft()'s layout (8 per coded byte; any
         int8, -128 counts with magnitude 128) -> (eti_images, stats), stats: decode_soft_stats(i) per output.  A stream of its
         own beside decode()'s: the two histories do not see each other."""
-        soft = np.ascontiguousarray(soft, np.int8).reshape(-1)
-        per = 8 * self.geometry["tf_input_bytes"]
-        if soft.size % per:
-            raise DabGpuError("decode: input size not valid (whole transmission frames of soft metrics)")
-        n_tf = soft.size // per
-        n = n_tf * CIFS_PER_FRAME[self.geometry["mode"]]
-        ref = None
-        if ref_eti is not None:
-            ref = np.ascontiguousarray(ref_eti, np.uint8).reshape(-1)
-            if ref.size != n * ETI_FRAME_BYTES:
-                raise DabGpuError("decode: the reference is one 6144-byte ETI frame per output")
-        out = np.empty(max(n, 1) * ETI_FRAME_BYTES, np.uint8)
-        ob = C.c_size_t()
-        self._chk(self._lib.dabgpu_decode_soft(self._h, soft.ctypes.data, n_tf, out.ctypes.data, out.nbytes,
-                                               ref.ctypes.data if ref is not None else None, C.byref(ob)))
-        return out[:ob.value].reshape(n, ETI_FRAME_BYTES), [self.decode_soft_stats(i) for i in range(n)]
+        return self._decode_host(self._lib.dabgpu_decode_soft, self.decode_soft_stats, soft, np.int8,
+                                 8 * self.geometry["tf_input_bytes"], "soft metrics", ref_eti)
 
     def decode_soft_dev(self, d_soft, n_tf, d_eti_out, d_ref_eti=None, stream=None, queued=False):
         """Device path on torch tensors (int8 softs, uint8 images), asynchronous on the stream; the figures: decode_soft_stats."""
         if d_soft.numel() * d_soft.element_size() != 8 * n_tf * self.geometry["tf_input_bytes"]:
             raise DabGpuError("decode: input size not valid (whole transmission frames of soft metrics)")
-        ob = C.c_size_t()
-        self._dev_call(self._lib.dabgpu_decode_soft_dev, d_soft, stream, d_soft.data_ptr(), n_tf, d_eti_out.data_ptr(),
-                       d_eti_out.numel() * d_eti_out.element_size(),
-                       d_ref_eti.data_ptr() if d_ref_eti is not None else None, C.byref(ob), queued=queued)
-        return ob.value
+        return self._decode_dev(self._lib.dabgpu_decode_soft_dev, d_soft, n_tf, d_eti_out, d_ref_eti, stream, queued)
 
     def decode_soft_stats(self, frame, unit=-1):
         """Output `frame` of the most recent decode_soft() / decode_soft_dev() (waits for it): valid, metric, contra_sum (always

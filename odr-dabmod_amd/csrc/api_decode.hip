@@ -47,25 +47,21 @@ int check_decode(dabgpu_ctx *c, size_t n_tf, size_t out_cap, size_t *out_bytes)
     return check_out(c, n_tf * (size_t)c->fe_cifs * 6144, out_cap, out_bytes);
 }
 
-// What differs between the two metric widths beside DecodeStream::width: the args struct, where the input goes in it, the
-// LDS figure (hard: the steps of the layout's longest unit; soft: 8 x the punctured bytes of its largest) and the launches.
-void set_input(DecArgs &a, const dabgpu_ctx *c, const void *d_bits)
+// What differs between the two metric widths beside DecodeStream::width and the args struct: the LDS figure (hard: the steps
+// of the layout's longest unit; soft: 8 x the punctured bytes of its largest).
+int lds_bytes(const DecArgs &, const dabgpu_ctx *c)
 {
-    a.bits = (const uint8_t *)d_bits;
+    int steps = 0;
     const std::vector<uint32_t> &slot = c->decode.slot;
-    for (size_t u = 0; u + 1 < slot.size(); ++u) a.sym_bytes = std::max(a.sym_bytes, (int)(slot[u + 1] - slot[u]));
+    for (size_t u = 0; u + 1 < slot.size(); ++u) steps = std::max(steps, (int)(slot[u + 1] - slot[u]));
+    return steps;
 }
-void set_input(DecSoftArgs &a, const dabgpu_ctx *c, const void *d_soft)
+int lds_bytes(const DecSoftArgs &, const dabgpu_ctx *c)
 {
-    a.soft = (const int8_t *)d_soft;
     unsigned out_bytes = (unsigned)c->fe_fic_out;
     for (uint32_t i = 0; i < c->fe_layout.nst; ++i) out_bytes = std::max(out_bytes, 8u * (unsigned)c->fe_layout.sub[i].cu);
-    a.lds_bytes = (int)(8 * out_bytes);
+    return (int)(8 * out_bytes);
 }
-hipError_t launch_rows(const DecArgs &a, hipStream_t s) { return launch_dec_rows(a, s); }
-hipError_t launch_rows(const DecSoftArgs &a, hipStream_t s) { return launch_dec_soft_rows(a, s); }
-hipError_t launch_decode(const DecArgs &a, hipStream_t s) { return launch_dec_decode(a, s); }
-hipError_t launch_decode(const DecSoftArgs &a, hipStream_t s) { return launch_dec_soft_decode(a, s); }
 
 // one call on `s`, for either width (Args: DecArgs on st = decode.hard, DecSoftArgs on decode.soft).  The buffers of the
 // first use: rows, survivor scratch and records for max_frames transmission frames.
@@ -87,7 +83,8 @@ int queue_decode(dabgpu_ctx *c, DecodeStream &st, const void *d_in, size_t n_tf,
         st.zero_pending = false;
     }
     HIPCHK(c, hipMemsetAsync(d_out, 0, n * 6144, s));
-    set_input(a, c, d_in);
+    a.in = (decltype(a.in))d_in;
+    a.lds_bytes = lds_bytes(a, c);
     a.rows = (decltype(a.rows))st.rows.p;
     a.prbs = (const uint8_t *)c->d_fe_prbs.p;
     a.units = (const FeUnit *)c->d_fe_units.p;
@@ -99,8 +96,8 @@ int queue_decode(dabgpu_ctx *c, DecodeStream &st, const void *d_in, size_t n_tf,
     a.n_out = (int)n; a.n_units = c->fe_units; a.cifs = c->fe_cifs; a.fic_out = c->fe_fic_out;
     const unsigned long long lead = st.pos < (unsigned long long)kFeHistory ? (unsigned long long)kFeHistory - st.pos : 0;
     a.first_valid = (int)std::min<unsigned long long>(lead, n);
-    HIPCHK(c, launch_rows(a, s));
-    HIPCHK(c, launch_decode(a, s));
+    HIPCHK(c, launch_dec_rows(a, s));
+    HIPCHK(c, launch_dec_decode(a, s));
     // the last fifteen rows move to the front, in stream order (through a second buffer where they overlap)
     const char *last = (const char *)st.rows.p + n * row;
     if (n >= (size_t)kFeHistory) {
@@ -147,6 +144,25 @@ int decode_host(dabgpu_ctx *c, DecodeStream &st, const void *in, size_t n_tf, ui
     HIPCHK(c, c->decode.out.reserve(need));
     if ((rc = queue_decode<Args>(c, st, st.in.p, n_tf, c->decode.out.p, ref_eti ? c->decode.ref.p : nullptr, c->stream))) return rc;
     return io.out(eti_out, c->decode.out.p, need);
+}
+
+// The statistics getter of either width: the checks, the wait for the call, the frame's records (Unit each) from the device,
+// *out zeroed but for `valid`; add(record) sums one unit's record into *out.  `none`: the refusal of a frame without figures
+template <typename Unit, typename Out, typename Add>
+int get_stats(dabgpu_ctx *c, DecodeStream DecodeState::*which, const char *none, size_t frame, int unit, Out *out, Add add)
+{
+    CTXCHK(c);
+    if (!out) return fail(c, DABGPU_E_INVALID, "null argument");
+    const DecodeStream &st = c->decode.*which;
+    if (frame >= st.frames) return fail(c, DABGPU_E_INVALID, none);
+    if (unit < -1 || unit >= c->fe_units) return fail(c, DABGPU_E_INVALID, "decode: unit is -1 (the frame), 0 (the FIC) or 1 + a sub-channel");
+    HIPCHK(c, wait_result(c, st.stream));
+    std::vector<Unit> rec((size_t)c->fe_units);
+    HIPCHK(c, hipMemcpy(rec.data(), (const Unit *)st.stats.p + frame * (size_t)c->fe_units, rec.size() * sizeof(Unit), hipMemcpyDeviceToHost));
+    std::memset(out, 0, sizeof *out);
+    out->valid = frame >= st.first_valid;
+    for (int u = unit < 0 ? 0 : unit; u < (unit < 0 ? c->fe_units : unit + 1); ++u) add(rec[u]);
+    return DABGPU_OK;
 }
 
 // both streams back at their start: the next call of each zeroes its history
@@ -218,24 +234,13 @@ int dabgpu_decode(dabgpu_ctx *c, const uint8_t *bits, size_t n_tf, uint8_t *eti_
 
 int dabgpu_get_decode_stats(dabgpu_ctx *c, size_t frame, int unit, dabgpu_decode_stats *out)
 {
-    CTXCHK(c);
-    if (!out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (frame >= c->decode.hard.frames)
-        return fail(c, DABGPU_E_INVALID, "no decoder statistics for this frame (no call yet, or frame index out of range)");
-    if (unit < -1 || unit >= c->fe_units) return fail(c, DABGPU_E_INVALID, "decode: unit is -1 (the frame), 0 (the FIC) or 1 + a sub-channel");
-    HIPCHK(c, wait_result(c, c->decode.hard.stream));
-    std::vector<DecUnitStats> st((size_t)c->fe_units);
-    HIPCHK(c, hipMemcpy(st.data(), (const DecUnitStats *)c->decode.hard.stats.p + frame * (size_t)c->fe_units,
-                        st.size() * sizeof(DecUnitStats), hipMemcpyDeviceToHost));
-    std::memset(out, 0, sizeof *out);
-    out->valid = frame >= c->decode.hard.first_valid;
-    for (int u = unit < 0 ? 0 : unit; u < (unit < 0 ? c->fe_units : unit + 1); ++u) {
-        out->corrected += st[u].corrected;
-        out->coded_bits += st[u].coded_bits;
-        out->bit_errors += st[u].bit_errors;
-        out->n_bits += st[u].n_bits;
-    }
-    return DABGPU_OK;
+    return get_stats<DecUnitStats>(c, &DecodeState::hard, "no decoder statistics for this frame (no call yet, or frame index out of range)",
+                                   frame, unit, out, [&](const DecUnitStats &u) {
+                                       out->corrected += u.corrected;
+                                       out->coded_bits += u.coded_bits;
+                                       out->bit_errors += u.bit_errors;
+                                       out->n_bits += u.n_bits;
+                                   });
 }
 
 int dabgpu_decode_soft_dev(dabgpu_ctx *c, const void *d_soft, size_t n_tf, void *d_eti_out, size_t out_cap, const void *d_ref_eti,
@@ -253,28 +258,18 @@ int dabgpu_decode_soft(dabgpu_ctx *c, const int8_t *soft, size_t n_tf, uint8_t *
 
 int dabgpu_get_decode_soft_stats(dabgpu_ctx *c, size_t frame, int unit, dabgpu_decode_soft_stats *out)
 {
-    CTXCHK(c);
-    if (!out) return fail(c, DABGPU_E_INVALID, "null argument");
-    if (frame >= c->decode.soft.frames)
-        return fail(c, DABGPU_E_INVALID, "no soft decoder statistics for this frame (no call yet, or frame index out of range)");
-    if (unit < -1 || unit >= c->fe_units) return fail(c, DABGPU_E_INVALID, "decode: unit is -1 (the frame), 0 (the FIC) or 1 + a sub-channel");
-    HIPCHK(c, wait_result(c, c->decode.soft.stream));
-    std::vector<DecSoftUnitStats> st((size_t)c->fe_units);
-    HIPCHK(c, hipMemcpy(st.data(), (const DecSoftUnitStats *)c->decode.soft.stats.p + frame * (size_t)c->fe_units,
-                        st.size() * sizeof(DecSoftUnitStats), hipMemcpyDeviceToHost));
-    std::memset(out, 0, sizeof *out);
-    out->valid = frame >= c->decode.soft.first_valid;
-    for (int u = unit < 0 ? 0 : unit; u < (unit < 0 ? c->fe_units : unit + 1); ++u) {
-        out->metric += st[u].metric;
-        out->contra_sum += st[u].contra_sum;
-        out->soft_sum += st[u].soft_sum;
-        out->corrected += st[u].corrected;
-        out->erasures += st[u].erasures;
-        out->coded_bits += st[u].coded_bits;
-        out->bit_errors += st[u].bit_errors;
-        out->n_bits += st[u].n_bits;
-    }
-    return DABGPU_OK;
+    return get_stats<DecSoftUnitStats>(c, &DecodeState::soft,
+                                       "no soft decoder statistics for this frame (no call yet, or frame index out of range)", frame, unit, out,
+                                       [&](const DecSoftUnitStats &u) {
+                                           out->metric += u.metric;
+                                           out->contra_sum += u.contra_sum;
+                                           out->soft_sum += u.soft_sum;
+                                           out->corrected += u.corrected;
+                                           out->erasures += u.erasures;
+                                           out->coded_bits += u.coded_bits;
+                                           out->bit_errors += u.bit_errors;
+                                           out->n_bits += u.n_bits;
+                                       });
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include <initializer_list>
 #include <type_traits>
 
+#include "conv_code.h"
 #include "resampler_runs.h"
 
 namespace dabgpu {
@@ -442,19 +443,7 @@ hipError_t launch_format(const float *in, size_t nfloats, int fmt, void *out, un
 hipError_t launch_lut(const float2 *in, size_t nsamples, float scale, const float *lut,
                       float2 *out, hipStream_t s);
 
-// The front-end (frontend.hip).  One FeUnit per FIC / sub-channel: where its payload lies in the ETI frame, where its punctured
-// bytes go, and the flattened puncturing segments -- segment r covers the 4-byte groups g0[r] ... g0[r + 1] - 1 of the mother
-// code's output with pattern pat[r], its first kept bit at bit base[r] of the unit's output; entry nseg is the 24-bit tail.
-constexpr int kFeCifBytes = 864 * 8;      // one CIF; also the length of the dispersal table
-constexpr int kFeHistory = 15;            // frames the time interleaver looks back
-struct FeUnit {
-    uint32_t in_off, in_bytes;            // payload inside the 6144-byte frame
-    uint32_t out_bytes;                   // punctured and padded: the FIC's 288 / 384, or 8 x CU
-    uint32_t dst_off;                     // byte offset inside the CIF row (8 x SAD); 0 for the FIC
-    int32_t owner;                        // sub-channel index in STC order; -1: the FIC
-    uint32_t nseg;
-    uint32_t g0[6], base[6], pat[6];      // (4 rules + the tail + the end)
-};
+// The front-end (frontend.hip).  FeUnit, a unit's place in the frame and its puncturing segments: conv_code.h.
 struct FeArgs {
     const uint8_t *eti;                   // n_eti x 6144
     const uint8_t *prbs;                  // kFeCifBytes: the x^9 + x^5 + 1 sequence
@@ -480,42 +469,34 @@ constexpr int kDecMaxSteps = 48 * 1024;   // trellis steps of one unit the kerne
 struct DecUnitStats {                     // per (output, unit); plain stores, every record of a launch is written
     uint32_t corrected, coded_bits, bit_errors, n_bits;
 };
-struct DecArgs {
-    const uint8_t *bits;                  // n_tf transmission frames in the chain's input layout (dword aligned)
-    uint8_t *rows;                        // (kFeHistory + n_out) x (fic_out + kFeCifBytes)
+struct DecSoftUnitStats {
+    uint32_t metric, contra_sum, soft_sum, corrected, erasures, coded_bits, bit_errors, n_bits;
+};
+// One struct for either metric width, hard (In = uint8_t: coded bits, rows of fic_out + kFeCifBytes bytes) and soft (In =
+// int8_t: one metric per coded bit, rows eight times as long); survivor scratch and slots are shared
+template <typename In, typename Stats>
+struct DecArgsT {
+    const In *in;                         // n_tf transmission frames in the chain's input layout, soft: x 8 (dword aligned)
+    In *rows;                             // (kFeHistory + n_out) rows
     const uint8_t *prbs;
     const FeUnit *units;
     const uint32_t *slot;                 // n_units + 1: where a unit's survivor words start inside an output's scratch
     unsigned long long *surv;             // n_out x slot[n_units] survivor words
     uint8_t *out;                         // n_out x 6144, zeroed before the launch
     const uint8_t *ref;                   // nullptr, or n_out x 6144
-    DecUnitStats *stats;                  // n_out x n_units
+    Stats *stats;                         // n_out x n_units
     int n_out, n_units, cifs, fic_out;
-    int sym_bytes;                        // the steps of the layout's longest unit, rounded up to 64: the workgroup's LDS
+    // what sizes the workgroup's LDS.  Hard: the steps of the layout's longest unit, rounded up to 64.  Soft: 8 x out_bytes
+    // of the layout's largest unit, the punctured softs a workgroup stages
+    int lds_bytes;
     int first_valid;                      // outputs before this one lie before the start of the stream: nothing is decoded
 };
+using DecArgs = DecArgsT<uint8_t, DecUnitStats>;
+using DecSoftArgs = DecArgsT<int8_t, DecSoftUnitStats>;
 hipError_t launch_dec_rows(const DecArgs &a, hipStream_t s);
+hipError_t launch_dec_rows(const DecSoftArgs &a, hipStream_t s);
 hipError_t launch_dec_decode(const DecArgs &a, hipStream_t s);
-// The soft decoder: the same on int8 metrics, one per coded bit (rows eight times as long); survivor scratch and slots shared
-struct DecSoftUnitStats {                 // per (output, unit); plain stores, every record of a launch is written
-    uint32_t metric, contra_sum, soft_sum, corrected, erasures, coded_bits, bit_errors, n_bits;
-};
-struct DecSoftArgs {
-    const int8_t *soft;                   // n_tf x 8 tf_input_bytes (dword aligned)
-    int8_t *rows;                         // (kFeHistory + n_out) x 8 (fic_out + kFeCifBytes)
-    const uint8_t *prbs;
-    const FeUnit *units;
-    const uint32_t *slot;
-    unsigned long long *surv;
-    uint8_t *out;                         // n_out x 6144, zeroed before the launch
-    const uint8_t *ref;                   // nullptr, or n_out x 6144
-    DecSoftUnitStats *stats;              // n_out x n_units
-    int n_out, n_units, cifs, fic_out;
-    int lds_bytes;                        // 8 x out_bytes of the layout's largest unit: the punctured softs a workgroup stages
-    int first_valid;
-};
-hipError_t launch_dec_soft_rows(const DecSoftArgs &a, hipStream_t s);
-hipError_t launch_dec_soft_decode(const DecSoftArgs &a, hipStream_t s);
+hipError_t launch_dec_decode(const DecSoftArgs &a, hipStream_t s);
 
 // Resampler (reference src/Resampler.cpp:131-195), power-of-two FFT sizes.
 struct ResamplerArgs {

@@ -9,7 +9,8 @@
 //   fe_assemble_kernel  one lane per output dword: the 16-frame time interleaver (src/TimeInterleaver.cpp:66-93), the CIF over
 //                       its padding (FrameMultiplexer, src/FrameMultiplexer.cpp:58-92) and the BlockPartitioner layout
 //                       (src/BlockPartitioner.cpp:111-117).
-// Integer work on independent bits: the same bytes as the CPU classes of host/Frontend.cpp.
+// Integer work on independent bits: the same bytes as the CPU classes of host/Frontend.cpp.  The code itself -- mother_code,
+// keep_bits, the segment lookup, delay_mask, the frame's words as rows -- is conv_code.h's, shared with decode.hip.
 #include "dabgpu_internal.h"
 
 namespace dabgpu {
@@ -18,33 +19,6 @@ namespace {
 
 constexpr int kFeThreads = 256;
 constexpr int kFeRowWords = kFeCifBytes / 4;
-
-// The 32 code bits of one input byte: they depend on the byte and on the six bits before it.  The reference's register is
-// seven bits wide, the new bit enters at bit 6, and the generators 133, 171, 145, 133 (octal) read it as the masks 0x5b, 0x79,
-// 0x65, 0x5b.  Here the last 14 input bits sit in `s` oldest first (MSB), so the window of step k is the register mirrored,
-// and so are the masks: 0x6d, 0x4f, 0x53, 0x6d.
-__device__ __forceinline__ uint32_t mother_code(uint32_t prev, uint32_t byte)
-{
-    const uint32_t s = ((prev & 0x3fu) << 8) | byte;
-    uint32_t w = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t win = (s >> (7 - k)) & 0x7fu;
-        w = (w << 4) | ((__popc(win & 0x6du) & 1u) << 3) | ((__popc(win & 0x4fu) & 1u) << 2) | ((__popc(win & 0x53u) & 1u) << 1) |
-            (__popc(win & 0x6du) & 1u);
-    }
-    return w;
-}
-
-// the bits of w that the pattern keeps, in order, MSB first, right-aligned
-__device__ __forceinline__ uint32_t keep_bits(uint32_t w, uint32_t pattern)
-{
-    uint32_t acc = 0;
-#pragma unroll
-    for (int b = 31; b >= 0; --b)
-        if ((pattern >> b) & 1u) acc = (acc << 1) | ((w >> b) & 1u);
-    return acc;
-}
 
 __global__ __launch_bounds__(kFeThreads) void fe_encode_kernel(FeArgs a)
 {
@@ -64,15 +38,12 @@ __global__ __launch_bounds__(kFeThreads) void fe_encode_kernel(FeArgs a)
     for (uint32_t i = threadIdx.x; i <= in_bytes; i += kFeThreads) {
         const uint32_t byte = i < in_bytes ? s_in[i] : 0u, prev = i ? s_in[i - 1] : 0u;
         const uint32_t w = mother_code(prev, byte);
-        uint32_t r = 0;
-        while (r < u.nseg && i >= u.g0[r + 1]) ++r;
-        const uint32_t pattern = u.pat[r], kept = __popc(pattern);
-        if (!kept) continue;
-        const uint32_t at = u.base[r] + (i - u.g0[r]) * kept;
-        const unsigned long long v = (unsigned long long)keep_bits(w, pattern) << (64 - kept - (at & 31u));
+        const FeSegment g = fe_segment(u, i);
+        if (!g.kept) continue;
+        const unsigned long long v = (unsigned long long)keep_bits(w, g.pattern) << (64 - g.kept - (g.at & 31u));
         const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
-        if (hi) atomicOr(&s_out[at >> 5], hi);
-        if (lo) atomicOr(&s_out[(at >> 5) + 1], lo);
+        if (hi) atomicOr(&s_out[g.at >> 5], hi);
+        if (lo) atomicOr(&s_out[(g.at >> 5) + 1], lo);
     }
     __syncthreads();
     // (what lies behind the last kept bit is the zero padding up to 8 x CU)
@@ -90,33 +61,26 @@ __global__ __launch_bounds__(kFeThreads) void fe_encode_kernel(FeArgs a)
     }
 }
 
-// Bit 0x80 >> b of an even byte comes from the frame delayed by {0,8,4,12,2,10,6,14}[b], of an odd byte by
-// {1,9,5,13,3,11,7,15}[b]: as the mask a delay has on a little-endian dword of two (even, odd) byte pairs.
-__device__ __forceinline__ uint32_t delay_mask(int d)
-{
-    // b = the 3-bit reversal of d >> 1
-    const int h = d >> 1, b = ((h & 1) << 2) | (h & 2) | (h >> 2);
-    const uint32_t m = 0x80u >> b;
-    return (d & 1) ? m * 0x01000100u : m * 0x00010001u;
-}
-
 __global__ __launch_bounds__(kFeThreads) void fe_assemble_kernel(FeArgs a, size_t total)
 {
     const size_t idx = (size_t)blockIdx.x * kFeThreads + threadIdx.x;
     if (idx >= total) return;
-    const uint32_t fic_words = (uint32_t)(a.cifs * a.fic_out) / 4, tf_words = fic_words + (uint32_t)a.cifs * kFeRowWords;
+    const uint32_t fic_row = (uint32_t)a.fic_out / 4, tf_words = (uint32_t)a.cifs * (fic_row + kFeRowWords);
     const size_t tf = idx / tf_words;
-    const uint32_t w = (uint32_t)(idx % tf_words);
+    // the word's ETI frame of the call and its place there: in the frame's FIC, or behind it in its CIF.  (The FIC branch pays
+    // a division for its row that it could do without: the FICs lie in frame order, word w of them at tf * fic_words + w.)
+    const RowWord r = tf_row_word((uint32_t)(idx % tf_words), (uint32_t)a.cifs, fic_row, kFeRowWords);
+    const size_t frame = tf * a.cifs + r.k;
     uint32_t v;
-    if (w < fic_words) {
-        v = ((const uint32_t *)a.fic)[tf * fic_words + w];
+    if (r.at < fic_row) {
+        v = ((const uint32_t *)a.fic)[frame * fic_row + r.at];
     } else {
-        const uint32_t j = w - fic_words, cif = j / kFeRowWords, jj = j % kFeRowWords;
+        const uint32_t jj = r.at - fic_row;
         if (a.owner[jj >> 1] < 0) {
             v = ((const uint32_t *)a.prbs)[jj];
         } else {
             // row of this CIF's own frame; a sub-channel starts on an even byte, so the CIF's byte parity is its parity
-            const uint32_t *row = (const uint32_t *)a.hist + ((size_t)kFeHistory + tf * a.cifs + cif) * kFeRowWords + jj;
+            const uint32_t *row = (const uint32_t *)a.hist + ((size_t)kFeHistory + frame) * kFeRowWords + jj;
             v = 0;
 #pragma unroll
             for (int d = 0; d < 16; ++d) v |= row[-(ptrdiff_t)d * kFeRowWords] & delay_mask(d);
