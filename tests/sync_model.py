@@ -57,10 +57,18 @@ def _second_lowest_non_adjacent(S, b):
     return float(S[far].min())
 
 
+def _lowest_other(S, b):
+    """the lowest S over every window but b, the adjacent ones included (inf where b is the only window)"""
+    other = np.delete(S, b)
+    return float(other.min()) if other.size else float("inf")
+
+
 def sync_model(x, mode, max_shift, max_frames):
     """Steps 1 - 6 on the capture x.  -> dict: n_frames, coarse0, null_depth, frames (one dict per candidate: start, shift,
-    valid, eps, cfo_hz, quality, null_depth) and margins (per candidate: d_runner_up, c_runner_up; s_second, s_lowest once) --
-    how far each integer decision was from going the other way."""
+    valid, eps, cfo_hz, quality, null_depth) and margins (per candidate: d_runner_up, c_runner_up; s_second, s_next, s_lowest
+    once) -- how far each integer decision was from going the other way.  s_second leaves the chosen window's neighbours out;
+    s_next does not: the device adds its block powers in fp32, so the coarse decision is the model's only where the chosen
+    window wins over EVERY other by far more than fp32's error."""
     g = geometry(mode)
     N, K, L, null, sym, CP, tf, B, NB = (g[k] for k in ("N", "K", "L", "null", "sym", "CP", "tf", "B", "NB"))
     x = as_complex(x)
@@ -118,7 +126,7 @@ def sync_model(x, mode, max_shift, max_frames):
                             c_runner_up=float(c2[far].max() / c2[l_star]) if c2[l_star] > 0 else 0.0))
         k += 1
     return dict(n_frames=len(frames), coarse0=coarse0, null_depth=null_depth, frames=frames, margins=margins,
-                s_lowest=float(S[b_star]), s_second=_second_lowest_non_adjacent(S, b_star))
+                s_lowest=float(S[b_star]), s_second=_second_lowest_non_adjacent(S, b_star), s_next=_lowest_other(S, b_star))
 
 
 def extract_slots(n_samples, mode, max_frames):

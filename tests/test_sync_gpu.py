@@ -2,7 +2,18 @@
 integers of the float64 model (tests/sync_model.py) exactly and its real figures and extracted frames within measured bars; the
 whole receiver on the device, capture -> sync -> extract -> demod (-> decode), back to the input bits; byte-identical repeats;
 frames that do not fit the buffer; refusals.  tests/test_sync_cpu.py checks on the model that every integer decision asked
-for here is far from going the other way."""
+for here is far from going the other way.
+
+The eight cases visit one start residue per mode on the block grid B = N / 32, shifts up to -20, max_shift 31 and two frames.
+tests/test_sync_axes_gpu.py sweeps the rest with the bars below (tests/sync_cases.py::FAMILIES): start residues 0 ... 2 B and
+the last block of the search range; max_shift 0, 1, 7, 31 with the offset at both ends of the shift loop and |eps| up to 0.48;
+more frames than the context takes, more slots than candidates, a candidate before the buffer, a frame that ends on the last
+sample and one that ends a sample past it, the shortest capture; s16 in Modes II - IV; one echo; TII at shift 31; a fine start
+exactly N / 2 off the coarse one.  slack = null - NB B is 32 / 8 / 1 / 16 samples in Modes I - IV: the coarse window at block
+boundary b B lies inside a null symbol at s when 0 <= b B - s <= slack.  Equality is asked only where
+tests/test_sync_axes_cpu.py has shown on the model that the chosen window's S is exactly 0 or wins over EVERY other window by
+1e-3 (the device adds block powers in fp32, relative error about B 2^-24 <= 4e-6: 1e-3 is 250 times that), the runner-up
+|D|^2 and |c|^2 are at most 0.6 of the peak and eps is at least 1e-3 away from +-1/2."""
 import numpy as np
 import pytest
 
