@@ -8,7 +8,7 @@ using namespace dabgpu;
 using namespace dabgpu_api;
 
 namespace {
-enum { kXN = SPECTRUM_NFFT, kXAcc = 4 * SPECTRUM_NFFT + 1, kSums = DPD_MAX_BINS * DPD_FIGURES + 2, kDpdMaxRuns = 4096 };
+enum { kXN = SPECTRUM_NFFT, kXAcc = 4 * SPECTRUM_NFFT + 1, kSums = DPD_MAX_BINS * DPD_FIGURES + 2 };
 const unsigned long long kDpdSampleCap = 1ull << 31;
 const char *const kBadTxFormat = "dpd: tx is complexf (format 0) or DABGPU_FMT_S16; rx is complexf";
 
@@ -17,14 +17,6 @@ size_t tx_bytes(int format) { return format == 0 ? sizeof(float2) : 4; }
 int dpd_ready(dabgpu_ctx *c)
 {
     if (c->dpd.ready) return DABGPU_OK;
-    if (c->g.N != kXN) {                                               // (Mode I: the context's own table is this one)
-        std::vector<float2> tw(kXN);
-        for (int m = 0; m < kXN; ++m) {
-            const double a = 2.0 * M_PI * (double)m / (double)kXN;
-            tw[m] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-        HIPCHK(c, upload(c->dpd.tw, tw, c->stream));
-    }
     HIPCHK(c, c->dpd.xacc.reserve(kXAcc * sizeof(double)));
     HIPCHK(c, c->dpd.sums.reserve(kSums * sizeof(unsigned long long)));
     HIPCHK(c, c->dpd.edge.reserve((DPD_MAX_BINS + 1) * sizeof(float)));
@@ -48,20 +40,16 @@ int check_pair(dabgpu_ctx *c, const void *tx, int format, const void *rx, size_t
 
 int queue_xspectrum(dabgpu_ctx *c, const void *d_tx, int format, const void *d_rx, size_t n, long long rx_offset, hipStream_t s)
 {
-    int rc = dpd_ready(c);
-    if (rc) return rc;
     DpdXspecArgs a{};
+    int rc = dpd_ready(c);
+    if (!rc) rc = welch_twiddle(c, &a.twiddle);
+    if (rc) return rc;
     a.tx = d_tx;
     a.fmt = format;
     a.rx = (const float2 *)d_rx;
     a.rx_offset = rx_offset;
     dpd_segments(n, rx_offset, &a.seg_first, &a.n_segments);
-    spectrum_runs(a.n_segments, c->dpd.run_segments, &a.n_runs, &a.segs_per_run);
-    if (a.n_runs > kDpdMaxRuns) {                                      // (a row is 64 KiB: never more than 256 MiB of them)
-        a.segs_per_run = (int)((a.n_segments + kDpdMaxRuns - 1) / kDpdMaxRuns);
-        a.n_runs = (int)((a.n_segments + a.segs_per_run - 1) / a.segs_per_run);
-    }
-    a.twiddle = (const float2 *)(c->g.N == kXN ? c->d_twiddle.p : c->dpd.tw.p);
+    spectrum_runs(a.n_segments, c->dpd.run_segments, kDpdMaxRuns, &a.n_runs, &a.segs_per_run);
     HIPCHK(c, c->dpd.rows.reserve(std::max<size_t>((size_t)a.n_runs, 1) * 4 * kXN * sizeof(double)));
     a.rows = (double *)c->dpd.rows.p;
     a.acc = (double *)c->dpd.xacc.p;
@@ -70,14 +58,10 @@ int queue_xspectrum(dabgpu_ctx *c, const void *d_tx, int format, const void *d_r
     return DABGPU_OK;
 }
 
-int fetch_xspectrum(dabgpu_ctx *c, std::vector<double> &host)
+int fetch_xspectrum(dabgpu_ctx *c, std::vector<double> &host, unsigned long long *segments = nullptr)
 {
-    host.assign(kXAcc, 0.0);
-    if (c->dpd.ready) {
-        HIPCHK(c, wait_result(c, c->dpd.stream));
-        HIPCHK(c, hipMemcpy(host.data(), c->dpd.xacc.p, host.size() * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return DABGPU_OK;
+    unsigned long long n;
+    return fetch_welch_sums(c, c->dpd.ready, c->dpd.xacc, c->dpd.stream, 4 * kXN, host, segments ? segments : &n);
 }
 
 // S as the C-ABI hands it out: re / im interleaved
@@ -201,16 +185,13 @@ int dabgpu_get_dpd_xspectrum(dabgpu_ctx *c, double *s2048x2, double *p_tx2048, d
 {
     CTXCHK(c);
     std::vector<double> host;
-    int rc = fetch_xspectrum(c, host);
+    unsigned long long n;
+    int rc = fetch_xspectrum(c, host, &n);
     if (rc) return rc;
     if (s2048x2) interleave_s(host, s2048x2);
     if (p_tx2048) std::memcpy(p_tx2048, &host[2 * kXN], kXN * sizeof(double));
     if (p_rx2048) std::memcpy(p_rx2048, &host[3 * kXN], kXN * sizeof(double));
-    if (segments) {
-        unsigned long long n;
-        std::memcpy(&n, &host[4 * kXN], sizeof n);
-        *segments = n;
-    }
+    if (segments) *segments = n;
     return DABGPU_OK;
 }
 

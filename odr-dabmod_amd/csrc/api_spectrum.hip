@@ -43,19 +43,10 @@ double window_sum_w2(int window)
     return s;
 }
 
-
 // tables and sums on first use: written once, never rewritten, so that a call on any stream may read them
 int spectrum_ready(dabgpu_ctx *c)
 {
     if (c->spectrum.ready) return DABGPU_OK;
-    if (c->g.N != SPECTRUM_NFFT) {                                     // (Mode I: the context's own table is this one)
-        std::vector<float2> tw(SPECTRUM_NFFT);
-        for (int m = 0; m < SPECTRUM_NFFT; ++m) {
-            const double a = 2.0 * M_PI * (double)m / (double)SPECTRUM_NFFT;
-            tw[m] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-        HIPCHK(c, upload(c->spectrum.tw, tw, c->stream));
-    }
     std::vector<float> win(kWindows * SPECTRUM_NFFT);
     for (int w = 0; w < kWindows; ++w) window_table(w, win.data() + (size_t)w * SPECTRUM_NFFT);
     HIPCHK(c, upload(c->spectrum.win, win, c->stream));
@@ -84,14 +75,14 @@ int check_spectrum(dabgpu_ctx *c, const void *iq, int format, size_t n_samples, 
 int queue_spectrum(dabgpu_ctx *c, const void *d_iq, int format, size_t n_samples, int window, bool accumulate, double rate_hz,
                    hipStream_t s)
 {
-    int rc = spectrum_ready(c);
-    if (rc) return rc;
     SpectrumArgs a{};
+    int rc = spectrum_ready(c);
+    if (!rc) rc = welch_twiddle(c, &a.twiddle);
+    if (rc) return rc;
     a.iq = d_iq;
     a.fmt = format;
-    a.n_segments = n_samples >= (size_t)SPECTRUM_NFFT ? (long long)((n_samples - SPECTRUM_NFFT) / (SPECTRUM_NFFT / 2)) + 1 : 0;
-    spectrum_runs(a.n_segments, c->spectrum.run_segments, &a.n_runs, &a.segs_per_run);
-    a.twiddle = (const float2 *)(c->g.N == SPECTRUM_NFFT ? c->d_twiddle.p : c->spectrum.tw.p);
+    a.n_segments = welch_n_segments(n_samples);
+    spectrum_runs(a.n_segments, c->spectrum.run_segments, kSpectrumMaxRuns, &a.n_runs, &a.segs_per_run);
     a.window = (const float *)c->spectrum.win.p + (size_t)window * SPECTRUM_NFFT;
     a.acc = (double *)c->spectrum.acc.p;
     a.accumulate = accumulate ? 1 : 0;
@@ -153,16 +144,12 @@ int dabgpu_spectrum(dabgpu_ctx *c, const void *iq, int format, size_t n_samples,
 int dabgpu_get_spectrum(dabgpu_ctx *c, double *raw2048, dabgpu_spectrum_info *info)
 {
     CTXCHK(c);
-    std::vector<double> host(SPECTRUM_NFFT + 1, 0.0);
-    if (c->spectrum.ready) {
-        HIPCHK(c, wait_result(c, c->spectrum.stream));
-        HIPCHK(c, hipMemcpy(host.data(), c->spectrum.acc.p, host.size() * sizeof(double), hipMemcpyDeviceToHost));
-    }
+    std::vector<double> host;
+    unsigned long long n;
+    if (int rc = fetch_welch_sums(c, c->spectrum.ready, c->spectrum.acc, c->spectrum.stream, SPECTRUM_NFFT, host, &n)) return rc;
     if (raw2048) std::memcpy(raw2048, host.data(), SPECTRUM_NFFT * sizeof(double));
     if (info) {
         std::memset(info, 0, sizeof *info);
-        unsigned long long n;
-        std::memcpy(&n, &host[SPECTRUM_NFFT], sizeof n);
         info->segments = n;
         info->nfft = SPECTRUM_NFFT;
         info->window = c->spectrum.window;

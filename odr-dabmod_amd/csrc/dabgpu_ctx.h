@@ -142,11 +142,11 @@ struct CsiState {
     bool unit_weights = false;            // dabgpu_debug_csi_unit_weights
 };
 
-// The spectrum monitor (api_spectrum.hip): the 2048-entry twiddle table (the context's own in Mode I), the three window
-// tables, the rows of one launch, the sums (2048 float64 and the segment count) and the host-pointer entry's staging.
-// One accumulator: monitored calls stay on lane 0.  window: the window the sums were formed with, -1 = none yet.
+// The spectrum monitor (api_spectrum.hip): the three window tables, the rows of one launch, the sums (2048 float64 and the
+// segment count) and the host-pointer entry's staging.  One accumulator: monitored calls stay on lane 0.  window: the window
+// the sums were formed with, -1 = none yet.
 struct SpectrumState {
-    DevBuf tw, win, rows, acc, in;
+    DevBuf win, rows, acc, in;
     bool ready = false;
     int window = -1;
     double rate_hz = 0.0;
@@ -154,12 +154,12 @@ struct SpectrumState {
     int run_segments = 0;                 // dabgpu_debug_spectrum_run_segments: segments per workgroup, 0 = by the input size
 };
 
-// The DPD measurement (api_dpd.hip): the 2048-entry twiddle table (the context's own in Mode I), the cross-spectrum's rows
-// and sums (4 x 2048 float64 and the segment count), the statistics' integer sums (256 bins x 6 figures, overflow, samples
-// used), the squared bin edges and the host-pointer entries' staging.  peak / bins: what the sums were formed with (0: none
-// yet); offered: samples offered since they started over (the cap).
+// The DPD measurement (api_dpd.hip): the cross-spectrum's rows and sums (4 x 2048 float64 and the segment count), the
+// statistics' integer sums (256 bins x 6 figures, overflow, samples used), the squared bin edges and the host-pointer entries'
+// staging.  peak / bins: what the sums were formed with (0: none yet); offered: samples offered since they started over (the
+// cap).
 struct DpdState {
-    DevBuf tw, rows, xacc, sums, edge, tx, rx;
+    DevBuf rows, xacc, sums, edge, tx, rx;
     bool ready = false;
     float peak = 0.f;
     int bins = 0;
@@ -352,6 +352,7 @@ struct dabgpu_ctx {
     dabgpu_api::CsiState csi;
     dabgpu_api::SpectrumState spectrum;
     dabgpu_api::DpdState dpd;
+    dabgpu_api::DevBuf welch_tw;          // the 2048-entry twiddle table of both in modes II - IV (welch_twiddle)
     dabgpu_api::DecodeState decode;
     dabgpu_api::SyncState sync;
     dabgpu_api::ChannelState channel;
@@ -662,6 +663,38 @@ struct DevCall {
 inline hipError_t wait_result(dabgpu_ctx *c, hipStream_t result_stream)
 {
     return hipStreamSynchronize(result_stream ? result_stream : c->stream);
+}
+
+// ---- what the two Welch measurements (the spectrum monitor, the DPD cross-spectrum) share on the host
+// The 2048-entry twiddle table: the context's own in Mode I, else a buffer built on first use -- written once, and the context's
+// stream has been waited for (upload) before this returns, so a call on any stream may read it.
+inline int welch_twiddle(dabgpu_ctx *c, const float2 **table)
+{
+    if (c->g.N != SPECTRUM_NFFT && !c->welch_tw.p) {
+        std::vector<float2> tw(SPECTRUM_NFFT);
+        for (int m = 0; m < SPECTRUM_NFFT; ++m) {
+            const double a = 2.0 * M_PI * (double)m / (double)SPECTRUM_NFFT;
+            tw[m] = make_float2((float)std::cos(a), (float)std::sin(a));
+        }
+        DevBuf b;
+        HIPCHK(c, upload(b, tw, c->stream));
+        c->welch_tw = std::move(b);
+    }
+    *table = (const float2 *)(c->g.N == SPECTRUM_NFFT ? c->d_twiddle.p : c->welch_tw.p);
+    return DABGPU_OK;
+}
+// `width` float64 sums and the segment count behind them (acc, complete on `result_stream`); zeros when nothing has run (ready
+// false)
+inline int fetch_welch_sums(dabgpu_ctx *c, bool ready, const DevBuf &acc, hipStream_t result_stream, size_t width, std::vector<double> &sums,
+                            unsigned long long *segments)
+{
+    sums.assign(width + 1, 0.0);
+    if (ready) {
+        HIPCHK(c, wait_result(c, result_stream));
+        HIPCHK(c, hipMemcpy(sums.data(), acc.p, sums.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    std::memcpy(segments, &sums[width], sizeof *segments);
+    return DABGPU_OK;
 }
 
 // The host-pointer form of a capture stage, after its checks: the context idle, the capture in `staging`, the stage's _dev

@@ -10,6 +10,7 @@
 
 #include "conv_code.h"
 #include "resampler_runs.h"
+#include "welch.h"
 
 namespace dabgpu {
 
@@ -380,39 +381,35 @@ struct CirArgs {
     double *pdp, *resp;       // N each
 };
 hipError_t launch_cir(const CirArgs &a, hipStream_t s);
-// spectrum.hip: Welch periodogram of one sample buffer (dabgpu_spectrum*, the spectrum monitor): segments of SPECTRUM_NFFT
-// samples at a hop of half that, in every transmission mode
-enum { SPECTRUM_NFFT = 2048, kSpectrumMaxRuns = 1 << 16 };
-struct SpectrumArgs {
-    const void *iq;           // the samples: cf32 (fmt 0), s16 pairs (1), u8 pairs, value byte - 128 (2), s8 pairs (3)
-    int fmt;
-    long long n_segments;     // floor((n_samples - 2048) / 1024) + 1, or 0
+// welch.h: what the two Welch launches share -- the run geometry (spectrum_runs), the table, the rows and the sums
+struct WelchArgs {
+    long long n_segments;     // the segments used: one range, every lane sees the same
     int n_runs, segs_per_run; // (spectrum_runs)
     const float2 *twiddle;    // exp(+2 pi i m / 2048), 2048 entries
+    double *rows;             // scratch, n_runs rows: a workgroup's partial sums, bins in FFT order
+    double *acc;              // the sums (a row's width), then the segment count as one unsigned long long
+};
+// what either launch checks of them first (spectrum.hip)
+hipError_t check_welch(const WelchArgs &a, int max_runs);
+// spectrum.hip: Welch periodogram of one sample buffer (dabgpu_spectrum*, the spectrum monitor): segments of SPECTRUM_NFFT
+// samples at a hop of half that, in every transmission mode.  n_segments: welch_n_segments.  A row is 2048 sums.
+struct SpectrumArgs : WelchArgs {
+    const void *iq;           // the samples: cf32 (fmt 0), s16 pairs (1), u8 pairs, value byte - 128 (2), s8 pairs (3)
+    int fmt;
     const float *window;      // 2048 fp32 factors
-    double *rows;             // scratch, n_runs x 2048: a workgroup's partial sums, bins in FFT order
-    double *acc;              // 2048 sums, then the segment count as one unsigned long long
     int accumulate;           // the reduce kernel adds to acc (else stores)
 };
-void spectrum_runs(long long n_segments, int forced, int *n_runs, int *segs_per_run);
 hipError_t launch_spectrum(const SpectrumArgs &a, hipStream_t s);
-// dpd.hip: the predistortion measurement (dabgpu_dpd_*).  The cross-spectrum uses the spectrum kernel's geometry (segments of
-// SPECTRUM_NFFT samples at a hop of half that, rectangular window, runs of segments, rows and a reduce in workgroup order).
+// dpd.hip: the predistortion measurement (dabgpu_dpd_*).  The cross-spectrum is the spectrum kernel's walk over two buffers
+// (welch.h), rectangular window; a row is 4 x 2048 sums: Re S, Im S, P_tx, P_rx.
 enum { DPD_TAPS = 32, DPD_TAP_CENTRE = 15, DPD_MAX_BINS = 256, DPD_TILE_MAX = 2048, DPD_FIGURES = 6 };
-struct DpdXspecArgs {
+struct DpdXspecArgs : WelchArgs {
     const void *tx;           // cf32 (fmt 0) or s16 pairs (fmt 1)
     int fmt;
     const float2 *rx;         // cf32; segment i of rx is samples 1024 i + rx_offset ... + 2047
     long long rx_offset;
-    long long seg_first;      // the first segment whose rx range lies inside the buffer, and how many follow it (the
-    long long n_segments;     //   segments used form one range: launch_dpd_xspectrum forms it, every lane sees the same)
-    int n_runs, segs_per_run; // (spectrum_runs)
-    const float2 *twiddle;    // exp(+2 pi i m / 2048), 2048 entries
-    double *rows;             // scratch, n_runs x 4 x 2048: Re S, Im S, P_tx, P_rx, bins in FFT order
-    double *acc;              // 4 x 2048 sums, then the segment count as one unsigned long long
+    long long seg_first;      // the first segment whose rx range lies inside the buffer; n_segments follow it (dpd_segments)
 };
-// the range of segments of an n-sample pair whose rx range (shifted by rx_offset) lies inside the buffer
-void dpd_segments(size_t n, long long rx_offset, long long *first, long long *count);
 // (n_samples: of either buffer; the launch checks the range of segments in `a` against it)
 hipError_t launch_dpd_xspectrum(const DpdXspecArgs &a, size_t n_samples, hipStream_t s);
 struct DpdStatsArgs {

@@ -1,9 +1,9 @@
 // dpd.hip -- what a predistortion estimator needs from a block of transmitted samples (tx) and the matching capture of the
 // amplifier's feedback path (rx), formed on the device:
-//   dpd_xspectrum_kernel<FMT_TX>  Welch cross-spectrum of the two buffers in spectrum_kernel's geometry (2048-sample
-//                                 segments at a hop of 1024, rectangular window, Fft<11>::run<-1>, float64 sums per lane, one
-//                                 row per workgroup) and dpd_xspectrum_reduce_kernel, which adds the rows in workgroup order.
-//                                 Integer lag, sub-sample delay, gain and coherence follow from it on the host.
+//   dpd_xspectrum_kernel<FMT_TX>  Welch cross-spectrum of the two buffers: spectrum_kernel's segments, runs and walk (welch.h),
+//                                 rectangular window, Fft<11>::run<-1>, float64 sums per lane, one row per workgroup; and
+//                                 dpd_xspectrum_reduce_kernel, welch.h's row sum.  Only the four cross products are this
+//                                 file's own.  Integer lag, sub-sample delay, gain and coherence follow on the host.
 //   dpd_stats_kernel<FMT_TX>      the aligned amplitude-bin statistics: one lane per tx sample, the rx window of a tile
 //                                 through LDS (each rx sample is read from memory once per tile), a 32-tap fractional-delay
 //                                 filter and a complex gain on rx, the bin from |tx|^2, six figures per bin.
@@ -17,54 +17,42 @@ namespace dabgpu {
 namespace {
 
 typedef Fft<11> SF;
-static_assert(SF::N == SPECTRUM_NFFT && SF::T == 256, "2048 points on 256 lanes");
+static_assert(SF::N == SPECTRUM_NFFT && SF::T == kWelchLanes, "2048 points on 256 lanes");
 
-// One workgroup = one run of consecutive segments, as in spectrum_kernel; run segment s is segment a.seg_first + s of the
-// buffers.  Lane t holds samples t + 256 m of the current segment of either buffer; the second half of a segment is the first
-// half of the next, so every sample is read once per run.  After the two transforms lane t holds bins t + 256 m (FFT order)
-// of TX and RX: S += TX conj(RX), P_tx += |TX|^2, P_rx += |RX|^2, products in fp32, sums in float64.
+// One workgroup = one run of consecutive segments (welch_run); run segment s is segment a.seg_first + s of the buffers, walked
+// by two WelchWalkers: tx, and rx at a.rx_offset.  After the two transforms lane t holds bins t + 256 m (FFT order) of TX and
+// RX: S += TX conj(RX), P_tx += |TX|^2, P_rx += |RX|^2, products in fp32, sums in float64.
 template <int FMT> __global__ __launch_bounds__(SF::T) void dpd_xspectrum_kernel(DpdXspecArgs a)
 {
-    constexpr int T = SF::T, HOP = SPECTRUM_NFFT / 2;
+    constexpr int T = SF::T;
     __shared__ cf xbuf[2 * SF::LDS_ELEMS];
 
     const int t = (int)threadIdx.x;
-    const long long s0 = (long long)blockIdx.x * a.segs_per_run;
-    const long long s1 = s0 + a.segs_per_run < a.n_segments ? s0 + a.segs_per_run : a.n_segments;
-    if (s0 >= s1) return;
+    const WelchRun run = welch_run(blockIdx.x, a.segs_per_run, a.n_segments);
+    if (run.idle) return;
 
     cf tw[SF::NTW];
     SF::template load_twiddles<false>(a.twiddle, t, tw);
 
     // (launch_dpd_xspectrum has made sure that every segment of the range lies inside both buffers)
-    const size_t tbase = (size_t)((a.seg_first + s0) * HOP) + (size_t)t;
-    const size_t rbase = (size_t)((a.seg_first + s0) * HOP + a.rx_offset) + (size_t)t;
-    cf xt[8], xr[8];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        xt[4 + m] = load_sample<FMT>(a.tx, tbase + T * m);
-        xr[4 + m] = a.rx[rbase + T * m];
-    }
+    auto xt = welch_walker<cf>([tx = a.tx](long long i) { return load_sample<FMT>(tx, i); });
+    auto xr = welch_walker<cf>([rx = a.rx](long long i) { return rx[i]; });
+    xt.start((a.seg_first + run.s0) * kWelchHop, t);
+    xr.start((a.seg_first + run.s0) * kWelchHop + a.rx_offset, t);
 
     double sre[8], sim[8], ptx[8], prx[8];
 #pragma unroll
     for (int m = 0; m < 8; ++m) sre[m] = sim[m] = ptx[m] = prx[m] = 0.;
     int par = 0;
-    for (long long s = s0; s < s1; ++s) {
-        const size_t half = (size_t)(s - s0 + 1) * HOP;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            xt[m] = xt[4 + m];
-            xr[m] = xr[4 + m];
-            xt[4 + m] = load_sample<FMT>(a.tx, tbase + half + T * m);
-            xr[4 + m] = a.rx[rbase + half + T * m];
-        }
+    for (long long s = run.s0; s < run.s1; ++s) {
+        xt.advance(s + 1 < run.s1);
+        xr.advance(s + 1 < run.s1);
         cf u[8], v[8];
 #pragma unroll
-        for (int m = 0; m < 8; ++m) u[m] = xt[m];
+        for (int m = 0; m < 8; ++m) u[m] = xt.raw[m];
         SF::template run<-1, true, cf, false>(u, xbuf, par, tw, t);
 #pragma unroll
-        for (int m = 0; m < 8; ++m) v[m] = xr[m];
+        for (int m = 0; m < 8; ++m) v[m] = xr.raw[m];
         SF::template run<-1, true, cf, false>(v, xbuf, par, tw, t);
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
@@ -85,17 +73,10 @@ template <int FMT> __global__ __launch_bounds__(SF::T) void dpd_xspectrum_kernel
     }
 }
 
-// One lane per entry of a row: the rows in workgroup order into the context's sums (always stored: a cross-spectrum call
-// starts over).  Lane 0 keeps the segment count behind the 4 x 2048 sums.
+// (always stored: a cross-spectrum call starts over)
 __global__ __launch_bounds__(64) void dpd_xspectrum_reduce_kernel(DpdXspecArgs a)
 {
-    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (k >= 4 * SPECTRUM_NFFT) return;
-    const double *row = a.rows + k;
-    double s = 0.;
-    for (int r = 0; r < a.n_runs; ++r) s += row[(size_t)r * (4 * SPECTRUM_NFFT)];
-    a.acc[k] = s;
-    if (k == 0) *reinterpret_cast<unsigned long long *>(a.acc + 4 * SPECTRUM_NFFT) = (unsigned long long)a.n_segments;
+    welch_row_sum<4 * SPECTRUM_NFFT>(a.rows, a.n_runs, a.n_segments, a.acc, false, (int)(blockIdx.x * blockDim.x + threadIdx.x));
 }
 
 // dpd_stats_kernel: workgroup w owns the tx samples (a.tile_first + w) tile ... + tile - 1; lane t takes samples t + 256 k of
@@ -173,31 +154,13 @@ template <int FMT> __global__ __launch_bounds__(256) void dpd_stats_kernel(DpdSt
 
 }  // namespace
 
-void dpd_segments(size_t n, long long rx_offset, long long *first, long long *count)
-{
-    const long long HOP = SPECTRUM_NFFT / 2, N = SPECTRUM_NFFT, nn = (long long)n;
-    *first = 0;
-    *count = 0;
-    if (nn < N) return;
-    const long long n_seg = (nn - N) / HOP + 1;
-    const long long lo = rx_offset < 0 ? (-rx_offset + HOP - 1) / HOP : 0;        // 1024 i + rx_offset >= 0
-    const long long room = nn - N - rx_offset;                                    // 1024 i <= room
-    if (room < 0) return;
-    const long long hi = std::min(n_seg, room / HOP + 1);
-    if (lo >= hi) return;
-    *first = lo;
-    *count = hi - lo;
-}
-
 hipError_t launch_dpd_xspectrum(const DpdXspecArgs &a, size_t n_samples, hipStream_t s)
 {
     long long first, count;
     dpd_segments(n_samples, a.rx_offset, &first, &count);
-    if (first != a.seg_first || count != a.n_segments || a.n_runs < 0 || a.segs_per_run < 1 || a.n_runs > kSpectrumMaxRuns ||
-        (long long)a.n_runs * a.segs_per_run < a.n_segments || (a.n_segments > 0 && a.n_runs < 1) || !a.acc || !a.rows)
-        return hipErrorInvalidValue;
+    if (first != a.seg_first || count != a.n_segments || check_welch(a, kDpdMaxRuns) != hipSuccess) return hipErrorInvalidValue;
     if (a.n_segments > 0) {
-        if (!a.tx || !a.rx || !a.twiddle) return hipErrorInvalidValue;
+        if (!a.tx || !a.rx) return hipErrorInvalidValue;
         const dim3 grid((unsigned)a.n_runs), block(SF::T);
         switch (a.fmt) {
         case 0: DABGPU_LAUNCH(dpd_xspectrum_kernel<0>, grid, block, 0, s, a); break;

@@ -144,6 +144,29 @@ def test_cross_spectrum_run_geometry_and_determinism(pkg):
         md.close()
 
 
+def test_short_forced_runs_follow_the_float64_model(pkg):
+    """Runs of 3 segments and a shorter last one, then of one segment each, against the float64 model rather than the library's
+    own default geometry: a half-segment that either walk over a run (welch.h: tx, and rx at rx_offset) shifted would be
+    compared with itself there.  The first 2048 + 6 x 1024 samples, tx s16 in a Mode II context (the built table), rx_offset 0
+    (7 segments) and -300 (6: the first has no rx range).  The model alone has 967 bins or more of every array at or above its
+    mean level at this length: figure (a) is formed over them."""
+    n = 2048 + 6 * 1024
+    md = pkg.Modulator(mode=2, max_frames=1)
+    try:
+        d_tx, d_rx = _cuda(DC.block_s16()[:2 * n]), _cuda(DC.capture(0.37)[:n])
+        ok = True
+        for off, segs in ((0, 7), (-300, 6)):
+            model = _xmodel("s16", n, off)
+            assert model[3] == segs and all(np.count_nonzero(np.abs(m) >= np.abs(m).mean()) >= 1 for m in model[:3])
+            for run in (3, 1):
+                md.set_dpd_geometry(run_segments=run)
+                md.dpd_xspectrum_dev(d_tx, d_rx, off)
+                ok = _xcheck(md.dpd_xspectrum_result(), model, "s16 n %d offset %d in runs of %d" % (n, off, run)) and ok
+        assert ok
+    finally:
+        md.close()
+
+
 def test_align_on_the_device_finds_the_delay(pkg):
     """The two passes on the device against the two passes of the model (tests/test_dpd_cpu.py holds the solve itself)."""
     md = pkg.Modulator(mode=1, max_frames=1)

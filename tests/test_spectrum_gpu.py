@@ -65,10 +65,13 @@ def _figures(dev, model):
     return float(np.max(err[strong] / model[strong])), float(np.max(err / (model + 1e-9 * model.mean())))
 
 
-def _dev(fmt, n_samples=None):
+def _dev_array(y):
     import torch
-    y = SC.samples(fmt) if n_samples is None else SC.truncated(fmt, n_samples)
     return torch.from_numpy(np.array(y)).cuda()
+
+
+def _dev(fmt, n_samples=None):
+    return _dev_array(SC.samples(fmt) if n_samples is None else SC.truncated(fmt, n_samples))
 
 
 def _same_but_for_order(got, want, segments):
@@ -150,6 +153,57 @@ def test_run_geometry_and_determinism(pkg):
         assert np.array_equal(md.spectrum_stats()["raw"].view(np.uint64), first["raw"].view(np.uint64))
     finally:
         md.close()
+
+
+def test_short_forced_runs_follow_the_float64_model(pkg):
+    """Runs of 3, 3 and 1 segments, then of one segment each, against the float64 model rather than the library's own default
+    geometry: a half-segment that the walk over a run (welch.h) shifted or took from the wrong place would be compared with
+    itself there.  The first 2048 + 6 x 1024 samples of the s16 case, 7 segments, Blackman-Harris; Mode II, so the table is the
+    built one.  The model alone has 7 bins within 40 dB of its largest at this length: figure (a) is formed over them."""
+    n = 2048 + 6 * 1024
+    md = pkg.Modulator(mode=FMT_MODE["s16"], max_frames=1)
+    try:
+        d = _dev("s16", n)
+        model, segs = _model(pkg, "s16", 2, n)
+        assert segs == 7 and np.count_nonzero(model >= 1e-4 * model.max()) >= 1
+        ok = True
+        for run in (3, 1):
+            md.set_spectrum_run_segments(run)
+            md.spectrum_dev(d, 2)
+            st = md.spectrum_stats()
+            assert st["segments"] == 7
+            a, b = _figures(st["raw"], model)
+            print("s16, 7 segments in runs of %d: (a) %.3g  (b) %.3g" % (run, a, b))
+            ok_a = record_bound("spectrum (a), 7 segments in runs of %d, s16" % run, a, BAR_A)
+            ok_b = record_bound("spectrum (b), 7 segments in runs of %d, s16" % run, b, _bar_b_short(7))
+            ok = ok and ok_a and ok_b
+        assert ok
+    finally:
+        md.close()
+
+
+def test_spectrum_and_cross_spectrum_share_one_table_in_either_order(pkg):
+    """Modes II - IV build the 2048-entry twiddle table on first use, one per context for both measurements: a context that
+    runs the spectrum first and one that runs the cross-spectrum first give the same bits.  3072 samples, 2 segments."""
+    from tests import dpd_cases as DC
+    n = 3072
+    d_iq, d_tx, d_rx = _dev("s16", n), _dev_array(DC.block_s16()[:2 * n]), _dev_array(DC.capture(0.37)[:n])
+    got = []
+    for spectrum_first in (True, False):
+        md = pkg.Modulator(mode=2, max_frames=1)
+        try:
+            for step in ((0, 1) if spectrum_first else (1, 0)):
+                if step == 0:
+                    md.spectrum_dev(d_iq, 2)
+                else:
+                    md.dpd_xspectrum_dev(d_tx, d_rx, 0)
+            st, x = md.spectrum_stats(), md.dpd_xspectrum_result()
+            assert st["segments"] == 2 and x["segments"] == 2 and st["raw"].any() and x["S"].any()
+            got.append([st["raw"], x["S"], x["p_tx"], x["p_rx"]])
+        finally:
+            md.close()
+    for one, other in zip(*got):
+        assert np.array_equal(one.view(np.uint64), other.view(np.uint64))
 
 
 # --------------------------------------------------------------------------- 4. accumulate
